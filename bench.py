@@ -4,11 +4,20 @@ batches through the drop-in path (MultiModalTrainer step -> MultiModal.forward -
 backward -> fused AdamW), BASELINE.json configs[1]: 1 session, spike + behaviour, d_model=256,
 5+5 layers, T=100 bins per modality.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--dtype fp32|bf16]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dtype fp32|bf16] [--dump-outputs DIR] [--full]
 
 N>1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL); every rank
 processes its own batch of B samples (weak scaling) and gradients are mean-all-reduced in buckets
 overlapped with backward.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what
+takes runs of its own: the per-kernel HIP-event profile and the roofline built from it, the short
+legs of other configurations (exact masker stream, fp32 parity, multi-session, config 5) and the
+CPU-oracle baseline (each of them can still be left out with its --no-* option).
+
+--dump-outputs DIR writes, after the timed steps, what rank 0's last timed step returned to its
+caller as DIR/<name>.npy (see dump_outputs()); the inputs depend only on the arguments, so two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -36,6 +45,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("MMFM_BENCH_BATCH", "1024")), help="samples per GPU per step")
     ap.add_argument("--dtype", default=os.environ.get("MMFM_DTYPE", "bf16"), choices=["fp32", "bf16"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel profile + roofline, the extra configuration legs and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (loss, per-modality losses / counts / predictions, updated parameters) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--host-inputs", action="store_true",
                     help="batches start in pinned HOST memory and cross PCIe inside the timed region (the PCIe-inclusive rate quoted in "
@@ -271,6 +285,37 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_PARAMS_CAP = 10 * 2 ** 20          # elements: the model has 9.4 M parameters, so they are written whole
+DUMP_PREDS_CAP = 2 * 2 ** 20            # elements per modality: 'ap' at B = 1024 has 68 M predictions, a fixed sample of them is written
+
+
+def dump_outputs(out_dir, out, params):
+    """What one timed step hands its caller: the loss, the per-modality losses and masked-element counts (float64), the per-modality
+    predictions (float32, flattened) and the parameters after the optimizer step (float32, every parameter flattened and concatenated
+    in named_parameters() order).  An array longer than its cap is replaced by a fixed sample: the elements at sorted indices drawn by
+    torch.randint from a CPU generator seeded 0, so the same shape always gives the same indices.  At most 14 M float32 elements in all
+    (< 64 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def flat(t, cap):
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        return t.float().cpu().numpy()
+
+    arrays = {"loss": np.asarray([float(out.loss.detach())], dtype=np.float64)}
+    for mod in out.mod_preds:
+        arrays[f"mod_loss_{mod}"] = np.asarray([float(out.mod_loss[mod])], dtype=np.float64)
+        arrays[f"mod_n_examples_{mod}"] = np.asarray([float(out.mod_n_examples[mod])], dtype=np.float64)
+        arrays[f"mod_preds_{mod}"] = flat(out.mod_preds[mod], DUMP_PREDS_CAP)
+    arrays["params"] = flat(torch.cat([p.detach().reshape(-1) for p in params]), DUMP_PARAMS_CAP)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -340,7 +385,7 @@ def main():
         opt.step()
         sch.step()
         opt.zero_grad()
-        return out.loss
+        return out
 
     def barrier():
         if world > 1:
@@ -350,7 +395,7 @@ def main():
     if rank == 0:
         log(f"model built ({a.dtype}, B={B}/GPU, world={world}); warm-up {a.warmup} steps")
     for i in range(a.warmup):
-        loss = step(i)
+        out = step(i)
     barrier()
     if rank == 0:
         log(f"timing {a.steps} steps")
@@ -361,7 +406,7 @@ def main():
         prof.enable()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        loss = step(a.warmup + i)
+        out = step(a.warmup + i)
     if prof is not None:
         prof.disable()
         import io, pstats
@@ -376,11 +421,14 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
-    last_loss = loss.item()
+    last_loss = out.loss.item()
 
     inner = getattr(model, "module", model)
     eng = inner._engine
     res = None
+    if rank == 0 and a.dump_outputs:
+        nbytes = dump_outputs(a.dump_outputs, out, [p for _, p in inner.named_parameters()])
+        log(f"outputs of the last timed step: {nbytes / 2 ** 20:.1f} MB in {a.dump_outputs}")
     if rank == 0:
         ms = dt / a.steps * 1e3
         value = world * B * a.steps / dt
@@ -401,7 +449,7 @@ def main():
         res["masker_token_mask_only"] = bool(getattr(model.masker, "token_mask_only", False))
         res["fused_mask"] = eng._fused_mask(B * 200)
         log(f"{ms:.2f} ms/step, {value:.1f} samples/s")
-        if not a.no_kernel_profile:
+        if a.full and not a.no_kernel_profile:
             log("per-kernel HIP-event profile")
             agg, subs = kernel_profile(eng, eng._last)
             tot = sum(v[1] for v in agg.values())
@@ -481,7 +529,7 @@ def main():
                                    traffic=traffic, avg_launch_ms=round(v[1] / v[0], 4), algorithmic_flops_per_launch=v[2] / v[0],
                                    algorithmic_bytes_per_launch=v[3] / v[0], flop_per_byte=round(v[2] / max(byts, 1.0), 1),
                                    ridge_flop_per_byte=round(RIDGE, 1))
-        if world == 1 and not a.no_extra_legs:
+        if a.full and world == 1 and not a.no_extra_legs:
             try:
                 log("extra legs: exact masker stream, fp32 parity mode, multi-session, config 5")
                 dt = leg_trainer(dev, a.dtype, B, exact_masker=True, steps=6)
@@ -501,7 +549,7 @@ def main():
                                  note="BASELINE configs[4] on one GPU: H=512, I=1024, dh=64, T=200, ap+behavior+lfp (L=600), bf16"))
             except Exception as e:                      # the extra legs never take the headline down with them
                 res["extra_legs_error"] = repr(e)[:300]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("CPU baseline (oracle on host cores)")
             res["cpu_baseline"] = cpu_baseline(a.cpu_steps)
         print(json.dumps(res), flush=True)
