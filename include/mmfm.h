@@ -132,6 +132,20 @@ int mmfm_layernorm_bwd(int dtype, const void* dy, const void* x, const float* me
                        int accumulate, int64_t R, int H, int destitch_L, int destitch_T,
                        void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- ScaleNorm
+ * ScaleNorm(sqrt(H)) of `use_scalenorm: true` (mm_utils.py:31-39; encoder_embeddings.py:98,100; decoder_embeddings.py:118-126):
+ *   y = x * g / max(||x||_2, eps)   per row, g ONE fp32 scalar (device pointer), fp32 statistics, one wavefront per row.
+ * rinv[r] = 1 / max(||x_r||, eps), NEGATED for a clamped row (||x_r|| <= eps).  The backward (x_hat = x * |rinv|, v = g * dy):
+ *   dx = dres + |rinv| * (v - x_hat * (x_hat . v))     (dx = dres + |rinv| * v for a clamped row: the clamp passes no gradient)
+ *   dg (+)= sum over rows of x_hat . dy     (per-block partials in the workspace, reduced in a fixed order: deterministic)
+ * dres may be NULL; dx may alias dres. */
+int mmfm_scalenorm_fwd(int dtype, const void* x, const float* g, void* y, float* rinv, int64_t R, int H, float eps,
+                       mmfm_stream stream);
+int64_t mmfm_scalenorm_bwd_workspace(int64_t R, int H);
+int mmfm_scalenorm_bwd(int dtype, const void* dy, const void* x, const float* rinv, const float* g, const void* dres, void* dx,
+                       float* dg, int accumulate, int64_t R, int H, void* workspace, int64_t workspace_bytes,
+                       mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- attention
  * F.scaled_dot_product_attention with the reference's masks (mm_utils.py:105-111,143-149;
  * mm.py:152-158,178-194) without materialising [B,h,L,L]:
@@ -277,7 +291,9 @@ int mmfm_bits_per_spike_neurons(const float* rates, const float* spikes, int64_t
  *   Wp[n][k] = bf16(W[n][k] * gamma[k]),  WpT = Wp^T,  bp[n] = bias[n] + sum_k W[n][k] * beta[k]
  * so that  linear(layernorm(x)) = Wp . x_hat + bp  with  x_hat = (x - mean) * rstd.  gamma / beta / bias / Wp / WpT / bp / WpP / WpTP
  * may be NULL (plain bf16 copies / transposes of a weight).  `entries` is a DEVICE array; entry e covers blocks
- * [tile0, tile0 + ceil(N/32)); total_tiles = sum of ceil(N/32). */
+ * [tile0, tile0 + ceil(N/32)); total_tiles = sum of ceil(N/32).
+ * scalar_gain = 1 (a ScaleNorm-fed linear): gamma points to ONE float g (the ScaleNorm's gain) and beta is ignored:
+ *   Wp = bf16(g * W),  WpT = Wp^T,  bp = bias,   so that  linear(scalenorm(x)) = Wp . x_hat + bp  with  x_hat = x / max(||x||, eps). */
 typedef struct {
     const float* W;          /* [N][K] fp32 master weight */
     const float* gamma;      /* [K] or NULL */
@@ -288,7 +304,7 @@ typedef struct {
     float* bp;               /* fp32 [N] or NULL */
     int N, K;
     int tile0;
-    int pad_;
+    int scalar_gain;         /* 0: gamma / beta per k (LayerNorm);  1: gamma[0] is a scalar gain for every k, no beta (ScaleNorm) */
     void* WpP;               /* bf16 [N][K] or NULL: Wp with the 8-byte units of every aligned 32-byte group of a row in the order
                                 0, 2, 1, 3 ("unit-permuted": the order in which an MFMA accumulator tile, used as the next product's
                                 operand, holds its k index - rowchain.h).  LDS-DMA cannot permute on the way in, so the kernels that
@@ -301,11 +317,15 @@ typedef struct {
 int mmfm_prep_weights(const mmfm_prep_entry* entries, int n_entries, int total_tiles, mmfm_stream stream);
 
 /* y[R][N] = epi( pro(x)[R][K] . w[N][K]^T ), bf16 storage, fp32 accumulate; K in {256, 512, 768}, N % 32 == 0.
- *   ln != 0 (K = 256): pro(x) = x_hat = (x - mean(x)) * rstd(x) per row (statistics in fp32); x_hat (bf16 [R][256]) and rstd
+ *   ln = 1 (K = 256): pro(x) = x_hat = (x - mean(x)) * rstd(x) per row (statistics in fp32); x_hat (bf16 [R][256]) and rstd
  *                      (fp32 [R]) are written when non-NULL (the backward's saved tensors); w / bias are the PREPARED Wp / bp.
+ *   ln = 2 (K = 256): ScaleNorm: pro(x) = x_hat = x * rstd, rstd = 1 / max(||x||, eps), saved NEGATED for a clamped row (as
+ *                      mmfm_scalenorm_fwd's rinv); w / bias prepared with mmfm_prep_entry.scalar_gain = 1.
  *   epilogue: + bias[n], + residual[m*ldr + n], store.
- *   ln_bwd != 0 (N = 256): v = x . w^T is d(x_hat) of a LayerNorm whose output fed the forward linear (w = WpT of it) and
- *                      y = residual + bwd_rstd * (v - mean(v) - bwd_xhat * mean(v * bwd_xhat))   (residual = running gradient or NULL). */
+ *   ln_bwd = 1 (N = 256): v = x . w^T is d(x_hat) of a LayerNorm whose output fed the forward linear (w = WpT of it) and
+ *                      y = residual + bwd_rstd * (v - mean(v) - bwd_xhat * mean(v * bwd_xhat))   (residual = running gradient or NULL).
+ *   ln_bwd = 2 (N = 256): the same for a ScaleNorm (x_hat / rstd saved by ln = 2):
+ *                      y = residual + |bwd_rstd| * (v - bwd_xhat * sum(v * bwd_xhat)),  the sum dropped where bwd_rstd < 0 (clamped). */
 typedef struct {
     int64_t R;
     int K, N;
@@ -351,6 +371,9 @@ typedef struct {
     void* dx; int lddx;               /* dx == NULL: front half only - t1, g, du are written and the call returns; rstd / w_up_t are not read.
                                          The caller finishes with mmfm_rowgemm(x = du, w = WpT of up_proj, K = 512, residual = dy, ln_bwd) */
     int rotate;                       /* 1: workgroups start at different intermediate tiles (spreads the concurrent L2 reads) */
+    int scalenorm;                    /* 0: ln2 is a LayerNorm;  1: a ScaleNorm (fwd: x_hat = x / max(||x||, eps), rstd saved as by
+                                         mmfm_rowgemm ln = 2, w_up / b_up prepared with scalar_gain = 1).  The one-launch backward (dx != NULL)
+                                         refuses it: the front half + mmfm_rowgemm(ln_bwd = 2) is the ScaleNorm backward */
 } mmfm_mlp_desc;
 int mmfm_mlp_fwd(const mmfm_mlp_desc* d, mmfm_stream stream);
 int mmfm_mlp_bwd(const mmfm_mlp_desc* d, mmfm_stream stream);
@@ -366,6 +389,12 @@ int64_t mmfm_ln_linear_grad_workspace(int K);
 int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float* gamma, const float* beta, int N, int K,
                         float* dW, float* dbias, float* dgamma, float* dbeta, int accumulate_ln,
                         void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+/* The same for a ScaleNorm-fed linear (scalar gain g, one float; Gdb from x_hat = x / max(||x||, eps)):
+ *   dW = g * G;   dbias = db;   dg (+)= sum_{n,k} W[n][k] * G[n][k]      (accumulate selects +=)
+ * Deterministic (per-block partials summed in a fixed order by the last block).  Same workspace (size, zeroing, one per concurrent
+ * launch) as mmfm_ln_linear_grad. */
+int mmfm_sn_linear_grad(const float* Gdb, const float* W, const float* g, int N, int K, float* dW, float* dbias, float* dg,
+                        int accumulate, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,7 @@ class AttnDesc(C.Structure):
 
 class PrepEntry(C.Structure):
     _fields_ = [("W", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("bias", C.c_void_p), ("Wp", C.c_void_p),
-                ("WpT", C.c_void_p), ("bp", C.c_void_p), ("N", C.c_int), ("K", C.c_int), ("tile0", C.c_int), ("pad_", C.c_int),
+                ("WpT", C.c_void_p), ("bp", C.c_void_p), ("N", C.c_int), ("K", C.c_int), ("tile0", C.c_int), ("scalar_gain", C.c_int),
                 ("WpP", C.c_void_p), ("WpTP", C.c_void_p)]
 
 
@@ -75,7 +75,7 @@ class MlpDesc(C.Structure):
                 ("b_up", C.c_void_p), ("w_down", C.c_void_p), ("b_down", C.c_void_p), ("drop", Dropout), ("y", C.c_void_p),
                 ("ldy", C.c_int), ("xhat", C.c_void_p), ("rstd", C.c_void_p), ("dy", C.c_void_p), ("lddy", C.c_int),
                 ("w_down_t", C.c_void_p), ("w_up_t", C.c_void_p), ("t1", C.c_void_p), ("g", C.c_void_p), ("du", C.c_void_p),
-                ("dx", C.c_void_p), ("lddx", C.c_int), ("rotate", C.c_int)]
+                ("dx", C.c_void_p), ("lddx", C.c_int), ("rotate", C.c_int), ("scalenorm", C.c_int)]
 
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -95,6 +95,9 @@ _PROTOS = {
     "mmfm_layernorm_fwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _i, _i, _vp]),
     "mmfm_layernorm_bwd_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_layernorm_bwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _i64, _vp]),
+    "mmfm_scalenorm_fwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
+    "mmfm_scalenorm_bwd_workspace": (C.c_int64, [_i64, _i]),
+    "mmfm_scalenorm_bwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp, _i64, _vp]),
     "mmfm_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _vp]),
     "mmfm_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), _vp]),
     "mmfm_attn_keepbits_bytes": (C.c_int64, [_i, _i, _i, _i]),
@@ -117,6 +120,7 @@ _PROTOS = {
     "mmfm_mlp_bwd": (C.c_int, [C.POINTER(MlpDesc), _vp]),
     "mmfm_ln_linear_grad_workspace": (C.c_int64, [_i]),
     "mmfm_ln_linear_grad": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp]),
+    "mmfm_sn_linear_grad": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp]),
     "mmfm_r2_series": (C.c_int, [_vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _i, _i, _i, _vp, _vp]),
     "mmfm_bits_per_spike_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_bits_per_spike": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),

@@ -1,6 +1,9 @@
-// LayerNorm forward/backward (mmfm_layernorm_fwd / _bwd in include/mmfm.h).
+// LayerNorm and ScaleNorm forward/backward (mmfm_layernorm_fwd / _bwd, mmfm_scalenorm_fwd / _bwd in include/mmfm.h).
 // One 64-lane wavefront per row; H/64 elements per lane held in registers (H <= 1024, H % 4 == 0);
-// two-pass statistics in fp32 (mean, then centred variance) like torch's CPU/GPU kernels.
+// LayerNorm: two-pass statistics in fp32 (mean, then centred variance) like torch's CPU/GPU kernels.
+// ScaleNorm (SN = true, mm_utils.py:31-39): y = x * g / max(||x||, eps) with ONE scalar gain g; the same row code without the
+// mean, the clamped L2 norm in place of the standard deviation and g in place of gamma / beta.  The saved per-row statistic is
+// 1 / max(||x||, eps), negated for clamped rows (||x|| <= eps: the clamp passes no gradient to the norm).
 // HBM-bound: algorithmic bytes fwd = 2*R*H*sizeof(T) (+8R stats), bwd = 4*R*H*sizeof(T).
 #include "common.h"
 #include <algorithm>
@@ -21,7 +24,7 @@ __device__ __forceinline__ int64_t destitch_row(int64_t r, int L, int T, int64_t
 // waves than the extra rows in flight buy); backward 135 / 113 / 103 us at UNR = 1 / 2 / 4.  The kernels are
 // latency-bound at one row per wave (16 waves/CU x 1.5 KB in flight = 3 TB/s by Little's law, measured 137 us for
 // the [204800, 256] bf16 backward = 3.07 TB/s): all loads of UNR consecutive rows are issued before the first use.
-template <typename T, int NV, int UNR>
+template <typename T, int NV, int UNR, bool SN = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, T* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int64_t R, int H,
@@ -33,7 +36,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     for (int i = 0; i < NV; ++i) {
         const int c = i * 256 + lane * 4;
         g[i] = bt[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < H) { g[i] = *reinterpret_cast<const float4*>(gamma + c); bt[i] = *reinterpret_cast<const float4*>(beta + c); }
+        if (SN) g[i] = make_float4(gamma[0], gamma[0], gamma[0], gamma[0]);          // the scalar gain; no shift
+        else if (c < H) { g[i] = *reinterpret_cast<const float4*>(gamma + c); bt[i] = *reinterpret_cast<const float4*>(beta + c); }
     }
     const float invH = 1.f / (float)H;
     for (int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * UNR; row0 < R; row0 += (int64_t)gridDim.x * 4 * UNR) {
@@ -50,10 +54,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
         for (int u = 0; u < UNR; ++u) {
             const int64_t row = row0 + u;
             if (row >= R) break;                   // wave-uniform
-            float s = 0.f;
+            float mu = 0.f, rs;
+            if constexpr (!SN) {
+                float s = 0.f;
 #pragma unroll
-            for (int i = 0; i < NV; ++i) s += v[u][i].x + v[u][i].y + v[u][i].z + v[u][i].w;   // zero beyond H
-            const float mu = wave_sum(s) * invH;
+                for (int i = 0; i < NV; ++i) s += v[u][i].x + v[u][i].y + v[u][i].z + v[u][i].w;   // zero beyond H
+                mu = wave_sum(s) * invH;
+            }
             float q = 0.f;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
@@ -63,8 +70,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                     q += a * a + b * b + cc * cc + dd * dd;
                 }
             }
-            const float rs = rsqrtf(wave_sum(q) * invH + eps);
-            if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+            if constexpr (SN) {
+                const float n = sqrtf(wave_sum(q));
+                rs = 1.f / fmaxf(n, eps);
+                if (lane == 0) rstd[row] = n > eps ? rs : -rs;
+            } else {
+                rs = rsqrtf(wave_sum(q) * invH + eps);
+                if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+            }
             const int64_t orow = destitch_row(row, dsL, dsT, Btot);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
@@ -83,7 +96,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 }
 
 // dx = dres + rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat));  per-block partial dgamma/dbeta
-template <typename T, int NV, int UNR>
+// SN: dx = dres + rinv * (g*dy - xhat * sum(g*dy*xhat)), the sum dropped for clamped rows;  per-block partial dg = sum xhat . dy
+template <typename T, int NV, int UNR, bool SN = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, const T* dres, T* dx,
@@ -96,7 +110,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     for (int i = 0; i < NV; ++i) {
         ag[i] = ab[i] = g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         const int c = i * 256 + lane * 4;
-        if (c < H) g[i] = *reinterpret_cast<const float4*>(gamma + c);
+        if (SN) g[i] = make_float4(gamma[0], gamma[0], gamma[0], gamma[0]);
+        else if (c < H) g[i] = *reinterpret_cast<const float4*>(gamma + c);
     }
     const float invH = 1.f / (float)H;
     for (int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * UNR; row0 < R; row0 += (int64_t)gridDim.x * 4 * UNR) {
@@ -106,7 +121,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
         for (int u = 0; u < UNR; ++u) {
             const int64_t row = row0 + u;
             const bool ok = row < R;
-            mu[u] = ok ? mean[row] : 0.f;
+            mu[u] = (ok && !SN) ? mean[row] : 0.f;
             rs[u] = ok ? rstd[row] : 0.f;
             const int64_t yrow = ok ? destitch_row(row, dsL, dsT, Btot) : 0;
 #pragma unroll
@@ -126,6 +141,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
             if (row >= R) break;                   // wave-uniform
             float4 xh[NV];
             float s1 = 0.f, s2 = 0.f;
+            const bool clamped = SN && rs[u] < 0.f;
+            if (SN) rs[u] = fabsf(rs[u]);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = i * 256 + lane * 4;
@@ -141,7 +158,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                     s2 += dd.x * xh[i].x + dd.y * xh[i].y + dd.z * xh[i].z + dd.w * xh[i].w;
                 }
             }
-            const float m1 = wave_sum(s1) * invH, m2 = wave_sum(s2) * invH;
+            float m1, m2;
+            if constexpr (SN) { m1 = 0.f; m2 = clamped ? 0.f : wave_sum(s2); }
+            else { m1 = wave_sum(s1) * invH; m2 = wave_sum(s2) * invH; }
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = i * 256 + lane * 4;
@@ -155,6 +174,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                 }
             }
         }
+    }
+    if constexpr (SN) {
+        // dg: the lane's column partials, then the wave, then the four waves in a fixed order (deterministic)
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) s += ag[i].x + ag[i].y + ag[i].z + ag[i].w;
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        return;
     }
     // cross-wave reduction of the column partials, fixed order (deterministic)
 #pragma unroll
@@ -252,4 +282,43 @@ extern "C" int mmfm_layernorm_bwd(int dtype, const void* dy, const void* x, cons
         return mmfm_reduce_slabs(dgamma, (const float*)workspace, 2 * (int64_t)H, nblk, 2 * (int64_t)H, accumulate, stream);
     if (int rc = mmfm_reduce_slabs(dgamma, (const float*)workspace, H, nblk, 2 * (int64_t)H, accumulate, stream)) return rc;
     return mmfm_reduce_slabs(dbeta, (const float*)workspace + H, H, nblk, 2 * (int64_t)H, accumulate, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ScaleNorm
+extern "C" int mmfm_scalenorm_fwd(int dtype, const void* x, const float* g, void* y, float* rinv, int64_t R, int H, float eps,
+                                  mmfm_stream stream) {
+    MMFM_REQUIRE(x && g && y && rinv, "mmfm_scalenorm_fwd: null pointer");
+    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "mmfm_scalenorm_fwd: H=%d must be a multiple of 4, <= 1024", H);
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "mmfm_scalenorm_fwd: bad dtype %d", dtype);
+    dim3 grid(ln_blocks(R)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SN_FWD(TT, NVV, UU) hipLaunchKernelGGL((ln_fwd_kernel<TT, NVV, UU, true>), grid, block, 0, st, (const TT*)x, g, nullptr, (TT*)y, nullptr, rinv, R, H, eps, 0, 0)
+#define SN_FWD_T(TT) if (H <= 256) SN_FWD(TT, 1, 2); else if (H <= 512) SN_FWD(TT, 2, 2); else SN_FWD(TT, 4, 1)
+    if (dtype == MMFM_F32) { SN_FWD_T(float); } else { SN_FWD_T(uint16_t); }
+#undef SN_FWD_T
+#undef SN_FWD
+    MMFM_LAUNCH_CHECK("mmfm_scalenorm_fwd");
+    return 0;
+}
+
+extern "C" int64_t mmfm_scalenorm_bwd_workspace(int64_t R, int H) { (void)H; return (int64_t)ln_bwd_blocks(R) * sizeof(float); }
+
+extern "C" int mmfm_scalenorm_bwd(int dtype, const void* dy, const void* x, const float* rinv, const float* g, const void* dres, void* dx,
+                                  float* dg, int accumulate, int64_t R, int H, void* workspace, int64_t workspace_bytes,
+                                  mmfm_stream stream) {
+    MMFM_REQUIRE(dy && x && rinv && g && dx && dg, "mmfm_scalenorm_bwd: null pointer");
+    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "mmfm_scalenorm_bwd: H=%d must be a multiple of 4, <= 1024", H);
+    MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_scalenorm_bwd_workspace(R, H), "mmfm_scalenorm_bwd: workspace too small");
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "mmfm_scalenorm_bwd: bad dtype %d", dtype);
+    const int nblk = ln_bwd_blocks(R);
+    const size_t lds = (size_t)4 * 2 * H * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+#define SN_BWD(TT, NVV, UU) hipLaunchKernelGGL((ln_bwd_kernel<TT, NVV, UU, true>), dim3(nblk), dim3(256), lds, st, (const TT*)dy, (const TT*)x, nullptr, rinv, g, (const TT*)dres, (TT*)dx, (float*)workspace, R, H, 0, 0)
+#define SN_BWD_T(TT) if (H <= 256) SN_BWD(TT, 1, 4); else if (H <= 512) SN_BWD(TT, 2, 2); else SN_BWD(TT, 4, 1)
+    if (dtype == MMFM_F32) { SN_BWD_T(float); } else { SN_BWD_T(uint16_t); }
+#undef SN_BWD_T
+#undef SN_BWD
+    MMFM_LAUNCH_CHECK("mmfm_scalenorm_bwd");
+    // per-block partials [nblk] -> dg, fixed order
+    return mmfm_reduce_slabs(dg, (const float*)workspace, 1, nblk, 1, accumulate, stream);
 }

@@ -363,6 +363,8 @@ constexpr int NT8 = 512;
 // Measured and not kept (round 3): a producer / consumer split of the pair (one wave LayerNorm + up-projection + GELU, the other the
 // down-projection one ring step behind): 222 / 199 us with and without dropout against 216 / 206 - the producer's GELU (1,300 cycles
 // per tile, as long as 40 MFMAs) becomes the critical path and the consumer idles at the barrier.
+// NORM: the ln2 prologue, 1 = LayerNorm, 2 = ScaleNorm (mmfm_mlp_desc.scalenorm)
+template <int NORM>
 __global__ __launch_bounds__(NT8) void mlp_fwd8_kernel(const mmfm_mlp_desc d) {
     constexpr int NPAIR = 4;
     constexpr int RING_B = RINGA_SLOTS * CHUNK2;
@@ -406,7 +408,7 @@ __global__ __launch_bounds__(NT8) void mlp_fwd8_kernel(const mmfm_mlp_desc d) {
         const uint32_t row = wrow0 + m;
         opnd x[16];
         load_rows_lines<4>(stg, x, X, wrow0, ldxb, lane, m, h);
-        const float rs = ln_rows(x, d.eps);
+        const float rs = norm_rows<NORM>(x, d.eps);
         store_rows_lines<4, true>(stg, XH, wrow0, 512u, lane, m, h, x);       // role 1: zero-sized buffer, dropped
         st4f(RS, h == 0 ? row * 4u : 0xfffffff0u, rs);
         f32x16 Yh[4];
@@ -542,6 +544,59 @@ __global__ __launch_bounds__(256) void ln_linear_grad_kernel(const float* __rest
     }
 }
 
+// ScaleNorm twin: dW = g * G; dg = sum_{n,k} W * G over the whole matrix.  Same grid; every block writes its dW rows and a partial per
+// column into `part`, and the LAST block of the whole grid (one agent-scope ticket) sums the LG_SPLIT x K partials in a fixed order.
+__global__ __launch_bounds__(256) void sn_linear_grad_kernel(const float* __restrict__ Gdb, const float* __restrict__ W,
+                                                            const float* __restrict__ gp, int N, int K, float* __restrict__ dW,
+                                                            float* __restrict__ dbias, float* __restrict__ dg, int accumulate,
+                                                            float* __restrict__ part, unsigned int* __restrict__ ticket) {
+    __shared__ float red[8][32];
+    __shared__ int is_last;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, k = blockIdx.x * 32 + tx, sp = blockIdx.y;
+    const float* db = Gdb + (size_t)N * K;
+    const int rows_per = (N + LG_SPLIT - 1) / LG_SPLIT, n0 = sp * rows_per, n1 = min(N, n0 + rows_per);
+    const float g = gp[0];
+    float ag = 0.f;
+    if (k < K) {
+        for (int n = n0 + ty; n < n1; n += 8) {
+            const float Gv = Gdb[(size_t)n * K + k];
+            dW[(size_t)n * K + k] = g * Gv;
+            ag = fmaf(W[(size_t)n * K + k], Gv, ag);
+        }
+    }
+    red[ty][tx] = ag;
+    __syncthreads();
+    if (ty == 0 && k < K) {
+        float sg = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sg += red[i][tx];
+        part[(size_t)sp * K + k] = sg;
+    }
+    if (blockIdx.x == 0) for (int n = n0 + threadIdx.x; n < n1; n += 256) dbias[n] = db[n];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int prev = __hip_atomic_fetch_add(&ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = (prev == gridDim.x * gridDim.y - 1u);
+        if (is_last) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); ticket[0] = 0u; }      // re-armed for the next launch
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (!is_last) return;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < LG_SPLIT * K; i += 256) s += __builtin_nontemporal_load(&part[i]);
+    s = wave_sum(s);
+    float* wred = &red[0][0];
+    if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s = wred[0] + wred[1] + wred[2] + wred[3];
+        dg[0] = accumulate ? dg[0] + s : s;
+    }
+}
+
 int grid_for(int64_t R, int per_cu, int nw = NW) {
     const int64_t npass = (R + 32 * nw - 1) / (32 * nw);
     return (int)std::max<int64_t>(1, std::min<int64_t>(npass, 256 * per_cu));
@@ -568,8 +623,13 @@ extern "C" int mmfm_mlp_fwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
     static const int per_cu = [] { const char* e = getenv("MMFM_MLP_WG_PER_CU"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
     {
         constexpr int LDS_A = RINGA_SLOTS * CHUNK2 + 8 * STG_BYTES + 4 * 4096 + 768 * 4;
-        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel), LDS_A, "mmfm_mlp_fwd")) return rc;
-        hipLaunchKernelGGL(mlp_fwd8_kernel, dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
+        if (d.scalenorm) {
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<2>), LDS_A, "mmfm_mlp_fwd")) return rc;
+            hipLaunchKernelGGL(mlp_fwd8_kernel<2>, dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
+        } else {
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<1>), LDS_A, "mmfm_mlp_fwd")) return rc;
+            hipLaunchKernelGGL(mlp_fwd8_kernel<1>, dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
+        }
     }
     MMFM_LAUNCH_CHECK("mmfm_mlp_fwd");
     return 0;
@@ -586,6 +646,7 @@ extern "C" int mmfm_mlp_bwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
         MMFM_LAUNCH_CHECK("mmfm_mlp_bwd(front half)");
         return 0;
     }
+    MMFM_REQUIRE(!d.scalenorm, "mmfm_mlp_bwd: the one-launch backward has no ScaleNorm epilogue (front half, then mmfm_rowgemm ln_bwd = 2)");
     constexpr int LDS_B = RINGA_SLOTS * CHUNK + 2 * NW * STG_BYTES + 512 * 4 + NW * 4 * STG_BYTES;
     if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_kernel), LDS_B, "mmfm_mlp_bwd")) return rc;
     hipLaunchKernelGGL(mlp_bwd_kernel, dim3(grid_for(d.R, per_cu)), dim3(NT), LDS_B, (hipStream_t)stream, d);
@@ -605,5 +666,17 @@ extern "C" int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float
     hipLaunchKernelGGL(ln_linear_grad_kernel, dim3(cdiv(K, 32), LG_SPLIT), dim3(256), 0, (hipStream_t)stream, Gdb, W, gamma, beta, N, K, dW, dbias, dgamma,
                        dbeta, accumulate_ln, part, ticket);
     MMFM_LAUNCH_CHECK("mmfm_ln_linear_grad");
+    return 0;
+}
+
+extern "C" int mmfm_sn_linear_grad(const float* Gdb, const float* W, const float* g, int N, int K, float* dW, float* dbias, float* dg,
+                                   int accumulate, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(Gdb && W && g && dW && dbias && dg && N > 0 && K > 0, "mmfm_sn_linear_grad: null argument");
+    MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_ln_linear_grad_workspace(K), "mmfm_sn_linear_grad: workspace too small (must be ZEROED once before first use)");
+    float* part = reinterpret_cast<float*>(workspace);
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(part + (size_t)LG_SPLIT * 2 * K);
+    hipLaunchKernelGGL(sn_linear_grad_kernel, dim3(cdiv(K, 32), LG_SPLIT), dim3(256), 0, (hipStream_t)stream, Gdb, W, g, N, K, dW, dbias, dg,
+                       accumulate, part, ticket);
+    MMFM_LAUNCH_CHECK("mmfm_sn_linear_grad");
     return 0;
 }

@@ -497,6 +497,46 @@ __device__ __forceinline__ float ln_rows(opnd (&x)[16], float eps) {
     }
     return rs;
 }
+// ScaleNorm without the gain (mm_utils.py:31-39; the scalar g is folded into the prepared weights): x <- x / max(||x||, eps);
+// returns 1 / max(||x||, eps), NEGATED when the norm was clamped (the backward then drops the projection term).
+__device__ __forceinline__ float sn_rows(opnd (&x)[16], float eps) {
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float f[8]; unpack8f(x[i], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q += f[j] * f[j];
+    }
+    const float n = sqrtf(xhalf(q));
+    const float rs = 1.f / fmaxf(n, eps);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float f[8]; unpack8f(x[i], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] *= rs;
+        x[i] = pack8o(f);
+    }
+    return n > eps ? rs : -rs;
+}
+// the row prologue of a norm-fed product: NORM 1 = LayerNorm, 2 = ScaleNorm (mmfm_rowgemm_desc.ln)
+template <int NORM>
+__device__ __forceinline__ float norm_rows(opnd (&x)[16], float eps) {
+    if constexpr (NORM == 2) return sn_rows(x, eps);
+    else return ln_rows(x, eps);
+}
+// the row statistics of the norm backward y = rs * (v - s1 - x_hat * s2) from the in-lane sums s1 = sum v, s2 = sum v * x_hat over
+// `nfeat` features (after the lane exchange): LayerNorm divides both by the width; ScaleNorm has no s1, keeps s2 as a sum and drops it
+// for a clamped row (rs < 0 as saved by sn_rows), leaving y = |rs| * v.
+template <int NORM>
+__device__ __forceinline__ void norm_bwd_stats(float& s1, float& s2, float& rs) {
+    if constexpr (NORM == 2) {
+        s1 = 0.f;
+        if (rs < 0.f) { rs = -rs; s2 = 0.f; }
+    } else {
+        s1 *= 1.f / 256.f;
+        s2 *= 1.f / 256.f;
+    }
+}
 
 // ---- dropout of the fused MLP kernels (forward epilogue, backward prologue): a lane owns ONE token row, so the hash is two-level like the
 // attention kernels' (attn_common.h Drop16): a full-strength 2 x 32-bit key per ROW, made once per row pass, and a 7-instruction

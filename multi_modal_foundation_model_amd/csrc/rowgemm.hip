@@ -26,7 +26,7 @@ constexpr int BIAS_MAX = 1024;                      // floats of bias kept in LD
 
 // NWV waves per workgroup (8 = two per SIMD wherever the registers allow: the barrier / LDS-write overhead of a chunk is
 // paid once per 256 rows instead of 128 and a SIMD's MFMA pipe is fed by two waves), 32 rows each
-template <int KP, bool LN, bool NTS, int NWV>
+template <int KP, int LN, bool NTS, int NWV>
 __global__ __launch_bounds__(NWV * 64, (KP == 1 ? 2 : 1)) void rowgemm_kernel(const mmfm_rowgemm_desc d) {
     constexpr int NT = NWV * 64, NW = NWV;
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + NW * STG_BYTES + BIAS_MAX * 4];
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(NWV * 64, (KP == 1 ? 2 : 1)) void rowgemm_kernel(co
         const bool live = wrow0 < (uint32_t)d.R;          // wave-uniform: a wave without rows only keeps the ring's barriers
         opnd x[16 * KP];
         if (live) load_rows_lines<4 * KP>(stg, x, X, wrow0, ldxb, lane, m, h);
-        if constexpr (LN) if (live) {
-            const float rs = ln_rows(x, d.eps);
+        if constexpr (LN != 0) if (live) {
+            const float rs = norm_rows<LN>(x, d.eps);
             store_rows_lines<4, true>(stg, XH, wrow0, 512u, lane, m, h, x);
             st4f(RS, h == 0 ? (wrow0 + m) * 4u : 0xfffffff0u, rs);
         }
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(NWV * 64, (KP == 1 ? 2 : 1)) void rowgemm_kernel(co
 // NPV = N / 64 when known at compile time (4: unrolled, residual allowed), 0 = runtime.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
-template <bool LN, bool NTS, int NPV>
+template <int LN, bool NTS, int NPV>
 __global__ __launch_bounds__(256, 2) void rowgemm_a_kernel(const mmfm_rowgemm_desc d) {
     constexpr int NT = 256, NW = 4, RING_B = RINGA_SLOTS * CHUNK;
     extern __shared__ __attribute__((aligned(16))) char smem[];       // RING_B + NW * STG_BYTES + BIAS_MAX * 4
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_a_kernel(const mmfm_rowgemm_de
         Lines res[NPV ? NPV : 1];
         if (live) {
             load_rows_lines<4>(stg, x, X, wrow0, ldxb, lane, m, h);
-            if constexpr (LN) {
-                const float rs = ln_rows(x, d.eps);
+            if constexpr (LN != 0) {
+                const float rs = norm_rows<LN>(x, d.eps);
                 store_rows_lines<4, true>(stg, XH, wrow0, 512u, lane, m, h, x);
                 st4f(RS, h == 0 ? (wrow0 + m) * 4u : 0xfffffff0u, rs);
             }
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void rowgemm_a_kernel(const mmfm_rowgemm_de
 // ------------------------------------------------------------------------------------------------ dX + LayerNorm backward
 // v = x . W^T (N = 256: the gradient wrt x_hat of the LayerNorm that fed the forward linear; W = prepared W'^T);
 // y = dres + rstd * (v - mean(v) - x_hat * mean(v * x_hat))
-template <int KP>
+template <int KP, int NORM>
 __global__ __launch_bounds__(NT) void rowgemm_lnbwd_kernel(const mmfm_rowgemm_desc d) {
     // + a 16 KB per-wave stash of the pass's x_hat rows (as in the MLP backward): the statistics loop fetches them once, the output
     // loop reads them from LDS instead of putting a second dependent round trip per line pair into every pass
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_kernel(const mmfm_rowgemm_de
         const uint32_t wrow0 = (uint32_t)(((int64_t)(blockIdx.x + (int64_t)pi * gridDim.x) * NW + wave) * 32);
         opnd x[16 * KP];
         load_rows_lines<4 * KP>(stg, x, X, wrow0, ldxb, lane, m, h);
-        const float rs = ld4f(RS, (wrow0 + m) * 4u);
+        float rs = ld4f(RS, (wrow0 + m) * 4u);
         f32x16 acc[8];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -266,8 +266,9 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_kernel(const mmfm_rowgemm_de
                 for (int i = 0; i < 16; ++i) { s1 += acc[2 * tp + j][i]; s2 = fmaf(acc[2 * tp + j][i], xt[i], s2); }
             }
         }
-        s1 = xhalf(s1) * (1.f / 256.f);
-        s2 = xhalf(s2) * (1.f / 256.f);
+        s1 = xhalf(s1);
+        s2 = xhalf(s2);
+        norm_bwd_stats<NORM>(s1, s2, rs);
         Lines rl4[4];                                   // the residual-gradient lines, requested together (the operand registers are dead here)
 #pragma unroll
         for (int tp = 0; tp < 4; ++tp) rl4[tp] = fetch_lines(RES, wrow0, ldrb, 128u * tp, lane);
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_kernel(const mmfm_rowgemm_de
 // the prefetch), so the loop issues nothing but ring requests and MFMAs.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
-template <int KP>
+template <int KP, int NORM>
 __global__ __launch_bounds__(NT) void rowgemm_lnbwd_a_kernel(const mmfm_rowgemm_desc d) {
     constexpr int RING_B = RINGA_SLOTS * CHUNK;
     extern __shared__ __attribute__((aligned(16))) char smem[];       // RING_B + NW * STG_BYTES + NW * 4 * STG_BYTES
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_a_kernel(const mmfm_rowgemm_
 #pragma unroll
             for (int tp = 0; tp < 4; ++tp) stage_lines(xstash + tp * STG_BYTES, xl[tp], lane);
         }
-        const float rs = ld4f(RS, (wrow0 + m) * 4u);
+        float rs = ld4f(RS, (wrow0 + m) * 4u);
         f32x16 acc[8];
 #pragma unroll
         for (int tt = 0; tt < 8; ++tt) {
@@ -360,8 +361,9 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_a_kernel(const mmfm_rowgemm_
                 for (int i = 0; i < 16; ++i) { s1 += acc[2 * tp + j][i]; s2 = fmaf(acc[2 * tp + j][i], xt[i], s2); }
             }
         }
-        s1 = xhalf(s1) * (1.f / 256.f);
-        s2 = xhalf(s2) * (1.f / 256.f);
+        s1 = xhalf(s1);
+        s2 = xhalf(s2);
+        norm_bwd_stats<NORM>(s1, s2, rs);
         Lines rl4[4];                                   // the residual-gradient lines, requested together (the operand registers are dead here)
 #pragma unroll
         for (int tp = 0; tp < 4; ++tp) rl4[tp] = fetch_lines(RES, wrow0, ldrb, 128u * tp, lane);
@@ -396,7 +398,7 @@ __global__ __launch_bounds__(NT) void rowgemm_lnbwd_a_kernel(const mmfm_rowgemm_
 // flight) -> two waves per SIMD fit where the one-wave version needed 512 registers and spent its time copying operands out
 // of the accumulator file.  A 32 KB chunk = the two groups' weight tiles of one (piece, tile) step; the row statistics of the
 // LayerNorm backward are summed across the pair through LDS behind one extra barrier per pass.
-template <int KP>
+template <int KP, int NORM>
 __global__ __launch_bounds__(512) void rowgemm_lnbwd8_kernel(const mmfm_rowgemm_desc d) {
     constexpr int NT = 512, NW = 8, NPAIR = 4;
     __shared__ __attribute__((aligned(16))) char smem[2 * CHUNK2 + NW * STG_BYTES + NW * 32 * 8];
@@ -466,9 +468,10 @@ __global__ __launch_bounds__(512) void rowgemm_lnbwd8_kernel(const mmfm_rowgemm_
         if (h == 0) exch[wave * 32 + m] = make_float2(s1, s2);
         __syncthreads();
         const float2 o2 = exch[(wave ^ 4) * 32 + m];
-        s1 = (s1 + o2.x) * (1.f / 256.f);
-        s2 = (s2 + o2.y) * (1.f / 256.f);
-        const float rs = ld4f(RS, (wrow0 + m) * 4u);
+        s1 = s1 + o2.x;
+        s2 = s2 + o2.y;
+        float rs = ld4f(RS, (wrow0 + m) * 4u);
+        norm_bwd_stats<NORM>(s1, s2, rs);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const Lines rl = fetch_lines(RES, wrow0, ldrb, 128u * (2 * half + q), lane);
@@ -489,7 +492,8 @@ __global__ __launch_bounds__(512) void rowgemm_lnbwd8_kernel(const mmfm_rowgemm_
 
 // ------------------------------------------------------------------------------------------------ weight preparation
 // One block per (entry, 32-row tile of W): Wp = bf16(W * gamma[k]) [N][K], WpT = its transpose [K][N] (WpP / WpTP: the same, unit-permuted),
-// bp[n] = bias[n] + sum_k W[n][k] * beta[k]  (the LayerNorm affine folded into the linear it feeds).
+// bp[n] = bias[n] + sum_k W[n][k] * beta[k]  (the LayerNorm affine folded into the linear it feeds).  scalar_gain: gamma is ONE float g
+// (a ScaleNorm's gain) applied to every k, no beta: Wp = bf16(g * W), bp = bias.
 __global__ __launch_bounds__(256) void prep_weights_kernel(const mmfm_prep_entry* __restrict__ E, int ne) {
     __shared__ float tile[32][33];
     int e = 0;
@@ -504,10 +508,11 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const mmfm_prep_entry
     // unit-permuted position of element i of a row: 4-element (8-byte) units 1 and 2 of every 16 swap places
     auto perm = [](int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); };
     float dot[4] = {0.f, 0.f, 0.f, 0.f};
+    const float gs = en.scalar_gain ? en.gamma[0] : 1.f;
     for (int k0 = 0; k0 < en.K; k0 += 32) {
         const int k = k0 + tx;
-        const float g = (en.gamma && k < en.K) ? en.gamma[k] : 1.f;
-        const float bt = (en.beta && k < en.K) ? en.beta[k] : 0.f;
+        const float g = en.scalar_gain ? gs : (en.gamma && k < en.K) ? en.gamma[k] : 1.f;
+        const float bt = (en.beta && k < en.K && !en.scalar_gain) ? en.beta[k] : 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int n = n0 + ty + 8 * j;
@@ -561,7 +566,8 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
     MMFM_REQUIRE(al16(d.x) && al16(d.w) && al16(d.y) && al16(d.residual) && al16(d.xhat) && al16(d.bwd_xhat) && al16(d.bias),
                  "mmfm_rowgemm: operands must be 16-byte aligned");
     MMFM_REQUIRE(!d.residual || (d.ldr % 8 == 0 && d.ldr >= d.N), "mmfm_rowgemm: ldr %d", d.ldr);
-    MMFM_REQUIRE(!d.ln || d.K == 256, "mmfm_rowgemm: the LayerNorm prologue needs K = 256");
+    MMFM_REQUIRE(d.ln >= 0 && d.ln <= 2 && d.ln_bwd >= 0 && d.ln_bwd <= 2, "mmfm_rowgemm: ln = %d, ln_bwd = %d (0, 1 = LayerNorm, 2 = ScaleNorm)", d.ln, d.ln_bwd);
+    MMFM_REQUIRE(!d.ln || d.K == 256, "mmfm_rowgemm: the norm prologue needs K = 256");
     const int64_t maxld = std::max<int64_t>(std::max(d.ldx, d.ldy), std::max(d.ldr, 256));
     MMFM_REQUIRE((d.R + 128) * maxld * 2 < (int64_t)1 << 31, "mmfm_rowgemm: tensors beyond 2 GiB are not addressable by the 32-bit buffer offsets");
     MMFM_REQUIRE(d.N <= BIAS_MAX, "mmfm_rowgemm: N = %d > %d", d.N, BIAS_MAX);
@@ -574,21 +580,25 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
     hipStream_t st = (hipStream_t)stream;
     if (d.ln_bwd) {
         MMFM_REQUIRE(d.N == 256 && d.bwd_xhat && d.bwd_rstd && !d.ln && !d.bias, "mmfm_rowgemm: ln_bwd needs N = 256, x_hat, rstd, no bias/ln");
+        const bool sn = d.ln_bwd == 2;
         if (d.K == 256) {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1, 4)), block(512);      // 4 row tiles (wave pairs) per pass
-            hipLaunchKernelGGL(rowgemm_lnbwd8_kernel<1>, grid, block, 0, st, d);
+            if (sn) hipLaunchKernelGGL((rowgemm_lnbwd8_kernel<1, 2>), grid, block, 0, st, d);
+            else hipLaunchKernelGGL((rowgemm_lnbwd8_kernel<1, 1>), grid, block, 0, st, d);
         } else {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1)), block(NT);
             static const int ring_env = [] { const char* e = getenv("MMFM_ROWGEMM_RING"); return (e ? atoi(e) : 3) & 2; }();   // bit 1 clear: register-staged ring
             constexpr int LDS_L = RINGA_SLOTS * CHUNK + NW * STG_BYTES + NW * 4 * STG_BYTES;
-            if (ring_env && d.K == 512) {
-                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_lnbwd_a_kernel<2>), LDS_L, "mmfm_rowgemm")) return rc;
-                hipLaunchKernelGGL(rowgemm_lnbwd_a_kernel<2>, grid, block, LDS_L, st, d);
-            } else if (ring_env) {
-                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_lnbwd_a_kernel<3>), LDS_L, "mmfm_rowgemm")) return rc;
-                hipLaunchKernelGGL(rowgemm_lnbwd_a_kernel<3>, grid, block, LDS_L, st, d);
-            } else if (d.K == 512) hipLaunchKernelGGL(rowgemm_lnbwd_kernel<2>, grid, block, 0, st, d);
-            else hipLaunchKernelGGL(rowgemm_lnbwd_kernel<3>, grid, block, 0, st, d);
+#define LNB_A(KP, NORM)                                                                                                     \
+            {                                                                                                               \
+                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_lnbwd_a_kernel<KP, NORM>), LDS_L, "mmfm_rowgemm")) return rc; \
+                hipLaunchKernelGGL((rowgemm_lnbwd_a_kernel<KP, NORM>), grid, block, LDS_L, st, d);                           \
+            }
+            if (ring_env && d.K == 512) { if (sn) LNB_A(2, 2) else LNB_A(2, 1) }
+            else if (ring_env) { if (sn) LNB_A(3, 2) else LNB_A(3, 1) }
+            else if (d.K == 512) { if (sn) hipLaunchKernelGGL((rowgemm_lnbwd_kernel<2, 2>), grid, block, 0, st, d); else hipLaunchKernelGGL((rowgemm_lnbwd_kernel<2, 1>), grid, block, 0, st, d); }
+            else { if (sn) hipLaunchKernelGGL((rowgemm_lnbwd_kernel<3, 2>), grid, block, 0, st, d); else hipLaunchKernelGGL((rowgemm_lnbwd_kernel<3, 1>), grid, block, 0, st, d); }
+#undef LNB_A
         }
     } else {
 #define RG_LAUNCH(KP, LN)                                                                                   \
@@ -596,7 +606,7 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
     else hipLaunchKernelGGL((rowgemm_kernel<KP, LN, false, 4>), grid, block, 0, st, d);
         if (d.K != 256) {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1, 4)), block(256);
-            if (d.K == 512) { RG_LAUNCH(2, false) } else { RG_LAUNCH(3, false) }
+            if (d.K == 512) { RG_LAUNCH(2, 0) } else { RG_LAUNCH(3, 0) }
         } else {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 2, 4)), block(256);
             static const int ring_env = [] { const char* e = getenv("MMFM_ROWGEMM_RING"); return (e ? atoi(e) : 3) & 1; }();   // bit 0 clear: register-staged ring
@@ -614,15 +624,16 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
                 static const int nsplit_env = [] { const char* e = getenv("MMFM_ROWGEMM_NSPLIT"); return e ? atoi(e) : 1; }();
                 const int ny = (nsplit_env && npass < 128) ? (int)std::max<int64_t>(1, std::min<int64_t>(np_all, 512 / npass)) : 1;
                 if (d.residual) {                                  // N = 256: four pairs in one block, or one pair in each of four
-                    if (ny >= 4) { grid.y = 4; RGA_LAUNCH2(false, 1) } else { RGA_LAUNCH2(false, 4) }
+                    if (ny >= 4) { grid.y = 4; RGA_LAUNCH2(0, 1) } else { RGA_LAUNCH2(0, 4) }
                 } else {
                     grid.y = (unsigned)((np_all + (np_all + ny - 1) / ny - 1) / ((np_all + ny - 1) / ny));      // blocks of ceil(np_all / ny) pairs
-                    if (d.ln) RGA_LAUNCH2(true, 0)
-                    else RGA_LAUNCH2(false, 0)
+                    if (d.ln == 2) RGA_LAUNCH2(2, 0)
+                    else if (d.ln) RGA_LAUNCH2(1, 0)
+                    else RGA_LAUNCH2(0, 0)
                 }
 #undef RGA_LAUNCH2
 #undef RGA_LAUNCH
-            } else if (d.ln) { RG_LAUNCH(1, true) } else { RG_LAUNCH(1, false) }
+            } else if (d.ln == 2) { RG_LAUNCH(1, 2) } else if (d.ln) { RG_LAUNCH(1, 1) } else { RG_LAUNCH(1, 0) }
         }
 #undef RG_LAUNCH
     }

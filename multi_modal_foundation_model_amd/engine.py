@@ -29,6 +29,7 @@ from . import _lib as L
 from . import ops as K
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
+BLOCK_NORMS = ("ln1", "ln2", "query_norm", "context_norm")     # the sites `use_scalenorm` switches (encoder_norm / decoder_norm stay LayerNorm)
 
 
 @dataclass
@@ -48,6 +49,7 @@ class EngineConfig:
     causal_mask: bool
     mods: List[Tuple[str, int]]                 # (name, channels) in avail_mod order
     loss_kind: Dict[str, int] = field(default_factory=lambda: dict(LOSS_KIND))
+    norm: str = "layernorm"                     # the transformer blocks' norms: "layernorm" or "scalenorm" (use_scalenorm: true)
 
     @staticmethod
     def from_model_config(mc, mods) -> "EngineConfig":
@@ -56,8 +58,8 @@ class EngineConfig:
         for k in ("hidden_size", "n_heads", "inter_size", "dropout"):
             if et[k] != dtf[k]:
                 raise ValueError(f"encoder/decoder transformer.{k} differ ({et[k]} vs {dtf[k]}): not supported")
-        if et["use_scalenorm"] or dtf["use_scalenorm"]:
-            raise NotImplementedError("use_scalenorm=true has no HIP kernel (mm.yaml default is false)")
+        if bool(et["use_scalenorm"]) != bool(dtf["use_scalenorm"]):
+            raise NotImplementedError("use_scalenorm differs between encoder and decoder: not built")
         if et["act"] != "gelu" or ee["act"] != "softsign":
             raise NotImplementedError("only act=gelu (transformer) / softsign (embedder) are built")
         scale = et["hidden_size"] ** 0.5 if ee["scale"] is None else ee["scale"]
@@ -65,7 +67,8 @@ class EngineConfig:
                             n_enc=et["n_layers"], n_dec=dtf["n_layers"], max_F=ee["max_F"], mult=ee["mult"],
                             n_modality=ee["n_modality"], embed_scale=float(scale), embed_dropout=ee["dropout"],
                             dropout=et["dropout"], sep_mask=bool(mc["decoder"]["decoder_sep_mask"]),
-                            causal_mask=bool(mc["decoder"]["decoder_causal_mask"]), mods=list(mods))
+                            causal_mask=bool(mc["decoder"]["decoder_causal_mask"]), mods=list(mods),
+                            norm="scalenorm" if et["use_scalenorm"] else "layernorm")
 
 
 def _align(n, a=8):
@@ -76,6 +79,8 @@ class ParamLayout:
     """name -> (offset, shape) in the flat buffer; `groups` are the DDP buckets' atoms."""
 
     def __init__(self, cfg: EngineConfig):
+        if cfg.norm not in ("layernorm", "scalenorm"):
+            raise ValueError(f"EngineConfig.norm = {cfg.norm!r}")
         H, I = cfg.hidden, cfg.inter
         self.entries: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self.alias: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
@@ -97,6 +102,9 @@ class ParamLayout:
             pad(); add(prefix + ".weight", (o, i)); pad(); add(prefix + ".bias", (o,))
 
         def ln(prefix):
+            if cfg.norm == "scalenorm" and prefix.rsplit(".", 1)[-1] in BLOCK_NORMS:
+                pad(); add(prefix + ".scale", ())          # ScaleNorm's 0-dim gain, its own aligned slot (mm_utils.py:31-35)
+                return
             pad(); add(prefix + ".weight", (H,)); pad(); add(prefix + ".bias", (H,))
 
         def fused(prefix, names, alias):
@@ -186,6 +194,7 @@ class Engine:
         self.code = L.F32 if dtype == "fp32" else L.BF16
         self.layout = ParamLayout(cfg)
         n = self.layout.n
+        self.scalenorm = cfg.norm == "scalenorm"
         self.P = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.G = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.Pw = self.P if dtype == "fp32" else torch.zeros(n, dtype=torch.bfloat16, device=self.device)
@@ -254,6 +263,10 @@ class Engine:
 
     def Gv(self, name):
         return self.layout.view(self.G, name)
+
+    def is_sn(self, lnname):
+        """True where the norm named `lnname` is a ScaleNorm (the block norms of a use_scalenorm model)."""
+        return self.scalenorm and lnname.rsplit(".", 1)[-1] in BLOCK_NORMS
 
     # ------------------------------------------------------------------ buffers
     def _select_pool(self, B, T):
@@ -335,7 +348,8 @@ class Engine:
 
     def _build_prep(self):
         """Prepared weights of the fused path: per LayerNorm-fed linear Wp = bf16(W * gamma), WpT, bp = b + W beta
-        (mmfm_prep_weights); per plain linear only the bf16 transpose (the dX products read K-contiguous rows)."""
+        (mmfm_prep_weights); per ScaleNorm-fed linear Wp = bf16(g * W), bp = b (scalar gain); per plain linear only the bf16
+        transpose (the dX products read K-contiguous rows)."""
         if getattr(self, "_prep", None) is not None:
             return self._prep
         c = self.cfg
@@ -372,8 +386,11 @@ class Engine:
                 e["WpP"] = v["WpP"] = Wpm[oP:oP + N * Kd].view(N, Kd)
                 oP += N * Kd
             if ln:
-                e.update(gamma=self.Pf(ln + ".weight"), beta=self.Pf(ln + ".bias"), bias=self.Pf(w + ".bias"),
-                         Wp=Wp[oW:oW + N * Kd].view(N, Kd), bp=bp[ob:ob + N])
+                if self.is_sn(ln):
+                    e.update(gamma=self.Pf(ln + ".scale"), scalar_gain=True)
+                else:
+                    e.update(gamma=self.Pf(ln + ".weight"), beta=self.Pf(ln + ".bias"))
+                e.update(bias=self.Pf(w + ".bias"), Wp=Wp[oW:oW + N * Kd].view(N, Kd), bp=bp[ob:ob + N])
                 oW += N * Kd
                 ob += N
                 v.update(Wp=e["Wp"], bp=e["bp"])
@@ -549,10 +566,17 @@ class Engine:
                     K.gemm(dY, self.W(wname + ".weight"), dX, Mr, Kd, N, lda=N, ldb=Kd, ldc=Kd, b_kcontig=0, dtype=code, plan=plan, **kw)
 
         def ln_f(plan, X, name, Y, tag, **kw):
+            if self.is_sn(name):
+                K.scalenorm_fwd(X, self.Pf(name + ".scale"), Y, buf(tag + "/rstd", (R,), f32), R, H, plan=plan)
+                return
             K.layernorm_fwd(X, self.Pf(name + ".weight"), self.Pf(name + ".bias"), Y, buf(tag + "/mean", (R,), f32),
                             buf(tag + "/rstd", (R,), f32), R, H, plan=plan, **kw)
 
         def ln_b(plan, dY, X, name, tag, dres, dX, **kw):
+            if self.is_sn(name):       # (ws/ln, sized for the LayerNorm backward, covers the ScaleNorm's per-block partials)
+                K.scalenorm_bwd(dY, X, self.b[tag + "/rstd"], self.Pf(name + ".scale"), dres, dX, self.Gv(name + ".scale"), R, H, ws_ln,
+                                plan=plan)
+                return
             K.layernorm_bwd(dY, X, self.b[tag + "/mean"], self.b[tag + "/rstd"], self.Pf(name + ".weight"), dres, dX,
                             self.Gv(name + ".weight"), self.Gv(name + ".bias"), R, H, ws_ln, plan=plan, **kw)
 
@@ -584,8 +608,8 @@ class Engine:
             ws_lng = self.b["ws/lng"]
 
         def ln_lin(plan, Xin, lnname, wname, Yout, N, tag, residual=None, alias=None):
-            """LayerNorm + the linear it feeds in one launch; x_hat / rstd saved for the backward when training.
-            alias = tag of an earlier call on the SAME input: x_hat / rstd do not depend on the LayerNorm's affine (it is folded
+            """LayerNorm (or ScaleNorm) + the linear it feeds in one launch; x_hat / rstd saved for the backward when training.
+            alias = tag of an earlier call on the SAME input: x_hat / rstd do not depend on the norm's affine / gain (it is folded
             into the prepared weights), so the earlier call's saved tensors serve this site's backward too and nothing is stored."""
             pw = prep["v"][wname]
             if alias is not None and grad:
@@ -594,10 +618,20 @@ class Engine:
             else:
                 xh = buf(tag + "/xh", (R, H)) if grad else None
                 rs = buf(tag + "/rs", (R,), f32) if grad else None
-            K.rowgemm(Xin, pw["Wp"], Yout, R, N, H, bias=pw["bp"], ln=True, xhat=xh, rstd=rs, residual=residual,
+            K.rowgemm(Xin, pw["Wp"], Yout, R, N, H, bias=pw["bp"], ln=2 if self.is_sn(lnname) else 1, xhat=xh, rstd=rs, residual=residual,
                       ldr=H if residual is not None else 0, stream_out=True, plan=plan)
 
         late_lng: list = []
+
+        def lin_norm_grad(plan, Gdb, wname, lnname, N):
+            """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]."""
+            if self.is_sn(lnname):
+                K.sn_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".scale"), N, H, self.Gv(wname + ".weight"),
+                                 self.Gv(wname + ".bias"), self.Gv(lnname + ".scale"), ws_lng, plan=plan)
+                return
+            K.ln_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".weight"), self.Pf(lnname + ".bias"), N, H,
+                             self.Gv(wname + ".weight"), self.Gv(wname + ".bias"), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
+                             ws_lng, plan=plan)
 
         def dlin_ln(plan, dYt, tag, wname, lnname, N):
             """Gradients of a LayerNorm-fed linear and of that LayerNorm's affine from G = dY^T x_hat (mmfm_ln_linear_grad)."""
@@ -636,14 +670,12 @@ class Engine:
                 K.gemm(dYt, xh, slab, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
                        slab_stride=stride, dtype=code, c_f32=1, colsum=slab.data_ptr() + 4 * N * H, plan=plan)
                 K.reduce_slabs(gdb, slab, N * H + N, S, stride, plan=plan)
-            K.ln_linear_grad(gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".weight"), self.Pf(lnname + ".bias"), N, H,
-                             self.Gv(wname + ".weight"), self.Gv(wname + ".bias"), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
-                             ws_lng, plan=plan)
+            lin_norm_grad(plan, gdb, wname, lnname, N)
 
-        def dx_ln(plan, dYt, Kd, tag, wname, dres, dXout):
-            """dX of a LayerNorm-fed linear with the LayerNorm backward (and the residual gradient) in its epilogue."""
+        def dx_ln(plan, dYt, Kd, tag, wname, lnname, dres, dXout):
+            """dX of a norm-fed linear with the norm's backward (and the residual gradient) in its epilogue."""
             K.rowgemm(dYt, prep["v"][wname]["WpT"], dXout, R, H, Kd, ldw=Kd, residual=dres, ldr=H if dres is not None else 0,
-                      ln_bwd=True, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
+                      ln_bwd=2 if self.is_sn(lnname) else 1, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
 
         enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
         dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)   # mm.py:178-194
@@ -694,7 +726,7 @@ class Engine:
                 d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=prep["v"][p + ".mlp.down_proj"]["WpP"],
                                 b_down=self.Pf(p + ".mlp.down_proj.bias"), drop=self._drop(tag + "/mlpdrop", dp), y=Xb,
                                 xhat=buf(tag + "/ln2/xh", (R, H)) if grad else None,
-                                rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None)
+                                rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None, scalenorm=self.is_sn(p + ".ln2"))
                 K.mlp_fwd(d_, plan=plan)
                 return Xb
             h, u, g = buf(tag + "/h2", (R, H)), buf(tag + "/u", (R, I)), buf(tag + "/g", (R, I))
@@ -760,9 +792,7 @@ class Engine:
                 K.reduce_slabs_multi(list(pend), self.device, plan=cur)
                 pend.clear()
             for g_site, wname, lnname, N in late_lng:
-                K.ln_linear_grad(g_site, self.Pf(wname + ".weight"), self.Pf(lnname + ".weight"), self.Pf(lnname + ".bias"), N, H,
-                                 self.Gv(wname + ".weight"), self.Gv(wname + ".bias"), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
-                                 ws_lng, plan=cur)
+                lin_norm_grad(cur, g_site, wname, lnname, N)
             late_lng.clear()
             slabm_off[0] = 0                  # the reduction has consumed the regions (stream order): the next segment reuses them
             bwd.append((name, cur))
@@ -785,13 +815,14 @@ class Engine:
             if F_MLP:
                 pu, pdn = prep["v"][p + ".mlp.up_proj"], prep["v"][p + ".mlp.down_proj"]
                 t1b, gb, dub = buf("d/t1m", (R, H)), buf("d/g", (R, I)), buf("d/du", (R, I))
-                split = os.environ.get("MMFM_MLP_BWD_SPLIT", "1") == "1"   # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step
+                # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step.  A ScaleNorm ln2 always splits (the one-launch kernel has no ScaleNorm epilogue)
+                split = os.environ.get("MMFM_MLP_BWD_SPLIT", "1") == "1" or self.is_sn(p + ".ln2")
                 d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=self._drop(tag + "/mlpdrop", dp), xhat=self.b[tag + "/ln2/xh"],
                                 rstd=self.b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
                                 dx=None if split else dS)
                 K.mlp_bwd(d_, plan=plan)
                 if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
-                    dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", dS, dS)
+                    dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
                 dlin(plan, t1b, gb, p + ".mlp.down_proj", R, H, I, defer=True)     # dW_down = t1^T g, db_down = colsum t1
                 dlin_ln(plan, dub, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", I)
                 flush_deferred(plan)
@@ -820,7 +851,7 @@ class Engine:
             if F_QKV:
                 dlin_ln(plan, dqkv, tag + "/ln1", p + ".attn.qkv", p + ".ln1", 3 * H)
                 flush_deferred(plan)
-                dx_ln(plan, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", dS, dS)
+                dx_ln(plan, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", dS, dS)
             else:
                 flush_deferred(plan)
                 dlin(plan, dqkv, self.b[tag + "/h1"], p + ".attn.qkv", R, 3 * H, H, dX=dh_)
@@ -838,9 +869,9 @@ class Engine:
             if F_LNL:
                 dlin_ln(cur, dqc, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", H)
                 flush_deferred(cur)
-                dx_ln(cur, dqc, H, tag + "/qn", p + ".cross_attn.query", dY, dY)
+                dx_ln(cur, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", dY, dY)
                 dlin_ln(cur, dkvc, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", 2 * H)
-                dx_ln(cur, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", None if first_ctx else dctx, dctx)
+                dx_ln(cur, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", None if first_ctx else dctx, dctx)
             else:
                 flush_deferred(cur)
                 dlin(cur, dqc, self.b[tag + "/hq"], p + ".cross_attn.query", R, H, H, dX=dh_)
@@ -856,7 +887,7 @@ class Engine:
         dX = buf("d/xstream", (R, H))
         if F_LNL:
             dlin_ln(cur, dctx, "encnorm", "decoder_proj_context", "encoder_norm", H)
-            dx_ln(cur, dctx, H, "encnorm", "decoder_proj_context", None, dX)
+            dx_ln(cur, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", None, dX)
         else:
             dlin(cur, dctx, enc_out, "decoder_proj_context", R, H, H, dX=dh_)
             ln_b(cur, dh_, enc_last, "encoder_norm", "encnorm", None, dX)

@@ -105,6 +105,21 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R, H, ws, a
                                              P(dbeta), int(accumulate), R, H, ds_L, ds_T, P(ws), ws.numel() * ws.element_size()))
 
 
+def scalenorm_fwd(x, g, y, rinv, R, H, eps=1e-5, plan=None):
+    """y = x * g / max(||x||, eps) per row; rinv = 1 / max(||x||, eps), negated for clamped rows (include/mmfm.h)."""
+    _emit(plan, L.lib().mmfm_scalenorm_fwd, (dt(x), P(x), P(g), P(y), P(rinv), R, H, eps))
+
+
+def scalenorm_bwd_workspace(R, H):
+    return int(L.lib().mmfm_scalenorm_bwd_workspace(R, H))
+
+
+def scalenorm_bwd(dy, x, rinv, g, dres, dx, dg, R, H, ws, accumulate=False, plan=None):
+    """dx = dres + ScaleNorm'(dy) (dx may alias dres); dg (+)= sum over rows of x_hat . dy (deterministic)."""
+    _emit(plan, L.lib().mmfm_scalenorm_bwd, (dt(x), P(dy), P(x), P(rinv), P(g), P(dres), P(dx), P(dg), int(accumulate), R, H, P(ws),
+                                             ws.numel() * ws.element_size()))
+
+
 def attn_desc(dtype, B, heads, Lq, Lk, dh, q, k, v, ldq, ldk, ldv, o, ldo, lse, keypad, mod_id, flags, scale,
               drop_p=None, drop_o=None, d_o=None, lddo=0, dq=None, dk=None, dv=None, lddq=0, lddk=0, lddv=0, keepbits=None):
     """keepbits: uint8 tensor of attn_keepbits_bytes(B, heads, Lq, Lk) bytes (one per attention site: the forward writes the keep
@@ -196,7 +211,8 @@ def collate_csr(B, max_T, max_N, pad_value, data, indices, indptr, indptr_off, n
 
 # ---------------------------------------------------------------------------------------------- row-owner fused kernels
 def prep_table(entries, device):
-    """entries: dicts with W (fp32 [N,K]) and optional gamma, beta, bias, Wp, WpT, bp, WpP, WpTP tensors -> (device table, n, tiles, keep)."""
+    """entries: dicts with W (fp32 [N,K]) and optional gamma, beta, bias, Wp, WpT, bp, WpP, WpTP tensors -> (device table, n, tiles, keep).
+    scalar_gain=True: gamma is a ScaleNorm's one-element gain, beta is not used (include/mmfm.h: mmfm_prep_entry.scalar_gain)."""
     import numpy as np
     arr = (L.PrepEntry * len(entries))()
     tile0 = 0
@@ -210,6 +226,10 @@ def prep_table(entries, device):
         a.W, a.gamma, a.beta, a.bias = P(e["W"]), P(e.get("gamma")), P(e.get("beta")), P(e.get("bias"))
         a.Wp, a.WpT, a.bp = P(e.get("Wp")), P(e.get("WpT")), P(e.get("bp"))
         a.WpP, a.WpTP = P(e.get("WpP")), P(e.get("WpTP"))
+        if e.get("scalar_gain"):
+            if e.get("gamma") is None or e["gamma"].numel() != 1 or e.get("beta") is not None:
+                raise ValueError(f"prep_table: entry {i}: scalar_gain needs a one-element gamma and no beta")
+            a.scalar_gain = 1
         a.N, a.K, a.tile0 = N, Kd, tile0
         tile0 += (N + 31) // 32
     raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
@@ -223,6 +243,7 @@ def prep_weights(table, n, tiles, plan=None):
 
 def rowgemm(x, w, y, R, N, K, *, ldx=None, ldw=None, ldy=None, bias=None, ln=False, eps=1e-5, xhat=None, rstd=None, residual=None,
             ldr=0, stream_out=False, ln_bwd=False, bwd_xhat=None, bwd_rstd=None, rotate=True, plan=None):
+    """ln / ln_bwd: False / True (or 0 / 1) = none / LayerNorm, 2 = ScaleNorm (include/mmfm.h: mmfm_rowgemm_desc)."""
     d = L.RowGemmDesc()
     d.R, d.K, d.N = R, K, N
     d.x, d.ldx, d.w, d.ldw = P(x), K if ldx is None else ldx, P(w), K if ldw is None else ldw
@@ -233,7 +254,8 @@ def rowgemm(x, w, y, R, N, K, *, ldx=None, ldw=None, ldy=None, bias=None, ln=Fal
 
 
 def mlp_desc(R, *, x=None, ldx=256, eps=1e-5, w_up=None, b_up=None, w_down=None, b_down=None, drop=None, y=None, ldy=256, xhat=None,
-             rstd=None, dy=None, lddy=256, w_down_t=None, w_up_t=None, t1=None, g=None, du=None, dx=None, lddx=256, rotate=True):
+             rstd=None, dy=None, lddy=256, w_down_t=None, w_up_t=None, t1=None, g=None, du=None, dx=None, lddx=256, rotate=True,
+             scalenorm=False):
     d = L.MlpDesc()
     d.R, d.x, d.ldx, d.eps = R, P(x), ldx, eps
     d.w_up, d.b_up, d.w_down, d.b_down = P(w_up), P(b_up), P(w_down), P(b_down)
@@ -241,6 +263,7 @@ def mlp_desc(R, *, x=None, ldx=256, eps=1e-5, w_up=None, b_up=None, w_down=None,
     d.y, d.ldy, d.xhat, d.rstd = P(y), ldy, P(xhat), P(rstd)
     d.dy, d.lddy, d.w_down_t, d.w_up_t = P(dy), lddy, P(w_down_t), P(w_up_t)
     d.t1, d.g, d.du, d.dx, d.lddx, d.rotate = P(t1), P(g), P(du), P(dx), lddx, int(rotate)
+    d.scalenorm = int(scalenorm)
     return d
 
 
@@ -260,3 +283,9 @@ def ln_linear_grad_workspace(K, device):
 def ln_linear_grad(Gdb, W, gamma, beta, N, K, dW, dbias, dgamma, dbeta, ws, accumulate_ln=False, plan=None):
     _emit(plan, L.lib().mmfm_ln_linear_grad, (P(Gdb), P(W), P(gamma), P(beta), N, K, P(dW), P(dbias), P(dgamma), P(dbeta), int(accumulate_ln),
                                               P(ws), ws.numel() * 4), keep=(ws,))
+
+
+def sn_linear_grad(Gdb, W, g, N, K, dW, dbias, dg, ws, accumulate=False, plan=None):
+    """ScaleNorm-fed linear: dW = g * G, dbias = db, dg (+)= sum W * G (mmfm_sn_linear_grad; ws as for ln_linear_grad)."""
+    _emit(plan, L.lib().mmfm_sn_linear_grad, (P(Gdb), P(W), P(g), N, K, P(dW), P(dbias), P(dg), int(accumulate), P(ws), ws.numel() * 4),
+          keep=(ws,))

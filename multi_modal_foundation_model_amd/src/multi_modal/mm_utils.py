@@ -50,6 +50,9 @@ def hip_linear(x, lin, act=0, pre_out=None, residual=None):
 
 
 def hip_layernorm(x, ln):
+    """The block norm `ln` (nn.LayerNorm, or ScaleNorm under use_scalenorm: true) through its kernel."""
+    if isinstance(ln, ScaleNorm):
+        return ln(x)
     _need_cuda(x, "hip_layernorm")
     x2 = _flat2d(x.float())
     R, H = x2.shape
@@ -59,7 +62,8 @@ def hip_layernorm(x, ln):
 
 
 class ScaleNorm(nn.Module):
-    """Declared for config parity (mm_utils.py:31-39); `use_scalenorm: true` has no HIP kernel."""
+    """x * scale / max(||x||, eps) per row (mm_utils.py:31-39), `use_scalenorm: true`.  Stand-alone forward through
+    mmfm_scalenorm_fwd (fp32, inference only); on the training path the engine runs it (folded into the linears in bf16)."""
 
     def __init__(self, scale, eps=1e-5):
         super().__init__()
@@ -67,7 +71,12 @@ class ScaleNorm(nn.Module):
         self.eps = eps
 
     def forward(self, x):
-        raise NotImplementedError("ScaleNorm is not built for the MI355X path (mm.yaml: use_scalenorm=false)")
+        _need_cuda(x, "ScaleNorm")
+        x2 = _flat2d(x.float())
+        R, H = x2.shape
+        y, rinv = torch.empty_like(x2), torch.empty(R, device=x.device)
+        K.scalenorm_fwd(x2, self.scale.detach().float().reshape(1).contiguous(), y, rinv, R, H, self.eps)
+        return y.view_as(x)
 
 
 class MLP(nn.Module):
