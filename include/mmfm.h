@@ -24,6 +24,11 @@ extern "C" {
 #define MMFM_VERSION 401
 #define MMFM_F32 0
 #define MMFM_BF16 1
+/* activation kinds of mmfm_mlp_desc.act (the fused MLP's transformer.act) */
+#define MMFM_MLP_GELU 0        /* exact-erf GELU (bf16: the polynomial of act 1) */
+#define MMFM_MLP_RELU 1
+#define MMFM_MLP_SIGMOID 2     /* u * sigmoid(act_beta * u): silu / swish (1), quick_gelu (1.702) */
+#define MMFM_MLP_GELU_TANH 3   /* gelu_new / gelu_pytorch_tanh / gelu_fast */
 
 typedef void* mmfm_stream;
 
@@ -59,6 +64,14 @@ int mmfm_rng_advance(void* state, mmfm_stream stream);
  *          (backward through the activation whose pre-activation the forward stored via pre_out);
  *   act 5: v *= (1 - |y| / act_scale)^2 * act_scale with y = gradmul_pre[..] the forward's act-2 OUTPUT: the same softsign'
  *          without a saved pre-activation (bf16 throughput mode; the fp32 parity path keeps act 4);
+ *   MLP activations other than GELU (transformer.act), forward / gradient pairs; the gradient kinds multiply by f'(u),
+ *   u = gradmul_pre[m*ldc+n] the pre-activation the forward stored via pre_out (as act 3):
+ *   act 6: v = relu(v) = max(v, 0)                     act 7: v *= (u > 0 ? 1 : 0)
+ *   act 8: v = v * sigmoid(act_scale * v)              act 9: v *= s + act_scale * u * s * (1 - s),  s = sigmoid(act_scale * u)
+ *          (silu / swish: act_scale = 1;  quick_gelu: act_scale = 1.702)
+ *   act 10: v = 0.5 v (1 + tanh(k (v + 0.044715 v^3))), k = sqrt(2 / pi)  (gelu_new / gelu_pytorch_tanh / gelu_fast)
+ *   act 11: v *= 0.5 (1 + t) + 0.5 u (1 - t^2) k (1 + 3 * 0.044715 u^2),  t = tanh(k (u + 0.044715 u^3))
+ *   Evaluated with the hardware exp / reciprocal, tanh-GELU as u * sigmoid(2 k (u + 0.044715 u^3)) (error bounds).
  *   v = dropout(v) (counter m*N+n);  v += residual[m*ldr+n];  C[m*ldc+n] = v
  */
 typedef struct {
@@ -345,6 +358,7 @@ int mmfm_rowgemm(const mmfm_rowgemm_desc* d, mmfm_stream stream);
 
 /* The MLP block in one launch (mm_utils.py:42-52 behind ln2, encoder_embeddings.py:114, decoder_embeddings.py:145):
  *   fwd:  y = x + dropout( down( gelu_erf( up( layernorm(x) ) ) ) )        the 512-wide intermediate never leaves the CU
+ *         (gelu stands for the activation `act` throughout: GELU unless the trailing field says otherwise)
  *         w_up / b_up are the prepared (gamma / beta folded) [512][256] / [512]; w_down = bf16 [256][512], UNIT-PERMUTED
  *         (mmfm_prep_entry.WpP of down_proj: the weights reach LDS by DMA, which cannot permute); x_hat / rstd are written for the backward.
  *   bwd:  recomputes u = up(x_hat) and g = gelu(u) from the saved x_hat instead of loading them, and produces
@@ -374,6 +388,9 @@ typedef struct {
     int scalenorm;                    /* 0: ln2 is a LayerNorm;  1: a ScaleNorm (fwd: x_hat = x / max(||x||, eps), rstd saved as by
                                          mmfm_rowgemm ln = 2, w_up / b_up prepared with scalar_gain = 1).  The one-launch backward (dx != NULL)
                                          refuses it: the front half + mmfm_rowgemm(ln_bwd = 2) is the ScaleNorm backward */
+    int act;                          /* MMFM_MLP_GELU (0, the zero-initialised default), _RELU, _SIGMOID or _GELU_TANH: the activation of
+                                         the forward, of g and of du = (t1 . W_down) * act'(u) in every backward mode */
+    float act_beta;                   /* MMFM_MLP_SIGMOID only: u * sigmoid(act_beta * u); 0 there means 1 (silu) */
 } mmfm_mlp_desc;
 int mmfm_mlp_fwd(const mmfm_mlp_desc* d, mmfm_stream stream);
 int mmfm_mlp_bwd(const mmfm_mlp_desc* d, mmfm_stream stream);

@@ -21,6 +21,10 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmfm.h")
 F32, BF16 = 0, 1
 ATTN_DIAG, ATTN_CAUSAL, ATTN_SEP = 1, 2, 4
 ACT_NONE, ACT_GELU, ACT_SOFTSIGN, ACT_GELU_GRAD, ACT_SOFTSIGN_GRAD, ACT_SOFTSIGN_GRAD_OUT = 0, 1, 2, 3, 4, 5
+# the other MLP activations (transformer.act): forward / gradient pairs; the sigmoid kind takes beta in act_scale
+ACT_RELU, ACT_RELU_GRAD, ACT_SIGMOID, ACT_SIGMOID_GRAD, ACT_GELU_TANH, ACT_GELU_TANH_GRAD = 6, 7, 8, 9, 10, 11
+# mmfm_mlp_desc.act (MMFM_MLP_*)
+MLP_GELU, MLP_RELU, MLP_SIGMOID, MLP_GELU_TANH = 0, 1, 2, 3
 
 
 class MmfmError(RuntimeError):
@@ -75,7 +79,8 @@ class MlpDesc(C.Structure):
                 ("b_up", C.c_void_p), ("w_down", C.c_void_p), ("b_down", C.c_void_p), ("drop", Dropout), ("y", C.c_void_p),
                 ("ldy", C.c_int), ("xhat", C.c_void_p), ("rstd", C.c_void_p), ("dy", C.c_void_p), ("lddy", C.c_int),
                 ("w_down_t", C.c_void_p), ("w_up_t", C.c_void_p), ("t1", C.c_void_p), ("g", C.c_void_p), ("du", C.c_void_p),
-                ("dx", C.c_void_p), ("lddx", C.c_int), ("rotate", C.c_int), ("scalenorm", C.c_int)]
+                ("dx", C.c_void_p), ("lddx", C.c_int), ("rotate", C.c_int), ("scalenorm", C.c_int),
+                ("act", C.c_int), ("act_beta", C.c_float)]
 
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float

@@ -25,7 +25,7 @@ def load_config():
 
 
 def model_config(H=None, heads=None, inter=None, n_enc=None, n_dec=None, max_F=None, dropout=None, emb_dropout=None,
-                 sep=None, causal=None, n_modality=None, scalenorm=None):
+                 sep=None, causal=None, n_modality=None, scalenorm=None, act=None):
     from utils.config_utils import DictConfig
     m = copy.deepcopy(dict(load_config()["model"]))
     for side in ("encoder", "decoder"):
@@ -38,6 +38,7 @@ def model_config(H=None, heads=None, inter=None, n_enc=None, n_dec=None, max_F=N
         if inter is not None: t["inter_size"] = inter
         if dropout is not None: t["dropout"] = dropout
         if scalenorm is not None: t["use_scalenorm"] = bool(scalenorm)
+        if act is not None: t["act"] = act
     if n_enc is not None: m["encoder"]["transformer"]["n_layers"] = n_enc
     if n_dec is not None: m["decoder"]["transformer"]["n_layers"] = n_dec
     if sep is not None: m["decoder"]["decoder_sep_mask"] = sep

@@ -221,6 +221,126 @@ template <int N> __device__ __forceinline__ void mul_gelu_grad_n(float* v, const
         v[i] *= a.x; v[i + 1] *= a.y;
     }
 }
+// ---- the other MLP activations (transformer.act): mmfm_gemm act 6-11, mmfm_mlp_desc.act (MMFM_MLP_*)
+//   relu       max(u, 0)                      f' = 1 if u > 0 else 0 (0 at u = 0, as torch)
+//   sigmoid    u s, s = sigmoid(b u)          f' = s + b u s (1 - s)          silu / swish (b = 1), quick_gelu (b = 1.702)
+//   gelu_tanh  0.5 u (1 + t), t = tanh(z)     f' = 0.5 (1 + t) + 0.5 u (1 - t^2) z'(u),  z = k (u + c u^3), k = sqrt(2 / pi), c = 0.044715
+// The derivatives are taken at a clamped argument (|b u| <= 200, |u| <= 20): beyond it s, t are exactly 0 / 1 / -1 in fp32, so f' is
+// exactly 0 or 1 there, and the clamp keeps b u * s (1 - s) and u (1 - t^2) u^2 away from inf * 0 for every finite u.  The forwards
+// multiply the unclamped u by the gate taken at the clamped argument (the same value).
+constexpr float kActSigClamp = 200.f, kActTanhClamp = 20.f;
+constexpr float kGeluTanhK = 0.79788456080286536f, kGeluTanhC = 0.044715f;
+// fp32 parity kernels (gemm.hip) and the scalar bf16 epilogue: sigmoid(z) = rcp(1 + __expf(-z)) (v_exp_f32 / v_rcp_f32: about 1e-6
+// relative, against the 1e-4 parity bound); tanh-GELU through 0.5 (1 + tanh z) = sigmoid(2 z), as the packed forms below.  (expf /
+// tanhf: their library slow paths cost the fp32 GEMM kernels 320 B of scratch.)
+template <int A> struct ActAcc;
+template <> struct ActAcc<MMFM_MLP_GELU> {
+    static __device__ __forceinline__ float f(float u, float) { return gelu_erf(u); }
+    static __device__ __forceinline__ float grad(float u, float) { return gelu_erf_grad(u); }
+};
+template <> struct ActAcc<MMFM_MLP_RELU> {
+    static __device__ __forceinline__ float f(float u, float) { return fmaxf(u, 0.f); }
+    static __device__ __forceinline__ float grad(float u, float) { return u > 0.f ? 1.f : 0.f; }
+};
+template <> struct ActAcc<MMFM_MLP_SIGMOID> {
+    static __device__ __forceinline__ float f(float u, float b) {
+        return u * __builtin_amdgcn_rcpf(1.f + __expf(-__builtin_amdgcn_fmed3f(b * u, -kActSigClamp, kActSigClamp)));
+    }
+    static __device__ __forceinline__ float grad(float u, float b) {
+        const float z = __builtin_amdgcn_fmed3f(b * u, -kActSigClamp, kActSigClamp), s = __builtin_amdgcn_rcpf(1.f + __expf(-z));
+        return fmaf(z * s, 1.f - s, s);
+    }
+};
+template <> struct ActAcc<MMFM_MLP_GELU_TANH> {
+    static __device__ __forceinline__ float f(float u, float) {
+        const float x = __builtin_amdgcn_fmed3f(u, -kActTanhClamp, kActTanhClamp);
+        return u * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * kGeluTanhK * fmaf(kGeluTanhC * x * x, x, x)));
+    }
+    static __device__ __forceinline__ float grad(float u, float) {      // h + 2 u h (1 - h) z'(u), h = sigmoid(2 z)
+        const float x = __builtin_amdgcn_fmed3f(u, -kActTanhClamp, kActTanhClamp), x2 = x * x;
+        const float h = __builtin_amdgcn_rcpf(1.f + __expf(-2.f * kGeluTanhK * fmaf(kGeluTanhC * x2, x, x)));
+        return fmaf(2.f * kGeluTanhK * x * h * (1.f - h), fmaf(3.f * kGeluTanhC, x2, 1.f), h);
+    }
+};
+// mmfm_gemm act 6 / 7 -> MMFM_MLP_RELU, 8 / 9 -> _SIGMOID, 10 / 11 -> _GELU_TANH (0 for every other act)
+__host__ __device__ __forceinline__ int gemm_act_kind(int act) { return act >= 6 ? (act - 4) >> 1 : 0; }
+
+// bf16-mode (packed, fast) forms: sigmoid(z) = 1 / (1 + 2^(-z log2 e)) through v_exp_f32 and v_rcp_f32 (1 ulp each); 2^x overflows to inf
+// or underflows to 0 at the ends and rcp(inf) = 0, so s is exactly 0 or 1 there.  tanh-GELU uses 0.5 (1 + tanh(z)) = sigmoid(2 z) and
+// 1 - t^2 = 4 h (1 - h), h = sigmoid(2 z): f = u h,  f' = h + 2 u h (1 - h) z'(u).  Error bounds: DESIGN.md 3g.
+__device__ __forceinline__ mmfm_f32x2 clamp2(mmfm_f32x2 x, float c) {
+    mmfm_f32x2 r;
+    r.x = __builtin_amdgcn_fmed3f(x.x, -c, c);
+    r.y = __builtin_amdgcn_fmed3f(x.y, -c, c);
+    return r;
+}
+__device__ __forceinline__ mmfm_f32x2 sigmoid2(mmfm_f32x2 z) {
+    const mmfm_f32x2 t = z * splat2(-1.4426950408889634f);
+    mmfm_f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(t.x));
+    r.y = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(t.y));
+    return r;
+}
+// MlpAct<A>: f(u), f'(u) and both at once for a pair of values; b = the sigmoid kind's beta (unused by the others).
+// MlpAct<MMFM_MLP_GELU> is the polynomial GELU above, unchanged.
+template <int A> struct MlpAct;
+template <> struct MlpAct<MMFM_MLP_GELU> {
+    static __device__ __forceinline__ mmfm_f32x2 f(mmfm_f32x2 x, float) { return gelu2(x); }
+    static __device__ __forceinline__ mmfm_f32x2 grad(mmfm_f32x2 x, float) { return gelu_grad2(x); }
+    static __device__ __forceinline__ void both(mmfm_f32x2 x, float, mmfm_f32x2& g, mmfm_f32x2& dg) { gelu_both2(x, g, dg); }
+};
+template <> struct MlpAct<MMFM_MLP_RELU> {
+    static __device__ __forceinline__ mmfm_f32x2 f(mmfm_f32x2 x, float) {
+        mmfm_f32x2 r; r.x = fmaxf(x.x, 0.f); r.y = fmaxf(x.y, 0.f); return r;
+    }
+    static __device__ __forceinline__ mmfm_f32x2 grad(mmfm_f32x2 x, float) {
+        mmfm_f32x2 r; r.x = x.x > 0.f ? 1.f : 0.f; r.y = x.y > 0.f ? 1.f : 0.f; return r;
+    }
+    static __device__ __forceinline__ void both(mmfm_f32x2 x, float b, mmfm_f32x2& g, mmfm_f32x2& dg) { g = f(x, b); dg = grad(x, b); }
+};
+template <> struct MlpAct<MMFM_MLP_SIGMOID> {
+    static __device__ __forceinline__ void both(mmfm_f32x2 x, float b, mmfm_f32x2& g, mmfm_f32x2& dg) {
+        const mmfm_f32x2 z = clamp2(x * splat2(b), kActSigClamp), s = sigmoid2(z);
+        g = x * s;
+        dg = s * __builtin_elementwise_fma(z, splat2(1.f) - s, splat2(1.f));
+    }
+    static __device__ __forceinline__ mmfm_f32x2 f(mmfm_f32x2 x, float b) { return x * sigmoid2(clamp2(x * splat2(b), kActSigClamp)); }
+    static __device__ __forceinline__ mmfm_f32x2 grad(mmfm_f32x2 x, float b) { mmfm_f32x2 g, dg; both(x, b, g, dg); return dg; }
+};
+template <> struct MlpAct<MMFM_MLP_GELU_TANH> {
+    static __device__ __forceinline__ void both(mmfm_f32x2 x, float, mmfm_f32x2& g, mmfm_f32x2& dg) {
+        const mmfm_f32x2 xc = clamp2(x, kActTanhClamp), x2 = xc * xc;
+        const mmfm_f32x2 h = sigmoid2(xc * __builtin_elementwise_fma(x2, splat2(2.f * kGeluTanhK * kGeluTanhC), splat2(2.f * kGeluTanhK)));
+        g = x * h;
+        const mmfm_f32x2 dz = __builtin_elementwise_fma(x2, splat2(6.f * kGeluTanhK * kGeluTanhC), splat2(2.f * kGeluTanhK));   // d(2z)/du
+        dg = h * __builtin_elementwise_fma(xc * dz, splat2(1.f) - h, splat2(1.f));
+    }
+    static __device__ __forceinline__ mmfm_f32x2 f(mmfm_f32x2 x, float) {
+        const mmfm_f32x2 xc = clamp2(x, kActTanhClamp), x2 = xc * xc;
+        return x * sigmoid2(xc * __builtin_elementwise_fma(x2, splat2(2.f * kGeluTanhK * kGeluTanhC), splat2(2.f * kGeluTanhK)));
+    }
+    static __device__ __forceinline__ mmfm_f32x2 grad(mmfm_f32x2 x, float b) { mmfm_f32x2 g, dg; both(x, b, g, dg); return dg; }
+};
+// mmfm_gemm act 6..11 in the bf16 epilogues (kind A = gemm_act_kind(act)): in place on an even-length array / v *= f'(u)
+template <int A, int N> __device__ __forceinline__ void mlp_act_n(float* v, float b) {
+#pragma unroll
+    for (int i = 0; i < N; i += 2) { mmfm_f32x2 a; a.x = v[i]; a.y = v[i + 1]; a = MlpAct<A>::f(a, b); v[i] = a.x; v[i + 1] = a.y; }
+}
+template <int A, int N> __device__ __forceinline__ void mul_mlp_act_grad_n(float* v, const float* u, float b) {
+#pragma unroll
+    for (int i = 0; i < N; i += 2) {
+        if constexpr (A == MMFM_MLP_RELU) {           // a select, as torch's threshold backward
+            v[i] = u[i] > 0.f ? v[i] : 0.f; v[i + 1] = u[i + 1] > 0.f ? v[i + 1] : 0.f;
+        } else {
+            mmfm_f32x2 a; a.x = u[i]; a.y = u[i + 1];
+            a = MlpAct<A>::grad(a, b);
+            v[i] *= a.x; v[i + 1] *= a.y;
+        }
+    }
+}
+// one element (the scalar epilogue of gemm_bf16.hip): f(v), and f'(u)
+template <int A> __device__ __forceinline__ float mlp_act1(float v, float b) { return ActAcc<A>::f(v, b); }
+template <int A> __device__ __forceinline__ float mlp_act_grad1(float u, float b) { return ActAcc<A>::grad(u, b); }
 __device__ __forceinline__ float softsign_f(float x) { return x / (1.f + fabsf(x)); }
 __device__ __forceinline__ float softsign_grad(float x) { float d = 1.f + fabsf(x); return 1.f / (d * d); }
 // the same derivative from the activation's OUTPUT y = s * x / (1 + |x|):  1 / (1 + |x|) = 1 - |y| / s  (act 5: the tokeniser's

@@ -87,18 +87,22 @@ __device__ __forceinline__ void r2s(float* __restrict__ S, const float4 (&r)[4],
     }
 }
 
-// ---- fused epilogue for one element
-template <typename TO>
+// ---- fused epilogue for one element.  AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; every
+// other act runs the AK = 0 kernels, whose code does not change with them
+template <typename TO, int AK = 0>
 __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Drop& dr, float v, int m, int n) {
     typedef io<TO> O;
     if (d.bias) v += d.bias[n];
     if (d.pre_out) O::st(reinterpret_cast<TO*>(d.pre_out) + (size_t)m * d.ldc + n, v);
     if (d.act == 1) v = gelu_erf(v);
     else if (d.act == 2) v = softsign_f(v) * d.act_scale;
+    else if (AK && !(d.act & 1)) v = ActAcc<AK ? AK : MMFM_MLP_RELU>::f(v, d.act_scale);
     if (d.gradmul_pre) {
         const float u = O::ld(reinterpret_cast<const TO*>(d.gradmul_pre) + (size_t)m * d.ldc + n);
-        // act kinds 3/4 = multiply by gelu'(u) / softsign'(u)*scale (backward through the activation)
-        v *= (d.act == 3) ? gelu_erf_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
+        // act kinds 3/4 = multiply by gelu'(u) / softsign'(u)*scale (backward through the activation); 7/9/11 the MLP activations'
+        if (AK == MMFM_MLP_RELU) v = u > 0.f ? v : 0.f;          // a select, as torch's threshold backward
+        else if (AK) v *= ActAcc<AK ? AK : MMFM_MLP_RELU>::grad(u, d.act_scale);
+        else v *= (d.act == 3) ? gelu_erf_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
     }
     v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
     if (d.residual) v += O::ld(reinterpret_cast<const TO*>(d.residual) + (size_t)m * d.ldr + n);
@@ -112,7 +116,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
-template <bool AKC, bool BKC>
+template <bool AKC, bool BKC, int AK = 0>
 __global__ __launch_bounds__(NTHREADS) void gemm_f32_kernel(const mmfm_gemm_desc d, const int vecA, const int vecB) {
     __shared__ __attribute__((aligned(16))) float As[BK * LDT];
     __shared__ __attribute__((aligned(16))) float Bs[BK * LDT];
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_f32_kernel(const mmfm_gemm_desc
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const int n = n0 + wn * 64 + j * 32 + l31;
-                if (m < d.M && n < d.N) epilogue_store<float>(d, dr, acc[i][j][r], m, n);
+                if (m < d.M && n < d.N) epilogue_store<float, AK>(d, dr, acc[i][j][r], m, n);
             }
 }
 
@@ -306,9 +310,12 @@ static int gemm_check(const mmfm_gemm_desc* dp, mmfm_gemm_desc& d) {
     MMFM_REQUIRE(d.ldb >= (d.b_kcontig ? d.K : d.N), "mmfm_gemm: ldb %d too small", d.ldb);
     MMFM_REQUIRE(d.ldc >= d.N, "mmfm_gemm: ldc %d < N %d", d.ldc, d.N);
     MMFM_REQUIRE(!(d.a_kcontig == 0 && d.b_kcontig == 1), "mmfm_gemm: layout (A row-contig, B k-contig) is not built");
-    MMFM_REQUIRE(d.act >= 0 && d.act <= 5, "mmfm_gemm: bad act %d", d.act);
-    MMFM_REQUIRE(!d.gradmul_pre || d.act >= 3, "mmfm_gemm: gradmul_pre needs act 3 (gelu'), 4 (softsign') or 5 (softsign' from the output)");
-    MMFM_REQUIRE(d.gradmul_pre || d.act <= 2, "mmfm_gemm: act %d needs gradmul_pre", d.act);
+    MMFM_REQUIRE(d.act >= 0 && d.act <= 11, "mmfm_gemm: bad act %d", d.act);
+    // gradient kinds: 3, 4, 5 and the odd codes from 7 on
+    const bool grad_act = (d.act >= 3 && d.act <= 5) || (d.act >= 7 && (d.act & 1));
+    MMFM_REQUIRE(!d.gradmul_pre || grad_act,
+                 "mmfm_gemm: gradmul_pre needs a gradient act (3 gelu', 4 softsign', 5 softsign' from the output, 7 relu', 9 sigmoid-gate', 11 tanh-gelu')");
+    MMFM_REQUIRE(d.gradmul_pre || !grad_act, "mmfm_gemm: act %d needs gradmul_pre", d.act);
     if (d.splits <= 1) {
         d.splits = 1;
         d.kchunk = d.K;
@@ -336,9 +343,17 @@ extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
     const int vecA = (d.lda % 4 == 0) && ((uintptr_t)d.A % 16 == 0);
     const int vecB = (d.ldb % 4 == 0) && ((uintptr_t)d.B % 16 == 0);
     dim3 grid(tiles, d.splits), block(NTHREADS);
-    if (d.a_kcontig && d.b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, st, d, vecA, vecB);
-    else if (d.a_kcontig && !d.b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, st, d, vecA, vecB);
-    else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, st, d, vecA, vecB);
+#define F32_LAUNCH(AKV)                                                                                            \
+    if (d.a_kcontig && d.b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, true, AKV>), grid, block, 0, st, d, vecA, vecB);        \
+    else if (d.a_kcontig && !d.b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, false, AKV>), grid, block, 0, st, d, vecA, vecB); \
+    else hipLaunchKernelGGL((gemm_f32_kernel<false, false, AKV>), grid, block, 0, st, d, vecA, vecB);
+    switch (gemm_act_kind(d.act)) {          // relu / sigmoid gate / tanh-GELU and their gradients: a kernel per kind
+    case MMFM_MLP_RELU: { F32_LAUNCH(MMFM_MLP_RELU) } break;
+    case MMFM_MLP_SIGMOID: { F32_LAUNCH(MMFM_MLP_SIGMOID) } break;
+    case MMFM_MLP_GELU_TANH: { F32_LAUNCH(MMFM_MLP_GELU_TANH) } break;
+    default: { F32_LAUNCH(0) }
+    }
+#undef F32_LAUNCH
     MMFM_LAUNCH_CHECK("mmfm_gemm(f32)");
     return 0;
 }

@@ -111,16 +111,21 @@ __device__ __forceinline__ bf16x8v frag(const char* __restrict__ S, int rowbase,
     }
 }
 
-template <typename TO>
+// AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; the AK = 0 kernels run every other act, and
+// their code does not change with these
+template <typename TO, int AK = 0>
 __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Drop& dr, float v, int m, int n) {
     typedef io<uint16_t> I16;
     if (d.bias) v += d.bias[n];
     if (d.pre_out) I16::st(reinterpret_cast<uint16_t*>(d.pre_out) + (size_t)m * d.ldc + n, v);
     if (d.act == 1) v = gelu_poly(v);
     else if (d.act == 2) v = softsign_f(v) * d.act_scale;
+    else if (AK && !(d.act & 1)) v = mlp_act1<AK>(v, d.act_scale);
     if (d.gradmul_pre) {
         const float u = I16::ld(reinterpret_cast<const uint16_t*>(d.gradmul_pre) + (size_t)m * d.ldc + n);
-        v *= (d.act == 3) ? gelu_poly_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
+        if (AK == MMFM_MLP_RELU) v = u > 0.f ? v : 0.f;          // a select, as torch's threshold backward
+        else if (AK) v *= mlp_act_grad1<AK>(u, d.act_scale);
+        else v *= (d.act == 3) ? gelu_poly_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
     }
     v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
     if (d.residual) v += I16::ld(reinterpret_cast<const uint16_t*>(d.residual) + (size_t)m * d.ldr + n);
@@ -170,7 +175,7 @@ __device__ __forceinline__ void stg8(uint16_t* p, uint4 v, bool a16, bool hi, bo
 
 // EPI_LOADS = false: the instantiation of the persistent bf16-output kernel, launched only without a saved pre-activation /
 // residual operand (their registers would sit on top of the next tile's prefetched slice)
-template <typename TO, bool EPI_LOADS = true>
+template <typename TO, bool EPI_LOADS = true, int AK = 0>
 __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&acc)[2][2], char* smem, int m0, int n0, int z, int vec_epi,
                                               int t, int wm, int wn, int kh, int l31) {
     // ---- epilogue.  Fast path (row-aligned shapes): the fp32 tile is staged through LDS half a tile at a time
@@ -252,7 +257,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
                 else if (d.act == 2) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = softsign_f(v[e]) * d.act_scale;
-                }
+                } else if (AK && !(d.act & 1)) mlp_act_n<AK, 8>(v, d.act_scale);
                 if (EPI_LOADS && d.gradmul_pre) {
                     float u[8];
                     unpack8(gu[c], u);
@@ -260,7 +265,8 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
                     else if (d.act == 4) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] *= softsign_grad(u[e]) * d.act_scale;
-                    } else {
+                    } else if (AK) mul_mlp_act_grad_n<AK, 8>(v, u, d.act_scale);
+                    else {
                         const float inv_s = 1.f / d.act_scale;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] *= softsign_grad_from_out(u[e], inv_s) * d.act_scale;
@@ -303,7 +309,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const int n = n0 + wn * 64 + j * 32 + l31;
-                if (m < d.M && n < d.N) epilogue_store<TO>(d, dr, acc[i][j][r], m, n);
+                if (m < d.M && n < d.N) epilogue_store<TO, AK>(d, dr, acc[i][j][r], m, n);
             }
 }
 
@@ -315,7 +321,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
 // 130 -> 90 us).  bf16-output launches stay one item per workgroup: their epilogue LOADS (bias, residual, saved
 // pre-activation) are issued after the prefetch and vmcnt retires in order, so the epilogue would wait for the whole
 // prefetch; hoisting those loads above the prefetch costs 40 VGPRs, spills, and measured 30 % slower (194 -> 261 us).
-template <bool ARC, bool BRC, typename TO, int BK, bool PERSIST = (sizeof(TO) == 4)>
+template <bool ARC, bool BRC, typename TO, int BK, bool PERSIST = (sizeof(TO) == 4), int AK = 0>
 __global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(const mmfm_gemm_desc d, const int alignA, const int alignB,
                                                                               const int vec_epi, const int total_items) {
     constexpr int TILE_BYTES = Geo<BK>::TILE_BYTES;
@@ -414,7 +420,7 @@ __global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(c
                 d.colsum[(d.splits > 1 ? (size_t)z * d.slab_stride : 0) + m0 + t] = sum;
             }
         }
-        epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2)>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
+        epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
         if (!more) break;
         w = wn_; m0 = m0n; n0 = n0n; z = zn; kbeg = kbegn; kend = kendn;
     }
@@ -471,7 +477,8 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     // K >= 1336 (token embedding) the prefetch registers spill and it measured 30 % SLOWER, hence the K bound.
     // MMFM_GEMM_PERSIST_BF16 = 0 turns it off.
     static const int persist_bf16 = [] { const char* e = getenv("MMFM_GEMM_PERSIST_BF16"); return e ? atoi(e) : 1; }();
-    const bool pb = !f32out && persist_bf16 && !d.gradmul_pre && !d.residual && !d.pre_out && (vec & 1) && d.K <= 768;
+    const int ak = gemm_act_kind(d.act);  // relu / sigmoid gate / tanh-GELU and their gradients: a kernel per kind (BK = 64 only)
+    const bool pb = !f32out && !ak && persist_bf16 && !d.gradmul_pre && !d.residual && !d.pre_out && (vec & 1) && d.K <= 768;
     dim3 grid((f32out || pb) ? std::min(total_items, 256 * wg_per_cu) : total_items), block(NTHREADS);   // persistent: 3 resident workgroups per CU
     // occupancy probe: unused dynamic LDS bytes per workgroup (60000 -> one workgroup per CU less, 100000 -> one per CU)
     static const int pad_lds = [] { const char* e = getenv("MMFM_GEMM_PAD_LDS"); return e ? atoi(e) : 0; }();
@@ -479,11 +486,19 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);  \
     else if (pb) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV, true>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items); \
     else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);
-#define LAUNCH(ARC, BRC) if (BKsel == 128) { LAUNCH2(ARC, BRC, 128) } else { LAUNCH2(ARC, BRC, 64) }
+#define LAUNCH_AK(ARC, BRC, AKV)                                                                                  \
+    if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, 64, true, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items); \
+    else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, 64, false, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);
+#define LAUNCH(ARC, BRC)                                                                                          \
+    if (ak == MMFM_MLP_RELU) { LAUNCH_AK(ARC, BRC, MMFM_MLP_RELU) }                                                \
+    else if (ak == MMFM_MLP_SIGMOID) { LAUNCH_AK(ARC, BRC, MMFM_MLP_SIGMOID) }                                     \
+    else if (ak == MMFM_MLP_GELU_TANH) { LAUNCH_AK(ARC, BRC, MMFM_MLP_GELU_TANH) }                                 \
+    else if (BKsel == 128) { LAUNCH2(ARC, BRC, 128) } else { LAUNCH2(ARC, BRC, 64) }
     if (d.a_kcontig && d.b_kcontig) { LAUNCH(false, false) }
     else if (d.a_kcontig && !d.b_kcontig) { LAUNCH(false, true) }
     else { LAUNCH(true, true) }
 #undef LAUNCH
+#undef LAUNCH_AK
 #undef LAUNCH2
     MMFM_LAUNCH_CHECK("mmfm_gemm(bf16)");
     return 0;

@@ -66,6 +66,9 @@ __device__ __forceinline__ void issue_ktile(char* buf, const uint16_t* const (&p
 #define LDS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define LDS_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
+// AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; the AK = 0 kernel runs every other act, and
+// its code does not change with these
+template <int AK = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const mmfm_gemm_desc& d = a.d;
@@ -207,6 +210,16 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
                             const float v = acc[2 * ip + e][j][r];
                             acc[2 * ip + e][j][r] = v * __builtin_amdgcn_rcpf(1.f + fabsf(v)) * d.act_scale;      // v_rcp_f32: 1 ulp, far below bf16
                         }
+                } else if (AK && !(d.act & 1)) {                                          // relu / sigmoid gate / tanh-GELU (common.h)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        float v[16];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) v[r] = acc[2 * ip + e][j][r];
+                        mlp_act_n<AK, 16>(v, d.act_scale);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[2 * ip + e][j][r] = v[r];
+                    }
                 } else if (d.gradmul_pre) {
                     const Lines L = fetch_lines(Gb, wrow0, ldcb, (uint32_t)ncol0 * 2u, lane);
                     stage_lines(stg, L, lane);
@@ -214,7 +227,14 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
                     for (int e = 0; e < 2; ++e) {
                         const f32x16 u = unstage_tile(stg, e, m, h);
                         f32x16& v = acc[2 * ip + e][j];
-                        if (d.act == 3) {
+                        if (AK) {
+                            float uu[16], vv[16];
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) { uu[r] = u[r]; vv[r] = v[r]; }
+                            mul_mlp_act_grad_n<AK, 16>(vv, uu, d.act_scale);
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) v[r] = vv[r];
+                        } else if (d.act == 3) {
 #pragma unroll
                             for (int r = 0; r < 16; r += 2) {
                                 mmfm_f32x2 uu; uu.x = u[r]; uu.y = u[r + 1];
@@ -284,7 +304,12 @@ int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
         !al16(d.gradmul_pre) || !al16(d.residual) || !al16(d.bias))
         return -1000;
     if ((int64_t)d.M * std::max(d.ldc, d.ldr) * 2 >= (int64_t)1 << 31) return -1000;        // 32-bit buffer offsets of the epilogue
-    if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(gemm_big_kernel), LDS_ALL, "mmfm_gemm(bf16, 256 tile)")) return rc;
+    const int ak = gemm_act_kind(d.act);   // relu / sigmoid gate / tanh-GELU and their gradients: a kernel per kind
+    const void* kern = ak == MMFM_MLP_RELU ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_RELU>)
+                     : ak == MMFM_MLP_SIGMOID ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_SIGMOID>)
+                     : ak == MMFM_MLP_GELU_TANH ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_GELU_TANH>)
+                     : reinterpret_cast<const void*>(gemm_big_kernel<0>);
+    if (int rc = mmfm_lds_opt_in(kern, LDS_ALL, "mmfm_gemm(bf16, 256 tile)")) return rc;
     static const int nt_env = [] { const char* e = getenv("MMFM_GEMM_NT"); return e ? atoi(e) : 3; }();
     BigArgs a;
     a.d = d;
@@ -293,7 +318,10 @@ int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     a.nk = d.K / BK;
     a.nt_c = nt_env & 1;
     a.nt_pre = (nt_env >> 1) & 1;
-    hipLaunchKernelGGL(gemm_big_kernel, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    if (ak == MMFM_MLP_RELU) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_RELU>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    else if (ak == MMFM_MLP_SIGMOID) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_SIGMOID>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    else if (ak == MMFM_MLP_GELU_TANH) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_GELU_TANH>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    else hipLaunchKernelGGL(gemm_big_kernel<0>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
     MMFM_LAUNCH_CHECK("mmfm_gemm(bf16, 256 tile)");
     return 0;
 }

@@ -18,6 +18,7 @@
 #include "rowchain.h"
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 
 using namespace rowchain;
 
@@ -46,6 +47,12 @@ constexpr int NT = 256, NW = 4;
 #ifndef MMFM_PROBE
 #define MMFM_PROBE 0
 #endif
+// the sigmoid kind's beta (mmfm_mlp_desc.act_beta, 0 = 1); the other kinds never read the field
+template <int ACT> __device__ __forceinline__ float act_beta(const mmfm_mlp_desc& d) {
+    return ACT == MMFM_MLP_SIGMOID ? (d.act_beta != 0.f ? d.act_beta : 1.f) : 0.f;
+}
+// ACT: the activation (mmfm_mlp_desc.act, MMFM_MLP_*) in every kernel below
+template <int ACT>
 __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
     // LDS: three 16 KB ring slots (asynchronous ring, rowchain.h) | per-wave staging for g and du (the g area doubles as the
     // prologue / epilogue staging) | b_up | a 16 KB per-wave stash of the pass's x_hat rows (four [32 rows][128 B] staging images):
@@ -80,6 +87,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
     float* lb_up = reinterpret_cast<float*>(smem + RING_B + 2 * NW * STG_BYTES);
     stage_vec(lb_up, d.b_up, 512, t, NT);
     const Drop dr = drop_init(d.drop);
+    const float ab = act_beta<ACT>(d);
     const GBuf XH = gbuf(d.xhat, d.R * 512), RS = gbuf(d.rstd, d.R * 4), DY = gbuf(d.dy, d.R * d.lddy * 2), T1 = gbuf(d.t1, d.R * 512);
     const GBuf G = gbuf(d.g, d.R * 1024), DU = gbuf(d.du, d.R * 1024), DX = gbuf(d.dx, d.R * d.lddx * 2);
     const uint32_t lddyb = d.lddy * 2, lddxb = d.lddx * 2;
@@ -138,7 +146,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
 #define DH_MMAS(SET, Q) do { DH[2 * (Q)] = mfma_u4(wv[SET][0], d0, DH[2 * (Q)]); DH[2 * (Q) + 1] = mfma_u4(wv[SET][2], d0, DH[2 * (Q) + 1]);  \
                              DH[2 * (Q)] = mfma_u4(wv[SET][1], d1, DH[2 * (Q)]); DH[2 * (Q) + 1] = mfma_u4(wv[SET][3], d1, DH[2 * (Q) + 1]);  \
                              __builtin_amdgcn_sched_barrier(0); } while (0)
-#define GELU_PAIRS(I0) do { gelu_fb_pair(U, Gt, DG, I0); gelu_fb_pair(U, Gt, DG, (I0) + 2); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define GELU_PAIRS(I0) do { act_fb_pair<ACT>(U, Gt, DG, I0, ab); act_fb_pair<ACT>(U, Gt, DG, (I0) + 2, ab); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define MLP_BWD_TILE(TI, ODD, FIRST, EXTRA_AB)                                                   \
         {                                                                                        \
             const int ti = (TI), tt = (ti + rot) & 15;                                           \
@@ -159,7 +167,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
             STAMP(2);                                                                            \
             f32x16 Gt;                                                                           \
             if (FIRST) {                                                                         \
-                gelu_fwd_bwd16(U, Gt, DG);                                                       \
+                act_fwd_bwd16<ACT>(U, Gt, DG, ab);                                               \
             } else {                                                                             \
                 RINGA_SYNC(src, slot, 0);                                                        \
                 STAMP(1);                                                                        \
@@ -252,6 +260,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
 // runs one wave per SIMD at 448 registers and pays every LDS / MFMA latency once) and a pass streams 2 x 256 KB of weights for 256
 // rows instead of 3 x 256 KB for 128; what it costs: du is read back once (210 MB at R = 204,800).
 constexpr int NTD = 512, NWD = 8;
+template <int ACT>
 __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc d) {
     constexpr int RING_B = RINGA_SLOTS * CHUNK;
     extern __shared__ __attribute__((aligned(16))) char smem[];        // RING_B + 2 * NWD * STG_BYTES + 512 * 4
@@ -274,6 +283,7 @@ __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc 
     float* lb_up = reinterpret_cast<float*>(smem + RING_B + 2 * NWD * STG_BYTES);
     stage_vec(lb_up, d.b_up, 512, t, NTD);
     const Drop dr = drop_init(d.drop);
+    const float ab = act_beta<ACT>(d);
     const GBuf XH = gbuf(d.xhat, d.R * 512), DY = gbuf(d.dy, d.R * d.lddy * 2), T1 = gbuf(d.t1, d.R * 512);
     const GBuf G = gbuf(d.g, d.R * 1024), DU = gbuf(d.du, d.R * 1024);
     const uint32_t lddyb = d.lddy * 2;
@@ -331,7 +341,7 @@ __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc 
                 DG = mma16a<4>(slot, fr, t1, zero16(), [&](int g_) { if (g_ < 1024 / NTD) RINGA_PIECE(g_); }); \
             }                                                                                    \
             f32x16 Gt;                                                                           \
-            gelu_fwd_bwd16(U, Gt, DG);                                                           \
+            act_fwd_bwd16<ACT>(U, Gt, DG, ab);                                                   \
             stage_tile(stg_g, ODD, m, h, Gt);                                                    \
             stage_tile(stg_du, ODD, m, h, DG);                                                   \
             if (ODD) {                          /* the pair (tt-1, tt) is complete -> whole 128-B lines */ \
@@ -364,7 +374,7 @@ constexpr int NT8 = 512;
 // down-projection one ring step behind): 222 / 199 us with and without dropout against 216 / 206 - the producer's GELU (1,300 cycles
 // per tile, as long as 40 MFMAs) becomes the critical path and the consumer idles at the barrier.
 // NORM: the ln2 prologue, 1 = LayerNorm, 2 = ScaleNorm (mmfm_mlp_desc.scalenorm)
-template <int NORM>
+template <int NORM, int ACT>
 __global__ __launch_bounds__(NT8) void mlp_fwd8_kernel(const mmfm_mlp_desc d) {
     constexpr int NPAIR = 4;
     constexpr int RING_B = RINGA_SLOTS * CHUNK2;
@@ -395,6 +405,7 @@ __global__ __launch_bounds__(NT8) void mlp_fwd8_kernel(const mmfm_mlp_desc d) {
     stage_vec(lb_up, d.b_up, 512, t, NT8);
     stage_vec(lb_dn, d.b_down, 256, t, NT8);
     const Drop dr = drop_init(d.drop);
+    const float ab = act_beta<ACT>(d);
     const GBuf X = gbuf(d.x, d.R * d.ldx * 2), Y = gbuf(d.y, d.R * d.ldy * 2);
     const GBuf XH = gbuf(role == 0 ? d.xhat : nullptr, d.R * 512), RS = gbuf(role == 0 ? d.rstd : nullptr, d.R * 4);
     const uint32_t ldxb = d.ldx * 2, ldyb = d.ldy * 2;
@@ -426,7 +437,7 @@ __global__ __launch_bounds__(NT8) void mlp_fwd8_kernel(const mmfm_mlp_desc d) {
             }
             STAMP(2);
             add_vec(U, lb_up, 2 * u + role, h);
-            gelu16(U);
+            act16<ACT>(U, ab);
             opnd g0, g1;
             acc_to_opnd(U, g0, g1);
             *reinterpret_cast<uint4*>(exch + role * 2048 + lane * 16) = as_u4(g0);
@@ -602,8 +613,19 @@ int grid_for(int64_t R, int per_cu, int nw = NW) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(npass, 256 * per_cu));
 }
 
+// f(std::integral_constant<int, A>) for the activation A = act (MMFM_MLP_*): picks the kernel instantiation
+template <typename F> int with_act(int act, F&& f) {
+    switch (act) {
+    case MMFM_MLP_GELU: return f(std::integral_constant<int, MMFM_MLP_GELU>());
+    case MMFM_MLP_RELU: return f(std::integral_constant<int, MMFM_MLP_RELU>());
+    case MMFM_MLP_SIGMOID: return f(std::integral_constant<int, MMFM_MLP_SIGMOID>());
+    default: return f(std::integral_constant<int, MMFM_MLP_GELU_TANH>());
+    }
+}
+
 int check(const mmfm_mlp_desc& d, bool bwd) {
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    MMFM_REQUIRE(d.act >= MMFM_MLP_GELU && d.act <= MMFM_MLP_GELU_TANH, "mmfm_mlp: bad act %d", d.act);
     MMFM_REQUIRE(d.R > 0 && d.w_up && d.b_up, "mmfm_mlp: null operand / empty problem");
     MMFM_REQUIRE((d.R + 128) * (int64_t)std::max(std::max(d.ldx, d.ldy), std::max(std::max(d.lddy, d.lddx), 512)) * 2 < (int64_t)1 << 31,
                  "mmfm_mlp: tensors beyond 2 GiB are not addressable by the 32-bit buffer offsets");
@@ -621,18 +643,19 @@ extern "C" int mmfm_mlp_fwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
     const mmfm_mlp_desc d = *dp;
     if (int rc = check(d, false)) return rc;
     static const int per_cu = [] { const char* e = getenv("MMFM_MLP_WG_PER_CU"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-    {
+    return with_act(d.act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
         constexpr int LDS_A = RINGA_SLOTS * CHUNK2 + 8 * STG_BYTES + 4 * 4096 + 768 * 4;
         if (d.scalenorm) {
-            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<2>), LDS_A, "mmfm_mlp_fwd")) return rc;
-            hipLaunchKernelGGL(mlp_fwd8_kernel<2>, dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<2, ACT>), LDS_A, "mmfm_mlp_fwd")) return rc;
+            hipLaunchKernelGGL((mlp_fwd8_kernel<2, ACT>), dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
         } else {
-            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<1>), LDS_A, "mmfm_mlp_fwd")) return rc;
-            hipLaunchKernelGGL(mlp_fwd8_kernel<1>, dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_fwd8_kernel<1, ACT>), LDS_A, "mmfm_mlp_fwd")) return rc;
+            hipLaunchKernelGGL((mlp_fwd8_kernel<1, ACT>), dim3(grid_for(d.R, per_cu, 4)), dim3(NT8), LDS_A, (hipStream_t)stream, d);
         }
-    }
-    MMFM_LAUNCH_CHECK("mmfm_mlp_fwd");
-    return 0;
+        MMFM_LAUNCH_CHECK("mmfm_mlp_fwd");
+        return 0;
+    });
 }
 
 extern "C" int mmfm_mlp_bwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
@@ -640,18 +663,24 @@ extern "C" int mmfm_mlp_bwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
     if (int rc = check(d, true)) return rc;
     static const int per_cu = [] { const char* e = getenv("MMFM_MLP_WG_PER_CU"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
     if (d.dx == nullptr) {            // front half only (t1, g, du): the caller finishes with mmfm_rowgemm(ln_bwd)
-        constexpr int LDS_D = RINGA_SLOTS * CHUNK + 2 * NWD * STG_BYTES + 512 * 4;
-        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_du_kernel), LDS_D, "mmfm_mlp_bwd(front half)")) return rc;
-        hipLaunchKernelGGL(mlp_bwd_du_kernel, dim3(grid_for(d.R, per_cu, NWD)), dim3(NTD), LDS_D, (hipStream_t)stream, d);
-        MMFM_LAUNCH_CHECK("mmfm_mlp_bwd(front half)");
-        return 0;
+        return with_act(d.act, [&](auto A) {
+            constexpr int ACT = decltype(A)::value;
+            constexpr int LDS_D = RINGA_SLOTS * CHUNK + 2 * NWD * STG_BYTES + 512 * 4;
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_du_kernel<ACT>), LDS_D, "mmfm_mlp_bwd(front half)")) return rc;
+            hipLaunchKernelGGL(mlp_bwd_du_kernel<ACT>, dim3(grid_for(d.R, per_cu, NWD)), dim3(NTD), LDS_D, (hipStream_t)stream, d);
+            MMFM_LAUNCH_CHECK("mmfm_mlp_bwd(front half)");
+            return 0;
+        });
     }
     MMFM_REQUIRE(!d.scalenorm, "mmfm_mlp_bwd: the one-launch backward has no ScaleNorm epilogue (front half, then mmfm_rowgemm ln_bwd = 2)");
-    constexpr int LDS_B = RINGA_SLOTS * CHUNK + 2 * NW * STG_BYTES + 512 * 4 + NW * 4 * STG_BYTES;
-    if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_kernel), LDS_B, "mmfm_mlp_bwd")) return rc;
-    hipLaunchKernelGGL(mlp_bwd_kernel, dim3(grid_for(d.R, per_cu)), dim3(NT), LDS_B, (hipStream_t)stream, d);
-    MMFM_LAUNCH_CHECK("mmfm_mlp_bwd");
-    return 0;
+    return with_act(d.act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        constexpr int LDS_B = RINGA_SLOTS * CHUNK + 2 * NW * STG_BYTES + 512 * 4 + NW * 4 * STG_BYTES;
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_kernel<ACT>), LDS_B, "mmfm_mlp_bwd")) return rc;
+        hipLaunchKernelGGL(mlp_bwd_kernel<ACT>, dim3(grid_for(d.R, per_cu)), dim3(NT), LDS_B, (hipStream_t)stream, d);
+        MMFM_LAUNCH_CHECK("mmfm_mlp_bwd");
+        return 0;
+    });
 }
 
 extern "C" int64_t mmfm_ln_linear_grad_workspace(int K) { return ((int64_t)LG_SPLIT * 2 * K + cdiv(K, 32) + 64) * 4; }

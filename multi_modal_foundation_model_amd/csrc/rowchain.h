@@ -583,29 +583,42 @@ __device__ __forceinline__ void drop8(const RowDrop& rd, float (&f)[8], int k0) 
     }
 }
 
-// ---- GELU on accumulator tiles: the packed polynomial of common.h (phi2), two registers per instruction
-__device__ __forceinline__ void gelu16(f32x16& U) {
+// ---- the MLP activation on accumulator tiles: MlpAct<A> of common.h (GELU: the packed polynomial phi2), two registers per
+// instruction; b = the sigmoid kind's beta
+template <int A>
+__device__ __forceinline__ void act16(f32x16& U, float b) {
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
         mmfm_f32x2 a; a.x = U[i]; a.y = U[i + 1];
-        a = gelu2(a);
+        a = MlpAct<A>::f(a, b);
         U[i] = a.x; U[i + 1] = a.y;
     }
 }
+__device__ __forceinline__ void gelu16(f32x16& U) { act16<MMFM_MLP_GELU>(U, 0.f); }
 __device__ __forceinline__ void gelu_pair(f32x16& U, int i) {                  // registers i, i + 1 (i even)
     mmfm_f32x2 a; a.x = U[i]; a.y = U[i + 1];
     a = gelu2(a);
     U[i] = a.x; U[i + 1] = a.y;
 }
-// G = gelu(U), D *= gelu'(U)
-__device__ __forceinline__ void gelu_fwd_bwd16(const f32x16& U, f32x16& G, f32x16& D) {
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        mmfm_f32x2 a, g, dg; a.x = U[i]; a.y = U[i + 1];
-        gelu_both2(a, g, dg);
+// one register pair (i, i+1; i even): G = act(U), D *= act'(U).  relu's D is a select (what torch's threshold backward computes: a
+// non-finite upstream gradient stays 0 where u <= 0)
+template <int A>
+__device__ __forceinline__ void act_fb_pair(const f32x16& U, f32x16& G, f32x16& D, int i, float b) {
+    mmfm_f32x2 a, g, dg; a.x = U[i]; a.y = U[i + 1];
+    if constexpr (A == MMFM_MLP_RELU) {
+        G[i] = fmaxf(a.x, 0.f); G[i + 1] = fmaxf(a.y, 0.f);
+        D[i] = a.x > 0.f ? D[i] : 0.f; D[i + 1] = a.y > 0.f ? D[i + 1] : 0.f;
+    } else {
+        MlpAct<A>::both(a, b, g, dg);
         G[i] = g.x; G[i + 1] = g.y;
         D[i] *= dg.x; D[i + 1] *= dg.y;
     }
+}
+// G = act(U), D *= act'(U) on the whole tile
+template <int A>
+__device__ __forceinline__ void act_fwd_bwd16(const f32x16& U, f32x16& G, f32x16& D, float b) {
+#pragma unroll
+    for (int i = 0; i < 16; i += 2) act_fb_pair<A>(U, G, D, i, b);
 }
 
 // 16 MFMAs of one [32][256] chunk against 16 operands, weight operands fetched 8 at a time (the ds_read latency of a
@@ -621,14 +634,6 @@ __device__ __forceinline__ f32x16 mma16(const char* slot, const opnd* x, f32x16 
         for (int s = 0; s < DEPTH; ++s) acc = mfma(wf[s], x[DEPTH * part + s], acc);
     }
     return acc;
-}
-
-// one register pair (i, i+1; i even) of gelu_fwd_bwd16
-__device__ __forceinline__ void gelu_fb_pair(const f32x16& U, f32x16& G, f32x16& D, int i) {
-    mmfm_f32x2 a, g, dg; a.x = U[i]; a.y = U[i + 1];
-    gelu_both2(a, g, dg);
-    G[i] = g.x; G[i + 1] = g.y;
-    D[i] *= dg.x; D[i + 1] *= dg.y;
 }
 
 // ---- full-line global stores / loads through a per-wave LDS staging area -----------------------------------------------

@@ -50,6 +50,7 @@ class EngineConfig:
     mods: List[Tuple[str, int]]                 # (name, channels) in avail_mod order
     loss_kind: Dict[str, int] = field(default_factory=lambda: dict(LOSS_KIND))
     norm: str = "layernorm"                     # the transformer blocks' norms: "layernorm" or "scalenorm" (use_scalenorm: true)
+    act: Tuple[int, float] = (L.MLP_GELU, 1.0)  # the MLP activation (transformer.act): (MMFM_MLP_* kind, sigmoid beta), ops.mlp_act
 
     @staticmethod
     def from_model_config(mc, mods) -> "EngineConfig":
@@ -60,15 +61,18 @@ class EngineConfig:
                 raise ValueError(f"encoder/decoder transformer.{k} differ ({et[k]} vs {dtf[k]}): not supported")
         if bool(et["use_scalenorm"]) != bool(dtf["use_scalenorm"]):
             raise NotImplementedError("use_scalenorm differs between encoder and decoder: not built")
-        if et["act"] != "gelu" or ee["act"] != "softsign":
-            raise NotImplementedError("only act=gelu (transformer) / softsign (embedder) are built")
+        if et["act"] != dtf["act"]:
+            raise NotImplementedError(f"transformer.act differs between encoder and decoder ({et['act']} vs {dtf['act']}): not built")
+        act = K.mlp_act(et["act"])
+        if ee["act"] != "softsign":
+            raise NotImplementedError("only act=softsign (embedder) is built")
         scale = et["hidden_size"] ** 0.5 if ee["scale"] is None else ee["scale"]
         return EngineConfig(hidden=et["hidden_size"], heads=et["n_heads"], inter=et["inter_size"],
                             n_enc=et["n_layers"], n_dec=dtf["n_layers"], max_F=ee["max_F"], mult=ee["mult"],
                             n_modality=ee["n_modality"], embed_scale=float(scale), embed_dropout=ee["dropout"],
                             dropout=et["dropout"], sep_mask=bool(mc["decoder"]["decoder_sep_mask"]),
                             causal_mask=bool(mc["decoder"]["decoder_causal_mask"]), mods=list(mods),
-                            norm="scalenorm" if et["use_scalenorm"] else "layernorm")
+                            norm="scalenorm" if et["use_scalenorm"] else "layernorm", act=act)
 
 
 def _align(n, a=8):
@@ -429,6 +433,7 @@ class Engine:
             return self.plans[key]
         c = self.cfg
         H, I, heads = c.hidden, c.inter, c.heads
+        act_fwd, act_grad = K.GEMM_ACTS[c.act[0]]       # the un-fused MLP's mmfm_gemm act codes (beta: c.act[1])
         dh = H // heads
         M = len(c.mods)
         Lq = M * T
@@ -726,12 +731,13 @@ class Engine:
                 d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=prep["v"][p + ".mlp.down_proj"]["WpP"],
                                 b_down=self.Pf(p + ".mlp.down_proj.bias"), drop=self._drop(tag + "/mlpdrop", dp), y=Xb,
                                 xhat=buf(tag + "/ln2/xh", (R, H)) if grad else None,
-                                rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None, scalenorm=self.is_sn(p + ".ln2"))
+                                rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None, scalenorm=self.is_sn(p + ".ln2"),
+                                act=c.act[0], act_beta=c.act[1])
                 K.mlp_fwd(d_, plan=plan)
                 return Xb
             h, u, g = buf(tag + "/h2", (R, H)), buf(tag + "/u", (R, I)), buf(tag + "/g", (R, I))
             ln_f(plan, X, p + ".ln2", h, tag + "/ln2")
-            lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=L.ACT_GELU)
+            lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=act_fwd, act_scale=c.act[1])
             lin(plan, g, p + ".mlp.down_proj", Xb, R, H, I, drop=self._drop(tag + "/mlpdrop", dp), residual=X, ldr=H)
             return Xb
 
@@ -819,7 +825,7 @@ class Engine:
                 split = os.environ.get("MMFM_MLP_BWD_SPLIT", "1") == "1" or self.is_sn(p + ".ln2")
                 d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=self._drop(tag + "/mlpdrop", dp), xhat=self.b[tag + "/ln2/xh"],
                                 rstd=self.b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
-                                dx=None if split else dS)
+                                dx=None if split else dS, act=c.act[0], act_beta=c.act[1])
                 K.mlp_bwd(d_, plan=plan)
                 if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
                     dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
@@ -831,7 +837,8 @@ class Engine:
             if dp > 0:                                                       # mm_utils.py:52 dropout(down_proj(.))
                 K.dropout_apply(dS, t1, R, H, self._drop(tag + "/mlpdrop", dp), plan=plan)
                 dSd = t1
-            dlin(plan, dSd, self.b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, act=L.ACT_GELU_GRAD, gradmul_pre=self.b[tag + "/u"])
+            dlin(plan, dSd, self.b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, act=act_grad, act_scale=c.act[1],
+                 gradmul_pre=self.b[tag + "/u"])
             dlin(plan, du, self.b[tag + "/h2"], p + ".mlp.up_proj", R, I, H, dX=dh_)
             ln_b(plan, dh_, X_in, p + ".ln2", tag + "/ln2", dS, dS)
 

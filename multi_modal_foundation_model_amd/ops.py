@@ -253,9 +253,28 @@ def rowgemm(x, w, y, R, N, K, *, ldx=None, ldw=None, ldy=None, bias=None, ln=Fal
     _emit(plan, L.lib().mmfm_rowgemm, (C.byref(d),), keep=(d,))
 
 
+# transformer.act (a `transformers` ACT2FN name) -> (MMFM_MLP_* kind, beta): the MLP activations the kernels build
+MLP_ACTS = {
+    "gelu": (L.MLP_GELU, 1.0),
+    "relu": (L.MLP_RELU, 1.0),
+    "silu": (L.MLP_SIGMOID, 1.0), "swish": (L.MLP_SIGMOID, 1.0), "quick_gelu": (L.MLP_SIGMOID, 1.702),
+    "gelu_new": (L.MLP_GELU_TANH, 1.0), "gelu_pytorch_tanh": (L.MLP_GELU_TANH, 1.0), "gelu_fast": (L.MLP_GELU_TANH, 1.0),
+}
+# MMFM_MLP_* kind -> the mmfm_gemm act codes of its forward and of its gradient (un-fused and fp32 paths)
+GEMM_ACTS = {L.MLP_GELU: (L.ACT_GELU, L.ACT_GELU_GRAD), L.MLP_RELU: (L.ACT_RELU, L.ACT_RELU_GRAD),
+             L.MLP_SIGMOID: (L.ACT_SIGMOID, L.ACT_SIGMOID_GRAD), L.MLP_GELU_TANH: (L.ACT_GELU_TANH, L.ACT_GELU_TANH_GRAD)}
+
+
+def mlp_act(name):
+    """(kind, beta) of a transformer.act name; NotImplementedError for names without a kernel."""
+    if name not in MLP_ACTS:
+        raise NotImplementedError(f"MLP act {name!r} has no kernel; accepted: {', '.join(MLP_ACTS)}")
+    return MLP_ACTS[name]
+
+
 def mlp_desc(R, *, x=None, ldx=256, eps=1e-5, w_up=None, b_up=None, w_down=None, b_down=None, drop=None, y=None, ldy=256, xhat=None,
              rstd=None, dy=None, lddy=256, w_down_t=None, w_up_t=None, t1=None, g=None, du=None, dx=None, lddx=256, rotate=True,
-             scalenorm=False):
+             scalenorm=False, act=L.MLP_GELU, act_beta=1.0):
     d = L.MlpDesc()
     d.R, d.x, d.ldx, d.eps = R, P(x), ldx, eps
     d.w_up, d.b_up, d.w_down, d.b_down = P(w_up), P(b_up), P(w_down), P(b_down)
@@ -263,7 +282,7 @@ def mlp_desc(R, *, x=None, ldx=256, eps=1e-5, w_up=None, b_up=None, w_down=None,
     d.y, d.ldy, d.xhat, d.rstd = P(y), ldy, P(xhat), P(rstd)
     d.dy, d.lddy, d.w_down_t, d.w_up_t = P(dy), lddy, P(w_down_t), P(w_up_t)
     d.t1, d.g, d.du, d.dx, d.lddx, d.rotate = P(t1), P(g), P(du), P(dx), lddx, int(rotate)
-    d.scalenorm = int(scalenorm)
+    d.scalenorm, d.act, d.act_beta = int(scalenorm), int(act), float(act_beta)
     return d
 
 

@@ -36,7 +36,7 @@ def _flat2d(x):
     return x.contiguous().view(-1, x.shape[-1])
 
 
-def hip_linear(x, lin, act=0, pre_out=None, residual=None):
+def hip_linear(x, lin, act=0, pre_out=None, residual=None, act_scale=1.0):
     """y = act(x @ W^T + b) through mmfm_gemm (fp32)."""
     _need_cuda(x, "hip_linear")
     x2 = _flat2d(x.float())
@@ -44,7 +44,7 @@ def hip_linear(x, lin, act=0, pre_out=None, residual=None):
     N = lin.weight.shape[0]
     y = torch.empty(M, N, device=x.device)
     K.gemm(x2, lin.weight.detach().float().contiguous(), y, M, N, Kd, lda=Kd, ldb=Kd, ldc=N,
-           bias=None if lin.bias is None else lin.bias.detach().float().contiguous(), act=act, pre_out=pre_out,
+           bias=None if lin.bias is None else lin.bias.detach().float().contiguous(), act=act, act_scale=act_scale, pre_out=pre_out,
            residual=residual, ldr=N if residual is not None else 0)
     return y.view(*x.shape[:-1], N)
 
@@ -82,8 +82,7 @@ class ScaleNorm(nn.Module):
 class MLP(nn.Module):
     def __init__(self, hidden_size, inter_size, act, use_bias, dropout):
         super().__init__()
-        if act != "gelu":
-            raise NotImplementedError(f"MLP act '{act}': only exact-erf gelu has a kernel")
+        self.act_kind, self.act_beta = K.mlp_act(act)       # NotImplementedError for a name without a kernel
         self.up_proj = nn.Linear(hidden_size, inter_size, bias=use_bias)
         self.down_proj = nn.Linear(inter_size, hidden_size, bias=use_bias)
         self.dropout = nn.Dropout(dropout)
@@ -91,7 +90,7 @@ class MLP(nn.Module):
     def forward(self, x):
         if self.training and self.dropout.p > 0:
             raise RuntimeError("stand-alone MLP.forward is inference-only; train through MultiModal.forward")
-        return hip_linear(hip_linear(x, self.up_proj, act=L.ACT_GELU), self.down_proj)
+        return hip_linear(hip_linear(x, self.up_proj, act=K.GEMM_ACTS[self.act_kind][0], act_scale=self.act_beta), self.down_proj)
 
 
 class _AttentionBase(nn.Module):
