@@ -186,9 +186,11 @@ typedef struct {
     void* dq; void* dk; void* dv;
     int lddq, lddk, lddv;
     /* optional (round 4): workspace of mmfm_attn_keepbits_bytes(B, heads, Lq, Lk) bytes for the keep decisions of drop_p, one bit
-     * per (b, head, query, key).  With it, launches the dh = 32 fast kernels take (bf16, Lq <= 256, Lk <= 224, both % 8 == 0, no
-     * CAUSAL / SEP, 16-B aligned operands) draw the decisions ONCE - mmfm_attn_fwd runs a generator kernel in front of the
-     * forward - and mmfm_attn_bwd reads the same bits: the caller leaves the buffer alone between the two calls.  The drop
+     * per (b, head, query, key).  With it, launches the dh = 32 fast kernels take (bf16, Lq <= 256, Lk <= 224, both % 8 == 0,
+     * 16-B aligned operands; any combination of DIAG, CAUSAL and SEP) draw the decisions ONCE - mmfm_attn_fwd runs a generator
+     * kernel in front of the forward - and mmfm_attn_bwd reads the same bits: the caller leaves the buffer alone between the two
+     * calls.  Bits of elements the mask rule does not allow are unspecified (under CAUSAL / SEP whole tiles are never read).  The
+     * dh = 64 keep-bit kernels take no CAUSAL / SEP: such launches run on the general kernels, with or without this buffer.  The drop
      * probability is then honoured to 2^-10: keep = mmfm_attn_keep_prob(drop_p.p), survivors are scaled by 1 / keep.
      * NULL (or a shape the fast kernels do not take): both directions re-derive the decisions from the counter hash. */
     void* keepbits;

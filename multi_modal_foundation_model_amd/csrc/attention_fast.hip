@@ -1,6 +1,7 @@
 // bf16 attention, dh = 32, heads of up to 224 keys / 256 queries (the d_model-256 configurations: L = 200): the straight-line
 // forward and the single-pass backward that the step spends its attention time in.  Same contract as attention_bf16.hip
-// (masks: key padding and DIAG; CAUSAL / SEP stay with the general kernels), reference: mm_utils.py:97-152.
+// (masks: the whole rule of include/mmfm.h - key padding, DIAG, CAUSAL, SEP; the dense / DIAG launches run the instantiations they
+// always ran, CAUSAL / SEP launches the MASKED ones, see "mask tiles" below), reference: mm_utils.py:97-152, mm.py:178-194.
 //
 // Round 4: attention-probability dropout no longer hashes inside these kernels.  Both were VALU-issue bound and the counter
 // hash was 27 % of the forward's vector instructions (479 of 1,768) and ~60 us of every backward launch.  Now a generator kernel
@@ -63,6 +64,44 @@ __global__ __launch_bounds__(256) void attn_keepbits_kernel(const KeepArgs a) {
     a.bits[gid] = r;
 }
 
+// ---------------------------------------------------------------------------------------------- mask tiles (CAUSAL / SEP)
+// The MASKED instantiations of both kernels implement the whole rule of include/mmfm.h,
+//   allowed(b,q,k) = (DIAG && q==k) | (CAUSAL ? k<=q : keypad[b][k]) | (SEP && mod_id[q]!=mod_id[k]),
+// by classifying every (query tile, key tile) with wave-uniform values: tq / tk = the tile's modality when all of its 32 positions
+// carry the same mod_id byte, T_MIXED otherwise (the prologue votes per 32-position tile; positions beyond L repeat the last byte).
+//   T_SKIP : no element allowed (above the diagonal under CAUSAL, SEP adding nothing): the tile is not computed at all;
+//   T_BIAS : the rule is the per-key bias the accumulator starts from anyway (key padding, plus the dense kernels' diagonal fix);
+//   T_ZERO : every existing key allowed (below the diagonal under CAUSAL; tiles of two different modalities under SEP);
+//   T_MIXED: the diagonal tile under CAUSAL, tiles with a modality boundary inside under SEP: each accumulator start is set to
+//            0 / -inf from the query index, the key index and the mod_id bytes in LDS, on a branch of its own.
+constexpr int T_SKIP = 0, T_BIAS = 1, T_ZERO = 2, T_MIXED = 3, TMOD_MIXED = 256;
+__device__ __forceinline__ int tile_class(bool causal, bool sep, int tq, int tk, int qt, int kt) {
+    const bool sep_mixed = sep && (tq == TMOD_MIXED || tk == TMOD_MIXED);
+    if (sep && !sep_mixed && tq != tk) return T_ZERO;
+    if (causal) {
+        if (kt < qt) return T_ZERO;
+        if (kt == qt) return T_MIXED;
+        return sep_mixed ? T_MIXED : T_SKIP;
+    }
+    return sep_mixed ? T_MIXED : T_BIAS;
+}
+// the lane's position t of the head: its mod_id byte into LDS, and the vote of its 32-position tile (t >> 5) into tmod[0..7]
+__device__ __forceinline__ void stage_mod(uint8_t* modb, int* tmod, int t, int LP, uint32_t mv) {
+    const int lane = t & 63;
+    if (t < LP) modb[t] = (uint8_t)mv;
+    const uint32_t first = (uint32_t)__shfl((int)mv, lane & 32);
+    const uint64_t eq = __ballot(mv == first);
+    const uint32_t half = (lane & 32) ? (uint32_t)(eq >> 32) : (uint32_t)eq;
+    if ((lane & 31) == 0 && (t >> 5) < 8) tmod[t >> 5] = half == 0xffffffffu ? (int)mv : TMOD_MIXED;
+}
+// accumulator start of one element of a T_MIXED tile: bias = the key's padding bias (0 / -inf)
+__device__ __forceinline__ float mixed_start(int flags, int q, int key, int Lk, float bias, uint32_t mq, uint32_t mk) {
+    bool al = (flags & MMFM_ATTN_CAUSAL) ? key <= q : bias == 0.f;
+    if (flags & MMFM_ATTN_DIAG) al = al || key == q;
+    if (flags & MMFM_ATTN_SEP) al = al || mq != mk;
+    return (al && key < Lk) ? 0.f : -INFINITY;
+}
+
 // ---------------------------------------------------------------------------------------------- forward
 // One key tile (32 keys x 32 queries, lane = query): probabilities of the scores `st` (key bias already inside) against the row's
 // reference exponent, dropout, O^T += V^T P^T.  G = 8-key groups of the tile that exist (registers 4g .. 4g+3), mk = the tile's 16
@@ -110,7 +149,8 @@ constexpr int F_KRS = 80, F_VRS = 64, F_ORS = 80, F_MAXKT = 7;
 constexpr float F_OVERFLOW = 1.2676506e30f;                    // 2^100: a row sum beyond it sends the wave to the exact pass
 
 // NKT = key tiles of the head when known at compile time (7: the L = 200 / 224 step shapes), 0 = read from the descriptor.
-template <int NW, bool DROP, int NKT>
+// MASKED = the launch carries CAUSAL and / or SEP (see "mask tiles" above); false compiles to the dense / DIAG kernel as it was.
+template <int NW, bool DROP, int NKT, bool MASKED>
 __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale) {
     constexpr int NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -126,6 +166,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     char* ost = reinterpret_cast<char*>(kbias + LkP);
     int* wflag = reinterpret_cast<int*>(ost + NW * 32 * F_ORS);          // per-wave "a key of this head is padded" votes (no static LDS:
                                                                          // it would shift the 16-B aligned carve-up, Guideline 17)
+    int* tmod = wflag + 8;                                               // MASKED: per-tile modality votes (second half of the 64 bytes)
+    float* kzero = reinterpret_cast<float*>(wflag + 16);                 // MASKED: 0 for every existing key, -inf beyond Lk
+    uint8_t* modb = reinterpret_cast<uint8_t*>(kzero + LkP);             // MASKED: mod_id bytes
+    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * 32;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * 32;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * 32;
@@ -153,6 +197,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
         if (qt < nqt && q < Lq) qv[ks] = *reinterpret_cast<const uint4*>(qg + (size_t)q * d.ldq + ks * 16 + 8 * kh);
     }
     if (t < Lk && d.keypad != nullptr) kpv = d.keypad[(size_t)b * Lk + t];          // NT >= LkP for every launch shape
+    uint32_t mv = 0u;
+    if constexpr (MASKED) {
+        if (sep && t < LkP) mv = d.mod_id[min(t, Lk - 1)];
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = t + NT * j, row = c >> 2, col = c & 3;
@@ -161,8 +209,12 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
             *reinterpret_cast<uint4*>(Vs + row * F_VRS + col * 16) = vc[j];
         }
     }
-    const bool kok = t < Lk && kpv != 0;
+    const bool kok = t < Lk && (kpv != 0 || causal);    // CAUSAL replaces the key padding: every existing key has bias 0
     if (t < LkP) kbias[t] = kok ? 0.f : -INFINITY;
+    if constexpr (MASKED) {
+        if (t < LkP) kzero[t] = t < Lk ? 0.f : -INFINITY;
+        stage_mod(modb, tmod, t, LkP, mv);
+    }
     const int pad = (t < Lk && !kok) ? 1 : 0;
     const int wv = __any(pad) ? 1 : 0;                  // all 64 lanes vote before any divergence
     if (lane == 0) wflag[wave] = wv;
@@ -180,21 +232,55 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     const bool fixdiag = anypad && (d.flags & MMFM_ATTN_DIAG);
     // the wave's keep-bit tiles: [bh][qt][kt] x 128 B, wave-uniform addresses
     const masks_ptr mkp = reinterpret_cast<masks_ptr>(reinterpret_cast<uintptr_t>(d.keepbits)) + ((size_t)bh_ * nqt + qt) * nkt;
+    // MASKED: the classes of this wave's key tiles as bit sets (bit kt), and the tiles that are walked at all: [0, nkt_run)
+    int m_skip = 0, m_zero = 0, m_mix = 0, nkt_run = nkt;
+    if constexpr (MASKED) {
+        const int tq = sep ? tmod[qt] : 0;
+        nkt_run = 1;
+        for (int kt = 0; kt < nkt; ++kt) {
+            const int c = tile_class(causal, sep, tq, sep ? tmod[kt] : 0, qt, kt);
+            m_skip |= (c == T_SKIP) << kt;
+            m_zero |= (c == T_ZERO) << kt;
+            m_mix |= (c == T_MIXED) << kt;
+            if (c != T_SKIP) nkt_run = kt + 1;
+        }
+        m_skip = __builtin_amdgcn_readfirstlane(m_skip);
+        m_zero = __builtin_amdgcn_readfirstlane(m_zero);
+        m_mix = __builtin_amdgcn_readfirstlane(m_mix);
+        nkt_run = __builtin_amdgcn_readfirstlane(nkt_run);
+    }
+    auto skipped = [&](int kt) { return MASKED && ((m_skip >> kt) & 1); };
 
     // S^T tile: rows = keys (registers), lane = query; the accumulator starts at the key bias
     auto score = [&](int kt) {
         // rare: padded keys in the head and `eye |` (a query always sees itself): the diagonal tile drops the key bias on the diagonal
         const bool dfix = fixdiag && kt == qt;
+        const float* bias = kbias;
+        if constexpr (MASKED) bias = ((m_zero >> kt) & 1) ? kzero : kbias;
         f32x16 a;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const float4 kb4 = *reinterpret_cast<const float4*>(kbias + kt * 32 + 8 * g + 4 * kh);
+            const float4 kb4 = *reinterpret_cast<const float4*>(bias + kt * 32 + 8 * g + 4 * kh);
             a[4 * g + 0] = kb4.x; a[4 * g + 1] = kb4.y; a[4 * g + 2] = kb4.z; a[4 * g + 3] = kb4.w;
         }
         if (dfix) {
             asm volatile("" ::: "memory");               // keeps this a branch: as selects it costs every tile 16 instructions and 32 SGPRs
 #pragma unroll
             for (int r = 0; r < 16; ++r) a[r] = (mrow(r, kh) == l31) ? 0.f : a[r];
+        }
+        if constexpr (MASKED) {
+            if ((m_mix >> kt) & 1) {                     // T_MIXED: the whole rule per element, on a branch like dfix
+                asm volatile("" ::: "memory");
+                const int fl = d.flags;
+                const uint32_t mq = sep ? modb[q] : 0u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const uint32_t mw = sep ? *reinterpret_cast<const uint32_t*>(modb + kt * 32 + 8 * g + 4 * kh) : 0u;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        a[4 * g + i] = mixed_start(fl, q, kt * 32 + 8 * g + 4 * kh + i, Lk, a[4 * g + i], mq, (mw >> (8 * i)) & 0xffu);
+                }
+            }
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -232,12 +318,22 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
                                                 : tile_max<4>(sc[0]), -1e30f / c2) * c2;
 #pragma unroll
         for (int kt = 0; kt < F_MAXKT; ++kt) {
-            if (kt + 1 < nkt) {
-                sc[(kt + 1) & 1] = score(kt + 1);
-                if (DROP) mk[(kt + 1) & 1] = ld_masks(mkp + (kt + 1));
+            if constexpr (!MASKED) {
+                if (kt + 1 < nkt) {
+                    sc[(kt + 1) & 1] = score(kt + 1);
+                    if (DROP) mk[(kt + 1) & 1] = ld_masks(mkp + (kt + 1));
+                }
+                tile(kt, sc[kt & 1], mk[kt & 1]);
+                if (kt + 1 >= nkt) break;
+            } else {
+                // tile 0 is never T_SKIP (k = 0 <= q); skipped tiles cost two scalar branches
+                if (kt + 1 < nkt_run && !skipped(kt + 1)) {
+                    sc[(kt + 1) & 1] = score(kt + 1);
+                    if (DROP) mk[(kt + 1) & 1] = ld_masks(mkp + (kt + 1));
+                }
+                if (!skipped(kt)) tile(kt, sc[kt & 1], mk[kt & 1]);
+                if (kt + 1 >= nkt_run) break;
             }
-            tile(kt, sc[kt & 1], mk[kt & 1]);
-            if (kt + 1 >= nkt) break;
         }
     }
     float l_tot = xhalf_sum(l_run);
@@ -247,7 +343,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
         l_run = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int kt = 0; kt < nkt; ++kt) {
+        for (int kt = 0; kt < nkt_run; ++kt) {
+            if (skipped(kt)) continue;
             const f32x16 st = score(kt);
             Masks16 mk;
             if (DROP) mk = ld_masks(mkp + kt);
@@ -297,9 +394,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     }
 }
 
-size_t fwd_fast_lds(int Lk, int nw) {
+size_t fwd_fast_lds(int Lk, int nw, bool masked) {
     const int LkP = (Lk + 31) & ~31;
-    return (size_t)LkP * (F_KRS + F_VRS + 4) + (size_t)nw * 32 * F_ORS + 64;
+    return (size_t)LkP * (F_KRS + F_VRS + 4) + (size_t)nw * 32 * F_ORS + 64 + (masked ? (size_t)LkP * 5 : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- backward (single pass)
@@ -380,7 +477,8 @@ __device__ __forceinline__ void bwd_tile(const f32x16& s, const f32x16& dpv, flo
 
 // NQT = query tiles of the head when known at compile time (7: the L = 200 / 224 step shapes - the query-tile loop is then straight-line
 // code and every LDS address in it a lane constant plus an immediate), 0 = read from the descriptor.
-template <bool DROP, int NQT>
+// MASKED: as in the forward; a compute wave (one key tile) classifies its query tiles, a skipped tile stages zeros for the dQ wave.
+template <bool DROP, int NQT, bool MASKED>
 __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale) {
     constexpr int NW = B_NW, CW = B_CW, TS = B_TS, TILE = B_TILE, RS = B_RS, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -398,6 +496,9 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     char* stg = reinterpret_cast<char*>(kbias + LkP); // [2][CW][32 keys x TS] dS^T tiles; first the K image (prologue only)
     char* sc7 = stg + 2 * CW * TILE;                  // [32 x B_QRS] dQ transpose tile of wave 7
     uint32_t* flags = reinterpret_cast<uint32_t*>(sc7 + 32 * B_QRS);      // [0..7]: per-wave pad votes
+    int* tmod = reinterpret_cast<int*>(flags + 8);                        // MASKED: per-tile modality votes (rest of the 64 bytes)
+    uint8_t* modb = reinterpret_cast<uint8_t*>(flags + 16);               // MASKED: mod_id bytes [LqP]
+    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * 32;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * 32;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * 32;
@@ -442,6 +543,10 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     uint8_t kpv = 1;
     if (t < Lq) lsev = d.lse[(size_t)bh_ * Lq + t];                               // NT = 512 >= LqP >= LkP
     if (t < Lk && d.keypad != nullptr) kpv = d.keypad[(size_t)b * Lk + t];
+    uint32_t mv = 0u;
+    if constexpr (MASKED) {
+        if (sep && t < LqP) mv = d.mod_id[min(t, Lq - 1)];
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = t + NT * j, row = c >> 2, col = c & 3;
@@ -468,8 +573,9 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
         if (row < LkP) *reinterpret_cast<uint4*>(stg + img_off(row, col)) = kc[j];     // K image, for wave 7's K^T operands only
     }
     if (t < LqP) lse2[t] = lsev * LOG2E;
-    const bool kok = t < Lk && kpv != 0;
+    const bool kok = t < Lk && (kpv != 0 || causal);    // CAUSAL replaces the key padding
     if (t < LkP) kbias[t] = kok ? 0.f : -INFINITY;
+    if constexpr (MASKED) stage_mod(modb, tmod, t, LqP, mv);
     const int pad = (t < Lk && !kok) ? 1 : 0;
     const int wv = __any(pad) ? 1 : 0;
     if (lane == 0) flags[wave] = (uint32_t)wv;
@@ -496,13 +602,49 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
         }
         const float kbv = active ? kbias[key] : 0.f;
         f32x16 s, dpv;
+        // MASKED: the classes of this wave's query tiles as bit sets (bit qt)
+        int m_skip = 0, m_zero = 0, m_mix = 0;
+        if constexpr (MASKED) {
+            if (active) {
+                const int tk = sep ? tmod[kt] : 0;
+                for (int qt = 0; qt < nqt; ++qt) {
+                    const int c = tile_class(causal, sep, sep ? tmod[qt] : 0, tk, qt, kt);
+                    m_skip |= (c == T_SKIP) << qt;
+                    m_zero |= (c == T_ZERO) << qt;
+                    m_mix |= (c == T_MIXED) << qt;
+                }
+            }
+            m_skip = __builtin_amdgcn_readfirstlane(m_skip);
+            m_zero = __builtin_amdgcn_readfirstlane(m_zero);
+            m_mix = __builtin_amdgcn_readfirstlane(m_mix);
+        }
         // lane-constant part of the operand row addresses (row 32 qt + l31 of a swizzled image: + qt * 2048 per tile)
         const int roff0 = l31 * RS + (((0 + kh) ^ ((l31 >> 2) & 3)) << 4), roff1 = l31 * RS + (((2 + kh) ^ ((l31 >> 2) & 3)) << 4);
         auto scoresA = [&](int qt) {
             const char* Aq = As + qt * (32 * RS);
             const char* Bq = Bs + qt * (32 * RS);
             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (!anypad) {
+            bool zero_start = !anypad, mixed = false;
+            if constexpr (MASKED) {
+                zero_start = zero_start || ((m_zero >> qt) & 1);
+                mixed = (m_mix >> qt) & 1;
+            }
+            if (mixed) {
+                // T_MIXED: the whole rule per element (lane = key, register = query)
+                const int fl = d.flags;
+                const uint32_t mk = sep ? modb[key] : 0u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const uint32_t mw = sep ? *reinterpret_cast<const uint32_t*>(modb + qt * 32 + 8 * g + 4 * kh) : 0u;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        s[4 * g + i] = mixed_start(fl, qt * 32 + 8 * g + 4 * kh + i, key, Lk, kbv, (mw >> (8 * i)) & 0xffu, mk);
+                }
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Aq, roff0), kfr[0], s, 0, 0, 0);
+                dpv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Bq, roff0), vfr[0], zero, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Aq, roff1), kfr[1], s, 0, 0, 0);
+                dpv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Bq, roff1), vfr[1], dpv, 0, 0, 0);
+            } else if (zero_start) {
                 // no padded key in this head (the usual case): both products start from the literal zero, no register is initialised
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Aq, roff0), kfr[0], zero, 0, 0, 0);               // S[q][key]
                 dpv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Bq, roff0), vfr[0], zero, 0, 0, 0);             // dP[q][key]
@@ -524,7 +666,15 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
         const int gtail = ((Lq - (nqt - 1) * 32) + 7) >> 3;            // valid 8-query groups of the last query tile (Lq % 8 == 0)
         __syncthreads();                               // wave 7 has its K^T operands: the K image is dead, the staging slots free
         auto step = [&](int qt) {
-            if (active) {
+            bool skip = false;
+            if constexpr (MASKED) skip = (m_skip >> qt) & 1;
+            if (active && skip) {
+                // T_SKIP: nothing of this (query tile, key tile) is allowed; the dQ wave still reads the slot
+                if (DROP) kw_next = kbp[(size_t)min(qt + 1, nqt - 1) * kw_stride];
+                char* slot = stg + ((qt & 1) * CW + wave) * TILE + l31 * TS;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<uint2*>(slot + (8 * j + 4 * kh) * 2) = make_uint2(0u, 0u);
+            } else if (active) {
                 scoresA(qt);
                 uint32_t wq = 0u;
                 if (DROP) {
@@ -591,9 +741,10 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     }
 }
 
-size_t bwd_fast_lds(int Lq, int Lk) {
+size_t bwd_fast_lds(int Lq, int Lk, bool masked) {
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31;
-    return (size_t)2 * LqP * B_RS + (size_t)2 * LqP * 4 + (size_t)LkP * 4 + (size_t)2 * B_CW * B_TILE + (size_t)32 * B_QRS + 64;
+    return (size_t)2 * LqP * B_RS + (size_t)2 * LqP * 4 + (size_t)LkP * 4 + (size_t)2 * B_CW * B_TILE + (size_t)32 * B_QRS + 64 +
+           (masked ? (size_t)LqP : 0);
 }
 
 }  // namespace
@@ -629,7 +780,9 @@ int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st) {
 // Shapes the fast kernels take.  Returns -1000 when the general kernels must run.
 int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_FAST"); return e && atoi(e) == 0; }();
-    if (off || d.dh != 32 || (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP))) return -1000;
+    if (off || d.dh != 32) return -1000;
+    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
+    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return -1000;
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32;
     if (d.Lq % 8 || d.Lk % 8 || nqt > 8 || nkt > B_CW || nkt > nqt) return -1000;
     const bool drop = d.drop_p.p > 0.f && d.drop_p.state != nullptr;
@@ -653,13 +806,14 @@ int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
     if (!backward) {
         if (drop) { if (int rc = mmfm_attn_keepbits_launch(d, st)) return rc; }
         const int nw = nqt <= 4 ? 4 : (nqt == 7 ? 7 : (nqt <= 6 ? 6 : 8));
-        const size_t lds = fwd_fast_lds(d.Lk, nw);
-#define FWDF3(NWV, DRP, NKT)                                                                                        \
+        const size_t lds = fwd_fast_lds(d.Lk, nw, masked);
+#define FWDF4(NWV, DRP, NKT, MSK)                                                                                   \
         {                                                                                                           \
-            auto kern = attn_fwd_fast_kernel<NWV, DRP, NKT>;                                                        \
+            auto kern = attn_fwd_fast_kernel<NWV, DRP, NKT, MSK>;                                                   \
             if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_fwd(bf16, dh 32)")) return rc; \
             hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, st, d, keep_scale);                           \
         }
+#define FWDF3(NWV, DRP, NKT) { if (masked) FWDF4(NWV, DRP, NKT, true) else FWDF4(NWV, DRP, NKT, false) }
 #define FWDF(NWV)                                                                                                   \
         {                                                                                                           \
             if (drop) { if (nkt == 7 && NWV >= 7) FWDF3(NWV, true, 7) else FWDF3(NWV, true, 0) }                    \
@@ -668,19 +822,22 @@ int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         if (nw == 4) FWDF(4) else if (nw == 6) FWDF(6) else if (nw == 7) FWDF(7) else FWDF(8)
 #undef FWDF
 #undef FWDF3
+#undef FWDF4
         MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, dh 32)");
         return 0;
     }
-    const size_t lds = nqt == 7 ? bwd_fast_lds(224, 224) : bwd_fast_lds(d.Lq, d.Lk);
-#define BWDF3(DRP, NQ)                                                                                              \
+    const size_t lds = nqt == 7 ? bwd_fast_lds(224, 224, masked) : bwd_fast_lds(d.Lq, d.Lk, masked);
+#define BWDF4(DRP, NQ, MSK)                                                                                         \
     {                                                                                                               \
-        auto kern = attn_bwd_fast_kernel<DRP, NQ>;                                                                  \
+        auto kern = attn_bwd_fast_kernel<DRP, NQ, MSK>;                                                             \
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16, dh 32)")) return rc; \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(B_NW * 64), lds, st, d, keep_scale);                              \
     }
+#define BWDF3(DRP, NQ) { if (masked) BWDF4(DRP, NQ, true) else BWDF4(DRP, NQ, false) }
     if (drop) { if (nqt == 7) BWDF3(true, 7) else BWDF3(true, 0) }
     else { if (nqt == 7) BWDF3(false, 7) else BWDF3(false, 0) }
 #undef BWDF3
+#undef BWDF4
     MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, dh 32)");
     return 0;
 }

@@ -683,7 +683,9 @@ class Engine:
                       ln_bwd=2 if self.is_sn(lnname) else 1, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
 
         enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
-        dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)   # mm.py:178-194
+        # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
+        # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
+        dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)
 
         # ============================================================ forward
         K.mask_prep(B, T, [self.b[f"mask/{m}"] for m in range(M)], [1] * M, attn, [n for _, n in c.mods], tokmask, keypad, keep0,
