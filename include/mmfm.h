@@ -415,6 +415,20 @@ int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float* gamma, co
 int mmfm_sn_linear_grad(const float* Gdb, const float* W, const float* g, int N, int K, float* dW, float* dbias, float* dg,
                         int accumulate, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
+/* ------------------------------------------------------------------ MT19937 jump-ahead (HOST memory, no device, no HIP call)
+ * Moves an MT19937 state (the engine of torch's CPU generator) on by n 32-bit outputs without drawing them: what the masker's
+ * discarded [B, T, N] corruption draws (models/masker.py:157-163 under mm.py:267) amount to.  Works in a process that never
+ * initialised HIP.
+ *   state624: the 624 state words, regenerated in place as the engine does;
+ *   consumed: in/out, words of the current block already handed out, 0..624 (624: the next output regenerates first; a freshly
+ *             seeded engine, which has handed out nothing of its seed block, is 624 too);
+ *   n:        outputs to skip.  Afterwards consumed is 1..624 whenever a block boundary was crossed.
+ * The result is bit-identical to n real draws.  Long moves jump whole blocks through t^(624 D) mod phi (phi: the characteristic
+ * polynomial, found once per process; one polynomial per block count D is cached), short ones step the recurrence. */
+int mmfm_mt19937_jump(uint32_t* state624, int32_t* consumed, uint64_t n);
+/* Drops the cached polynomials (the next long jump pays for phi and its power again): cold-cost measurements. */
+int mmfm_mt19937_jump_reset(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,8 @@ _PROTOS = {
     "mmfm_bits_per_spike": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "mmfm_bits_per_spike_neurons_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_bits_per_spike_neurons": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
+    "mmfm_mt19937_jump": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_uint64]),
+    "mmfm_mt19937_jump_reset": (C.c_int, []),
 }
 
 _lib = None

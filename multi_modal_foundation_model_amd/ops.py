@@ -308,3 +308,19 @@ def sn_linear_grad(Gdb, W, g, N, K, dW, dbias, dg, ws, accumulate=False, plan=No
     """ScaleNorm-fed linear: dW = g * G, dbias = db, dg (+)= sum W * G (mmfm_sn_linear_grad; ws as for ln_linear_grad)."""
     _emit(plan, L.lib().mmfm_sn_linear_grad, (P(Gdb), P(W), P(g), N, K, P(dW), P(dbias), P(dg), int(accumulate), P(ws), ws.numel() * 4),
           keep=(ws,))
+
+
+def mt19937_jump(state, consumed, n):
+    """Moves an MT19937 state on by `n` outputs without drawing (mmfm_mt19937_jump; host memory, no device involved).
+    `state`: contiguous CPU int32 tensor of the 624 state words, updated in place; `consumed`: words of the current block
+    already handed out (0..624).  Returns the new `consumed`."""
+    if state.device.type != "cpu" or state.dtype != torch.int32 or state.numel() != 624 or not state.is_contiguous():
+        raise TypeError("mt19937_jump: state must be a contiguous CPU int32 tensor of 624 words")
+    c = C.c_int32(int(consumed))
+    L.check(L.lib().mmfm_mt19937_jump(state.data_ptr(), C.byref(c), int(n)), "mmfm_mt19937_jump")
+    return c.value
+
+
+def mt19937_jump_reset():
+    """Drops the cached jump polynomials (cold-cost measurements)."""
+    L.check(L.lib().mmfm_mt19937_jump_reset(), "mmfm_mt19937_jump_reset")

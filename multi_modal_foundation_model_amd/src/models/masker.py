@@ -8,6 +8,7 @@ generator calls below are what makes the masks bit-exact against the reference
 bernoulli(zero_ratio x shape), bernoulli(random_ratio x shape), rand(shape) — all on the CPU
 generator, wherever `spikes` lives.
 """
+import os
 import random
 
 import numpy as np
@@ -83,8 +84,12 @@ class Masker(nn.Module):
     def _no_mask(spikes):
         return spikes, torch.zeros_like(spikes).to(torch.int64)
 
-    def forward(self, spikes, neuron_regions=None, token_mask_only=False):
-        """`token_mask_only=True` (callers that discard the returned spikes only): skip the zero / random corruption draws."""
+    def forward(self, spikes, neuron_regions=None, token_mask_only=False, spikes_discarded=False):
+        """`token_mask_only=True` (callers that discard the returned spikes only): skip the zero / random corruption draws.
+        `spikes_discarded=True` (the same callers): stay on the reference's generator stream, but move the CPU generator past the
+        three [B, T, N] corruption draws by jump-ahead (rngjump.py) instead of taking them; the spikes come back untouched, the masks
+        and the generator state afterwards are those of the drawing path.  MMFM_MASKER_JUMP=0 takes the three draws for real (and
+        still leaves the spikes alone)."""
         inactive = (not self.training and not self.force_active) or self.target_regions is None \
             or self.mask_regions is None or self.ratio == 0
         if inactive:
@@ -156,7 +161,19 @@ class Masker(nn.Module):
         else:
             mask = drawn.bool()
 
-        if not token_mask_only:
+        if token_mask_only:
+            pass
+        elif spikes_discarded:
+            # bernoulli(zero_ratio x shape), bernoulli(random_ratio x shape), rand(shape): one 32-bit output per element each, and
+            # nobody reads the values
+            if os.environ.get("MMFM_MASKER_JUMP", "1") != "0":
+                from multi_modal_foundation_model_amd.rngjump import advance_cpu_generator
+                advance_cpu_generator(3 * B * T * N)
+            else:
+                torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio)))
+                torch.bernoulli(torch.full((B, T, N), float(self.random_ratio)))
+                torch.rand((B, T, N))
+        else:
             zero_idx = torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio))).to(dev).bool() & mask
             spikes[zero_idx] = 0
             rand_idx = torch.bernoulli(torch.full((B, T, N), float(self.random_ratio))).to(dev).bool() & mask & ~zero_idx

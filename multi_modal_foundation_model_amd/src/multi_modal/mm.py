@@ -152,8 +152,10 @@ class MultiModal(nn.Module):
                 raise UnboundLocalError("local variable 'mask' referenced before assignment "
                                         "(upstream behaviour of mask_type='input', mm.py:256-272)")
             if d['eval_mask'] is None:
-                # the corrupted spikes are discarded here (mm.py:267), so the trainer's token-mask-only switch applies
-                _, mask = self.masker(d['inputs'].clone(), regions, token_mask_only=bool(self.masker.token_mask_only))
+                # the corrupted spikes are discarded here (mm.py:267), so the trainer's token-mask-only switch applies; on the
+                # reference-exact stream the masker skips their draws by jump-ahead (same masks, same generator state afterwards)
+                _, mask = self.masker(d['inputs'].clone(), regions, token_mask_only=bool(self.masker.token_mask_only),
+                                      spikes_discarded=True)
             else:
                 mask = d['eval_mask']
             mask = mask[:, :, 0] & d['inputs_attn_mask']

@@ -103,7 +103,9 @@ class MultiModalTrainer():
         # (mm.py:262-267), so the masker's three full-size [B, T, N] host draws are dead work (330 ms per step at B = 1024, ten GPU
         # steps).  The trainer therefore switches the masker to its token-mask-only stream - identically distributed masks, a
         # shorter walk through the host generator - unless `training.exact_masker_stream: true` (or MMFM_EXACT_MASKER=1) asks for
-        # the reference's exact generator stream, which the parity tests do.
+        # the reference's exact generator stream, which the parity tests do.  That stream no longer pays for the dead draws either: the
+        # model tells the masker that the spikes are discarded and the masker moves the generator past them by jump-ahead (rngjump.py,
+        # under 1 ms of host time per call), bit-identical to drawing.
         masker = getattr(self.model, "masker", None)
         exact = bool(self.config.training.get("exact_masker_stream", False)) if hasattr(self.config.training, "get") else False
         exact = exact or os.environ.get("MMFM_EXACT_MASKER", "0") == "1"
@@ -114,7 +116,10 @@ class MultiModalTrainer():
                 print("(train) masker stream: " + (
                     "token-mask-only (same mask distribution; from the second masker call on NOT the reference's generator stream - "
                     "set training.exact_masker_stream: true or MMFM_EXACT_MASKER=1 for bit-exact masks)" if masker.token_mask_only
-                    else "reference-exact (every [B,T,N] corruption draw of models/masker.py is taken)"))
+                    else "reference-exact (the discarded [B,T,N] corruption draws of models/masker.py are skipped by MT19937 jump-ahead: "
+                         "same masks, same generator state; MMFM_MASKER_JUMP=0 takes them for real)"
+                    if os.environ.get("MMFM_MASKER_JUMP", "1") != "0"
+                    else "reference-exact (every [B,T,N] corruption draw of models/masker.py is taken: MMFM_MASKER_JUMP=0)"))
         # host-side constants of the batch -> mod_dict translation, built once instead of every step: the
         # modality-index scalars (a pageable H2D copy each = a stream drain per call) and the [B, N] region array
         self._mod_index_cache = {}
