@@ -189,10 +189,19 @@ typedef struct {
      * per (b, head, query, key).  With it, launches the dh = 32 fast kernels take (bf16, Lq <= 256, Lk <= 224, both % 8 == 0,
      * 16-B aligned operands; any combination of DIAG, CAUSAL and SEP) draw the decisions ONCE - mmfm_attn_fwd runs a generator
      * kernel in front of the forward - and mmfm_attn_bwd reads the same bits: the caller leaves the buffer alone between the two
-     * calls.  Bits of elements the mask rule does not allow are unspecified (under CAUSAL / SEP whole tiles are never read).  The
-     * dh = 64 keep-bit kernels take no CAUSAL / SEP: such launches run on the general kernels, with or without this buffer.  The drop
+     * calls.  Bits of elements the mask rule does not allow are unspecified (under CAUSAL / SEP whole tiles are never read).  The drop
      * probability is then honoured to 2^-10: keep = mmfm_attn_keep_prob(drop_p.p), survivors are scaled by 1 / keep.
-     * NULL (or a shape the fast kernels do not take): both directions re-derive the decisions from the counter hash. */
+     * NULL (or a shape the fast kernels do not take): both directions re-derive the decisions from the counter hash.
+     * dh = 64 (bf16, any Lq / Lk % 8 == 0, 16-B aligned operands, leading dims % 8 == 0; any combination of DIAG, CAUSAL and SEP,
+     * CAUSAL / SEP with Lq == Lk): here the workspace SELECTS the kernel pair, with or without drop_p - a non-NULL keepbits sends
+     * both directions to the keep-bit kernels, NULL to the general ones.  On that pair (i) dq is scratch until mmfm_attn_bwd
+     * returns: a first kernel writes the output-dropout'd d_o there and the dQ phase overwrites it with dq, so dq must not alias
+     * d_o, q, k or v; (ii) the tail of the workspace, behind the bit tiles, holds one float per (b, head, query) - the backward's
+     * delta - which is why mmfm_attn_keepbits_bytes is more than the tiles; (iii) gradient tensors that are not 16-B aligned with
+     * leading dims % 8 == 0 are an error, not a fallback (the forward already took its decisions from the bits).  The kernels'
+     * LDS grows with Lk (key bias; under CAUSAL / SEP also a second bias row, the mod_id bytes and the tile votes): when the
+     * forward or the dQ phase would need more than the 160 KB a workgroup can have (Lk above ~22,000 dense, ~9,800 with CAUSAL /
+     * SEP), the shape runs on the general kernels in both directions, as every other shape this pair does not take. */
     void* keepbits;
 } mmfm_attn_desc;
 int mmfm_attn_fwd(const mmfm_attn_desc* d, mmfm_stream stream);

@@ -74,17 +74,7 @@ __global__ __launch_bounds__(256) void attn_keepbits_kernel(const KeepArgs a) {
 //   T_ZERO : every existing key allowed (below the diagonal under CAUSAL; tiles of two different modalities under SEP);
 //   T_MIXED: the diagonal tile under CAUSAL, tiles with a modality boundary inside under SEP: each accumulator start is set to
 //            0 / -inf from the query index, the key index and the mod_id bytes in LDS, on a branch of its own.
-constexpr int T_SKIP = 0, T_BIAS = 1, T_ZERO = 2, T_MIXED = 3, TMOD_MIXED = 256;
-__device__ __forceinline__ int tile_class(bool causal, bool sep, int tq, int tk, int qt, int kt) {
-    const bool sep_mixed = sep && (tq == TMOD_MIXED || tk == TMOD_MIXED);
-    if (sep && !sep_mixed && tq != tk) return T_ZERO;
-    if (causal) {
-        if (kt < qt) return T_ZERO;
-        if (kt == qt) return T_MIXED;
-        return sep_mixed ? T_MIXED : T_SKIP;
-    }
-    return sep_mixed ? T_MIXED : T_BIAS;
-}
+// (T_SKIP .. T_MIXED, tile_class and mixed_start live in attn_common.h: attention_long.hip classifies its tiles the same way.)
 // the lane's position t of the head: its mod_id byte into LDS, and the vote of its 32-position tile (t >> 5) into tmod[0..7]
 __device__ __forceinline__ void stage_mod(uint8_t* modb, int* tmod, int t, int LP, uint32_t mv) {
     const int lane = t & 63;
@@ -94,14 +84,6 @@ __device__ __forceinline__ void stage_mod(uint8_t* modb, int* tmod, int t, int L
     const uint32_t half = (lane & 32) ? (uint32_t)(eq >> 32) : (uint32_t)eq;
     if ((lane & 31) == 0 && (t >> 5) < 8) tmod[t >> 5] = half == 0xffffffffu ? (int)mv : TMOD_MIXED;
 }
-// accumulator start of one element of a T_MIXED tile: bias = the key's padding bias (0 / -inf)
-__device__ __forceinline__ float mixed_start(int flags, int q, int key, int Lk, float bias, uint32_t mq, uint32_t mk) {
-    bool al = (flags & MMFM_ATTN_CAUSAL) ? key <= q : bias == 0.f;
-    if (flags & MMFM_ATTN_DIAG) al = al || key == q;
-    if (flags & MMFM_ATTN_SEP) al = al || mq != mk;
-    return (al && key < Lk) ? 0.f : -INFINITY;
-}
-
 // ---------------------------------------------------------------------------------------------- forward
 // One key tile (32 keys x 32 queries, lane = query): probabilities of the scores `st` (key bias already inside) against the row's
 // reference exponent, dropout, O^T += V^T P^T.  G = 8-key groups of the tile that exist (registers 4g .. 4g+3), mk = the tile's 16

@@ -1,6 +1,7 @@
 // bf16 attention, dh = 64, any sequence length (BASELINE configs[4]: d_model 512, 8 heads, L = 600): the keep-bit kernels for heads
-// whose K / V images do not fit the LDS.  Same contract as attention_bf16.hip (masks: key padding and DIAG; CAUSAL / SEP stay with the
-// general kernels), reference: mm_utils.py:97-152.  They replace the round-1 tiled pair (attention_bf16.hip: 0.99 ms forward, 2.64 ms
+// whose K / V images do not fit the LDS.  Same contract as attention_bf16.hip (masks: the whole rule of include/mmfm.h - key padding,
+// DIAG, CAUSAL, SEP; dense / DIAG launches run the instantiations they always ran, CAUSAL / SEP launches the MASKED ones, see "mask
+// tiles" below), reference: mm_utils.py:97-152, mm.py:178-194.  They replace the round-1 tiled pair (attention_bf16.hip: 0.99 ms forward, 2.64 ms
 // two-phase backward per launch at B = 256, L = 600 - 54 of the 98 ms config-5 step) whenever the caller provides the keep-bit
 // workspace (mmfm_attn_desc.keepbits):
 //   * dropout decisions are the generator kernel's bit tiles (attention_fast.hip): scalar lane masks where the lane is the query
@@ -63,10 +64,12 @@ __device__ __forceinline__ float tile_max16(const f32x16& st) {
 
 // key bias of a head (0 / -inf per key, -inf beyond Lk) into LDS + "some key of the head is padded" (wave-uniform)
 template <int NW>
-__device__ __forceinline__ int stage_kbias(float* kbias, int* wflag, const uint8_t* keypad, int b, int Lk, int LkP, int t, int wave, int lane) {
+__device__ __forceinline__ int stage_kbias(float* kbias, int* wflag, const uint8_t* keypad, int b, int Lk, int LkP, int t, int wave, int lane,
+                                           bool causal = false) {
     int pad = 0;
     for (int i = t; i < LkP; i += NW * 64) {
-        const bool ok = i < Lk && (keypad == nullptr || keypad[(size_t)b * Lk + i] != 0);
+        // CAUSAL replaces the key padding: every existing key has bias 0
+        const bool ok = i < Lk && (causal || keypad == nullptr || keypad[(size_t)b * Lk + i] != 0);
         kbias[i] = ok ? 0.f : -INFINITY;
         pad |= (i < Lk && !ok) ? 1 : 0;
     }
@@ -79,8 +82,81 @@ __device__ __forceinline__ int stage_kbias(float* kbias, int* wflag, const uint8
     return __builtin_amdgcn_readfirstlane(any);
 }
 
-// S^T tile of key tile (rows kl*32.. of the K image) against the wave's Q fragments, starting from the key bias
-__device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, int kl, const bf16x8v (&qf)[KS], bool dfix, int kh, int l31) {
+// ---------------------------------------------------------------------------------------------- mask tiles (CAUSAL / SEP)
+// The MASKED instantiations of the three kernels implement the whole rule of include/mmfm.h with the four tile classes of
+// attention_fast.hip (attn_common.h: tile_class, mixed_start).  Heads have any length here, so what the dh = 32 kernels keep in eight
+// words lives in LDS arrays sized by the padded length LP (Lq == Lk: launcher), behind the key bias:
+//   tmod[LP / 32]  the vote of every 32-position tile: its modality if all 32 mod_id bytes agree (positions beyond L repeat the last
+//                  byte), TMOD_MIXED otherwise;
+//   cneed[nch]     1 when some wave of the workgroup has a tile of streamed chunk c that is not T_SKIP: a chunk nobody needs is neither
+//                  loaded nor staged (a workgroup-uniform walk, so the chunk barriers stay matched);
+//   modb[LP]       the mod_id bytes, for the per-element rule of T_MIXED tiles;
+// and (forward, dQ phase) kzero[LP], the second bias row of T_ZERO tiles: 0 for every existing key, -inf beyond Lk.
+struct MaskLds {
+    int* tmod;
+    int* cneed;
+    uint8_t* modb;
+};
+__device__ __forceinline__ MaskLds carve_mask(void* p, int LP) {
+    MaskLds m;
+    m.tmod = reinterpret_cast<int*>(p);
+    m.cneed = m.tmod + (LP >> 5);
+    m.modb = reinterpret_cast<uint8_t*>(m.cneed + (LP + CH - 1) / CH);
+    return m;
+}
+size_t mask_lds(int LP) { return (size_t)(LP >> 5) * 4 + (size_t)((LP + CH - 1) / CH) * 4 + (size_t)LP + 16; }
+
+// mod_id bytes and tile votes of the head, cneed cleared.  The caller's next workgroup barrier publishes them.
+template <int NT>
+__device__ __forceinline__ void stage_mask(const MaskLds& m, const uint8_t* mod_id, bool sep, int L, int LP, int nch, int t) {
+    const int lane = t & 63;
+    for (int i0 = 0; i0 < LP; i0 += NT) {          // workgroup-uniform trip count: every lane of a wave takes part in the ballot
+        const int i = i0 + t;
+        uint32_t mv = 0u;
+        if (sep && i < LP) mv = mod_id[min(i, L - 1)];
+        const uint32_t first = (uint32_t)__shfl((int)mv, lane & 32);
+        const uint64_t eq = __ballot(mv == first);
+        const uint32_t half = (lane & 32) ? (uint32_t)(eq >> 32) : (uint32_t)eq;
+        if (i < LP) {                               // LP % 32 == 0: a wave half lies wholly inside or wholly outside
+            m.modb[i] = (uint8_t)mv;
+            if ((lane & 31) == 0) m.tmod[i >> 5] = half == 0xffffffffu ? (int)mv : TMOD_MIXED;
+        }
+    }
+    for (int i = t; i < nch; i += NT) m.cneed[i] = 0;
+}
+// every active wave marks the streamed chunks in which its own tile (a query tile when OWN_Q, else a key tile) meets a tile that is
+// not T_SKIP; ends with the barrier that publishes cneed
+template <bool OWN_Q>
+__device__ __forceinline__ void vote_chunks(const MaskLds& m, bool causal, bool sep, bool active, int own, int ntiles, int nch, int lane) {
+    if (active) {
+        const int town = sep ? m.tmod[own] : 0;
+        for (int c = lane; c < nch; c += 64) {
+            bool need = false;
+            for (int j = 0; j < CH / 32; ++j) {
+                const int o = c * (CH / 32) + j;
+                if (o < ntiles) {
+                    const int toth = sep ? m.tmod[o] : 0;
+                    need |= (OWN_Q ? tile_class(causal, sep, town, toth, own, o) : tile_class(causal, sep, toth, town, o, own)) != T_SKIP;
+                }
+            }
+            if (need) m.cneed[c] = 1;
+        }
+    }
+    __syncthreads();
+}
+// the first needed chunk after c (nch: none); workgroup-uniform
+__device__ __forceinline__ int next_needed(const int* cneed, int c, int nch) {
+    int n = c + 1;
+    while (n < nch && __builtin_amdgcn_readfirstlane(cneed[n]) == 0) ++n;
+    return n;
+}
+
+// S^T tile of key tile (rows kl*32.. of the K image) against the wave's Q fragments, starting from the key bias.  MASKED and `mixed`
+// (a T_MIXED tile): every accumulator start is set from the whole rule, for query q and keys key0 + .., on a branch like dfix
+template <bool MASKED = false>
+__device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, int kl, const bf16x8v (&qf)[KS], bool dfix, int kh, int l31,
+                                             bool mixed = false, int flags = 0, int q = 0, int key0 = 0, int Lk = 0,
+                                             const uint8_t* modb = nullptr) {
     f32x16 a;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -92,6 +168,20 @@ __device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, in
 #pragma unroll
         for (int r = 0; r < 16; ++r) a[r] = (mrow(r, kh) == l31) ? 0.f : a[r];
     }
+    if constexpr (MASKED) {
+        if (mixed) {
+            asm volatile("" ::: "memory");
+            const bool sep = flags & MMFM_ATTN_SEP;
+            const uint32_t mq = sep ? modb[q] : 0u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t mw = sep ? *reinterpret_cast<const uint32_t*>(modb + key0 + 8 * g + 4 * kh) : 0u;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    a[4 * g + i] = mixed_start(flags, q, key0 + 8 * g + 4 * kh + i, Lk, a[4 * g + i], mq, (mw >> (8 * i)) & 0xffu);
+            }
+        }
+    }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
         a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Ks, (kl * 32 + l31) * RS + ks * 32 + kh * 16), qf[ks], a, 0, 0, 0);
@@ -100,7 +190,8 @@ __device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, in
 
 // ---------------------------------------------------------------------------------------------- forward
 constexpr int F_NW = 8;
-template <bool DROP>
+// MASKED = the launch carries CAUSAL and / or SEP (see "mask tiles" above); false compiles to the dense / DIAG kernel as it was.
+template <bool DROP, bool MASKED>
 __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_attn_desc d, const float keep_scale) {
     constexpr int NW = F_NW, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -115,6 +206,9 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
     char* ost = Vs + CH * RS;                          // [NW][32][RS] output transpose tiles
     float* kbias = reinterpret_cast<float*>(ost + NW * 32 * RS);
     int* wflag = reinterpret_cast<int*>(kbias + LkP);
+    float* kzero = reinterpret_cast<float*>(wflag + 16);           // MASKED: the bias row of T_ZERO tiles
+    const MaskLds ml = carve_mask(kzero + LkP, LkP);               // MASKED: tile votes, chunk votes, mod_id bytes
+    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * DH;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * DH;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * DH;
@@ -131,7 +225,16 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
         if (active && q < Lq) v = *reinterpret_cast<const uint4*>(qg + (size_t)q * d.ldq + ks * 16 + 8 * kh);
         qf[ks] = __builtin_bit_cast(bf16x8v, v);
     }
-    const int anypad = stage_kbias<NW>(kbias, wflag, d.keypad, b, Lk, LkP, t, wave, lane);
+    if constexpr (MASKED) {
+        for (int i = t; i < LkP; i += NT) kzero[i] = i < Lk ? 0.f : -INFINITY;
+        stage_mask<NT>(ml, d.mod_id, sep, Lk, LkP, nch, t);
+    }
+    const int anypad = stage_kbias<NW>(kbias, wflag, d.keypad, b, Lk, LkP, t, wave, lane, causal);
+    int tq = 0;                                        // MASKED: the vote of this wave's query tile
+    if constexpr (MASKED) {
+        vote_chunks<true>(ml, causal, sep, active, qt, nkt, nch, lane);
+        if (sep && active) tq = __builtin_amdgcn_readfirstlane(ml.tmod[qt]);
+    }
     const bool fixdiag = anypad && (d.flags & MMFM_ATTN_DIAG);
     const float c2 = d.scale * LOG2E;
     const masks_ptr mkp = reinterpret_cast<masks_ptr>(reinterpret_cast<uintptr_t>(d.keepbits)) + ((size_t)bh_ * nqt + (active ? qt : 0)) * nkt;
@@ -147,17 +250,28 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
         for (int i = 0; i < DT; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        for (int c = 0; c < nch; ++c) {
+        // MASKED: the walk visits the chunks some wave needs (chunk 0 always is: tile 0 is never T_SKIP, k = 0 <= q)
+        for (int c = 0, cn; c < nch; c = cn) {
+            cn = c + 1;
+            if constexpr (MASKED) cn = next_needed(ml.cneed, c, nch);
             __syncthreads();                           // readers of the previous chunk are done
             stg.store(Ks, Vs, t);
             // the next chunk's loads fly while this one is multiplied (after the last chunk: chunk 0 again, for a possible second pass)
-            stg.load(kg, d.ldk, vg, d.ldv, (c + 1 < nch ? c + 1 : 0) * CH, Lk, t);
+            stg.load(kg, d.ldk, vg, d.ldv, (cn < nch ? cn : 0) * CH, Lk, t);
             __syncthreads();
             if (!active) continue;
             const int ntl = min(CH / 32, nkt - c * (CH / 32));
             for (int kl = 0; kl < ntl; ++kl) {
                 const int kt = c * (CH / 32) + kl;
-                const f32x16 st = score_tile(Ks, kbias + kt * 32, kl, qf, fixdiag && kt == qt, kh, l31);
+                const float* kb = kbias;
+                bool mixed = false;
+                if constexpr (MASKED) {
+                    const int cls = __builtin_amdgcn_readfirstlane(tile_class(causal, sep, tq, sep ? ml.tmod[kt] : 0, qt, kt));
+                    if (cls == T_SKIP) continue;       // contributes exactly nothing; its keep bits are never read
+                    if (cls == T_ZERO) kb = kzero;
+                    mixed = cls == T_MIXED;
+                }
+                const f32x16 st = score_tile<MASKED>(Ks, kb + kt * 32, kl, qf, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
                 Masks16 mk;
                 if (DROP) mk = ld_masks(mkp + kt);
                 if (EXACT) {
@@ -242,9 +356,9 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
             *reinterpret_cast<uint4*>(og + (size_t)(q0 + row) * d.ldo + 8 * c) = *reinterpret_cast<const uint4*>(tl + row * RS + c * 16);
     }
 }
-size_t fwd_long_lds(int Lk) {
+size_t fwd_long_lds(int Lk, bool masked) {
     const int LkP = (Lk + 31) & ~31;
-    return (size_t)2 * CH * RS + (size_t)F_NW * 32 * RS + (size_t)LkP * 4 + 64;
+    return (size_t)2 * CH * RS + (size_t)F_NW * 32 * RS + (size_t)LkP * 4 + 64 + (masked ? (size_t)LkP * 4 + mask_lds(LkP) : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- backward: per-query constants
@@ -287,7 +401,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_prep_kernel(const mmfm_attn
 // ---------------------------------------------------------------------------------------------- backward, dQ phase
 // A workgroup owns eight query tiles (one per wave: Q, d_o', lse, delta in registers, the query on the lane) and streams K / V.
 constexpr int Q_NW = 8;
-template <bool DROP>
+template <bool DROP, bool MASKED>
 __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
     constexpr int NW = Q_NW, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -302,6 +416,9 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
     char* sct = Vs + CH * RS;                          // [NW][32][RS] dQ transpose tiles
     float* kbias = reinterpret_cast<float*>(sct + NW * 32 * RS);
     int* wflag = reinterpret_cast<int*>(kbias + LkP);
+    float* kzero = reinterpret_cast<float*>(wflag + 16);           // MASKED: as in the forward
+    const MaskLds ml = carve_mask(kzero + LkP, LkP);
+    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * DH;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * DH;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * DH;
@@ -331,7 +448,16 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
         lq = d.lse[(size_t)bh_ * Lq + q] * LOG2E;
         dq_ = dl[(size_t)bh_ * Lq + q];
     }
-    const int anypad = stage_kbias<NW>(kbias, wflag, d.keypad, b, Lk, LkP, t, wave, lane);
+    if constexpr (MASKED) {
+        for (int i = t; i < LkP; i += NT) kzero[i] = i < Lk ? 0.f : -INFINITY;
+        stage_mask<NT>(ml, d.mod_id, sep, Lk, LkP, nch, t);
+    }
+    const int anypad = stage_kbias<NW>(kbias, wflag, d.keypad, b, Lk, LkP, t, wave, lane, causal);
+    int tq = 0;
+    if constexpr (MASKED) {
+        vote_chunks<true>(ml, causal, sep, active, qt, nkt, nch, lane);
+        if (sep && active) tq = __builtin_amdgcn_readfirstlane(ml.tmod[qt]);
+    }
     const bool fixdiag = anypad && (d.flags & MMFM_ATTN_DIAG);
     const float c2 = d.scale * LOG2E, osc = d.scale * keep_scale;
     const masks_ptr mkp = reinterpret_cast<masks_ptr>(reinterpret_cast<uintptr_t>(d.keepbits)) + ((size_t)bh_ * nqt + (active ? qt : 0)) * nkt;
@@ -342,7 +468,9 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
         for (int r = 0; r < 16; ++r) dQt[i][r] = 0.f;
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (int c = 0; c < nch; ++c) {
+    for (int c = 0, cn; c < nch; c = cn) {             // MASKED: the chunks some wave needs, as in the forward
+        cn = c + 1;
+        if constexpr (MASKED) cn = next_needed(ml.cneed, c, nch);
         // (no register prefetch of the next chunk here: with Q, d_o' and two dQ tiles resident the 16 staging registers spill)
         if (c > 0) stg.load(kg, d.ldk, vg, d.ldv, c * CH, Lk, t);
         __syncthreads();
@@ -352,7 +480,16 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
         const int ntl = min(CH / 32, nkt - c * (CH / 32));
         for (int kl = 0; kl < ntl; ++kl) {
             const int kt = c * (CH / 32) + kl;
-            const f32x16 s = score_tile(Ks, kbias + kt * 32, kl, qfr, fixdiag && kt == qt, kh, l31);       // S^T[key][q] + key bias
+            const float* kb = kbias;
+            bool mixed = false;
+            if constexpr (MASKED) {
+                const int cls = __builtin_amdgcn_readfirstlane(tile_class(causal, sep, tq, sep ? ml.tmod[kt] : 0, qt, kt));
+                if (cls == T_SKIP) continue;
+                if (cls == T_ZERO) kb = kzero;
+                mixed = cls == T_MIXED;
+            }
+            // S^T[key][q] + key bias
+            const f32x16 s = score_tile<MASKED>(Ks, kb + kt * 32, kl, qfr, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
             f32x16 dpv = zero;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)                                                                    // dP^T[key][q]
@@ -386,16 +523,18 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
     store_tile_T<DH, DT>(sct + wave * 32 * RS, RS, dQt, reinterpret_cast<uint16_t*>(d.dq) + (size_t)b * Lq * d.lddq + h * DH, d.lddq, qt * 32, Lq,
                          lane, osc);
 }
-size_t dq_long_lds(int Lk) {
+size_t dq_long_lds(int Lk, bool masked) {
     const int LkP = (Lk + 31) & ~31;
-    return (size_t)2 * CH * RS + (size_t)Q_NW * 32 * RS + (size_t)LkP * 4 + 64;
+    return (size_t)2 * CH * RS + (size_t)Q_NW * 32 * RS + (size_t)LkP * 4 + 64 + (masked ? (size_t)LkP * 4 + mask_lds(LkP) : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- backward, dK / dV phase
 // A workgroup owns four key tiles (one per wave: K, V operands and the 2 x 2 accumulator tiles in registers, the key on the lane) and
 // streams Q / d_o' with their per-query constants.  128 accumulator + operand registers per wave: two waves per SIMD.
 constexpr int K_NW = 4;
-template <bool DROP>
+// MASKED: a wave (one key tile) classifies the query tiles it meets; the walk visits the query chunks some wave needs - under CAUSAL
+// those from the workgroup's first diagonal tile on, unless SEP allows something before it.
+template <bool DROP, bool MASKED>
 __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
     constexpr int NW = K_NW, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -411,6 +550,8 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     float* dlc = lse2 + CH;                                         // [CH] delta / dropout scale
     char* sct = reinterpret_cast<char*>(dlc + CH);                  // [NW][32][RS] output transpose tiles
     int* wflag = reinterpret_cast<int*>(sct + NW * 32 * RS);
+    const MaskLds ml = carve_mask(wflag + 16, LqP);                 // MASKED: tile votes, chunk votes, mod_id bytes
+    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * DH;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * DH;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * DH;
@@ -420,13 +561,13 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     const bool active = kt < nkt;
     const int key = kt * 32 + l31;
     Stager<NT> stg;
-    stg.load(qg, d.ldq, dog, d.lddq, 0, Lq, t);
+    if constexpr (!MASKED) stg.load(qg, d.ldq, dog, d.lddq, 0, Lq, t);         // MASKED: the first chunk is known after the votes
     float lse_n = 0.f, dl_n = 0.f;                     // the next chunk's per-query constants (threads 0 .. CH-1)
     auto load_consts = [&](int c0) {
         lse_n = 0.f; dl_n = 0.f;
         if (t < CH && c0 + t < Lq) { lse_n = d.lse[(size_t)bh_ * Lq + c0 + t] * LOG2E; dl_n = dl[(size_t)bh_ * Lq + c0 + t]; }
     };
-    load_consts(0);
+    if constexpr (!MASKED) load_consts(0);
     bf16x8v kfr[KS], vfr[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -440,21 +581,29 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     }
     // key bias of this lane's key; "a key of the head is padded" decides between the literal-zero and the bias-initialised S product
     int pad = 0;
-    for (int i = t; i < Lk; i += NT) pad |= (d.keypad != nullptr && d.keypad[(size_t)b * Lk + i] == 0) ? 1 : 0;
+    for (int i = t; i < Lk; i += NT) pad |= (!causal && d.keypad != nullptr && d.keypad[(size_t)b * Lk + i] == 0) ? 1 : 0;   // CAUSAL replaces the padding
     const int wv = __any(pad) ? 1 : 0;
     if (lane == 0) wflag[wave] = wv;
-    const bool kok = key < Lk && (d.keypad == nullptr || d.keypad[(size_t)b * Lk + (key < Lk ? key : 0)] != 0);
+    const bool kok = key < Lk && (causal || d.keypad == nullptr || d.keypad[(size_t)b * Lk + (key < Lk ? key : 0)] != 0);
     const float kbv = kok ? 0.f : -INFINITY;
     // keep words of (query tile i, this wave's key tile): key l31 = mrow(r, kh') sits in word 2 r + kh' of its tile
     const uint32_t* kbp = reinterpret_cast<const uint32_t*>(d.keepbits) + ((size_t)bh_ * nqt * nkt + min(kt, nkt - 1)) * 32 +
                           2 * ((l31 & 3) + 4 * (l31 >> 3)) + ((l31 >> 2) & 1);
     const int kw_stride = nkt * 32;
     uint32_t kw_next = 0u;
-    if (DROP) kw_next = kbp[0];
+    if (DROP && !MASKED) kw_next = kbp[0];
+    if constexpr (MASKED) stage_mask<NT>(ml, d.mod_id, sep, Lq, LqP, nch, t);
     __syncthreads();
     int anypad = 0;
 #pragma unroll
     for (int w = 0; w < NW; ++w) anypad |= wflag[w];
+    int c0 = 0, tk = 0;                                // MASKED: the first chunk of the walk, the vote of this wave's key tile
+    if constexpr (MASKED) {
+        vote_chunks<false>(ml, causal, sep, active, kt, nqt, nch, lane);
+        if (sep && active) tk = __builtin_amdgcn_readfirstlane(ml.tmod[kt]);
+        c0 = next_needed(ml.cneed, -1, nch);
+        if (c0 < nch) { stg.load(qg, d.ldq, dog, d.lddq, c0 * CH, Lq, t); load_consts(c0 * CH); }
+    }
     // (keys beyond Lk need no bias here: their K / V rows are zero, their accumulator lanes are never stored and nothing is exchanged)
     anypad = __builtin_amdgcn_readfirstlane(anypad);
     const float c2 = d.scale * LOG2E;
@@ -465,18 +614,39 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
         for (int r = 0; r < 16; ++r) { dKt[i][r] = 0.f; dVt[i][r] = 0.f; }
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (int c = 0; c < nch; ++c) {
+    for (int c = c0, cn; c < nch; c = cn) {
+        cn = c + 1;
+        if constexpr (MASKED) cn = next_needed(ml.cneed, c, nch);
         __syncthreads();
         stg.store(As, Bs, t);
         if (t < CH) { lse2[t] = lse_n; dlc[t] = dl_n; }
-        if (c + 1 < nch) { stg.load(qg, d.ldq, dog, d.lddq, (c + 1) * CH, Lq, t); load_consts((c + 1) * CH); }
+        if (cn < nch) { stg.load(qg, d.ldq, dog, d.lddq, cn * CH, Lq, t); load_consts(cn * CH); }
         __syncthreads();
         if (!active) continue;
         const int ntl = min(CH / 32, nqt - c * (CH / 32));
         for (int ql = 0; ql < ntl; ++ql) {
             const int qt = c * (CH / 32) + ql;
+            bool zstart = !anypad, mixed = false;
+            uint32_t kwv = 0u;
+            if constexpr (MASKED) {
+                const int cls = __builtin_amdgcn_readfirstlane(tile_class(causal, sep, sep ? ml.tmod[qt] : 0, tk, qt, kt));
+                if (cls == T_SKIP) continue;           // contributes exactly nothing; its keep bits are never read
+                zstart = zstart || cls == T_ZERO;
+                mixed = cls == T_MIXED;
+                if (DROP) kwv = kbp[(size_t)qt * kw_stride];          // no prefetch chain across skipped tiles: requested ahead of the MFMAs
+            }
             f32x16 s, dpv = zero;
-            if (!anypad) {
+            if (MASKED && mixed) {
+                // T_MIXED: the whole rule per element (lane = key, register = query)
+                const uint32_t mk = sep ? ml.modb[min(key, LkP - 1)] : 0u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const uint32_t mw = sep ? *reinterpret_cast<const uint32_t*>(ml.modb + qt * 32 + 8 * g + 4 * kh) : 0u;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        s[4 * g + i] = mixed_start(d.flags, qt * 32 + 8 * g + 4 * kh + i, key, Lk, kbv, (mw >> (8 * i)) & 0xffu, mk);
+                }
+            } else if (zstart) {
                 s = zero;
             } else {
                 const bool dfix = (d.flags & MMFM_ATTN_DIAG) && qt == kt;
@@ -493,8 +663,12 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
             }
             uint32_t wq = 0u;
             if (DROP) {
-                wq = kw_next >> (4 * kh);              // bit (r & 3) + 8 (r >> 2) is now register r's query
-                kw_next = kbp[(size_t)min(qt + 1, nqt - 1) * kw_stride];
+                if constexpr (MASKED) {
+                    wq = kwv >> (4 * kh);
+                } else {
+                    wq = kw_next >> (4 * kh);          // bit (r & 3) + 8 (r >> 2) is now register r's query
+                    kw_next = kbp[(size_t)min(qt + 1, nqt - 1) * kw_stride];
+                }
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -535,7 +709,9 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     store_tile_T<DH, DT>(tl, RS, dKt, reinterpret_cast<uint16_t*>(d.dk) + (size_t)b * Lk * d.lddk + h * DH, d.lddk, kt * 32, Lk, lane, d.scale * keep_scale);
     store_tile_T<DH, DT>(tl, RS, dVt, reinterpret_cast<uint16_t*>(d.dv) + (size_t)b * Lk * d.lddv + h * DH, d.lddv, kt * 32, Lk, lane, keep_scale);
 }
-size_t dkv_long_lds() { return (size_t)2 * CH * RS + (size_t)2 * CH * 4 + (size_t)K_NW * 32 * RS + 64; }
+size_t dkv_long_lds(int Lq, bool masked) {
+    return (size_t)2 * CH * RS + (size_t)2 * CH * 4 + (size_t)K_NW * 32 * RS + 64 + (masked ? mask_lds((Lq + 31) & ~31) : 0);
+}
 
 }  // namespace
 
@@ -544,8 +720,14 @@ int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st);         
 // dh = 64 with the keep-bit workspace.  Returns -1000 when the general kernels must run.
 int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_LONG"); return e && atoi(e) == 0; }();
-    if (off || d.dh != DH || d.keepbits == nullptr || (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP))) return -1000;
+    if (off || d.dh != DH || d.keepbits == nullptr) return -1000;
+    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
+    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return -1000;
     if (d.Lq % 8 || d.Lk % 8) return -1000;
+    // the key bias (and the MASKED kernels' second bias row, mod_id bytes and votes) grow with Lk: past what a workgroup can have,
+    // the whole shape - forward and backward alike - belongs to the general kernels
+    constexpr size_t LDS_MAX = 160 * 1024;
+    if (fwd_long_lds(d.Lk, masked) > LDS_MAX || dq_long_lds(d.Lk, masked) > LDS_MAX) return -1000;
     const bool drop = d.drop_p.p > 0.f && d.drop_p.state != nullptr;
     if (drop && d.drop_p.p >= 1.f) return -1000;
     const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
@@ -565,29 +747,33 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;                   \
         hipLaunchKernelGGL(kern, GRID, dim3(NTH), LDSB, st, __VA_ARGS__);                                           \
     }
+    // <dropout, MASKED>
+#define LAUNCH2(KERN, ...)                                                                                          \
+    {                                                                                                               \
+        if (drop) { if (masked) LAUNCH((KERN<true, true>), __VA_ARGS__) else LAUNCH((KERN<true, false>), __VA_ARGS__) }     \
+        else { if (masked) LAUNCH((KERN<false, true>), __VA_ARGS__) else LAUNCH((KERN<false, false>), __VA_ARGS__) }       \
+    }
     if (!backward) {
         if (drop) { if (int rc = mmfm_attn_keepbits_launch(d, st)) return rc; }
-        const size_t lds = fwd_long_lds(d.Lk);
+        const size_t lds = fwd_long_lds(d.Lk, masked);
         const dim3 grid(bh, (nqt + F_NW - 1) / F_NW);
-        if (drop) LAUNCH(attn_fwd_long_kernel<true>, grid, F_NW * 64, lds, "mmfm_attn_fwd(bf16, dh 64)", d, keep_scale)
-        else LAUNCH(attn_fwd_long_kernel<false>, grid, F_NW * 64, lds, "mmfm_attn_fwd(bf16, dh 64)", d, keep_scale)
+        LAUNCH2(attn_fwd_long_kernel, grid, F_NW * 64, lds, "mmfm_attn_fwd(bf16, dh 64)", d, keep_scale)
         MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, dh 64)");
         return 0;
     }
     const int64_t pieces = (int64_t)d.B * d.Lq * d.heads * C8;
     hipLaunchKernelGGL(attn_bwd_long_prep_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, d, dl, 1.f / keep_scale);
     {
-        const size_t lds = dkv_long_lds();
+        const size_t lds = dkv_long_lds(d.Lq, masked);
         const dim3 grid(bh, (nkt + K_NW - 1) / K_NW);
-        if (drop) LAUNCH(attn_bwd_long_dkv_kernel<true>, grid, K_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dK dV)", d, dl, keep_scale)
-        else LAUNCH(attn_bwd_long_dkv_kernel<false>, grid, K_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dK dV)", d, dl, keep_scale)
+        LAUNCH2(attn_bwd_long_dkv_kernel, grid, K_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dK dV)", d, dl, keep_scale)
     }
     {
-        const size_t lds = dq_long_lds(d.Lk);
+        const size_t lds = dq_long_lds(d.Lk, masked);
         const dim3 grid(bh, (nqt + Q_NW - 1) / Q_NW);
-        if (drop) LAUNCH(attn_bwd_long_dq_kernel<true>, grid, Q_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dQ)", d, dl, keep_scale)
-        else LAUNCH(attn_bwd_long_dq_kernel<false>, grid, Q_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dQ)", d, dl, keep_scale)
+        LAUNCH2(attn_bwd_long_dq_kernel, grid, Q_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dQ)", d, dl, keep_scale)
     }
+#undef LAUNCH2
 #undef LAUNCH
     MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, dh 64)");
     return 0;

@@ -1,4 +1,4 @@
-// Device helpers shared by the bf16 attention kernels (attention_bf16.hip, attention_fast.hip): operand fragments out of
+// Device helpers shared by the bf16 attention kernels (attention_bf16.hip, attention_fast.hip, attention_long.hip): operand fragments out of
 // row-major LDS images, the accumulator row map, head staging, transposed tile stores.
 #pragma once
 #include "common.h"
@@ -152,6 +152,28 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {          // one v_
     bf16x2v v;
     v[0] = (__bf16)a; v[1] = (__bf16)b;
     return __builtin_bit_cast(uint32_t, v);
+}
+
+// ---- mask tiles (CAUSAL / SEP) of the keep-bit kernels: the four wave-uniform classes of a (query tile, key tile) and the per-element
+// rule of a mixed tile.  The classes are described in attention_fast.hip ("mask tiles"); tq / tk = the tile's modality when all of its
+// 32 positions carry the same mod_id byte, TMOD_MIXED otherwise.
+constexpr int T_SKIP = 0, T_BIAS = 1, T_ZERO = 2, T_MIXED = 3, TMOD_MIXED = 256;
+__device__ __forceinline__ int tile_class(bool causal, bool sep, int tq, int tk, int qt, int kt) {
+    const bool sep_mixed = sep && (tq == TMOD_MIXED || tk == TMOD_MIXED);
+    if (sep && !sep_mixed && tq != tk) return T_ZERO;
+    if (causal) {
+        if (kt < qt) return T_ZERO;
+        if (kt == qt) return T_MIXED;
+        return sep_mixed ? T_MIXED : T_SKIP;
+    }
+    return sep_mixed ? T_MIXED : T_BIAS;
+}
+// accumulator start of one element of a T_MIXED tile: bias = the key's padding bias (0 / -inf)
+__device__ __forceinline__ float mixed_start(int flags, int q, int key, int Lk, float bias, uint32_t mq, uint32_t mk) {
+    bool al = (flags & MMFM_ATTN_CAUSAL) ? key <= q : bias == 0.f;
+    if (flags & MMFM_ATTN_DIAG) al = al || key == q;
+    if (flags & MMFM_ATTN_SEP) al = al || mq != mk;
+    return (al && key < Lk) ? 0.f : -INFINITY;
 }
 
 }  // namespace attn
