@@ -24,6 +24,10 @@ extern "C" {
 #define MMFM_VERSION 401
 #define MMFM_F32 0
 #define MMFM_BF16 1
+/* Feature macro: bias-free linears (attention_bias / mlp_bias: false).  With it defined the NULL contracts written next to
+ * mmfm_prep_entry, mmfm_rowgemm_desc, mmfm_mlp_desc, mmfm_ln_linear_grad and mmfm_sn_linear_grad hold.  No struct changed its layout and
+ * no export was added, so MMFM_VERSION stays: a caller built against the earlier 401 header runs unchanged. */
+#define MMFM_NULL_BIAS 1
 /* activation kinds of mmfm_mlp_desc.act (the fused MLP's transformer.act) */
 #define MMFM_MLP_GELU 0        /* exact-erf GELU (bf16: the polynomial of act 1) */
 #define MMFM_MLP_RELU 1
@@ -317,7 +321,10 @@ int mmfm_bits_per_spike_neurons(const float* rates, const float* spikes, int64_t
  * may be NULL (plain bf16 copies / transposes of a weight).  `entries` is a DEVICE array; entry e covers blocks
  * [tile0, tile0 + ceil(N/32)); total_tiles = sum of ceil(N/32).
  * scalar_gain = 1 (a ScaleNorm-fed linear): gamma points to ONE float g (the ScaleNorm's gain) and beta is ignored:
- *   Wp = bf16(g * W),  WpT = Wp^T,  bp = bias,   so that  linear(scalenorm(x)) = Wp . x_hat + bp  with  x_hat = x / max(||x||, eps). */
+ *   Wp = bf16(g * W),  WpT = Wp^T,  bp = bias,   so that  linear(scalenorm(x)) = Wp . x_hat + bp  with  x_hat = x / max(||x||, eps).
+ * Bias-free linear (bias == NULL): under a LayerNorm (gamma / beta set) the prepared bias still exists, bp = W . beta - beta is folded
+ *   into the linear whether or not the linear has a bias of its own; with scalar_gain = 1 nothing is left to add: pass bp = NULL (it is
+ *   not written) and hand NULL on as the bias of the consuming kernel.  A non-NULL bp there is written as zeros. */
 typedef struct {
     const float* W;          /* [N][K] fp32 master weight */
     const float* gamma;      /* [K] or NULL */
@@ -346,6 +353,8 @@ int mmfm_prep_weights(const mmfm_prep_entry* entries, int n_entries, int total_t
  *   ln = 2 (K = 256): ScaleNorm: pro(x) = x_hat = x * rstd, rstd = 1 / max(||x||, eps), saved NEGATED for a clamped row (as
  *                      mmfm_scalenorm_fwd's rinv); w / bias prepared with mmfm_prep_entry.scalar_gain = 1.
  *   epilogue: + bias[n], + residual[m*ldr + n], store.
+ *   bias == NULL adds nothing, in every mode and on both rings (the kernels keep the bias in LDS; a NULL one is staged as zeros, so
+ *                      the result is bit-identical to passing a zero vector).
  *   ln_bwd = 1 (N = 256): v = x . w^T is d(x_hat) of a LayerNorm whose output fed the forward linear (w = WpT of it) and
  *                      y = residual + bwd_rstd * (v - mean(v) - bwd_xhat * mean(v * bwd_xhat))   (residual = running gradient or NULL).
  *   ln_bwd = 2 (N = 256): the same for a ScaleNorm (x_hat / rstd saved by ln = 2):
@@ -378,7 +387,10 @@ int mmfm_rowgemm(const mmfm_rowgemm_desc* d, mmfm_stream stream);
  *         du = (t1 . W_down) * gelu'(u)          [R][512]   (operand of G_up = du^T x_hat, db_up = colsum du)
  *         dx = dy + LayerNorm'(du . Wp_up)       [R][256]   (LayerNorm backward in registers; needs w_up_t = Wp_up^T UNIT-PERMUTED =
  *                                                            mmfm_prep_entry.WpTP of up_proj, w_down_t = W_down^T)
- *   Weight / LayerNorm-parameter gradients then follow from mmfm_gemm (dW slabs) + mmfm_ln_linear_grad. */
+ *   Weight / LayerNorm-parameter gradients then follow from mmfm_gemm (dW slabs) + mmfm_ln_linear_grad.
+ *   Bias-free linears (mlp_bias: false): b_down may be NULL (nothing is added to Y).  b_up may be NULL only with scalenorm = 1; under a
+ *   LayerNorm b_up is the prepared W_up . beta and is always present (a NULL one is an argument error).  The backward kernels (one-launch
+ *   and front half) read the same b_up the forward read, so the recomputed u follows the same rule; they never read b_down. */
 typedef struct {
     int64_t R;
     const void* x; int ldx;           /* fwd: residual stream in (bf16 [R][256]) */
@@ -411,6 +423,8 @@ int mmfm_mlp_bwd(const mmfm_mlp_desc* d, mmfm_stream stream);
  *   dW[n][k] = gamma[k] * G[n][k] + db[n] * beta[k];   dbias = db;
  *   dgamma[k] (+)= sum_n W[n][k] * G[n][k];   dbeta[k] (+)= sum_n W[n][k] * db[n]      (accumulate_ln selects +=)
  * No per-row reduction is needed for the LayerNorm parameters.  Deterministic.
+ * dbias == NULL (a bias-free linear): nothing is written for it.  Gdb keeps its trailing db block - dW and dbeta need db because beta
+ * is folded into the linear.
  * workspace: mmfm_ln_linear_grad_workspace(K) bytes, ZEROED once before its first use (partial rows + arrival tickets that
  * the kernel re-arms itself); one workspace per concurrently running launch. */
 int64_t mmfm_ln_linear_grad_workspace(int K);
@@ -419,6 +433,8 @@ int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float* gamma, co
                         void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 /* The same for a ScaleNorm-fed linear (scalar gain g, one float; Gdb from x_hat = x / max(||x||, eps)):
  *   dW = g * G;   dbias = db;   dg (+)= sum_{n,k} W[n][k] * G[n][k]      (accumulate selects +=)
+ * dbias == NULL (a bias-free linear): nothing is written for it AND the trailing db block of Gdb is never read: Gdb may then be
+ * just G[N][K] (N * K floats), from a weight-gradient GEMM launched without colsum.
  * Deterministic (per-block partials summed in a fixed order by the last block).  Same workspace (size, zeroing, one per concurrent
  * launch) as mmfm_ln_linear_grad. */
 int mmfm_sn_linear_grad(const float* Gdb, const float* W, const float* g, int N, int K, float* dW, float* dbias, float* dg,

@@ -25,9 +25,14 @@ def load_config():
 
 
 def model_config(H=None, heads=None, inter=None, n_enc=None, n_dec=None, max_F=None, dropout=None, emb_dropout=None,
-                 sep=None, causal=None, n_modality=None, scalenorm=None, act=None):
+                 sep=None, causal=None, n_modality=None, scalenorm=None, act=None, attn_bias=None, mlp_bias=None):
+    """attn_bias / mlp_bias (transformer.attention_bias / mlp_bias): a bool for both sides or an (encoder, decoder) pair."""
     from utils.config_utils import DictConfig
     m = copy.deepcopy(dict(load_config()["model"]))
+    for key, val in (("attention_bias", attn_bias), ("mlp_bias", mlp_bias)):
+        if val is not None:
+            enc, dec = val if isinstance(val, (tuple, list)) else (val, val)
+            m["encoder"]["transformer"][key], m["decoder"]["transformer"][key] = bool(enc), bool(dec)
     for side in ("encoder", "decoder"):
         e, t = m[side]["embedder"], m[side]["transformer"]
         if max_F is not None: e["max_F"] = max_F

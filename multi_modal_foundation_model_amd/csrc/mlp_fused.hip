@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void ln_linear_grad_kernel(const float* __rest
         part[((size_t)sp * 2 + 0) * K + k] = sg;
         part[((size_t)sp * 2 + 1) * K + k] = sb;
     }
-    if (blockIdx.x == 0) for (int n = n0 + threadIdx.x; n < n1; n += 256) dbias[n] = db[n];
+    if (dbias && blockIdx.x == 0) for (int n = n0 + threadIdx.x; n < n1; n += 256) dbias[n] = db[n];      // NULL: a bias-free linear
     // publish the partial row, take a ticket; the last arriver of this column group reduces (cdna_hip_programming.md Guideline 16)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void sn_linear_grad_kernel(const float* __rest
         for (int i = 0; i < 8; ++i) sg += red[i][tx];
         part[(size_t)sp * K + k] = sg;
     }
-    if (blockIdx.x == 0) for (int n = n0 + threadIdx.x; n < n1; n += 256) dbias[n] = db[n];
+    if (dbias && blockIdx.x == 0) for (int n = n0 + threadIdx.x; n < n1; n += 256) dbias[n] = db[n];      // NULL: a bias-free linear
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -626,12 +626,15 @@ template <typename F> int with_act(int act, F&& f) {
 int check(const mmfm_mlp_desc& d, bool bwd) {
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     MMFM_REQUIRE(d.act >= MMFM_MLP_GELU && d.act <= MMFM_MLP_GELU_TANH, "mmfm_mlp: bad act %d", d.act);
-    MMFM_REQUIRE(d.R > 0 && d.w_up && d.b_up, "mmfm_mlp: null operand / empty problem");
+    MMFM_REQUIRE(d.R > 0 && d.w_up, "mmfm_mlp: null operand / empty problem");
+    // bias-free linears (mlp_bias: false): b_down may be NULL; b_up only behind a ScaleNorm - under LayerNorm it is the prepared W_up . beta.
+    // A NULL vector is staged as zeros (stage_vec), in the forward and in both backward kernels' recomputation of u alike.
+    MMFM_REQUIRE(d.b_up || d.scalenorm, "mmfm_mlp: b_up == NULL needs scalenorm = 1 (under LayerNorm b_up is the prepared W_up . beta)");
     MMFM_REQUIRE((d.R + 128) * (int64_t)std::max(std::max(d.ldx, d.ldy), std::max(std::max(d.lddy, d.lddx), 512)) * 2 < (int64_t)1 << 31,
                  "mmfm_mlp: tensors beyond 2 GiB are not addressable by the 32-bit buffer offsets");
     MMFM_REQUIRE(al16(d.x) && al16(d.w_up) && al16(d.w_down) && al16(d.y) && al16(d.xhat) && al16(d.dy) && al16(d.w_down_t) && al16(d.w_up_t) &&
                  al16(d.t1) && al16(d.g) && al16(d.du) && al16(d.dx) && al16(d.b_up) && al16(d.b_down), "mmfm_mlp: operands must be 16-byte aligned");
-    if (!bwd) MMFM_REQUIRE(d.x && d.w_down && d.b_down && d.y && d.ldx % 8 == 0 && d.ldy % 8 == 0 && d.ldx >= 256 && d.ldy >= 256, "mmfm_mlp_fwd: bad arguments");
+    if (!bwd) MMFM_REQUIRE(d.x && d.w_down && d.y && d.ldx % 8 == 0 && d.ldy % 8 == 0 && d.ldx >= 256 && d.ldy >= 256, "mmfm_mlp_fwd: bad arguments");
     else MMFM_REQUIRE(d.xhat && d.dy && d.w_down_t && d.g && d.du && d.t1 && d.lddy % 8 == 0 && d.lddy >= 256 &&
                       (d.dx == nullptr || (d.rstd && d.w_up_t && d.lddx % 8 == 0 && d.lddx >= 256)), "mmfm_mlp_bwd: bad arguments");
     return 0;
@@ -688,7 +691,7 @@ extern "C" int64_t mmfm_ln_linear_grad_workspace(int K) { return ((int64_t)LG_SP
 extern "C" int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float* gamma, const float* beta, int N, int K, float* dW,
                                    float* dbias, float* dgamma, float* dbeta, int accumulate_ln, void* workspace, int64_t workspace_bytes,
                                    mmfm_stream stream) {
-    MMFM_REQUIRE(Gdb && W && gamma && beta && dW && dbias && dgamma && dbeta && N > 0 && K > 0, "mmfm_ln_linear_grad: null argument");
+    MMFM_REQUIRE(Gdb && W && gamma && beta && dW && dgamma && dbeta && N > 0 && K > 0, "mmfm_ln_linear_grad: null argument");
     MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_ln_linear_grad_workspace(K), "mmfm_ln_linear_grad: workspace too small (must be ZEROED once before first use)");
     float* part = reinterpret_cast<float*>(workspace);
     unsigned int* ticket = reinterpret_cast<unsigned int*>(part + (size_t)LG_SPLIT * 2 * K);
@@ -700,7 +703,7 @@ extern "C" int mmfm_ln_linear_grad(const float* Gdb, const float* W, const float
 
 extern "C" int mmfm_sn_linear_grad(const float* Gdb, const float* W, const float* g, int N, int K, float* dW, float* dbias, float* dg,
                                    int accumulate, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
-    MMFM_REQUIRE(Gdb && W && g && dW && dbias && dg && N > 0 && K > 0, "mmfm_sn_linear_grad: null argument");
+    MMFM_REQUIRE(Gdb && W && g && dW && dg && N > 0 && K > 0, "mmfm_sn_linear_grad: null argument");
     MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_ln_linear_grad_workspace(K), "mmfm_sn_linear_grad: workspace too small (must be ZEROED once before first use)");
     float* part = reinterpret_cast<float*>(workspace);
     unsigned int* ticket = reinterpret_cast<unsigned int*>(part + (size_t)LG_SPLIT * 2 * K);

@@ -51,6 +51,12 @@ class EngineConfig:
     loss_kind: Dict[str, int] = field(default_factory=lambda: dict(LOSS_KIND))
     norm: str = "layernorm"                     # the transformer blocks' norms: "layernorm" or "scalenorm" (use_scalenorm: true)
     act: Tuple[int, float] = (L.MLP_GELU, 1.0)  # the MLP activation (transformer.act): (MMFM_MLP_* kind, sigmoid beta), ops.mlp_act
+    # transformer.attention_bias / transformer.mlp_bias, per side (the two YAML sections are independent): False = the side's
+    # attn / cross_attn query, key, value, out_proj (attention) or mlp up_proj, down_proj (mlp) are nn.Linear(bias=False)
+    enc_attn_bias: bool = True
+    enc_mlp_bias: bool = True
+    dec_attn_bias: bool = True
+    dec_mlp_bias: bool = True
 
     @staticmethod
     def from_model_config(mc, mods) -> "EngineConfig":
@@ -72,7 +78,9 @@ class EngineConfig:
                             n_modality=ee["n_modality"], embed_scale=float(scale), embed_dropout=ee["dropout"],
                             dropout=et["dropout"], sep_mask=bool(mc["decoder"]["decoder_sep_mask"]),
                             causal_mask=bool(mc["decoder"]["decoder_causal_mask"]), mods=list(mods),
-                            norm="scalenorm" if et["use_scalenorm"] else "layernorm", act=act)
+                            norm="scalenorm" if et["use_scalenorm"] else "layernorm", act=act,
+                            enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
+                            dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]))
 
 
 def _align(n, a=8):
@@ -102,8 +110,10 @@ class ParamLayout:
             pad()
             return self.n
 
-        def lin(prefix, o, i):
-            pad(); add(prefix + ".weight", (o, i)); pad(); add(prefix + ".bias", (o,))
+        def lin(prefix, o, i, bias=True):
+            pad(); add(prefix + ".weight", (o, i))
+            if bias:                                       # a bias-free linear has no entry and leaves no slot behind
+                pad(); add(prefix + ".bias", (o,))
 
         def ln(prefix):
             if cfg.norm == "scalenorm" and prefix.rsplit(".", 1)[-1] in BLOCK_NORMS:
@@ -111,12 +121,14 @@ class ParamLayout:
                 return
             pad(); add(prefix + ".weight", (H,)); pad(); add(prefix + ".bias", (H,))
 
-        def fused(prefix, names, alias):
+        def fused(prefix, names, alias, bias=True):
             pad()
             start = self.n
             for nm in names:
                 add(f"{prefix}.{nm}.weight", (H, H))
             self.alias[f"{prefix}.{alias}.weight"] = (start, (len(names) * H, H))
+            if not bias:
+                return
             pad()
             start = self.n
             for nm in names:
@@ -137,8 +149,9 @@ class ParamLayout:
         for i in range(cfg.n_enc):
             s = seg_begin()
             p = f"encoder.{i}"
-            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv"); lin(p + ".attn.out_proj", H, H)
-            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H); lin(p + ".mlp.down_proj", H, I)
+            ab, mb = cfg.enc_attn_bias, cfg.enc_mlp_bias
+            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv", ab); lin(p + ".attn.out_proj", H, H, ab)
+            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H, mb); lin(p + ".mlp.down_proj", H, I, mb)
             pad()
             self.segments.append((p, s, self.n))
         s = seg_begin()
@@ -148,11 +161,12 @@ class ParamLayout:
         for i in range(cfg.n_dec):
             s = seg_begin()
             p = f"decoder.{i}"
-            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv"); lin(p + ".attn.out_proj", H, H)
+            ab, mb = cfg.dec_attn_bias, cfg.dec_mlp_bias
+            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv", ab); lin(p + ".attn.out_proj", H, H, ab)
             ln(p + ".query_norm"); ln(p + ".context_norm")
-            lin(p + ".cross_attn.query", H, H); fused(p + ".cross_attn", ("key", "value"), "kv")
-            lin(p + ".cross_attn.out_proj", H, H)
-            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H); lin(p + ".mlp.down_proj", H, I)
+            lin(p + ".cross_attn.query", H, H, ab); fused(p + ".cross_attn", ("key", "value"), "kv", ab)
+            lin(p + ".cross_attn.out_proj", H, H, ab)
+            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H, mb); lin(p + ".mlp.down_proj", H, I, mb)
             pad()
             self.segments.append((p, s, self.n))
         s = seg_begin()
@@ -162,6 +176,9 @@ class ParamLayout:
         pad()
         self.segments.append(("head", s, self.n))
         self.n = _align(self.n, 64)
+
+    def has(self, name):
+        return name in self.entries or name in self.alias
 
     def view(self, flat, name):
         off, shape = self.entries[name] if name in self.entries else self.alias[name]
@@ -268,6 +285,12 @@ class Engine:
     def Gv(self, name):
         return self.layout.view(self.G, name)
 
+    def Pb(self, wname):         # the bias of linear `wname` (fp32 master view), None for a bias-free linear (attention_bias / mlp_bias: false)
+        return self.Pf(wname + ".bias") if self.layout.has(wname + ".bias") else None
+
+    def Gb(self, wname):         # its gradient, None likewise
+        return self.Gv(wname + ".bias") if self.layout.has(wname + ".bias") else None
+
     def is_sn(self, lnname):
         """True where the norm named `lnname` is a ScaleNorm (the block norms of a use_scalenorm model)."""
         return self.scalenorm and lnname.rsplit(".", 1)[-1] in BLOCK_NORMS
@@ -353,7 +376,8 @@ class Engine:
     def _build_prep(self):
         """Prepared weights of the fused path: per LayerNorm-fed linear Wp = bf16(W * gamma), WpT, bp = b + W beta
         (mmfm_prep_weights); per ScaleNorm-fed linear Wp = bf16(g * W), bp = b (scalar gain); per plain linear only the bf16
-        transpose (the dX products read K-contiguous rows)."""
+        transpose (the dX products read K-contiguous rows).  A bias-free linear behind a LayerNorm keeps bp = W beta (beta is folded
+        into the linear either way); behind a ScaleNorm it has no bp at all (None: the consuming kernel adds nothing)."""
         if getattr(self, "_prep", None) is not None:
             return self._prep
         c = self.cfg
@@ -369,7 +393,8 @@ class Engine:
                       (p + ".mlp.down_proj", None)]
         nW = sum(self.Pf(w + ".weight").numel() for w, _ in sites)
         nWp = sum(self.Pf(w + ".weight").numel() for w, ln in sites if ln)
-        nb = sum(self.Pf(w + ".bias").numel() for w, ln in sites if ln)
+        has_bp = {w: self.Pb(w) is not None or not self.is_sn(ln) for w, ln in sites if ln}
+        nb = sum(self.Pf(w + ".weight").shape[0] for w, ln in sites if ln and has_bp[w])
         # unit-permuted copies for the MLP kernels' LDS-DMA weight ring (include/mmfm.h: mmfm_prep_entry.WpP / WpTP)
         nPm = sum(self.Pf(w + ".weight").numel() for w, _ in sites if w.endswith(".mlp.up_proj") or w.endswith(".mlp.down_proj"))
         WpT = torch.zeros(nW + 64, dtype=torch.bfloat16, device=self.device)
@@ -394,9 +419,9 @@ class Engine:
                     e.update(gamma=self.Pf(ln + ".scale"), scalar_gain=True)
                 else:
                     e.update(gamma=self.Pf(ln + ".weight"), beta=self.Pf(ln + ".bias"))
-                e.update(bias=self.Pf(w + ".bias"), Wp=Wp[oW:oW + N * Kd].view(N, Kd), bp=bp[ob:ob + N])
+                e.update(bias=self.Pb(w), Wp=Wp[oW:oW + N * Kd].view(N, Kd), bp=bp[ob:ob + N] if has_bp[w] else None)
                 oW += N * Kd
-                ob += N
+                ob += N if has_bp[w] else 0
                 v.update(Wp=e["Wp"], bp=e["bp"])
             views[w] = v
             entries.append(e)
@@ -497,7 +522,7 @@ class Engine:
         ws_loss = buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
 
         def lin(plan, X, wname, Y, Mr, N, Kd, ldx=None, **kw):
-            K.gemm(X, self.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.Pf(wname + ".bias"),
+            K.gemm(X, self.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.Pb(wname),
                    dtype=code, plan=plan, **kw)
 
         used_wt: list = []
@@ -531,14 +556,15 @@ class Engine:
             ldx = row stride of X when its rows are padded."""
             S, kchunk = self._dw_split(N, Kd, Mr, ldn=ldx)
             ldx = ldx or Kd
-            gw, gb = self.Gv(wname + ".weight"), self.Gv(wname + ".bias")
+            gw, gb = self.Gv(wname + ".weight"), self.Gb(wname)
             # bf16: the bias gradient (column sums of dY) rides on the dW GEMM (mmfm_gemm_desc.colsum); when the bias
-            # gradient sits right behind the weight gradient in the flat buffer one slab reduction finishes both
-            fused = code == L.BF16
+            # gradient sits right behind the weight gradient in the flat buffer one slab reduction finishes both.
+            # A bias-free linear (gb None) has no column sum anywhere: the GEMM runs without colsum, its slabs hold the weight gradient only
+            fused = code == L.BF16 and gb is not None
             adjacent = fused and gb.data_ptr() == gw.data_ptr() + 4 * N * Kd
-            if defer and pair_ok and S > 1 and adjacent and dX is None and ldx == Kd:
+            if defer and pair_ok and S > 1 and (adjacent or gb is None) and dX is None and ldx == Kd:
                 flush_deferred(plan)
-                deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd))
+                deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd, nb=N if gb is not None else 0))
                 return
             if S == 1:
                 K.gemm(dY, X, gw, N, Kd, Mr, lda=N, ldb=ldx, ldc=Kd, a_kcontig=0, b_kcontig=0, dtype=code, c_f32=1,
@@ -560,10 +586,10 @@ class Engine:
                     pend.append((gw, sl, N * Kd, S, N * Kd, False))
                 else:
                     K.reduce_slabs(gw, sl, N * Kd, S, N * Kd, plan=plan)
-            if not fused or (S > 1 and not adjacent):
+            if gb is not None and (not fused or (S > 1 and not adjacent)):
                 K.colsum(dY, Mr, N, N, gb, ws_col, plan=plan)
             if dX is not None:
-                wT = self._w_transposed(wname, N, Kd, Mr) if fused else None
+                wT = self._w_transposed(wname, N, Kd, Mr) if code == L.BF16 else None
                 if wT is not None:      # reduction >= 512: the 256-tile kernel (csrc/gemm_big.hip) against the K-contiguous transpose W^T [Kd, N]
                     used_wt.append(wname)
                     K.gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
@@ -629,52 +655,62 @@ class Engine:
         late_lng: list = []
 
         def lin_norm_grad(plan, Gdb, wname, lnname, N):
-            """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]."""
+            """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]
+            (bias-free: dbias None; behind a ScaleNorm Gdb then has no colsum block, db_cols)."""
             if self.is_sn(lnname):
                 K.sn_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".scale"), N, H, self.Gv(wname + ".weight"),
-                                 self.Gv(wname + ".bias"), self.Gv(lnname + ".scale"), ws_lng, plan=plan)
+                                 self.Gb(wname), self.Gv(lnname + ".scale"), ws_lng, plan=plan)
                 return
             K.ln_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".weight"), self.Pf(lnname + ".bias"), N, H,
-                             self.Gv(wname + ".weight"), self.Gv(wname + ".bias"), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
+                             self.Gv(wname + ".weight"), self.Gb(wname), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
                              ws_lng, plan=plan)
+
+        def db_cols(wname, lnname, N):
+            """Width of the colsum block behind G in a norm-fed linear's Gdb: N, or 0 for a bias-free linear behind a ScaleNorm.
+            Behind a LayerNorm db = colsum dY stays even without a bias: dW and dbeta need it (beta is folded into the linear)."""
+            return N if (self.Gb(wname) is not None or not self.is_sn(lnname)) else 0
 
         def dlin_ln(plan, dYt, tag, wname, lnname, N):
             """Gradients of a LayerNorm-fed linear and of that LayerNorm's affine from G = dY^T x_hat (mmfm_ln_linear_grad)."""
             S, kchunk = self._dw_split(N, H, R)
             xh = self.b[tag + "/xh"]
+            nb = db_cols(wname, lnname, N)          # colsum block behind G (0: bias-free behind a ScaleNorm, nobody reads db)
+
+            def cs(t):
+                return t.data_ptr() + 4 * N * H if nb else None
             if deferred and S > 1 and deferred[-1]["Mr"] == R:
                 a = deferred.pop()
-                Na, Ka = a["N"], a["Kd"]
+                Na, Ka, nba = a["N"], a["Kd"], a["nb"]
                 Sa, kca, Sb, kcb = pair_splits(Na, Ka, N, H, R)
-                stra, strb = _align(Na * Ka + Na), _align(N * H + N)
+                stra, strb = _align(Na * Ka + nba), _align(N * H + nb)
                 slab_fits(slab2, Sa, stra, a["wname"]); slab_fits(slab, Sb, strb, wname)
                 da = K.gemm_desc(a["dY"], a["X"], slab2, Na, Ka, R, lda=Na, ldb=Ka, ldc=Ka, a_kcontig=0, b_kcontig=0, splits=Sa, kchunk=kca,
-                                 slab_stride=stra, dtype=code, c_f32=1, colsum=slab2.data_ptr() + 4 * Na * Ka)
+                                 slab_stride=stra, dtype=code, c_f32=1, colsum=slab2.data_ptr() + 4 * Na * Ka if nba else None)
                 db_ = K.gemm_desc(dYt, xh, slab, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=Sb, kchunk=kcb,
-                                  slab_stride=strb, dtype=code, c_f32=1, colsum=slab.data_ptr() + 4 * N * H)
+                                  slab_stride=strb, dtype=code, c_f32=1, colsum=cs(slab))
                 K.gemm_pair(da, db_, plan=plan)
-                K.reduce_slabs(self.Gv(a["wname"] + ".weight"), slab2, Na * Ka + Na, Sa, stra, plan=plan)
-                K.reduce_slabs(gdb, slab, N * H + N, Sb, strb, plan=plan)
+                K.reduce_slabs(self.Gv(a["wname"] + ".weight"), slab2, Na * Ka + nba, Sa, stra, plan=plan)
+                K.reduce_slabs(gdb, slab, N * H + nb, Sb, strb, plan=plan)
             elif S == 1:
                 K.gemm(dYt, xh, gdb, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, dtype=code, c_f32=1,
-                       colsum=gdb.data_ptr() + 4 * N * H, plan=plan)
+                       colsum=cs(gdb), plan=plan)
             elif batch_red:
                 # launch-bound regime: the slabs join the segment's ONE reduction launch (own region, own reduced buffer per site) and
                 # mmfm_ln_linear_grad runs behind it at the end of the segment (close_segment) - one reduction launch per site less
-                stride = _align(N * H + N)
+                stride = _align(N * H + nb)
                 sl = slab_region(S, stride)
                 g_site = buf(f"ws/gdb/{len(late_lng)}", (gdb.numel(),), f32)
                 K.gemm(dYt, xh, sl, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=stride, dtype=code, c_f32=1, colsum=sl.data_ptr() + 4 * N * H, plan=plan)
-                pend.append((g_site, sl, N * H + N, S, stride, False))
+                       slab_stride=stride, dtype=code, c_f32=1, colsum=cs(sl), plan=plan)
+                pend.append((g_site, sl, N * H + nb, S, stride, False))
                 late_lng.append((g_site, wname, lnname, N))
                 return
             else:
-                stride = _align(N * H + N)
+                stride = _align(N * H + nb)
                 slab_fits(slab, S, stride, wname)
                 K.gemm(dYt, xh, slab, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=stride, dtype=code, c_f32=1, colsum=slab.data_ptr() + 4 * N * H, plan=plan)
-                K.reduce_slabs(gdb, slab, N * H + N, S, stride, plan=plan)
+                       slab_stride=stride, dtype=code, c_f32=1, colsum=cs(slab), plan=plan)
+                K.reduce_slabs(gdb, slab, N * H + nb, S, stride, plan=plan)
             lin_norm_grad(plan, gdb, wname, lnname, N)
 
         def dx_ln(plan, dYt, Kd, tag, wname, lnname, dres, dXout):
@@ -707,7 +743,7 @@ class Engine:
 
         def out_proj(plan, a, wname, Xres, Xout):
             if F_OUT:
-                K.rowgemm(a, self.W(wname + ".weight"), Xout, R, H, H, bias=self.Pf(wname + ".bias"), residual=Xres, ldr=H, plan=plan)
+                K.rowgemm(a, self.W(wname + ".weight"), Xout, R, H, H, bias=self.Pb(wname), residual=Xres, ldr=H, plan=plan)
             else:
                 lin(plan, a, wname, Xout, R, H, H, residual=Xres, ldr=H)
 
@@ -731,7 +767,7 @@ class Engine:
             if F_MLP:
                 pu = prep["v"][p + ".mlp.up_proj"]
                 d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=prep["v"][p + ".mlp.down_proj"]["WpP"],
-                                b_down=self.Pf(p + ".mlp.down_proj.bias"), drop=self._drop(tag + "/mlpdrop", dp), y=Xb,
+                                b_down=self.Pb(p + ".mlp.down_proj"), drop=self._drop(tag + "/mlpdrop", dp), y=Xb,
                                 xhat=buf(tag + "/ln2/xh", (R, H)) if grad else None,
                                 rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None, scalenorm=self.is_sn(p + ".ln2"),
                                 act=c.act[0], act_beta=c.act[1])
@@ -827,7 +863,7 @@ class Engine:
                 split = os.environ.get("MMFM_MLP_BWD_SPLIT", "1") == "1" or self.is_sn(p + ".ln2")
                 d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=self._drop(tag + "/mlpdrop", dp), xhat=self.b[tag + "/ln2/xh"],
                                 rstd=self.b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
-                                dx=None if split else dS, act=c.act[0], act_beta=c.act[1])
+                                dx=None if split else dS, scalenorm=self.is_sn(p + ".ln2"), act=c.act[0], act_beta=c.act[1])
                 K.mlp_bwd(d_, plan=plan)
                 if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
                     dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
