@@ -256,20 +256,50 @@ int mmfm_collate_csr(int B, int max_T, int max_N, float pad_value, const uint8_t
                      const int32_t* N_b, float* out, int64_t* time_mask, int64_t* space_mask, mmfm_stream stream);
 
 /* ---------------------------------------------------------------------------------- masked loss
- * mm.py:79-82,217-239.  kind 0: PoissonNLL(log_input) exp(p) - t*p;  kind 1: MSE (p-t)^2.
+ * mm.py:79-82,217-239: an elementwise loss of (pred, target), times the [B,T] token mask, summed.  With d = p - t and
+ * `param` the kind's one float (ignored by the kinds that have none; must be >= 0):
+ *   kind                          torch module (reduction="none")          element                                  d/dp
+ *   0 MMFM_LOSS_POISSON_LOG       PoissonNLLLoss(log_input=True)           exp(p) - t p                             exp(p) - t
+ *   1 MMFM_LOSS_MSE               MSELoss                                  d^2                                      2 d
+ *   2 MMFM_LOSS_POISSON_RATE      PoissonNLLLoss(log_input=False, eps)     p - t log(p + eps)                       1 - t / (p + eps)
+ *   3 MMFM_LOSS_L1                L1Loss                                   |d|                                      sign(d), 0 at d == 0
+ *   4 MMFM_LOSS_SMOOTH_L1         SmoothL1Loss(beta)                       |d| < beta ? d^2 / (2 beta) : |d| - beta/2     |d| < beta ? d / beta : sign(d)
+ *   5 MMFM_LOSS_HUBER             HuberLoss(delta)                         |d| <= delta ? d^2 / 2 : delta (|d| - delta/2) |d| <= delta ? d : delta sign(d)
+ *   6 MMFM_LOSS_BCE_LOGITS        BCEWithLogitsLoss()                      max(p,0) - p t + log1p(exp(-|p|))        sigmoid(p) - t
+ * beta == 0 makes kind 4 the L1 loss, as in torch.  flags: MMFM_LOSS_FULL (kinds 0 and 2 only) = PoissonNLLLoss(full=True): adds
+ * Stirling's t log t - t + log(2 pi t) / 2 to the elements with t > 1; it has no gradient.
  * pred [R][N] (dtype), target [R][N] fp32, rowmask u8 [R] (element (b,t) at rowmask[b*mask_ld + t]).
- * fwd writes the modality's masked SUM to loss_sum[0] (fp32, deterministic two-stage). */
+ * fwd writes the modality's masked SUM to loss_sum[0] (fp32, deterministic two-stage).
+ * mmfm_masked_loss_fwd / _bwd are the two-kind entry points of every earlier 401 library (kind 0 or 1, no parameter, no flag) and
+ * stay as they were; mmfm_masked_loss_kind_fwd / _bwd take every kind, 0 and 1 included (same kernels, same bits), and share
+ * mmfm_masked_loss_workspace.  MMFM_LOSS_KINDS is the feature macro for them (MMFM_VERSION stays, as for MMFM_NULL_BIAS). */
+#define MMFM_LOSS_KINDS 1
+#define MMFM_LOSS_POISSON_LOG 0
+#define MMFM_LOSS_MSE 1
+#define MMFM_LOSS_POISSON_RATE 2
+#define MMFM_LOSS_L1 3
+#define MMFM_LOSS_SMOOTH_L1 4
+#define MMFM_LOSS_HUBER 5
+#define MMFM_LOSS_BCE_LOGITS 6
+#define MMFM_LOSS_FULL 1
 int64_t mmfm_masked_loss_workspace(int64_t R, int N);
 int mmfm_masked_loss_fwd(int dtype, int kind, const void* pred, const float* target, const uint8_t* rowmask,
                          int mask_ld, int T, int64_t R, int N, float* loss_sum,
                          void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_masked_loss_kind_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, float* loss_sum,
+                              void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 /* loss = sum_m loss_sum[m] / sum_m count[m]   (0/0 -> NaN like the reference);  inv_n = 1/sum count */
 int mmfm_loss_finalize(const float* loss_sum, const int64_t* count, int M, float* loss, float* inv_n,
                        mmfm_stream stream);
-/* dpred = grad_out[0] * inv_n[0] * rowmask * d/dp loss_elem */
+/* dpred = grad_out[0] * inv_n[0] * rowmask * d/dp loss_elem: exactly 0 on un-masked rows, NaN everywhere when inv_n is inf
+ * (nothing masked in any modality) */
 int mmfm_masked_loss_bwd(int dtype, int kind, const void* pred, const float* target, const uint8_t* rowmask,
                          int mask_ld, int T, int64_t R, int N, const float* grad_out, const float* inv_n,
                          void* dpred, mmfm_stream stream);
+int mmfm_masked_loss_kind_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const float* grad_out,
+                              const float* inv_n, void* dpred, mmfm_stream stream);
 
 /* ---------------------------------------------------------------------------------- elementwise
  * dst = dropout(src) with counter row*N + col (the backward of a dropout whose forward was fused

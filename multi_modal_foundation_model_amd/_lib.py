@@ -25,6 +25,9 @@ ACT_NONE, ACT_GELU, ACT_SOFTSIGN, ACT_GELU_GRAD, ACT_SOFTSIGN_GRAD, ACT_SOFTSIGN
 ACT_RELU, ACT_RELU_GRAD, ACT_SIGMOID, ACT_SIGMOID_GRAD, ACT_GELU_TANH, ACT_GELU_TANH_GRAD = 6, 7, 8, 9, 10, 11
 # mmfm_mlp_desc.act (MMFM_MLP_*)
 MLP_GELU, MLP_RELU, MLP_SIGMOID, MLP_GELU_TANH = 0, 1, 2, 3
+# masked-loss kinds (MMFM_LOSS_*) and the PoissonNLLLoss(full=True) flag
+LOSS_POISSON_LOG, LOSS_MSE, LOSS_POISSON_RATE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_BCE_LOGITS = range(7)
+LOSS_FULL = 1
 
 
 class MmfmError(RuntimeError):
@@ -114,8 +117,10 @@ _PROTOS = {
     "mmfm_stitch_bwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mmfm_masked_loss_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_masked_loss_fwd": (C.c_int, [_i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _i64, _vp]),
+    "mmfm_masked_loss_kind_fwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _i64, _vp]),
     "mmfm_loss_finalize": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mmfm_masked_loss_bwd": (C.c_int, [_i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
+    "mmfm_masked_loss_kind_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "mmfm_dropout_apply": (C.c_int, [_i, _vp, _vp, _i64, _i, Dropout, _vp]),
     "mmfm_cast_f32_to_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mmfm_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

@@ -1,23 +1,53 @@
-// Masked Poisson-NLL / MSE loss (mm.py:79-82,217-239), forward reduction and backward.
+// Masked elementwise losses (mm.py:79-82,217-239), forward reduction and backward: Poisson-NLL (log or rate input, optional Stirling
+// term), MSE, L1, smooth-L1, Huber and BCE on logits, each with torch's semantics (include/mmfm.h).
 // One wavefront per (b,t) row; unmasked rows are skipped without touching their data, so the
 // algorithmic bytes are (rows masked) * N * (sizeof(T) + 4).  fp32 accumulation, fixed-order
 // two-stage reduction (bitwise reproducible); n_examples is an exact int64 from mmfm_mask_prep.
+// The kind (and the Stirling flag) is a template parameter: the inner loop carries no per-element switch.
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
-__device__ __forceinline__ float loss_elem(int kind, float p, float t) {
-    if (kind == 0) return __expf(p) - t * p;     // PoissonNLLLoss(log_input=True, full=False)
-    const float d = p - t;
-    return d * d;                                  // MSELoss
+// a = the kind's parameter (eps / beta / delta).  Kinds 0 and 1 are the expressions the library has always used.
+template <int KIND, bool FULL>
+__device__ __forceinline__ float loss_elem(float p, float t, float a) {
+    float v;
+    if constexpr (KIND == MMFM_LOSS_POISSON_LOG) v = __expf(p) - t * p;     // PoissonNLLLoss(log_input=True)
+    else if constexpr (KIND == MMFM_LOSS_MSE) { const float d = p - t; v = d * d; }
+    else if constexpr (KIND == MMFM_LOSS_POISSON_RATE) v = p - t * logf(p + a);   // PoissonNLLLoss(log_input=False, eps=a)
+    else if constexpr (KIND == MMFM_LOSS_BCE_LOGITS) v = fmaxf(p, 0.f) - p * t + log1pf(__expf(-fabsf(p)));
+    else {
+        const float d = p - t, ad = fabsf(d);
+        if constexpr (KIND == MMFM_LOSS_L1) v = ad;
+        else if constexpr (KIND == MMFM_LOSS_SMOOTH_L1) v = ad < a ? 0.5f * d * d / a : ad - 0.5f * a;   // a == 0: never quadratic = L1
+        else v = ad <= a ? 0.5f * d * d : a * (ad - 0.5f * a);                                            // Huber
+    }
+    if constexpr (FULL) {                          // PoissonNLLLoss(full=True): Stirling's term where t > 1; it has no gradient in p
+        if (t > 1.f) v += t * logf(t) - t + 0.5f * logf(6.283185307179586f * t);
+    }
+    return v;
 }
-__device__ __forceinline__ float loss_grad(int kind, float p, float t) {
-    return kind == 0 ? __expf(p) - t : 2.f * (p - t);
+template <int KIND>
+__device__ __forceinline__ float loss_grad(float p, float t, float a) {
+    if constexpr (KIND == MMFM_LOSS_POISSON_LOG) return __expf(p) - t;
+    else if constexpr (KIND == MMFM_LOSS_MSE) return 2.f * (p - t);
+    else if constexpr (KIND == MMFM_LOSS_POISSON_RATE) return 1.f - t / (p + a);
+    else if constexpr (KIND == MMFM_LOSS_BCE_LOGITS) {                       // sigmoid(p) - t, from exp(-|p|) <= 1: no overflow
+        const float e = __expf(-fabsf(p)), r = 1.f / (1.f + e);
+        return (p >= 0.f ? r : e * r) - t;
+    } else {
+        const float d = p - t, ad = fabsf(d);
+        const float sg = d != d ? d : (float)(d > 0.f) - (float)(d < 0.f);     // sign(d): 0 at d == 0, NaN stays NaN
+        if constexpr (KIND == MMFM_LOSS_L1) return sg;
+        else if constexpr (KIND == MMFM_LOSS_SMOOTH_L1) return ad < a ? d / a : sg;
+        else return ad <= a ? d : a * sg;
+    }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void loss_fwd_kernel(int kind, const T* __restrict__ pred, const float* __restrict__ target,
+template <typename T, int KIND, bool FULL>
+__global__ __launch_bounds__(256) void loss_fwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target,
                                                        const uint8_t* __restrict__ rowmask, int mask_ld, int Tn, int64_t R, int N,
                                                        float* __restrict__ part) {
     __shared__ float red[4];
@@ -25,7 +55,7 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(int kind, const T* __rest
     float s = 0.f;
     for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < R; row += (int64_t)gridDim.x * 4) {
         if (!rowmask[(row / Tn) * mask_ld + (row % Tn)]) continue;
-        for (int c = lane; c < N; c += 64) s += loss_elem(kind, io<T>::ld(pred + (size_t)row * N + c), target[(size_t)row * N + c]);
+        for (int c = lane; c < N; c += 64) s += loss_elem<KIND, FULL>(io<T>::ld(pred + (size_t)row * N + c), target[(size_t)row * N + c], a);
     }
     s = wave_sum(s);
     if (lane == 0) red[wave] = s;
@@ -48,8 +78,8 @@ __global__ void loss_finalize_kernel(const float* loss_sum, const int64_t* count
     inv_n[0] = 1.f / (float)n;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void loss_bwd_kernel(int kind, const T* __restrict__ pred, const float* __restrict__ target,
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void loss_bwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target,
                                                        const uint8_t* __restrict__ rowmask, int mask_ld, int Tn, int64_t R, int N,
                                                        const float* __restrict__ grad_out, const float* __restrict__ inv_n,
                                                        T* __restrict__ dpred) {
@@ -61,12 +91,73 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(int kind, const T* __rest
             const size_t o = (size_t)row * N + c;
             // unmasked rows: mask * g with mask = 0 - i.e. 0 normally, NaN when nothing at all is masked (g = grad / 0 = inf), which is
             // what upstream's (loss * mask).sum() / mask.sum() hands to autograd (mm.py:217-239): every gradient of that step is NaN there
-            io<T>::st(dpred + o, on ? g * loss_grad(kind, io<T>::ld(pred + o), target[o]) : g * 0.f);
+            io<T>::st(dpred + o, on ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
         }
     }
 }
 
 int loss_blocks(int64_t R) { return (int)std::max<int64_t>(1, std::min<int64_t>(1024, (R + 3) / 4)); }
+
+template <int KIND, bool FULL> struct loss_tag {
+    static constexpr int kind = KIND;
+    static constexpr bool full = FULL;
+};
+// kind (checked by the caller) and the Stirling flag -> a compile-time tag, as with_act does in mlp_fused.hip
+template <typename F> int with_loss(int kind, bool full, F&& f) {
+    switch (kind) {
+    case MMFM_LOSS_POISSON_LOG: return full ? f(loss_tag<MMFM_LOSS_POISSON_LOG, true>()) : f(loss_tag<MMFM_LOSS_POISSON_LOG, false>());
+    case MMFM_LOSS_MSE: return f(loss_tag<MMFM_LOSS_MSE, false>());
+    case MMFM_LOSS_POISSON_RATE: return full ? f(loss_tag<MMFM_LOSS_POISSON_RATE, true>()) : f(loss_tag<MMFM_LOSS_POISSON_RATE, false>());
+    case MMFM_LOSS_L1: return f(loss_tag<MMFM_LOSS_L1, false>());
+    case MMFM_LOSS_SMOOTH_L1: return f(loss_tag<MMFM_LOSS_SMOOTH_L1, false>());
+    case MMFM_LOSS_HUBER: return f(loss_tag<MMFM_LOSS_HUBER, false>());
+    default: return f(loss_tag<MMFM_LOSS_BCE_LOGITS, false>());
+    }
+}
+
+// the kind's own argument rules; the shape rules are the entry points'
+bool loss_kind_ok(int kind, float param, int flags) {
+    const bool poisson = kind == MMFM_LOSS_POISSON_LOG || kind == MMFM_LOSS_POISSON_RATE;
+    return kind >= MMFM_LOSS_POISSON_LOG && kind <= MMFM_LOSS_BCE_LOGITS && param >= 0.f && (flags & ~MMFM_LOSS_FULL) == 0 &&
+           (flags == 0 || poisson);
+}
+
+// `what` = the entry point's name in the error text; arguments are checked by the caller
+int launch_fwd(const char* what, int dtype, int kind, float param, int flags, const void* pred, const float* target, const uint8_t* rowmask,
+               int mask_ld, int T, int64_t R, int N, float* loss_sum, void* workspace, mmfm_stream stream) {
+    const int nb = loss_blocks(R);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "%s: bad dtype %d", what, dtype);
+    const int rc = with_loss(kind, (flags & MMFM_LOSS_FULL) != 0, [&](auto K) {
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_fwd_kernel<float, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, st, param, (const float*)pred, target, rowmask, mask_ld, T, R, N, (float*)workspace);
+        else
+            hipLaunchKernelGGL((loss_fwd_kernel<uint16_t, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, st, param, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, (float*)workspace);
+        MMFM_LAUNCH_CHECK(what);
+        return 0;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nb, loss_sum);
+    MMFM_LAUNCH_CHECK(what);
+    return 0;
+}
+
+int launch_bwd(const char* what, int dtype, int kind, float param, const void* pred, const float* target, const uint8_t* rowmask, int mask_ld,
+               int T, int64_t R, int N, const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream) {
+    const int nb = loss_blocks(R);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "%s: bad dtype %d", what, dtype);
+    return with_loss(kind, false, [&](auto K) {            // the Stirling term has no gradient: one backward per kind
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_bwd_kernel<float, Kd::kind>), dim3(nb), dim3(256), 0, st, param, (const float*)pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, (float*)dpred);
+        else
+            hipLaunchKernelGGL((loss_bwd_kernel<uint16_t, Kd::kind>), dim3(nb), dim3(256), 0, st, param, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, (uint16_t*)dpred);
+        MMFM_LAUNCH_CHECK(what);
+        return 0;
+    });
+}
 
 }  // namespace
 
@@ -77,18 +168,17 @@ extern "C" int mmfm_masked_loss_fwd(int dtype, int kind, const void* pred, const
     MMFM_REQUIRE(pred && target && rowmask && loss_sum, "mmfm_masked_loss_fwd: null pointer");
     MMFM_REQUIRE((kind == 0 || kind == 1) && R > 0 && N > 0 && T > 0 && R % T == 0 && mask_ld >= T, "mmfm_masked_loss_fwd: bad arguments");
     MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_masked_loss_workspace(R, N), "mmfm_masked_loss_fwd: workspace too small");
-    const int nb = loss_blocks(R);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMFM_F32)
-        hipLaunchKernelGGL(loss_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, kind, (const float*)pred, target, rowmask, mask_ld, T, R, N, (float*)workspace);
-    else if (dtype == MMFM_BF16)
-        hipLaunchKernelGGL(loss_fwd_kernel<uint16_t>, dim3(nb), dim3(256), 0, st, kind, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, (float*)workspace);
-    else
-        return mmfm_set_error(-1, "mmfm_masked_loss_fwd: bad dtype %d", dtype);
-    MMFM_LAUNCH_CHECK("mmfm_masked_loss_fwd");
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nb, loss_sum);
-    MMFM_LAUNCH_CHECK("mmfm_masked_loss_fwd(sum)");
-    return 0;
+    return launch_fwd("mmfm_masked_loss_fwd", dtype, kind, 0.f, 0, pred, target, rowmask, mask_ld, T, R, N, loss_sum, workspace, stream);
+}
+
+extern "C" int mmfm_masked_loss_kind_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, float* loss_sum, void* workspace,
+                                         int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && rowmask && loss_sum, "mmfm_masked_loss_kind_fwd: null pointer");
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_kind_fwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(R > 0 && N > 0 && T > 0 && R % T == 0 && mask_ld >= T, "mmfm_masked_loss_kind_fwd: bad arguments");
+    MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_masked_loss_workspace(R, N), "mmfm_masked_loss_kind_fwd: workspace too small");
+    return launch_fwd("mmfm_masked_loss_kind_fwd", dtype, kind, param, flags, pred, target, rowmask, mask_ld, T, R, N, loss_sum, workspace, stream);
 }
 
 extern "C" int mmfm_loss_finalize(const float* loss_sum, const int64_t* count, int M, float* loss, float* inv_n, mmfm_stream stream) {
@@ -102,14 +192,14 @@ extern "C" int mmfm_masked_loss_bwd(int dtype, int kind, const void* pred, const
                                     int T, int64_t R, int N, const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream) {
     MMFM_REQUIRE(pred && target && rowmask && grad_out && inv_n && dpred, "mmfm_masked_loss_bwd: null pointer");
     MMFM_REQUIRE((kind == 0 || kind == 1) && R > 0 && N > 0 && T > 0 && R % T == 0 && mask_ld >= T, "mmfm_masked_loss_bwd: bad arguments");
-    const int nb = loss_blocks(R);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMFM_F32)
-        hipLaunchKernelGGL(loss_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, kind, (const float*)pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, (float*)dpred);
-    else if (dtype == MMFM_BF16)
-        hipLaunchKernelGGL(loss_bwd_kernel<uint16_t>, dim3(nb), dim3(256), 0, st, kind, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, (uint16_t*)dpred);
-    else
-        return mmfm_set_error(-1, "mmfm_masked_loss_bwd: bad dtype %d", dtype);
-    MMFM_LAUNCH_CHECK("mmfm_masked_loss_bwd");
-    return 0;
+    return launch_bwd("mmfm_masked_loss_bwd", dtype, kind, 0.f, pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, dpred, stream);
+}
+
+extern "C" int mmfm_masked_loss_kind_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const float* grad_out,
+                                         const float* inv_n, void* dpred, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && rowmask && grad_out && inv_n && dpred, "mmfm_masked_loss_kind_bwd: null pointer");
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_kind_bwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(R > 0 && N > 0 && T > 0 && R % T == 0 && mask_ld >= T, "mmfm_masked_loss_kind_bwd: bad arguments");
+    return launch_bwd("mmfm_masked_loss_kind_bwd", dtype, kind, param, pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, dpred, stream);
 }

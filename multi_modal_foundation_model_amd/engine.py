@@ -48,7 +48,11 @@ class EngineConfig:
     sep_mask: bool
     causal_mask: bool
     mods: List[Tuple[str, int]]                 # (name, channels) in avail_mod order
-    loss_kind: Dict[str, int] = field(default_factory=lambda: dict(LOSS_KIND))
+    loss_kind: Dict[str, int] = field(default_factory=lambda: dict(LOSS_KIND))    # modality -> MMFM_LOSS_* kind
+    # per modality, for the kinds that have them (absent = 0): the kind's float (PoissonNLL eps, SmoothL1 beta, Huber delta) and its
+    # flags (L.LOSS_FULL = PoissonNLLLoss(full=True)).  A modality of kind 0 / 1 without flags runs the two-kind entry points
+    loss_param: Dict[str, float] = field(default_factory=dict)
+    loss_flags: Dict[str, int] = field(default_factory=dict)
     norm: str = "layernorm"                     # the transformer blocks' norms: "layernorm" or "scalenorm" (use_scalenorm: true)
     act: Tuple[int, float] = (L.MLP_GELU, 1.0)  # the MLP activation (transformer.act): (MMFM_MLP_* kind, sigmoid beta), ops.mlp_act
     # transformer.attention_bias / transformer.mlp_bias, per side (the two YAML sections are independent): False = the side's
@@ -519,6 +523,14 @@ class Engine:
         ws_col = buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
         ws_ln = buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
         ws_st = buf("ws/stitch", (max(1, L.lib().mmfm_stitch_bwd_workspace(code, B, T, Lq, H, c.max_F) // 4),), f32)
+
+        def loss_of(mod):        # (kind, param, flags) of the modality's loss
+            return c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
+
+        def two_kind(mod):       # PoissonNLL(log_input) / MSE without a flag: the two-kind entry points, call for call the plan it always was
+            kind, _, flags = loss_of(mod)
+            return kind in (L.LOSS_POISSON_LOG, L.LOSS_MSE) and flags == 0
+
         ws_loss = buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
 
         def lin(plan, X, wname, Y, Mr, N, Kd, ldx=None, **kw):
@@ -818,8 +830,11 @@ class Engine:
         for m, (mod, n) in enumerate(c.mods):
             pred = buf(f"pred/{m}", (BT, n))
             lin(fwd, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
-            K.masked_loss_fwd(c.loss_kind[mod], pred, self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n, loss_sum[m:m + 1],
-                              ws_loss, plan=fwd)
+            loss_args = (pred, self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n, loss_sum[m:m + 1], ws_loss)
+            if two_kind(mod):
+                K.masked_loss_fwd(c.loss_kind[mod], *loss_args, plan=fwd)
+            else:
+                K.masked_loss_kind_fwd(*loss_of(mod), *loss_args, plan=fwd)
         K.loss_finalize(loss_sum, count, M, self.b["loss"], self.b["inv_n"], plan=fwd)
 
         if not grad:
@@ -848,8 +863,11 @@ class Engine:
         du, dqkv, dctx = buf("d/u", (R, I)), buf("d/qkv", (R, 3 * H)), buf("d/ctx", (R, H))
         for m, (mod, n) in enumerate(c.mods):
             dpred = buf(f"d/pred/{m}", (BT, n))
-            K.masked_loss_bwd(c.loss_kind[mod], self.b[f"pred/{m}"], self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n,
-                              self.b["gout"], self.b["inv_n"], dpred, plan=cur)
+            loss_args = (self.b[f"pred/{m}"], self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n, self.b["gout"], self.b["inv_n"], dpred)
+            if two_kind(mod):
+                K.masked_loss_bwd(c.loss_kind[mod], *loss_args, plan=cur)
+            else:
+                K.masked_loss_kind_bwd(*loss_of(mod), *loss_args, plan=cur)
             dlin(cur, dpred, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[m * BT:(m + 1) * BT])
         ln_b(cur, dydec, dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
         close_segment("head")

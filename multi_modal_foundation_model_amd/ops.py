@@ -176,12 +176,23 @@ def masked_loss_fwd(kind, pred, target, rowmask, mask_ld, T, R, N, loss_sum, ws,
                                                ws.numel() * ws.element_size()))
 
 
+def masked_loss_kind_fwd(kind, param, flags, pred, target, rowmask, mask_ld, T, R, N, loss_sum, ws, plan=None):
+    """Every MMFM_LOSS_* kind (param = eps / beta / delta, flags = L.LOSS_FULL or 0); kinds 0 / 1 give masked_loss_fwd's bits."""
+    _emit(plan, L.lib().mmfm_masked_loss_kind_fwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(rowmask), mask_ld, T, R, N,
+                                                    P(loss_sum), P(ws), ws.numel() * ws.element_size()))
+
+
 def loss_finalize(loss_sum, count, M, loss, inv_n, plan=None):
     _emit(plan, L.lib().mmfm_loss_finalize, (P(loss_sum), P(count), M, P(loss), P(inv_n)))
 
 
 def masked_loss_bwd(kind, pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, dpred, plan=None):
     _emit(plan, L.lib().mmfm_masked_loss_bwd, (dt(pred), kind, P(pred), P(target), P(rowmask), mask_ld, T, R, N, P(grad_out), P(inv_n), P(dpred)))
+
+
+def masked_loss_kind_bwd(kind, param, flags, pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, dpred, plan=None):
+    _emit(plan, L.lib().mmfm_masked_loss_kind_bwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(rowmask), mask_ld, T, R, N,
+                                                    P(grad_out), P(inv_n), P(dpred)))
 
 
 def dropout_apply(src, dst, R, N, drop, plan=None):

@@ -20,6 +20,7 @@ from models.model_output import ModelOutput
 from multi_modal.decoder_embeddings import DecoderLayer
 from multi_modal.encoder_embeddings import EncoderLayer
 from multi_modal.mm_utils import create_context_mask  # noqa: F401  (re-exported like the reference)
+from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd.engine import Engine, EngineConfig
 from utils.config_utils import DictConfig
 
@@ -35,18 +36,56 @@ class MultiModalOutput(ModelOutput):
     mod_targets: Optional[Dict[str, torch.FloatTensor]] = None
 
 
-def _loss_kind(spec) -> int:
-    """loss_mod entry -> mmfm_masked_loss kind.  Entries are strings here; the reference's entries are
+# loss_mod strings of the kinds beyond the reference's two, with torch's default parameters: (MMFM_LOSS_* kind, param, flags)
+_LOSS_STRINGS = {"poisson_nll_rate": (L.LOSS_POISSON_RATE, 1e-8, 0), "l1": (L.LOSS_L1, 0.0, 0), "smooth_l1": (L.LOSS_SMOOTH_L1, 1.0, 0),
+                 "huber": (L.LOSS_HUBER, 1.0, 0), "bce_with_logits": (L.LOSS_BCE_LOGITS, 0.0, 0)}
+
+
+def _loss_spec(spec):
+    """loss_mod entry -> (MMFM_LOSS_* kind, param, flags) of mmfm_masked_loss_kind_*: param = the module's eps / beta / delta (0 where the
+    kind has none), flags = L.LOSS_FULL for PoissonNLLLoss(full=True).  Entries are strings here; the reference's entries are
     nn.PoissonNLLLoss(reduction="none", log_input=True) / nn.MSELoss(reduction="none") (mm.py:79-82), accepted too, so
-    `model.loss_mod['lfp'] = nn.MSELoss(reduction='none')` adds a modality exactly as it would upstream."""
+    `model.loss_mod['lfp'] = nn.MSELoss(reduction='none')` adds a modality exactly as it would upstream.  So do, by exact class,
+    nn.PoissonNLLLoss (either log_input, full), nn.L1Loss, nn.SmoothL1Loss, nn.HuberLoss and nn.BCEWithLogitsLoss, and the strings of
+    _LOSS_STRINGS.  What was accepted before those maps as it did: any other string or class name containing 'poisson' -> 0, 'mse' -> 1."""
+    if isinstance(spec, str):
+        if spec.lower() in _LOSS_STRINGS:
+            return _LOSS_STRINGS[spec.lower()]
+    else:
+        cls = type(spec)
+        legacy = cls is nn.PoissonNLLLoss and spec.log_input and not spec.full       # the reference's own spike loss: as before, unchecked
+        if cls in (nn.PoissonNLLLoss, nn.L1Loss, nn.SmoothL1Loss, nn.HuberLoss, nn.BCEWithLogitsLoss) and not legacy:
+            if spec.reduction != "none":
+                raise NotImplementedError(f"loss {spec!r}: reduction={spec.reduction!r} is not built - the reference multiplies the "
+                                          "per-element loss by the token mask (mm.py:217-239), which needs reduction='none'")
+            if cls is nn.BCEWithLogitsLoss and (spec.weight is not None or spec.pos_weight is not None):
+                raise NotImplementedError("BCEWithLogitsLoss with weight / pos_weight has no HIP kernel")
+            if cls is nn.PoissonNLLLoss:
+                kind, param = (L.LOSS_POISSON_LOG, 0.0) if spec.log_input else (L.LOSS_POISSON_RATE, spec.eps)      # log input: eps is not read
+                flags = L.LOSS_FULL if spec.full else 0
+            elif cls is nn.SmoothL1Loss:
+                kind, param, flags = L.LOSS_SMOOTH_L1, spec.beta, 0
+            elif cls is nn.HuberLoss:
+                kind, param, flags = L.LOSS_HUBER, spec.delta, 0
+            else:
+                kind, param, flags = (L.LOSS_L1 if cls is nn.L1Loss else L.LOSS_BCE_LOGITS), 0.0, 0
+            if not float(param) >= 0 or (cls is nn.HuberLoss and not float(param) > 0):      # torch rejects these when the loss is called
+                raise ValueError(f"loss {spec!r}: eps / beta must be >= 0 and delta > 0")
+            return kind, float(param), flags
     name = (spec if isinstance(spec, str) else type(spec).__name__).lower()
     if "poisson" in name:
         if not isinstance(spec, str) and not getattr(spec, "log_input", True):
-            raise NotImplementedError("PoissonNLLLoss(log_input=False) has no HIP kernel")
-        return 0
+            raise NotImplementedError(f"loss {spec!r}: log_input=False is built for nn.PoissonNLLLoss itself, not for this class")
+        return L.LOSS_POISSON_LOG, 0.0, 0
     if "mse" in name:
-        return 1
-    raise NotImplementedError(f"loss {spec!r}: only PoissonNLL(log_input) and MSE are built")
+        return L.LOSS_MSE, 0.0, 0
+    raise NotImplementedError(f"loss {spec!r}: no HIP kernel for this class / name - built are PoissonNLLLoss, MSELoss, L1Loss, SmoothL1Loss, "
+                              f"HuberLoss, BCEWithLogitsLoss (reduction='none') and the strings {sorted(_LOSS_STRINGS)}")
+
+
+def _loss_kind(spec) -> int:
+    """loss_mod entry -> its MMFM_LOSS_* kind alone (0 / 1 for everything the two-kind library accepted)."""
+    return _loss_spec(spec)[0]
 
 
 class MultiModal(nn.Module):
@@ -84,7 +123,8 @@ class MultiModal(nn.Module):
         self.decoder_proj_context = nn.Linear(self.hidden_size, self.hidden_size)
         self.decoder = nn.ModuleList([DecoderLayer(i, config.decoder.transformer) for i in range(self.n_dec_layers)])
         self.decoder_norm = nn.LayerNorm(self.hidden_size)
-        # loss per modality (mm.py:79-82): 'ap' PoissonNLL(log_input), 'behavior' MSE — computed by mmfm_masked_loss_*
+        # loss per modality (mm.py:79-82): 'ap' PoissonNLL(log_input), 'behavior' MSE — computed by mmfm_masked_loss_*; _loss_spec lists
+        # what an added or replaced entry may be
         self.loss_mod = {"ap": "poisson_nll_log_input", "behavior": "mse"}
 
         self._model_config = config
@@ -121,7 +161,10 @@ class MultiModal(nn.Module):
                 if m not in self.loss_mod:
                     raise Exception("Modality not implemented yet.")
             cfg = EngineConfig.from_model_config(self._model_config, mods)
-            cfg.loss_kind = {m: _loss_kind(self.loss_mod[m]) for m, _ in mods}
+            specs = {m: _loss_spec(self.loss_mod[m]) for m, _ in mods}
+            cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
+            cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
+            cfg.loss_flags = {m: sp[2] for m, sp in specs.items()}
             self._engine = Engine(cfg, dev, dtype=self.compute_dtype, seed=self.engine_seed)
             self._engine.adopt(named)
         elif not self._engine.owns(named):
