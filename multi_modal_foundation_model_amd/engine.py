@@ -984,9 +984,36 @@ class Engine:
             tw = self._wt_table()
             K.prep_weights(tw["table"], tw["n"], tw["tiles"], plan=fwd)
             fwd.insert(0, fwd.pop())
-        plan = dict(fwd=fwd, bwd=bwd, B=B, T=T, training=bool(training), M=M, R=R, BT=BT, runs=dict(fwd=0, bwd=0), graphs={}, b=self.b)
+        plan = dict(fwd=fwd, bwd=bwd, B=B, T=T, training=bool(training), M=M, R=R, BT=BT, runs=dict(fwd=0, bwd=0), graphs={}, b=self.b,
+                    fused=fm, use_keep=use_keep)
         self.plans[key] = plan
         return plan
+
+    def dropout_sites(self, B, T):
+        """Read-only description of the dropout sites of the built training plan of batch shape (B, T), for tests that read the masks
+        back off the kernels: one dict per site with
+          key    the site's name (`{side}/embdrop/{m}`, `<tag>/p`, `<tag>/o`, `<tag>/mlpdrop`),
+          site   its id in the counter hash, p its drop probability,
+          kind   "flat" (counter row * N + col over shape (R, N): GEMM epilogue / mmfm_dropout_apply / stitch_bwd / attention drop_o),
+                 "rowdrop" (the fused MLP's row-keyed hash over (R, 256)) or "attn" (drop_p over (B, heads, Lq, Lk)),
+          shape  as above, and for "attn" also dh and keepbits: the site's keep-bit workspace, or None when both directions hash.
+        Builds nothing and launches nothing: the plan must exist (one training forward ran at this shape)."""
+        plan = self.plans[(B, T, True, True)]
+        c = self.cfg
+        H, heads, Lq = c.hidden, c.heads, len(c.mods) * T
+        out = []
+        for key, site in self._sites.items():
+            if "/embdrop/" in key:
+                d = dict(p=c.embed_dropout, kind="flat", shape=(B * T, H))
+            elif key.endswith("/mlpdrop"):
+                d = dict(p=c.dropout, kind="rowdrop" if plan["fused"] & 4 else "flat", shape=(B * Lq, H))
+            elif key.endswith("/o"):
+                d = dict(p=c.dropout, kind="flat", shape=(B * Lq, H))
+            else:
+                d = dict(p=c.dropout, kind="attn", shape=(B, heads, Lq, Lq), dh=H // heads,
+                         keepbits=plan["b"].get(key[:-2] + "/keep") if plan["use_keep"] else None)
+            out.append(dict(key=key, site=site, **d))
+        return out
 
     def _run(self, plan, which, entries_fn, tag=None):
         """Run a piece of the plan: eagerly the first time (lazy one-off initialisation such as the >64 KB LDS

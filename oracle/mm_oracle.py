@@ -261,7 +261,17 @@ def softsign(x):
     return x / (1 + x.abs())
 
 
-def embed(sd, p, inputs, ts, mod_idx, cfg: OracleCfg, training, gen=None):
+def dropout(x, p, training, dropout_fn=None, site_key=None):
+    """nn.Dropout / F.dropout.  `dropout_fn(site_key, x)`, when given, stands in for torch's RNG at a training-mode site with
+    p > 0: it returns the multiplier tensor (0, or the survivor scale) of x's shape, so that a test can feed the oracle the masks
+    another implementation drew.  Site keys are the HIP engine's: `{side}/embdrop/{m}`, `<tag>/p`, `<tag>/o`, `<tag>/mlpdrop`
+    with <tag> = enc{i}/sa, dec{i}/sa, dec{i}/xa for the attention sites and enc{i}, dec{i} for the MLP ones."""
+    if dropout_fn is None or not training or p <= 0:
+        return F.dropout(x, p, training)
+    return x * dropout_fn(site_key, x)
+
+
+def embed(sd, p, inputs, ts, mod_idx, cfg: OracleCfg, training, gen=None, dropout_fn=None, site_key=None):
     """EncoderEmbeddingLayer.forward / DecoderEmbeddingLayer.forward
     (encoder_embeddings.py:44-61, decoder_embeddings.py:43-61)."""
     scale = cfg.hidden ** 0.5 if cfg.embed_scale is None else cfg.embed_scale
@@ -271,7 +281,7 @@ def embed(sd, p, inputs, ts, mod_idx, cfg: OracleCfg, training, gen=None):
     B, T, _ = inputs.shape
     e = sd[p + ".mod_emb.weight"][mod_idx][None, None, :].expand(B, T, -1).clone()
     e = e + sd[p + ".pos_embed.weight"][ts]
-    return F.dropout(x, cfg.embed_dropout, training), e
+    return dropout(x, cfg.embed_dropout, training, dropout_fn, site_key), e
 
 
 def zero_masked_tokens(tokens, mask):
@@ -303,7 +313,7 @@ def decoder_attn_mask(keypad, mod_mask, causal, sep):
     return m
 
 
-def attention(sd, p, xq, xkv, mask, heads, drop, training):
+def attention(sd, p, xq, xkv, mask, heads, drop, training, dropout_fn=None, tag=None):
     """Attention.forward / CrossAttention.forward (mm_utils.py:97-114, 139-152)."""
     B, Lq, H = xq.shape
     Lk = xkv.shape[1]
@@ -313,25 +323,26 @@ def attention(sd, p, xq, xkv, mask, heads, drop, training):
     v = F.linear(xkv, sd[p + ".value.weight"], sd[p + ".value.bias"]).view(B, Lk, heads, dh).transpose(1, 2)
     s = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(dh))
     s = s.masked_fill(~mask[:, None, :, :], float("-inf"))
-    a = F.dropout(torch.softmax(s, dim=-1), drop, training)
+    a = dropout(torch.softmax(s, dim=-1), drop, training, dropout_fn, f"{tag}/p")
     o = (a @ v).transpose(1, 2).contiguous().view(B, Lq, H)
-    return F.linear(F.dropout(o, drop, training), sd[p + ".out_proj.weight"], sd[p + ".out_proj.bias"])
+    return F.linear(dropout(o, drop, training, dropout_fn, f"{tag}/o"), sd[p + ".out_proj.weight"], sd[p + ".out_proj.bias"])
 
 
 def layer_norm(sd, p, x):
     return F.layer_norm(x, (x.shape[-1],), sd[p + ".weight"], sd[p + ".bias"], 1e-5)
 
 
-def mlp(sd, p, x, drop, training):
+def mlp(sd, p, x, drop, training, dropout_fn=None, tag=None):
     """MLP.forward (mm_utils.py:50-52); ACT2FN['gelu'] is the exact-erf GELU."""
     h = F.gelu(F.linear(x, sd[p + ".up_proj.weight"], sd[p + ".up_proj.bias"]))
-    return F.dropout(F.linear(h, sd[p + ".down_proj.weight"], sd[p + ".down_proj.bias"]), drop, training)
+    return dropout(F.linear(h, sd[p + ".down_proj.weight"], sd[p + ".down_proj.bias"]), drop, training, dropout_fn, f"{tag}/mlpdrop")
 
 
 def forward(sd, mod_dict, cfg: OracleCfg, training: bool = False, masker: Optional[OracleMasker] = None,
-            keep: bool = False):
+            keep: bool = False, dropout_fn=None):
     """MultiModal.forward (mm.py:242-308).  `mod_dict` as built by
-    MultiModalTrainer._forward_model_outputs (trainer/base.py:51-103).  Returns a dict."""
+    MultiModalTrainer._forward_model_outputs (trainer/base.py:51-103).  Returns a dict.
+    dropout_fn: optional mask source in place of torch's RNG at the five dropout sites (see `dropout`)."""
     mods = [m for m in mod_dict]
     mod_to_idx = {m: i for i, m in enumerate(cfg.avail_mod)}
     dp = cfg.dropout
@@ -349,17 +360,17 @@ def forward(sd, mod_dict, cfg: OracleCfg, training: bool = False, masker: Option
         else:
             mk = d["eval_mask"]
         masks[mod] = mk[:, :, 0] & d["inputs_attn_mask"]              # mm.py:270
-    for mod in mods:                                                   # mm.py:277-279
+    for m, mod in enumerate(mods):                                     # mm.py:277-279
         d = mod_dict[mod]
         x, e = embed(sd, f"encoder_embeddings.{mod}.embedder", d["inputs"], d["inputs_timestamp"],
-                     mod_to_idx[mod], cfg, training)
+                     mod_to_idx[mod], cfg, training, dropout_fn=dropout_fn, site_key=f"encoder/embdrop/{m}")
         x_e.append(x); e_e.append(e)
         keyp.append(d["inputs_attn_mask"])
         modm.append(torch.full_like(masks[mod], mod_to_idx[mod], dtype=torch.int16))
-    for mod in mods:                                                   # mm.py:283-285
+    for m, mod in enumerate(mods):                                     # mm.py:283-285
         d = mod_dict[mod]
         x, e = embed(sd, f"decoder_embeddings.{mod}.embedder", d["inputs"], d["inputs_timestamp"],
-                     mod_to_idx[mod], cfg, training)
+                     mod_to_idx[mod], cfg, training, dropout_fn=dropout_fn, site_key=f"decoder/embdrop/{m}")
         x_d.append(x); e_d.append(e)
     tok_mask = torch.cat([masks[m] for m in mods], 1)
     keypad = torch.cat(keyp, 1)
@@ -375,8 +386,8 @@ def forward(sd, mod_dict, cfg: OracleCfg, training: bool = False, masker: Option
     for i in range(cfg.n_enc):                                         # encoder_embeddings.py:106-116
         p = f"encoder.{i}"
         h = layer_norm(sd, p + ".ln1", x)
-        x = x + attention(sd, p + ".attn", h, h, am_enc, cfg.heads, dp, training)
-        x = x + mlp(sd, p + ".mlp", layer_norm(sd, p + ".ln2", x), dp, training)
+        x = x + attention(sd, p + ".attn", h, h, am_enc, cfg.heads, dp, training, dropout_fn, f"enc{i}/sa")
+        x = x + mlp(sd, p + ".mlp", layer_norm(sd, p + ".ln2", x), dp, training, dropout_fn, f"enc{i}")
     enc_out = layer_norm(sd, "encoder_norm", x)
     ctx_proj = F.linear(enc_out, sd["decoder_proj_context.weight"], sd["decoder_proj_context.bias"])
     context = ctx_proj + enc_emb                                       # mm.py:292
@@ -384,10 +395,10 @@ def forward(sd, mod_dict, cfg: OracleCfg, training: bool = False, masker: Option
     for i in range(cfg.n_dec):                                         # decoder_embeddings.py:133-147
         p = f"decoder.{i}"
         h = layer_norm(sd, p + ".ln1", y)
-        y = y + attention(sd, p + ".attn", h, h, am_dec, cfg.heads, dp, training)
+        y = y + attention(sd, p + ".attn", h, h, am_dec, cfg.heads, dp, training, dropout_fn, f"dec{i}/sa")
         y = y + attention(sd, p + ".cross_attn", layer_norm(sd, p + ".query_norm", y),
-                          layer_norm(sd, p + ".context_norm", context), am_enc, cfg.heads, dp, training)
-        y = y + mlp(sd, p + ".mlp", layer_norm(sd, p + ".ln2", y), dp, training)
+                          layer_norm(sd, p + ".context_norm", context), am_enc, cfg.heads, dp, training, dropout_fn, f"dec{i}/xa")
+        y = y + mlp(sd, p + ".mlp", layer_norm(sd, p + ".ln2", y), dp, training, dropout_fn, f"dec{i}")
     dec_out = layer_norm(sd, "decoder_norm", y)
 
     B = dec_out.shape[0]

@@ -1,0 +1,170 @@
+"""One whole training step with dropout ON against the oracle in double precision, fed the step's own masks.
+
+torch's RNG cannot reproduce the engine's masks and does not have to: every mask is a pure function of (state, site, index).  After
+one forward + backward the engine's RNG state is still the one the step used, so every site's multiplier is read back off the kernels
+(tests/dropout_refs.py: the flat hash through mmfm_dropout_apply, attention drop_p from the engine's own keep-bit workspaces or the
+one-hot-V read-out on the kernel family the plan runs, the fused MLP's RowDrop through the backward's t1) and handed to
+oracle.mm_oracle.forward through its dropout_fn hook.  The token masks are the ones the model's masker drew for the step.  What the
+oracle then computes is the step the engine claims to have run: loss, predictions and every parameter gradient must agree to the
+bounds of the dropout-free tests.  A backward that keys a site differently from its forward, a counter built from the wrong stride, a
+survivor scale applied twice or not at all, or a row-keyed hash off by a row each give a biased gradient that still trains - and
+fail here."""
+import numpy as np
+import pytest
+import torch
+
+import dropout_refs as DR
+from helpers import build_model, model_config, tiny_config
+from oracle import mm_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+VARIANTS = {"base": (dict(), None), "pad": (dict(), [0, 3, 1]), "sep": (dict(sep=True), [0, 2, 0]), "causal": (dict(causal=True), [1, 0, 0]),
+            "deep": (dict(n_enc=2, n_dec=2), [0, 0, 5])}
+
+
+def to_dev(md):
+    for d in md.values():
+        for k, v in list(d.items()):
+            if isinstance(v, torch.Tensor):
+                d[k] = v.cuda()
+        d["targets_modality"] = d["inputs_modality"]
+        d["targets_timestamp"] = d["inputs_timestamp"]
+    return md
+
+
+def cosine(a, b):
+    a, b = a.double().flatten(), b.double().flatten()
+    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
+
+
+def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed):
+    """One training step of the HIP engine, then the fp64 oracle (on the GPU, plain torch) with the step's token masks and dropout
+    multipliers.  Returns the model output, {name: grad}, the oracle's output dict, {name: oracle grad} and the engine."""
+    from multi_modal_foundation_model_amd import ops as K
+    model = build_model(mc, n_ap, n_beh, seed=model_seed)
+    model.compute_dtype = dtype
+    model.engine_seed = 77
+    model.cuda().train()
+    torch.manual_seed(5)
+    md = to_dev(O.make_mod_dict(batch, objective))
+    out = model(md)
+    out.loss.backward()
+    torch.cuda.synchronize()
+    eng = model._engine
+    B, T = batch["spikes_data"].shape[:2]
+    mults = {k: v.cuda() for k, v in DR.collect_step_multipliers(K, eng, B, T).items()}
+    cfg = O.OracleCfg.from_model_config(mc, {"ap": n_ap, "behavior": n_beh})
+    sd = O.share_mod_emb({k: v.detach().double().clone() for k, v in model.state_dict().items()}, cfg)
+    keys = O.trainable_keys(sd, cfg)
+    for k in keys:
+        sd[k].requires_grad_(True)
+    ref_md = O.make_mod_dict(batch, objective)
+    for m, d in ref_md.items():
+        for k, v in list(d.items()):
+            if isinstance(v, torch.Tensor):
+                d[k] = v.cuda().double() if v.is_floating_point() else v.cuda()
+        d["eval_mask"] = md[m]["inputs_mask"][:, :, None].to(torch.int64)          # the token masks the step ran with
+    used = set()
+    ref = O.forward(sd, ref_md, cfg, training=True, dropout_fn=DR.oracle_dropout_fn(mults, used))
+    assert used == set(mults), sorted(set(mults) ^ used)                           # every site of the engine is a site of the model
+    grads = dict(zip(keys, torch.autograd.grad(ref["loss"], [sd[k] for k in keys])))
+    named = {k: p.grad for k, p in model.named_parameters()}
+    assert set(named) == set(keys)
+    return out, named, ref, grads, eng
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("objective", ["encoding", "token_masking"])
+def test_fp32_dropout_step_vs_oracle_fed_the_steps_masks(variant, objective):
+    """fp32 parity engine, tiny config (H 32, 4 heads, dh 8: attention.hip's fp32 kernels, flat-hash dropout everywhere), dropout 0.4 /
+    embed dropout 0.2: loss, per-modality loss, n, predictions and every parameter gradient at the bounds of
+    test_tiny_forward_backward_vs_reference_fixture."""
+    kw, pad = VARIANTS[variant]
+    mc = tiny_config(dropout=0.4, emb_dropout=0.2, **kw)
+    batch = O.synth_batch(3, 8, 12, 2, seed=4, pad=pad)
+    out, named, ref, grads, eng = engine_step_and_oracle(mc, 12, 2, batch, objective, "fp32", 0)
+    sites = eng.dropout_sites(3, 8)
+    n_layers = 2 if variant == "deep" else 1
+    assert len(sites) == 4 + (3 + 5) * n_layers and all(s["kind"] in ("flat", "attn") for s in sites)
+    assert out.loss.item() == pytest.approx(ref["loss"].item(), rel=2e-5)
+    for m in ("ap", "behavior"):
+        assert int(out.mod_n_examples[m]) == int(ref["mod_n_examples"][m])
+        assert out.mod_loss[m].item() == pytest.approx(ref["mod_loss"][m].item(), rel=5e-5, abs=1e-6)
+        np.testing.assert_allclose(out.mod_preds[m].cpu().numpy(), ref["mod_preds"][m].detach().cpu().numpy(), rtol=1e-4, atol=2e-5)
+    for k, g in named.items():
+        r = grads[k].cpu().numpy()
+        np.testing.assert_allclose(g.cpu().numpy(), r, rtol=2e-3, atol=3e-6 + 1e-4 * np.abs(r).max(), err_msg=k)
+
+
+def bf16_stats(out, named, ref, grads):
+    """Worst loss error, gradient cosine (tensors of >= 256 / < 256 elements) and norm ratio error over all tensors but key.bias
+    (softmax is invariant to a key bias: its true gradient is 0)."""
+    st = dict(loss=abs(out.loss.item() / ref["loss"].item() - 1), cos_big=1.0, cos_small=1.0, norm=0.0)
+    for k, g in named.items():
+        r = grads[k]
+        if k.endswith("key.bias"):
+            continue
+        if float(r.abs().max()) == 0:
+            assert float(g.abs().max()) == 0, k
+            continue
+        c = cosine(g, r)
+        which = "cos_big" if r.numel() >= 256 else "cos_small"
+        if c < st[which]:
+            st[which], st[which + "_at"] = c, k
+        n = abs(g.double().norm().item() / r.norm().item() - 1)
+        if n > st["norm"]:
+            st["norm"], st["norm_at"] = n, k
+    return st
+
+
+def check_bf16(st, what):
+    print(f"{what}: {st}")
+    assert st["loss"] < 2e-2, (what, st)
+    assert st["cos_big"] > 0.995 and st["cos_small"] > 0.98, (what, st)
+    assert st["norm"] < 5e-2, (what, st)
+
+
+@pytest.mark.parametrize("dropout", ["off", "on"])
+def test_bf16_fused_dropout_step_vs_oracle_fed_the_steps_masks(monkeypatch, dropout):
+    """bf16, every row-owner group fused (MMFM_FUSED=15), default widths (hidden 256, 8 heads: the dh-32 keep-bit attention pair, the
+    fused MLP's RowDrop), n_enc = n_dec = 2, B = 16, T = 100, two padded trials, dropout 0.4 / 0.2, against the fp64 oracle at the bounds
+    test_bf16_fused_row_owner_path_matches_unfused_kernels states: loss within 2e-2, cosine > 0.995 (> 0.98 under 256 elements), norm
+    within 5e-2, key.bias skipped.  `off` is the same comparison at dropout 0: what bf16 alone costs against fp64.
+    Measured on the MI355X (worst over tensors):
+      dropout off: loss error 3.0e-5, cosine 0.999990 (>= 256 elements) / 0.999977 (< 256), norm error 3.7e-3
+      dropout on : loss error 1.5e-5, cosine 0.999990 / 0.999976, norm error 3.9e-3."""
+    monkeypatch.setenv("MMFM_FUSED", "15")
+    on = dropout == "on"
+    mc = model_config(n_enc=2, n_dec=2) if on else model_config(n_enc=2, n_dec=2, dropout=0.0, emb_dropout=0.0)
+    pad = [0] * 16
+    pad[3], pad[15] = 10, 37
+    batch = O.synth_batch(16, 100, 668, 2, seed=2, pad=pad)
+    out, named, ref, grads, eng = engine_step_and_oracle(mc, 668, 2, batch, "encoding", "bf16", 3)
+    assert eng._fused_mask(16 * 200) == 15
+    if on:
+        kinds = {s["key"]: s["kind"] for s in eng.dropout_sites(16, 100)}
+        assert len(kinds) == 4 + 2 * 3 + 2 * 5                         # 4 embdrop; p, o, mlpdrop per encoder layer; 2 x (p, o) + mlpdrop per decoder layer
+        assert all(v == "rowdrop" for k, v in kinds.items() if k.endswith("/mlpdrop"))
+        assert all(s["keepbits"] is not None and DR.keepbit_path(32, 200, 200) for s in eng.dropout_sites(16, 100) if s["kind"] == "attn")
+    check_bf16(bf16_stats(out, named, ref, grads), f"bf16 fused, dropout {dropout}")
+
+
+@pytest.mark.parametrize("dropout", ["off", "on"])
+def test_bf16_dh64_dropout_step_vs_oracle_fed_the_steps_masks(dropout):
+    """bf16 at dh = 64 (hidden 512, 8 heads, n_enc = n_dec = 1, B = 4, T = 100, CAUSAL + SEP on the decoder): every attention site runs
+    the keep-bit pair of csrc/attention_long.hip (forward epilogue and the prep kernel's dropout'(d_o) / delta), the MLP and the
+    tokenisers the un-fused kernels with the flat hash.  Same bounds as the fused test; `off` is the dropout-0 reference run.
+    Measured on the MI355X (worst over tensors):
+      dropout off: loss error 1.1e-4, cosine 0.999958 (>= 256 elements) / 0.999949 (< 256), norm error 6.3e-3
+      dropout on : loss error 1.0e-4, cosine 0.999957 / 0.999959, norm error 5.1e-3."""
+    on = dropout == "on"
+    kw = dict(H=512, heads=8, n_enc=1, n_dec=1, causal=True, sep=True)
+    mc = model_config(**kw) if on else model_config(dropout=0.0, emb_dropout=0.0, **kw)
+    batch = O.synth_batch(4, 100, 96, 2, seed=6, pad=[0, 10, 0, 37])
+    out, named, ref, grads, eng = engine_step_and_oracle(mc, 96, 2, batch, "encoding", "bf16", 3)
+    if on:
+        sites = eng.dropout_sites(4, 100)
+        assert len(sites) == 4 + 3 + 5 and all(s["kind"] == "flat" for s in sites if not s["key"].endswith("/p"))
+        assert all(s["dh"] == 64 and s["keepbits"] is not None and DR.keepbit_path(64, 200, 200) for s in sites if s["kind"] == "attn")
+    check_bf16(bf16_stats(out, named, ref, grads), f"bf16 dh 64, dropout {dropout}")

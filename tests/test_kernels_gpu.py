@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import load_npz
+from dropout_refs import extract_attn_keep_mask as _extract_attn_keep_mask, unpack_keepbits as _unpack_keepbits
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -731,45 +732,6 @@ def test_gemm_act5_softsign_grad_from_output_error_bound(ops):
     rel_bound = 1.5 * 2.0 ** -8 * (1 + xs.double().abs()) + 2.0 ** -7           # ~0.6 % x (1 + |x|): 5 % at |x| = 8, the whole value beyond ~170
     small = xs.abs() <= 32
     assert bool((err[small] / true[small] <= rel_bound[small]).all())
-
-
-def _extract_attn_keep_mask(ops, state, site, p, B, heads, Lq, Lk):
-    """keep[b, h, q, k] of the attention-probability dropout at (state, site), read off the kernel itself: the decisions depend on
-    (state, site, b, head, query, key) only, not on the data, so with q = k = 0 (uniform probabilities 1 / Lk) and a one-hot V block
-    (V[k, d] = 1 iff k == 32 blk + d) the forward output is keep(q, 32 blk + d) / (Lk (1 - p)): ceil(Lk / 32) launches show every key."""
-    from multi_modal_foundation_model_amd import _lib as Lb
-    dh = 32
-    H = heads * dh
-    q = torch.zeros(B * Lq, H, device="cuda", dtype=torch.bfloat16)
-    kp = torch.ones(B, Lk, dtype=torch.uint8, device="cuda")
-    keep = torch.zeros(B, heads, Lq, Lk, dtype=torch.bool, device="cuda")
-    kb = torch.empty(ops.attn_keepbits_bytes(B, heads, Lq, Lk), dtype=torch.uint8, device="cuda")
-    for blk in range((Lk + 31) // 32):
-        kv = torch.zeros(B, Lk, 2, heads, dh, device="cuda", dtype=torch.bfloat16)
-        n = min(32, Lk - 32 * blk)
-        kv[:, 32 * blk + torch.arange(n), 1, :, torch.arange(n)] = 1.0
-        kv = kv.view(B * Lk, 2 * H)
-        o, lse = torch.empty(B * Lq, H, device="cuda", dtype=torch.bfloat16), torch.empty(B, heads, Lq, device="cuda")
-        desc = ops.attn_desc(Lb.BF16, B, heads, Lq, Lk, dh, q.data_ptr(), kv.data_ptr(), kv.data_ptr() + H * 2, H, 2 * H, 2 * H, o.data_ptr(), H, lse,
-                             kp, None, 0, dh ** -0.5, drop_p=ops.dropout(state, site, p), keepbits=kb)
-        ops.attn_fwd(desc)
-        keep[:, :, :, 32 * blk:32 * blk + n] = (o.view(B, Lq, heads, dh).permute(0, 2, 1, 3)[..., :n] != 0)
-    return keep
-
-
-def _unpack_keepbits(kb, B, heads, Lq, Lk):
-    """keep[b, h, q, k] out of the documented bit-tile layout (csrc/attention_fast.hip header): words [bh][qt][kt][32], word 2 r + kh
-    of a tile = key 32 kt + (r & 3) + 8 (r >> 2) + 4 kh, bit j = query 32 qt + j."""
-    nqt, nkt = (Lq + 31) // 32, (Lk + 31) // 32
-    w = kb[:B * heads * nqt * nkt * 128].view(torch.int32).view(B * heads, nqt, nkt, 32).cpu().numpy().astype(np.uint32)      # (behind the tiles: scratch)
-    bits = ((w[..., None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool)          # [bh, qt, kt, word, qbit]
-    widx = np.arange(32)
-    key_of_word = ((widx >> 1) & 3) + 8 * (widx >> 3) + 4 * (widx & 1)
-    keep = np.zeros((B * heads, nqt * 32, nkt * 32), dtype=bool)
-    for qt in range(nqt):
-        for kt in range(nkt):
-            keep[:, 32 * qt:32 * qt + 32, 32 * kt + key_of_word] = bits[:, qt, kt].transpose(0, 2, 1)
-    return torch.from_numpy(keep[:, :Lq, :Lk]).view(B, heads, Lq, Lk)
 
 
 @pytest.mark.parametrize("B,heads,Lq,Lk,flags,pad", [(2, 8, 200, 200, 1, True), (2, 8, 200, 200, 0, False), (3, 4, 72, 40, 0, True), (2, 4, 224, 224, 1, False),

@@ -349,3 +349,99 @@ def test_full_size_mlp_forward_backward(ops):
     check(gg[idx], gl.detach(), 6e-3, "full-size g")
     check(du[idx], u.grad, 1.2e-2, "full-size du")
     check(dx[idx], xd.grad, 1.2e-2, "full-size dx")
+
+
+# ------------------------------------------------------------------------------------ the fused MLP with dropout on
+def mlp_setup_norm(ops, R, scalenorm, seed):
+    """mlp_setup, or its ScaleNorm twin: the up projection prepared with the scalar gain g = sqrt(256) (mmfm_prep_entry.scalar_gain)."""
+    if not scalenorm:
+        return mlp_setup(ops, R, seed=seed)
+    x = (rnd(R, 256, seed=seed + 1) * 1.5 + rnd(R, 1, seed=seed + 2)).to(BF)
+    Wu, bu = rnd(512, 256, seed=seed + 3, scale=1 / 16), 0.1 * rnd(512, seed=seed + 4)
+    Wd, bd = rnd(256, 512, seed=seed + 5, scale=1 / 22), 0.1 * rnd(256, seed=seed + 6)
+    g = torch.tensor([16.0], device="cuda")
+    up = dict(W=Wu, gamma=g, scalar_gain=True, bias=bu, Wp=torch.empty(512, 256, device="cuda", dtype=BF),
+              WpT=torch.empty(256, 512, device="cuda", dtype=BF), bp=torch.empty(512, device="cuda"))
+    table, n, tiles = ops.prep_table([up], "cuda")
+    ops.prep_weights(table, n, tiles)
+    torch.cuda.synchronize()
+    return x, Wu, bu, Wd, bd, g, None, up, prep(ops, Wd, None, None, bd)
+
+
+@pytest.mark.parametrize("R", [1000, 2333])                      # neither a multiple of the 128-row pass
+@pytest.mark.parametrize("norm,act", [("layernorm", "gelu"), ("scalenorm", "silu")])
+def test_mlp_dropout_forward_backward_vs_autograd(ops, R, norm, act):
+    """p = 0.4: y, g, du, dx and t1 of the real forward / backward (random dy) against fp64 autograd of x + mask * down(act(up(norm(x)))),
+    the mask (RowDrop, csrc/rowchain.h) read off t1 of a dy = 1 launch, at the bounds test_mlp_forward / test_mlp_backward use at p = 0
+    (6e-3 / 1.2e-2: dropout adds one multiply).  Both dx routes: the one-launch backward (LayerNorm only: it refuses ScaleNorm) and the
+    front half + mmfm_rowgemm(ln_bwd).  A wrong row or feature in either direction's hash, a missing or doubled 1 / (1 - p), or a
+    forward / backward pair that draws different masks all move y or the gradients by O(1)."""
+    import dropout_refs as DR
+    sn, p = norm == "scalenorm", 0.4
+    kind, beta = ops.mlp_act(act)
+    x, Wu, bu, Wd, bd, g, bt, up, dn = mlp_setup_norm(ops, R, sn, seed=120)
+    state = torch.zeros(2, dtype=torch.int32, device="cuda")
+    ops.rng_seed(state, 31)
+    drop = ops.dropout(state, 4, p)
+    mult = DR.rowdrop_multiplier(ops, state, 4, p, R).double()
+    rate = (mult != 0).double().mean().item()
+    assert abs(rate - (1 - p)) < 5 * math.sqrt(p * (1 - p) / mult.numel()) + 1e-4, f"keep rate {rate}"
+    mk = lambda n, dt=BF: torch.full((R + 1, n), 5.0, device="cuda", dtype=dt)
+    y, xhat, rstd = mk(256), torch.empty(R, 256, device="cuda", dtype=BF), torch.empty(R, device="cuda")
+    ops.mlp_fwd(ops.mlp_desc(R, x=x, w_up=up["Wp"], b_up=up["bp"], w_down=dn["WpP"], b_down=dn["bp"], y=y, xhat=xhat, rstd=rstd, drop=drop,
+                             scalenorm=sn, act=kind, act_beta=beta))
+    dy = rnd(R, 256, seed=79).to(BF)
+    t1, gg, du, dx = mk(256), mk(512), mk(512), mk(256)
+    ops.mlp_bwd(ops.mlp_desc(R, w_up=up["Wp"], b_up=up["bp"], drop=drop, xhat=xhat, dy=dy, w_down_t=dn["WpT"], t1=t1, g=gg, du=du, dx=None,
+                             scalenorm=sn, act=kind, act_beta=beta))
+    ops.rowgemm(du, up["WpT"], dx, R, 256, 512, ldw=512, residual=dy, ldr=256, ln_bwd=2 if sn else True, bwd_xhat=xhat, bwd_rstd=rstd)
+    for b in (y, t1, gg, du, dx):
+        assert torch.all(b[R:] == 5.0)
+    xd = x.double().requires_grad_(True)
+    if sn:
+        h = xd * g.double() / xd.norm(dim=-1, keepdim=True).clamp(min=1e-5)
+    else:
+        h = F.layer_norm(xd, (256,), g.double(), bt.double(), 1e-5)
+    u = h @ Wu.double().T + bu.double()
+    gl = F.silu(u) if act == "silu" else F.gelu(u)
+    out = xd + mult * (gl @ Wd.double().T + bd.double())
+    u.retain_grad()
+    out.backward(dy.double())
+    check(y[:R], out.detach(), 6e-3, f"{norm}/{act} y with dropout")
+    check(t1[:R], dy.double() * mult, 6e-3, "t1 = dropout'(dy)")           # one bf16 rounding of dy / (1 - p)
+    assert torch.equal(t1[:R] != 0, (mult != 0) & (dy != 0))
+    check(gg[:R], gl.detach(), 6e-3, "g")
+    check(du[:R], u.grad, 1.2e-2, "du")
+    check(dx[:R], xd.grad, 1.2e-2, "dx (front half + rowgemm)")
+    if not sn:
+        t1f, ggf, duf, dxf = mk(256), mk(512), mk(512), mk(256)
+        ops.mlp_bwd(ops.mlp_desc(R, w_up=up["Wp"], b_up=up["bp"], drop=drop, xhat=xhat, rstd=rstd, dy=dy, w_down_t=dn["WpT"], w_up_t=up["WpTP"],
+                                 t1=t1f, g=ggf, du=duf, dx=dxf, act=kind, act_beta=beta))
+        assert torch.equal(t1f, t1) and torch.equal(ggf, gg) and torch.equal(duf, du) and torch.all(dxf[R:] == 5.0)
+        check(dxf[:R], xd.grad, 1.2e-2, "dx (one-launch backward)")
+
+
+def test_rowdrop_hash_statistics(ops):
+    """The fused MLP's row-keyed hash (RowDrop, csrc/rowchain.h: a key per row, a short mix per feature pair) under the statistics and
+    bounds test_dropout_pair_hash_statistics applies to the flat hash, on 16,384 rows of 256 (4 M decisions, noise 5e-4): keep rate within
+    4 sigma, |corr| < 0.01 between the halves of a pair, along columns, along rows - the lags 127, 128, 129 straddle the 128-row pass
+    of a workgroup -, against another site and against the next step; same state and site give the same mask."""
+    import dropout_refs as DR
+    R, N, p = 16384, 256, 0.4
+    state = torch.zeros(2, dtype=torch.int32, device="cuda")
+    ops.rng_seed(state, 1234)
+    mask = lambda site: (DR.rowdrop_multiplier(ops, state, site, p, R) != 0).float()
+    k = mask(3)
+    assert abs(k.mean().item() - (1 - p)) < 4 * math.sqrt(p * (1 - p) / (R * N))
+    c = k - (1 - p)
+    var = p * (1 - p)
+    corr = lambda a, b: (a * b).mean().item() / var
+    assert abs(corr(c[:, 0::2], c[:, 1::2])) < 0.01                      # the two halves of one hash
+    for lag in (1, 2, 3, 4, 8, 16, 32, 64):
+        assert abs(corr(c[:, :-lag], c[:, lag:])) < 0.01, f"column lag {lag}"
+    for lag in (1, 2, 8, 127, 128, 129):
+        assert abs(corr(c[:-lag], c[lag:])) < 0.01, f"row lag {lag}"
+    assert abs(corr(c, mask(4) - (1 - p))) < 0.01                        # another site
+    assert torch.equal(k, mask(3))                                       # same state, same site: same mask
+    ops.rng_advance(state)
+    assert abs(corr(c, mask(3) - (1 - p))) < 0.01                        # next step
