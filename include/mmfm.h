@@ -169,7 +169,14 @@ int mmfm_scalenorm_bwd(int dtype, const void* dy, const void* x, const float* ri
  *   allowed(b,q,k) = (DIAG && q==k) | (CAUSAL ? k<=q : keypad[b][k]) | (SEP && mod_id[q]!=mod_id[k])
  * q/k/v/o are [B, L, heads*dh] views with row strides ldq/ldk/ldv/ldo (so a fused QKV buffer
  * works); lse is [B, heads, Lq] fp32.  drop_p acts on the probabilities, drop_o on the output
- * (the nn.Dropout in front of out_proj, mm_utils.py:114). */
+ * (the nn.Dropout in front of out_proj, mm_utils.py:114).
+ * dh (the head dim, hidden_size / n_heads) is 8, 16, 32, 64 or 128; every other value is an error at launch, and
+ * EngineConfig.from_model_config refuses it when the config is read.  Everything below holds at every one of them.  Which kernels
+ * serve which dh: fp32 - csrc/attention.hip at all five; bf16 - the general MFMA kernels of csrc/attention_bf16.hip at 16, 32, 64
+ * and 128 (at 128 always their chunk-streaming pair), fp32 compute on bf16 storage at 8; with the keep-bit workspace (keepbits
+ * below) the fast kernels of csrc/attention_fast.hip at dh 32 and the kernels of csrc/attention_long.hip at dh 64 and 128.  Not
+ * built: dh 128 on the dh-32 fast kernels' straight-line path (a head's K / V held in LDS for the whole launch), and any head dim
+ * outside {8, 16, 32, 64, 128}. */
 #define MMFM_ATTN_DIAG 1
 #define MMFM_ATTN_CAUSAL 2
 #define MMFM_ATTN_SEP 4
@@ -196,7 +203,7 @@ typedef struct {
      * calls.  Bits of elements the mask rule does not allow are unspecified (under CAUSAL / SEP whole tiles are never read).  The drop
      * probability is then honoured to 2^-10: keep = mmfm_attn_keep_prob(drop_p.p), survivors are scaled by 1 / keep.
      * NULL (or a shape the fast kernels do not take): both directions re-derive the decisions from the counter hash.
-     * dh = 64 (bf16, any Lq / Lk % 8 == 0, 16-B aligned operands, leading dims % 8 == 0; any combination of DIAG, CAUSAL and SEP,
+     * dh = 64 and dh = 128 (bf16, any Lq / Lk % 8 == 0, 16-B aligned operands, leading dims % 8 == 0; any combination of DIAG, CAUSAL and SEP,
      * CAUSAL / SEP with Lq == Lk): here the workspace SELECTS the kernel pair, with or without drop_p - a non-NULL keepbits sends
      * both directions to the keep-bit kernels, NULL to the general ones.  On that pair (i) dq is scratch until mmfm_attn_bwd
      * returns: a first kernel writes the output-dropout'd d_o there and the dQ phase overwrites it with dq, so dq must not alias
@@ -204,8 +211,10 @@ typedef struct {
      * delta - which is why mmfm_attn_keepbits_bytes is more than the tiles; (iii) gradient tensors that are not 16-B aligned with
      * leading dims % 8 == 0 are an error, not a fallback (the forward already took its decisions from the bits).  The kernels'
      * LDS grows with Lk (key bias; under CAUSAL / SEP also a second bias row, the mod_id bytes and the tile votes): when the
-     * forward or the dQ phase would need more than the 160 KB a workgroup can have (Lk above ~22,000 dense, ~9,800 with CAUSAL /
-     * SEP), the shape runs on the general kernels in both directions, as every other shape this pair does not take. */
+     * forward or the dQ phase would need more than the 160 KB a workgroup can have (dh 64: Lk above ~22,000 dense, ~9,800 with CAUSAL /
+     * SEP; dh 128, whose chunk images and transpose tiles take 136 KB: ~6,100 and ~2,600), the shape runs on the general kernels in
+     * both directions, as every other shape this pair does not take.  The workspace layout and mmfm_attn_keepbits_bytes do not
+     * depend on dh. */
     void* keepbits;
 } mmfm_attn_desc;
 int mmfm_attn_fwd(const mmfm_attn_desc* d, mmfm_stream stream);

@@ -1,7 +1,7 @@
 // Masked scaled-dot-product attention, forward and backward (mmfm_attn_fwd / mmfm_attn_bwd).
 //
 // fp32 parity path on v_mfma_f32_32x32x2_f32.  One workgroup (4 wavefronts) per (batch, head);
-// the head's K and V (L <= a few hundred tokens, dh <= 64) stay in LDS for the whole workgroup.
+// the head's K and V (L <= a few hundred tokens at dh <= 64, L <= 64 at dh 128) stay in LDS for the whole workgroup.
 // The [B,h,L,L] mask of the reference is never materialised: keypad bytes + flags.
 //
 // Forward (flash style, online softmax): each wave owns 32-query tiles and walks 32-key tiles.
@@ -393,10 +393,13 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const mmfm_attn_desc d) {
 // per wave) and STREAMS the other operand through LDS in 128-row chunks, keeping the flash-style running state in
 // registers across chunks.  No atomics, no cross-workgroup reduction: results are bitwise reproducible, and the dropout
 // decisions are the same function of (b, head, q, key) as in the untiled kernels.
-constexpr int TCH = 128;       // streamed rows per chunk
+// Waves per workgroup: four up to dh 64; two at dh 128, where four owned 32-row tiles plus a 128-row chunk of fp32 rows (516 B each)
+// pass the 160 KB.  A chunk always has as many rows as the workgroup owns: TCH = 32 * waves.
+constexpr int tiled_nw(int dh) { return dh > 64 ? 2 : 4; }
 
 template <typename T, int DH>
-__global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(const mmfm_attn_desc d) {
+__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_fwd_tiled_kernel(const mmfm_attn_desc d) {
+    constexpr int NW = tiled_nw(DH), NT = NW * 64, TCH = NW * 32;      // streamed rows per chunk
     constexpr int DT = (DH + 31) / 32;
     constexpr int LD = DH + 1;
     constexpr int DVL = DT * 32;
@@ -410,8 +413,8 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(const mmfm_attn_des
     const int Lmx = max(Lq, Lk);
     float* Ks = smem;                                  // [TCH][LD]
     float* Vs = Ks + TCH * LD;                         // [TCH][DVL]
-    float* Sc = Vs + TCH * DVL;                        // [4][32][SLD]
-    uint8_t* kpad = reinterpret_cast<uint8_t*>(Sc + 4 * 32 * SLD);   // [LkP]
+    float* Sc = Vs + TCH * DVL;                        // [NW][32][SLD]
+    uint8_t* kpad = reinterpret_cast<uint8_t*>(Sc + NW * 32 * SLD);   // [LkP]
     uint8_t* modl = kpad + LkP;                                      // [Lmx]
 
     const T* qg = reinterpret_cast<const T*>(d.q) + (size_t)b * Lq * d.ldq + h * DH;
@@ -419,15 +422,15 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(const mmfm_attn_des
     const T* vg = reinterpret_cast<const T*>(d.v) + (size_t)b * Lk * d.ldv + h * DH;
     T* og = reinterpret_cast<T*>(d.o) + (size_t)b * Lq * d.ldo + h * DH;
 
-    for (int i = t; i < LkP; i += 256) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
+    for (int i = t; i < LkP; i += NT) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
-        for (int i = t; i < Lmx; i += 256) modl[i] = d.mod_id[i];
+        for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
 
     MaskCtx mk{kpad, modl, modl, d.flags};
     const Drop dp = drop_init(d.drop_p), dout = drop_init(d.drop_o);
     float* sc = Sc + wave * 32 * SLD;
     const int nqt = (Lq + 31) / 32;
-    const int qt = blockIdx.y * 4 + wave;
+    const int qt = blockIdx.y * NW + wave;
     const bool active = qt < nqt;                      // inactive waves still take part in the chunk barriers
     const int q0 = qt * 32;
     {
@@ -456,10 +459,10 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(const mmfm_attn_des
     for (int c0 = 0; c0 < LkP; c0 += TCH) {
         const int rows = min(TCH, LkP - c0);
         __syncthreads();                               // readers of the previous chunk are done (and kpad/modl are visible)
-        load_head<T, DH>(Ks, LD, kg + (size_t)c0 * d.ldk, d.ldk, max(0, min(rows, Lk - c0)), rows, t, 256);
+        load_head<T, DH>(Ks, LD, kg + (size_t)c0 * d.ldk, d.ldk, max(0, min(rows, Lk - c0)), rows, t, NT);
         {
             constexpr int C4 = DVL / 4;
-            for (int idx = t; idx < rows * C4; idx += 256) {
+            for (int idx = t; idx < rows * C4; idx += NT) {
                 const int row = idx / C4, c = idx % C4;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (c0 + row < Lk && 4 * c < DH) v = io<T>::ld4(vg + (size_t)(c0 + row) * d.ldv + 4 * c);
@@ -538,7 +541,8 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(const mmfm_attn_des
 
 // PHASE 0: the workgroup owns 4 key tiles (dK, dV) and streams query chunks; PHASE 1: owns 4 query tiles (dQ), streams keys.
 template <typename T, int DH, int PHASE>
-__global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_desc d) {
+__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_bwd_tiled_kernel(const mmfm_attn_desc d) {
+    constexpr int NW = tiled_nw(DH), NT = NW * 64, TCH = NW * 32;
     constexpr int DT = (DH + 31) / 32;
     constexpr int LD = DH + 1;
     constexpr int SLD = 33;
@@ -555,8 +559,8 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
     float* Vs = Ks + TCH * LD;              // [TCH][LD]
     float* lse = Vs + TCH * LD;             // [TCH]
     float* dlt = lse + TCH;                 // [TCH]
-    float* Sc = dlt + TCH;                  // [4][32][SLD]
-    uint8_t* kpad = reinterpret_cast<uint8_t*>(Sc + 4 * 32 * SLD);
+    float* Sc = dlt + TCH;                  // [NW][32][SLD]
+    uint8_t* kpad = reinterpret_cast<uint8_t*>(Sc + NW * 32 * SLD);
     uint8_t* modl = kpad + LkP;
 
     const T* qg = reinterpret_cast<const T*>(d.q) + (size_t)b * Lq * d.ldq + h * DH;
@@ -567,13 +571,13 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
     const Drop dp = drop_init(d.drop_p), dout = drop_init(d.drop_o);
 
     auto load_keys = [&](int kw0, int rows) {
-        load_head<T, DH>(Ks, LD, kg + (size_t)kw0 * d.ldk, d.ldk, max(0, min(rows, Lk - kw0)), rows, t, 256);
-        load_head<T, DH>(Vs, LD, vg + (size_t)kw0 * d.ldv, d.ldv, max(0, min(rows, Lk - kw0)), rows, t, 256);
+        load_head<T, DH>(Ks, LD, kg + (size_t)kw0 * d.ldk, d.ldk, max(0, min(rows, Lk - kw0)), rows, t, NT);
+        load_head<T, DH>(Vs, LD, vg + (size_t)kw0 * d.ldv, d.ldv, max(0, min(rows, Lk - kw0)), rows, t, NT);
     };
     auto load_queries = [&](int qw0, int rows) {
-        load_head<T, DH>(Qs, LD, qg + (size_t)qw0 * d.ldq, d.ldq, max(0, min(rows, Lq - qw0)), rows, t, 256);
+        load_head<T, DH>(Qs, LD, qg + (size_t)qw0 * d.ldq, d.ldq, max(0, min(rows, Lq - qw0)), rows, t, NT);
         constexpr int C4 = DH / 4;
-        for (int idx = t; idx < rows * C4; idx += 256) {
+        for (int idx = t; idx < rows * C4; idx += NT) {
             const int row = idx / C4, c = idx % C4, qrow = qw0 + row;
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f), o = g;
             if (qrow < Lq) {
@@ -589,12 +593,12 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
             p[0] = dout.apply(g.x, base + 0); p[1] = dout.apply(g.y, base + 1);
             p[2] = dout.apply(g.z, base + 2); p[3] = dout.apply(g.w, base + 3);
         }
-        for (int i = t; i < rows; i += 256) lse[i] = (qw0 + i < Lq) ? d.lse[(size_t)bh_ * Lq + qw0 + i] : 0.f;
+        for (int i = t; i < rows; i += NT) lse[i] = (qw0 + i < Lq) ? d.lse[(size_t)bh_ * Lq + qw0 + i] : 0.f;
     };
 
-    for (int i = t; i < LkP; i += 256) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
+    for (int i = t; i < LkP; i += NT) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
-        for (int i = t; i < Lmx; i += 256) modl[i] = d.mod_id[i];
+        for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
     MaskCtx mk{kpad, modl, modl, d.flags};
     float* sc = Sc + wave * 32 * SLD;
     const uint64_t pbase = (uint64_t)bh_ * Lq;
@@ -602,7 +606,7 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
     const int tl = wave;                               // owned tile, local to the window
 
     if (PHASE == 0) {
-        const int kt = blockIdx.y * 4 + wave;
+        const int kt = blockIdx.y * NW + wave;
         const bool active = kt < LkP / 32;
         load_keys(own0, min(TCH, LkP - own0));         // own0 < LkP by grid construction
         f32x16 dKt[DT], dVt[DT];
@@ -678,7 +682,7 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
             }
         }
     } else {
-        const int qt = blockIdx.y * 4 + wave;
+        const int qt = blockIdx.y * NW + wave;
         const bool active = qt < LqP / 32;
         load_queries(own0, min(TCH, LqP - own0));
         f32x16 dQt[DT];
@@ -751,12 +755,12 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(const mmfm_attn_des
 }
 
 size_t fwd_tiled_lds_bytes(int Lq, int Lk, int dh) {
-    const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31, DVL = DT * 32;
-    return (size_t)(TCH * (dh + 1) + TCH * DVL + 4 * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16;
+    const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31, DVL = DT * 32, nw = tiled_nw(dh), tch = nw * 32;
+    return (size_t)(tch * (dh + 1) + tch * DVL + nw * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16;
 }
 size_t bwd_tiled_lds_bytes(int Lq, int Lk, int dh) {
-    const int LkP = (Lk + 31) & ~31;
-    return (size_t)(4 * TCH * (dh + 1) + 2 * TCH + 4 * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16;
+    const int LkP = (Lk + 31) & ~31, nw = tiled_nw(dh), tch = nw * 32;
+    return (size_t)(4 * tch * (dh + 1) + 2 * tch + nw * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16;
 }
 
 size_t fwd_lds_bytes(int Lq, int Lk, int dh) {
@@ -791,7 +795,7 @@ int set_lds(K kern, size_t bytes) {
 int check_common(const mmfm_attn_desc& d, const char* who) {
     MMFM_REQUIRE(d.dtype == MMFM_F32 || d.dtype == MMFM_BF16, "%s: bad dtype", who);
     MMFM_REQUIRE(d.B > 0 && d.heads > 0 && d.Lq > 0 && d.Lk > 0, "%s: bad shape", who);
-    MMFM_REQUIRE(d.dh == 8 || d.dh == 16 || d.dh == 32 || d.dh == 64, "%s: head dim %d not in {8,16,32,64}", who, d.dh);
+    MMFM_REQUIRE(d.dh == 8 || d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128, "%s: head dim %d not in {8,16,32,64,128}", who, d.dh);
     MMFM_REQUIRE(d.q && d.k && d.v && d.o && d.lse, "%s: null tensor", who);
     const int hd = d.heads * d.dh, al = 4;
     MMFM_REQUIRE(d.ldq >= hd && d.ldk >= hd && d.ldv >= hd && d.ldo >= hd, "%s: leading dim < heads*dh", who);
@@ -820,6 +824,7 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
             case 8: ATTN_DISPATCH(KERN, float, 8) break;                         \
             case 16: ATTN_DISPATCH(KERN, float, 16) break;                       \
             case 32: ATTN_DISPATCH(KERN, float, 32) break;                       \
+            case 128: ATTN_DISPATCH(KERN, float, 128) break;                     \
             default: ATTN_DISPATCH(KERN, float, 64) break;                       \
         }                                                                        \
     } else {                                                                     \
@@ -827,19 +832,20 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
             case 8: ATTN_DISPATCH(KERN, uint16_t, 8) break;                      \
             case 16: ATTN_DISPATCH(KERN, uint16_t, 16) break;                    \
             case 32: ATTN_DISPATCH(KERN, uint16_t, 32) break;                    \
+            case 128: ATTN_DISPATCH(KERN, uint16_t, 128) break;                  \
             default: ATTN_DISPATCH(KERN, uint16_t, 64) break;                    \
         }                                                                        \
     }
 
 int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_bf16.hip (bf16 MFMA)
 int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_fast.hip (bf16, dh 32, L <= 224)
-int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_long.hip (bf16, dh 64, keep-bit workspace)
+int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_long.hip (bf16, dh 64 / 128, keep-bit workspace)
 
 #define ATTN_TILED(KERN, GY, ...)                                                                                  \
     {                                                                                                              \
         auto kern = KERN<__VA_ARGS__>;                                                                             \
         if (int rc = set_lds(kern, lds)) return rc;                                                                \
-        hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(256), lds, (hipStream_t)stream, d);                 \
+        hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(tnw * 64), lds, (hipStream_t)stream, d);            \
     }
 #define ATTN_TILED_ALL(KERN, GY, ...)                                                                              \
     if (d.dtype == MMFM_F32) {                                                                                     \
@@ -847,6 +853,7 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
             case 8: ATTN_TILED(KERN, GY, float, 8 __VA_ARGS__) break;                                              \
             case 16: ATTN_TILED(KERN, GY, float, 16 __VA_ARGS__) break;                                            \
             case 32: ATTN_TILED(KERN, GY, float, 32 __VA_ARGS__) break;                                            \
+            case 128: ATTN_TILED(KERN, GY, float, 128 __VA_ARGS__) break;                                          \
             default: ATTN_TILED(KERN, GY, float, 64 __VA_ARGS__) break;                                            \
         }                                                                                                          \
     } else {                                                                                                       \
@@ -854,6 +861,7 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
             case 8: ATTN_TILED(KERN, GY, uint16_t, 8 __VA_ARGS__) break;                                           \
             case 16: ATTN_TILED(KERN, GY, uint16_t, 16 __VA_ARGS__) break;                                         \
             case 32: ATTN_TILED(KERN, GY, uint16_t, 32 __VA_ARGS__) break;                                         \
+            case 128: ATTN_TILED(KERN, GY, uint16_t, 128 __VA_ARGS__) break;                                       \
             default: ATTN_TILED(KERN, GY, uint16_t, 64 __VA_ARGS__) break;                                         \
         }                                                                                                          \
     }
@@ -883,8 +891,9 @@ extern "C" int mmfm_attn_fwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
     }
     if (use_tiled(d)) {
         const size_t lds = fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
-        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_fwd: Lq=%d Lk=%d needs %zu B of LDS for the mask bytes alone", d.Lq, d.Lk, lds);
-        const int gy = ((d.Lq + 31) / 32 + 3) / 4;
+        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_fwd: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)", d.dh,
+                     d.Lq, d.Lk, lds);
+        const int tnw = tiled_nw(d.dh), gy = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
         ATTN_TILED_ALL(attn_fwd_tiled_kernel, gy)
         MMFM_LAUNCH_CHECK("mmfm_attn_fwd(tiled)");
         return 0;
@@ -916,8 +925,9 @@ extern "C" int mmfm_attn_bwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
     }
     if (use_tiled(d)) {
         const size_t lds = bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
-        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_bwd: Lq=%d Lk=%d needs %zu B of LDS for the mask bytes alone", d.Lq, d.Lk, lds);
-        const int gk = ((d.Lk + 31) / 32 + 3) / 4, gq = ((d.Lq + 31) / 32 + 3) / 4;
+        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_bwd: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)", d.dh,
+                     d.Lq, d.Lk, lds);
+        const int tnw = tiled_nw(d.dh), gk = ((d.Lk + 31) / 32 + tnw - 1) / tnw, gq = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
 #define COMMA_PHASE0 , 0
 #define COMMA_PHASE1 , 1
         ATTN_TILED_ALL(attn_bwd_tiled_kernel, gk, COMMA_PHASE0)

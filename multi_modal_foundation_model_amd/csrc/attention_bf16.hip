@@ -802,8 +802,10 @@ bool bwd1_ok(int Lq, int Lk, int dh) {
 // mask-free fast path as the untiled kernels; no atomics, fixed summation order.
 constexpr int TCH16 = 128;       // streamed rows per chunk
 
+// (dh 128: the O tile is 64 accumulator registers, dK^T + dV^T are 128 beside 64 of K / V operands: those instantiations are compiled for
+// one wave per SIMD, 512 registers per lane; the dh <= 64 ones keep their two)
 template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_fwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
+__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_fwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
     constexpr int NW = 4, KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int KRS = DH * 2 + 16, VRS = DT * 64, SLD = DT * 32 + 1, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -943,7 +945,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_tiled_kernel(const mmfm_
 // PHASE 0: the workgroup owns 4 key tiles (dK, dV; K/V operands in registers) and streams Q / dO chunks;
 // PHASE 1: owns 4 query tiles (dQ; Q/dO operands and delta in registers) and streams K / V chunks.
 template <int DH, int PHASE>
-__global__ __launch_bounds__(256, 2) void attn_bwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
+__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_bwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
     constexpr int NW = 4, KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int RS = DH * 2 + 16, NT = NW * 64, C8 = DH / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1224,7 +1226,7 @@ int opt_in_lds(const void* kern, size_t bytes) {
 // returns MMFM_NOT_HANDLED (-1000) if this path does not take the shape (the caller falls back to the generic
 // kernel), 0 on launch, otherwise an error code
 int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
-    if (!(d.dh == 16 || d.dh == 32 || d.dh == 64)) return -1000;
+    if (!(d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128)) return -1000;
     const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
                     (uintptr_t)d.k % 16 == 0 && (uintptr_t)d.v % 16 == 0 && (uintptr_t)d.o % 16 == 0;
     if (!al) return -1000;
@@ -1236,7 +1238,8 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         const int nwf = fwd_waves(), nwb = bwd_waves();
         const bool fits = fwd_lds(d.Lq, d.Lk, d.dh, nwf) <= 160 * 1024 && bwd_lds(d.Lq, d.Lk, d.dh, nwb, 0) <= 160 * 1024 &&
                           bwd_lds(d.Lq, d.Lk, d.dh, nwb, 1) <= 160 * 1024;
-        if (!fits || force_env == 1) {
+        // dh 128 has no LDS-resident instantiation (a 200-token head's images alone are 109 KB): every shape goes tiled
+        if (!fits || force_env == 1 || d.dh == 128) {
             const int gq = ((d.Lq + 31) / 32 + 3) / 4, gk = ((d.Lk + 31) / 32 + 3) / 4;
 #define TILED16(KERN, GY, LDSB)                                                                                   \
             {                                                                                                     \
@@ -1252,14 +1255,16 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
                 if (lds > 160 * 1024) return -1000;
                 if (d.dh == 16) { TILED16((attn_bwd_bf16_tiled_kernel<16, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<16, 1>), gq, lds) }
                 else if (d.dh == 32) { TILED16((attn_bwd_bf16_tiled_kernel<32, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<32, 1>), gq, lds) }
-                else { TILED16((attn_bwd_bf16_tiled_kernel<64, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<64, 1>), gq, lds) }
+                else if (d.dh == 64) { TILED16((attn_bwd_bf16_tiled_kernel<64, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<64, 1>), gq, lds) }
+                else { TILED16((attn_bwd_bf16_tiled_kernel<128, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<128, 1>), gq, lds) }
                 MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, tiled)");
             } else {
                 const size_t lds = fwd_tiled16_lds(d.Lq, d.Lk, d.dh);
                 if (lds > 160 * 1024 || bwd_tiled16_lds(d.Lq, d.Lk, d.dh) > 160 * 1024) return -1000;
                 if (d.dh == 16) TILED16((attn_fwd_bf16_tiled_kernel<16>), gq, lds)
                 else if (d.dh == 32) TILED16((attn_fwd_bf16_tiled_kernel<32>), gq, lds)
-                else TILED16((attn_fwd_bf16_tiled_kernel<64>), gq, lds)
+                else if (d.dh == 64) TILED16((attn_fwd_bf16_tiled_kernel<64>), gq, lds)
+                else TILED16((attn_fwd_bf16_tiled_kernel<128>), gq, lds)
                 MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, tiled)");
             }
 #undef TILED16

@@ -1,4 +1,4 @@
-// bf16 attention, dh = 64, any sequence length (BASELINE configs[4]: d_model 512, 8 heads, L = 600): the keep-bit kernels for heads
+// bf16 attention, dh = 64 or 128, any sequence length (BASELINE configs[4]: d_model 512, 8 heads, L = 600): the keep-bit kernels for heads
 // whose K / V images do not fit the LDS.  Same contract as attention_bf16.hip (masks: the whole rule of include/mmfm.h - key padding,
 // DIAG, CAUSAL, SEP; dense / DIAG launches run the instantiations they always ran, CAUSAL / SEP launches the MASKED ones, see "mask
 // tiles" below), reference: mm_utils.py:97-152, mm.py:178-194.  They replace the round-1 tiled pair (attention_bf16.hip: 0.99 ms forward, 2.64 ms
@@ -23,16 +23,22 @@ using namespace attn;
 
 namespace {
 
-constexpr int DH = 64, KS = DH / 16, DT = DH / 32;
-constexpr int RS = DH * 2 + 16;          // 144-byte image rows: conflict-free 16-byte row fragments
+// What follows from the head dim DH (64 or 128), a template parameter of every kernel: KS = DH / 16 k-steps of a 32x32x16 MFMA over the
+// head dim, DT = DH / 32 accumulator tiles of an O / dQ / dK / dV tile, C8 = DH / 8 16-byte pieces per row, and
+// RS = 2 DH + 16 bytes per LDS image row: 144 B at dh 64, 272 B at dh 128.  Both are 16 B past a multiple of 128 B, so the 16-byte
+// fragments of eight consecutive rows cover all 32 banks once: conflict-free row fragments.
+constexpr int row_stride(int dh) { return dh * 2 + 16; }
 constexpr int CH = 128;                  // streamed rows per chunk (four 32-row tiles)
-constexpr int C8 = DH / 8;               // 16-byte pieces per row
+// waves per SIMD the register allocation must allow (__launch_bounds__): at dh 128 an O / dQ tile is 64 accumulator registers and the
+// dK^T + dV^T pair 128, beside twice the operand fragments - half the waves of the dh-64 instantiations, which keep their bounds
+constexpr int occ_q(int dh) { return dh > 64 ? 2 : 4; }       // forward, dQ phase (eight waves per workgroup)
+constexpr int occ_k(int dh) { return dh > 64 ? 1 : 2; }       // dK / dV phase (four waves per workgroup)
 constexpr float OVERFLOW_SUM = 1.2676506e30f;      // 2^100
 
 // ---- chunk streaming: rows [c0, c0 + CH) of two [L][ld] bf16 tensors -> registers -> two LDS images (RS-byte rows); NPT pieces per thread
-template <int NT>
+template <int NT, int DH>
 struct Stager {
-    static constexpr int NPT = CH * C8 / NT;
+    static constexpr int C8 = DH / 8, RS = row_stride(DH), NPT = CH * C8 / NT;
     uint4 x[NPT], y[NPT];
     __device__ __forceinline__ void load(const uint16_t* xg, int ldx, const uint16_t* yg, int ldy, int c0, int L, int t) {
 #pragma unroll
@@ -153,10 +159,11 @@ __device__ __forceinline__ int next_needed(const int* cneed, int c, int nch) {
 
 // S^T tile of key tile (rows kl*32.. of the K image) against the wave's Q fragments, starting from the key bias.  MASKED and `mixed`
 // (a T_MIXED tile): every accumulator start is set from the whole rule, for query q and keys key0 + .., on a branch like dfix
-template <bool MASKED = false>
-__device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, int kl, const bf16x8v (&qf)[KS], bool dfix, int kh, int l31,
+template <int DH, bool MASKED = false>
+__device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, int kl, const bf16x8v (&qf)[DH / 16], bool dfix, int kh, int l31,
                                              bool mixed = false, int flags = 0, int q = 0, int key0 = 0, int Lk = 0,
                                              const uint8_t* modb = nullptr) {
+    constexpr int KS = DH / 16, RS = row_stride(DH);
     f32x16 a;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -191,9 +198,9 @@ __device__ __forceinline__ f32x16 score_tile(const char* Ks, const float* kb, in
 // ---------------------------------------------------------------------------------------------- forward
 constexpr int F_NW = 8;
 // MASKED = the launch carries CAUSAL and / or SEP (see "mask tiles" above); false compiles to the dense / DIAG kernel as it was.
-template <bool DROP, bool MASKED>
-__global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_attn_desc d, const float keep_scale) {
-    constexpr int NW = F_NW, NT = NW * 64;
+template <int DH, bool DROP, bool MASKED>
+__global__ __launch_bounds__(F_NW * 64, occ_q(DH)) void attn_fwd_long_kernel(const mmfm_attn_desc d, const float keep_scale) {
+    constexpr int NW = F_NW, NT = NW * 64, KS = DH / 16, DT = DH / 32, C8 = DH / 8, RS = row_stride(DH);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, kh = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
     const int qt = blockIdx.y * NW + wave;
     const bool active = qt < nqt;                      // inactive waves still stage chunks and take part in the barriers
     const int q0 = qt * 32, q = q0 + l31;
-    Stager<NT> stg;
+    Stager<NT, DH> stg;
     stg.load(kg, d.ldk, vg, d.ldv, 0, Lk, t);          // chunk 0 in flight under the prologue
     bf16x8v qf[KS];
 #pragma unroll
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
                     if (cls == T_ZERO) kb = kzero;
                     mixed = cls == T_MIXED;
                 }
-                const f32x16 st = score_tile<MASKED>(Ks, kb + kt * 32, kl, qf, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
+                const f32x16 st = score_tile<DH, MASKED>(Ks, kb + kt * 32, kl, qf, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
                 Masks16 mk;
                 if (DROP) mk = ld_masks(mkp + kt);
                 if (EXACT) {
@@ -356,14 +363,16 @@ __global__ __launch_bounds__(F_NW * 64, 4) void attn_fwd_long_kernel(const mmfm_
             *reinterpret_cast<uint4*>(og + (size_t)(q0 + row) * d.ldo + 8 * c) = *reinterpret_cast<const uint4*>(tl + row * RS + c * 16);
     }
 }
-size_t fwd_long_lds(int Lk, bool masked) {
-    const int LkP = (Lk + 31) & ~31;
+size_t fwd_long_lds(int dh, int Lk, bool masked) {
+    const int LkP = (Lk + 31) & ~31, RS = row_stride(dh);
     return (size_t)2 * CH * RS + (size_t)F_NW * 32 * RS + (size_t)LkP * 4 + 64 + (masked ? (size_t)LkP * 4 + mask_lds(LkP) : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- backward: per-query constants
 // d_o' = dropout'(d_o) as bf16 -> the dq buffer (scratch until the dQ phase overwrites it with dq);  delta / dropout scale -> dl[bh][q]
+template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_long_prep_kernel(const mmfm_attn_desc d, float* dl, const float inv_keep) {
+    constexpr int C8 = DH / 8;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 16-byte piece per thread: (token row, head, piece)
     const int64_t total = (int64_t)d.B * d.Lq * d.heads * C8;
     const bool ok = idx < total;
@@ -401,9 +410,9 @@ __global__ __launch_bounds__(256) void attn_bwd_long_prep_kernel(const mmfm_attn
 // ---------------------------------------------------------------------------------------------- backward, dQ phase
 // A workgroup owns eight query tiles (one per wave: Q, d_o', lse, delta in registers, the query on the lane) and streams K / V.
 constexpr int Q_NW = 8;
-template <bool DROP, bool MASKED>
-__global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
-    constexpr int NW = Q_NW, NT = NW * 64;
+template <int DH, bool DROP, bool MASKED>
+__global__ __launch_bounds__(Q_NW * 64, occ_q(DH)) void attn_bwd_long_dq_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
+    constexpr int NW = Q_NW, NT = NW * 64, KS = DH / 16, DT = DH / 32, RS = row_stride(DH);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, kh = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -427,10 +436,11 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
     const int qt = blockIdx.y * NW + wave;
     const bool active = qt < nqt;
     const int q = qt * 32 + l31;
-    Stager<NT> stg;
+    Stager<NT, DH> stg;
     stg.load(kg, d.ldk, vg, d.ldv, 0, Lk, t);
     // Q fragments stay in registers; the d_o' fragments of the wave's rows live in its (until the end unused) transpose tile and are
-    // re-read per key tile: with both resident next to two dQ tiles, S and dP the kernel spills 33 registers
+    // re-read per key tile: at dh 64 (128 registers) the kernel spills 33 with both resident next to two dQ tiles, S and dP; the
+    // dh-128 form keeps the arrangement and has 232-238 of its 256 registers in use without a spill
     char* dot = sct + wave * 32 * RS;
     bf16x8v qfr[KS];
 #pragma unroll
@@ -471,7 +481,8 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
     for (int c = 0, cn; c < nch; c = cn) {             // MASKED: the chunks some wave needs, as in the forward
         cn = c + 1;
         if constexpr (MASKED) cn = next_needed(ml.cneed, c, nch);
-        // (no register prefetch of the next chunk here: with Q, d_o' and two dQ tiles resident the 16 staging registers spill)
+        // (no register prefetch of the next chunk here: at dh 64 the 16 staging registers spill beside Q, d_o' and two dQ tiles; at
+        // dh 128 they are 32, beside four dQ tiles, and do not fit either)
         if (c > 0) stg.load(kg, d.ldk, vg, d.ldv, c * CH, Lk, t);
         __syncthreads();
         stg.store(Ks, Vs, t);
@@ -489,7 +500,7 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
                 mixed = cls == T_MIXED;
             }
             // S^T[key][q] + key bias
-            const f32x16 s = score_tile<MASKED>(Ks, kb + kt * 32, kl, qfr, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
+            const f32x16 s = score_tile<DH, MASKED>(Ks, kb + kt * 32, kl, qfr, fixdiag && kt == qt, kh, l31, mixed, d.flags, q, kt * 32, Lk, ml.modb);
             f32x16 dpv = zero;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)                                                                    // dP^T[key][q]
@@ -523,20 +534,21 @@ __global__ __launch_bounds__(Q_NW * 64, 4) void attn_bwd_long_dq_kernel(const mm
     store_tile_T<DH, DT>(sct + wave * 32 * RS, RS, dQt, reinterpret_cast<uint16_t*>(d.dq) + (size_t)b * Lq * d.lddq + h * DH, d.lddq, qt * 32, Lq,
                          lane, osc);
 }
-size_t dq_long_lds(int Lk, bool masked) {
-    const int LkP = (Lk + 31) & ~31;
+size_t dq_long_lds(int dh, int Lk, bool masked) {
+    const int LkP = (Lk + 31) & ~31, RS = row_stride(dh);
     return (size_t)2 * CH * RS + (size_t)Q_NW * 32 * RS + (size_t)LkP * 4 + 64 + (masked ? (size_t)LkP * 4 + mask_lds(LkP) : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- backward, dK / dV phase
 // A workgroup owns four key tiles (one per wave: K, V operands and the 2 x 2 accumulator tiles in registers, the key on the lane) and
-// streams Q / d_o' with their per-query constants.  128 accumulator + operand registers per wave: two waves per SIMD.
+// streams Q / d_o' with their per-query constants.  dh 64: 128 accumulator + operand registers per wave, two waves per SIMD; dh 128:
+// the dK^T + dV^T tiles alone are 128 accumulator registers (152-160 AGPRs in all) beside 64 of K / V fragments, one wave per SIMD.
 constexpr int K_NW = 4;
 // MASKED: a wave (one key tile) classifies the query tiles it meets; the walk visits the query chunks some wave needs - under CAUSAL
 // those from the workgroup's first diagonal tile on, unless SEP allows something before it.
-template <bool DROP, bool MASKED>
-__global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
-    constexpr int NW = K_NW, NT = NW * 64;
+template <int DH, bool DROP, bool MASKED>
+__global__ __launch_bounds__(K_NW * 64, occ_k(DH)) void attn_bwd_long_dkv_kernel(const mmfm_attn_desc d, const float* dl, const float keep_scale) {
+    constexpr int NW = K_NW, NT = NW * 64, KS = DH / 16, DT = DH / 32, RS = row_stride(DH);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, kh = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -560,7 +572,7 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     const int kt = blockIdx.y * NW + wave;
     const bool active = kt < nkt;
     const int key = kt * 32 + l31;
-    Stager<NT> stg;
+    Stager<NT, DH> stg;
     if constexpr (!MASKED) stg.load(qg, d.ldq, dog, d.lddq, 0, Lq, t);         // MASKED: the first chunk is known after the votes
     float lse_n = 0.f, dl_n = 0.f;                     // the next chunk's per-query constants (threads 0 .. CH-1)
     auto load_consts = [&](int c0) {
@@ -709,7 +721,8 @@ __global__ __launch_bounds__(K_NW * 64, 2) void attn_bwd_long_dkv_kernel(const m
     store_tile_T<DH, DT>(tl, RS, dKt, reinterpret_cast<uint16_t*>(d.dk) + (size_t)b * Lk * d.lddk + h * DH, d.lddk, kt * 32, Lk, lane, d.scale * keep_scale);
     store_tile_T<DH, DT>(tl, RS, dVt, reinterpret_cast<uint16_t*>(d.dv) + (size_t)b * Lk * d.lddv + h * DH, d.lddv, kt * 32, Lk, lane, keep_scale);
 }
-size_t dkv_long_lds(int Lq, bool masked) {
+size_t dkv_long_lds(int dh, int Lq, bool masked) {
+    const int RS = row_stride(dh);
     return (size_t)2 * CH * RS + (size_t)2 * CH * 4 + (size_t)K_NW * 32 * RS + 64 + (masked ? mask_lds((Lq + 31) & ~31) : 0);
 }
 
@@ -717,17 +730,17 @@ size_t dkv_long_lds(int Lq, bool masked) {
 
 int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st);          // attention_fast.hip
 
-// dh = 64 with the keep-bit workspace.  Returns -1000 when the general kernels must run.
+// dh = 64 or 128 with the keep-bit workspace.  Returns -1000 when the general kernels must run.
 int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_LONG"); return e && atoi(e) == 0; }();
-    if (off || d.dh != DH || d.keepbits == nullptr) return -1000;
+    if (off || (d.dh != 64 && d.dh != 128) || d.keepbits == nullptr) return -1000;
     const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
     if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return -1000;
     if (d.Lq % 8 || d.Lk % 8) return -1000;
     // the key bias (and the MASKED kernels' second bias row, mod_id bytes and votes) grow with Lk: past what a workgroup can have,
     // the whole shape - forward and backward alike - belongs to the general kernels
     constexpr size_t LDS_MAX = 160 * 1024;
-    if (fwd_long_lds(d.Lk, masked) > LDS_MAX || dq_long_lds(d.Lk, masked) > LDS_MAX) return -1000;
+    if (fwd_long_lds(d.dh, d.Lk, masked) > LDS_MAX || dq_long_lds(d.dh, d.Lk, masked) > LDS_MAX) return -1000;
     const bool drop = d.drop_p.p > 0.f && d.drop_p.state != nullptr;
     if (drop && d.drop_p.p >= 1.f) return -1000;
     const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
@@ -735,7 +748,7 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
     if (!al) return -1000;
     const bool alb = !backward || (d.lddo % 8 == 0 && d.lddq % 8 == 0 && d.lddk % 8 == 0 && d.lddv % 8 == 0 && (uintptr_t)d.d_o % 16 == 0 &&
                                    (uintptr_t)d.dq % 16 == 0 && (uintptr_t)d.dk % 16 == 0 && (uintptr_t)d.dv % 16 == 0);
-    if (!alb) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 64): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 on the "
+    if (!alb) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 64 / 128): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 on the "
                                         "keep-bit path (mmfm_attn_desc.keepbits)");
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32, bh = d.B * d.heads;
     const float keep_scale = drop ? 1.f / mmfm_attn_keep_prob(d.drop_p.p) : 1.f;
@@ -747,34 +760,40 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;                   \
         hipLaunchKernelGGL(kern, GRID, dim3(NTH), LDSB, st, __VA_ARGS__);                                           \
     }
-    // <dropout, MASKED>
+    // <DH, dropout, MASKED>
+#define LAUNCH3(KERN, DHV, ...)                                                                                     \
+    {                                                                                                               \
+        if (drop) { if (masked) LAUNCH((KERN<DHV, true, true>), __VA_ARGS__) else LAUNCH((KERN<DHV, true, false>), __VA_ARGS__) }     \
+        else { if (masked) LAUNCH((KERN<DHV, false, true>), __VA_ARGS__) else LAUNCH((KERN<DHV, false, false>), __VA_ARGS__) }       \
+    }
 #define LAUNCH2(KERN, ...)                                                                                          \
     {                                                                                                               \
-        if (drop) { if (masked) LAUNCH((KERN<true, true>), __VA_ARGS__) else LAUNCH((KERN<true, false>), __VA_ARGS__) }     \
-        else { if (masked) LAUNCH((KERN<false, true>), __VA_ARGS__) else LAUNCH((KERN<false, false>), __VA_ARGS__) }       \
+        if (d.dh == 64) LAUNCH3(KERN, 64, __VA_ARGS__) else LAUNCH3(KERN, 128, __VA_ARGS__)                         \
     }
     if (!backward) {
         if (drop) { if (int rc = mmfm_attn_keepbits_launch(d, st)) return rc; }
-        const size_t lds = fwd_long_lds(d.Lk, masked);
+        const size_t lds = fwd_long_lds(d.dh, d.Lk, masked);
         const dim3 grid(bh, (nqt + F_NW - 1) / F_NW);
-        LAUNCH2(attn_fwd_long_kernel, grid, F_NW * 64, lds, "mmfm_attn_fwd(bf16, dh 64)", d, keep_scale)
-        MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, dh 64)");
+        LAUNCH2(attn_fwd_long_kernel, grid, F_NW * 64, lds, "mmfm_attn_fwd(bf16, keep bits)", d, keep_scale)
+        MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, keep bits)");
         return 0;
     }
-    const int64_t pieces = (int64_t)d.B * d.Lq * d.heads * C8;
-    hipLaunchKernelGGL(attn_bwd_long_prep_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, d, dl, 1.f / keep_scale);
+    const int64_t pieces = (int64_t)d.B * d.Lq * d.heads * (d.dh / 8);
+    if (d.dh == 64) hipLaunchKernelGGL(attn_bwd_long_prep_kernel<64>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, d, dl, 1.f / keep_scale);
+    else hipLaunchKernelGGL(attn_bwd_long_prep_kernel<128>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, d, dl, 1.f / keep_scale);
     {
-        const size_t lds = dkv_long_lds(d.Lq, masked);
+        const size_t lds = dkv_long_lds(d.dh, d.Lq, masked);
         const dim3 grid(bh, (nkt + K_NW - 1) / K_NW);
-        LAUNCH2(attn_bwd_long_dkv_kernel, grid, K_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dK dV)", d, dl, keep_scale)
+        LAUNCH2(attn_bwd_long_dkv_kernel, grid, K_NW * 64, lds, "mmfm_attn_bwd(bf16, keep bits, dK dV)", d, dl, keep_scale)
     }
     {
-        const size_t lds = dq_long_lds(d.Lk, masked);
+        const size_t lds = dq_long_lds(d.dh, d.Lk, masked);
         const dim3 grid(bh, (nqt + Q_NW - 1) / Q_NW);
-        LAUNCH2(attn_bwd_long_dq_kernel, grid, Q_NW * 64, lds, "mmfm_attn_bwd(bf16, dh 64, dQ)", d, dl, keep_scale)
+        LAUNCH2(attn_bwd_long_dq_kernel, grid, Q_NW * 64, lds, "mmfm_attn_bwd(bf16, keep bits, dQ)", d, dl, keep_scale)
     }
 #undef LAUNCH2
+#undef LAUNCH3
 #undef LAUNCH
-    MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, dh 64)");
+    MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, keep bits)");
     return 0;
 }

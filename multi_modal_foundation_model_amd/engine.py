@@ -29,6 +29,7 @@ from . import _lib as L
 from . import ops as K
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
+HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention kernels are instantiated for (csrc/attention.hip check_common)
 BLOCK_NORMS = ("ln1", "ln2", "query_norm", "context_norm")     # the sites `use_scalenorm` switches (encoder_norm / decoder_norm stay LayerNorm)
 
 
@@ -76,6 +77,13 @@ class EngineConfig:
         act = K.mlp_act(et["act"])
         if ee["act"] != "softsign":
             raise NotImplementedError("only act=softsign (embedder) is built")
+        hs, nh = int(et["hidden_size"]), int(et["n_heads"])
+        if nh <= 0 or hs % nh:
+            raise ValueError(f"transformer.hidden_size {hs} is not a multiple of n_heads {nh}: the attention kernels take a head dim "
+                             f"in {HEAD_DIMS}")
+        if hs // nh not in HEAD_DIMS:
+            raise ValueError(f"transformer.hidden_size {hs} / n_heads {nh} = head dim {hs // nh}: the attention kernels take a head dim "
+                             f"in {HEAD_DIMS}")
         scale = et["hidden_size"] ** 0.5 if ee["scale"] is None else ee["scale"]
         return EngineConfig(hidden=et["hidden_size"], heads=et["n_heads"], inter=et["inter_size"],
                             n_enc=et["n_layers"], n_dec=dtf["n_layers"], max_F=ee["max_F"], mult=ee["mult"],
