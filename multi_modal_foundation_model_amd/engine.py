@@ -18,8 +18,10 @@ Reference path: `MultiModal.forward` (src/multi_modal/mm.py:242-308) + autograd 
 """
 from __future__ import annotations
 
+import itertools
 import math
 import os
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -27,6 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops as K
+from .plan import PlanBuilder, _align, read_switches
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
 HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention kernels are instantiated for (csrc/attention.hip check_common)
@@ -95,8 +98,29 @@ class EngineConfig:
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]))
 
 
-def _align(n, a=8):
-    return (n + a - 1) // a * a
+# a block's linear: name, the norm that feeds it (None: plain), weight [N, K], has a bias, the adjacent nn.Linear's a fused projection aliases
+Lin = namedtuple("Lin", "name norm N K bias parts")
+
+
+def block_linears(cfg: EngineConfig, side: str, i: int) -> List[Lin]:
+    """THE description of a block: the linears of encoder / decoder layer i (or of the "bridge" between the two stacks) in forward
+    (= parameter) order.  ParamLayout, the prepared weights of the fused path (Engine._build_prep) and the plan's workspace sizing all
+    read the model's structure from here."""
+    H, I, p = cfg.hidden, cfg.inter, f"{side}.{i}"
+    if side == "bridge":
+        return [Lin("decoder_proj_context", "encoder_norm", H, H, True, None)]
+    ab, mb = (cfg.enc_attn_bias, cfg.enc_mlp_bias) if side == "encoder" else (cfg.dec_attn_bias, cfg.dec_mlp_bias)
+    attn = [Lin(p + ".attn.qkv", p + ".ln1", 3 * H, H, ab, ("query", "key", "value")), Lin(p + ".attn.out_proj", None, H, H, ab, None)]
+    cross = [Lin(p + ".cross_attn.query", p + ".query_norm", H, H, ab, None),
+             Lin(p + ".cross_attn.kv", p + ".context_norm", 2 * H, H, ab, ("key", "value")),
+             Lin(p + ".cross_attn.out_proj", None, H, H, ab, None)]
+    mlp = [Lin(p + ".mlp.up_proj", p + ".ln2", I, H, mb, None), Lin(p + ".mlp.down_proj", None, H, I, mb, None)]
+    return attn + (cross if side == "decoder" else []) + mlp
+
+
+def model_linears(cfg: EngineConfig) -> List[Lin]:
+    """Every block linear of the model in forward order: encoder layers, the bridge, decoder layers."""
+    return [l for side, n in (("encoder", cfg.n_enc), ("bridge", 1), ("decoder", cfg.n_dec)) for i in range(n) for l in block_linears(cfg, side, i)]
 
 
 class ParamLayout:
@@ -105,7 +129,7 @@ class ParamLayout:
     def __init__(self, cfg: EngineConfig):
         if cfg.norm not in ("layernorm", "scalenorm"):
             raise ValueError(f"EngineConfig.norm = {cfg.norm!r}")
-        H, I = cfg.hidden, cfg.inter
+        H = cfg.hidden
         self.entries: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self.alias: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self.segments: List[Tuple[str, int, int]] = []       # (segment name, start, end) in forward order
@@ -118,14 +142,17 @@ class ParamLayout:
         def pad():
             self.n = _align(self.n)
 
-        def seg_begin():
-            pad()
-            return self.n
-
-        def lin(prefix, o, i, bias=True):
-            pad(); add(prefix + ".weight", (o, i))
-            if bias:                                       # a bias-free linear has no entry and leaves no slot behind
-                pad(); add(prefix + ".bias", (o,))
+        def lin(prefix, o, i, bias=True, parts=None):
+            """weight [o, i] and (bias: a bias-free linear has no entry and leaves no slot behind) bias [o], each in its own aligned slot.
+            parts: the adjacent nn.Linear's it is made of, one entry each; `prefix` then is an alias over them."""
+            for kind, shape in ((".weight", (o, i)), (".bias", (o,)))[:2 if bias else 1]:
+                pad()
+                if not parts:
+                    add(prefix + kind, shape)
+                    continue
+                self.alias[prefix + kind] = (self.n, shape)
+                for nm in parts:
+                    add(f"{prefix.rsplit('.', 1)[0]}.{nm}{kind}", (o // len(parts),) + shape[1:])
 
         def ln(prefix):
             if cfg.norm == "scalenorm" and prefix.rsplit(".", 1)[-1] in BLOCK_NORMS:
@@ -133,60 +160,41 @@ class ParamLayout:
                 return
             pad(); add(prefix + ".weight", (H,)); pad(); add(prefix + ".bias", (H,))
 
-        def fused(prefix, names, alias, bias=True):
-            pad()
-            start = self.n
-            for nm in names:
-                add(f"{prefix}.{nm}.weight", (H, H))
-            self.alias[f"{prefix}.{alias}.weight"] = (start, (len(names) * H, H))
-            if not bias:
-                return
-            pad()
-            start = self.n
-            for nm in names:
-                add(f"{prefix}.{nm}.bias", (H,))
-            self.alias[f"{prefix}.{alias}.bias"] = (start, (len(names) * H,))
+        def layer(lins):
+            """The norms of a run of norm-fed linears lie in front of the run (query_norm, context_norm, then cross_attn.query, kv)."""
+            for j, l in enumerate(lins):
+                if l.norm and (j == 0 or not lins[j - 1].norm):
+                    for nl in itertools.takewhile(lambda nl: nl.norm, lins[j:]):
+                        ln(nl.norm)
+                lin(l.name, l.N, l.K, l.bias, l.parts)
 
-        s = seg_begin()
-        for side in ("encoder", "decoder"):
+        def segment(name, fill):
+            pad()
+            s = self.n
+            fill()
+            pad()
+            self.segments.append((name, s, self.n))
+
+        def embed():
+            for side in ("encoder", "decoder"):
+                for mod, n in cfg.mods:
+                    p = f"{side}_embeddings.{mod}.embedder"
+                    lin(p + ".token_embed", n * cfg.mult, n)
+                    lin(p + ".projection", H, n * cfg.mult)
+                    if side == "encoder":       # decoder's mod_emb IS this tensor (mm.py:84-87)
+                        pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
+                    pad(); add(p + ".pos_embed.weight", (cfg.max_F, H))
+
+        def head():
+            ln("decoder_norm")
             for mod, n in cfg.mods:
-                p = f"{side}_embeddings.{mod}.embedder"
-                lin(p + ".token_embed", n * cfg.mult, n)
-                lin(p + ".projection", H, n * cfg.mult)
-                if side == "encoder":       # decoder's mod_emb IS this tensor (mm.py:84-87)
-                    pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
-                pad(); add(p + ".pos_embed.weight", (cfg.max_F, H))
-        pad()
-        self.segments.append(("embed", s, self.n))
-        for i in range(cfg.n_enc):
-            s = seg_begin()
-            p = f"encoder.{i}"
-            ab, mb = cfg.enc_attn_bias, cfg.enc_mlp_bias
-            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv", ab); lin(p + ".attn.out_proj", H, H, ab)
-            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H, mb); lin(p + ".mlp.down_proj", H, I, mb)
-            pad()
-            self.segments.append((p, s, self.n))
-        s = seg_begin()
-        ln("encoder_norm"); lin("decoder_proj_context", H, H)
-        pad()
-        self.segments.append(("bridge", s, self.n))
-        for i in range(cfg.n_dec):
-            s = seg_begin()
-            p = f"decoder.{i}"
-            ab, mb = cfg.dec_attn_bias, cfg.dec_mlp_bias
-            ln(p + ".ln1"); fused(p + ".attn", ("query", "key", "value"), "qkv", ab); lin(p + ".attn.out_proj", H, H, ab)
-            ln(p + ".query_norm"); ln(p + ".context_norm")
-            lin(p + ".cross_attn.query", H, H, ab); fused(p + ".cross_attn", ("key", "value"), "kv", ab)
-            lin(p + ".cross_attn.out_proj", H, H, ab)
-            ln(p + ".ln2"); lin(p + ".mlp.up_proj", I, H, mb); lin(p + ".mlp.down_proj", H, I, mb)
-            pad()
-            self.segments.append((p, s, self.n))
-        s = seg_begin()
-        ln("decoder_norm")
-        for mod, n in cfg.mods:
-            lin(f"decoder_embeddings.{mod}.out", n, H)
-        pad()
-        self.segments.append(("head", s, self.n))
+                lin(f"decoder_embeddings.{mod}.out", n, H)
+
+        segment("embed", embed)
+        for side, n in (("encoder", cfg.n_enc), ("bridge", 1), ("decoder", cfg.n_dec)):
+            for i in range(n):
+                segment("bridge" if side == "bridge" else f"{side}.{i}", lambda: layer(block_linears(cfg, side, i)))
+        segment("head", head)
         self.n = _align(self.n, 64)
 
     def has(self, name):
@@ -247,6 +255,9 @@ class Engine:
         self._token = 0
         self._fwd_token = -1
         self._sites: Dict[str, int] = {}
+        self.linears = model_linears(cfg)
+        self._prep = None                                             # prepared weights of the fused path (_build_prep)
+        self._wt = dict(views={}, entries=[], table=None)             # bf16 transposes for the big-GEMM dX products (_w_transposed)
         self.grad_ready_hooks = []       # DDP: callables(segment_name) fired as backward completes a segment of G
         self.backward_done_hooks = []    # DDP: wait for the collectives (stream-side) before anyone reads G
         # hipGraph replay of the step plan: the plan neither allocates nor synchronises, so after one eager
@@ -348,29 +359,29 @@ class Engine:
         return K.dropout(self.rng, self._site(key), p) if p > 0 else None
 
     # ------------------------------------------------------------------ row-owner fused path (bf16, width 256 / 512)
-    def _fused_mask(self, R):
+    def _fused_mask(self, R, sw=None):
         """Which op groups run as row-owner fused kernels (csrc/rowchain.h): bit 0 ln1+qkv, bit 1 the other LayerNorm-fed
         linears (cross-attention query / key-value, decoder_proj_context), bit 2 the MLP block, bit 3 attention out_proj.
         MMFM_FUSED overrides (0 = the un-fused kernels of round 1)."""
-        c = self.cfg
+        c, sw = self.cfg, sw or read_switches()
         if self.dtype != "bf16" or c.hidden != 256 or c.inter != 512 or (R + 128) * 1024 * 2 >= 2 ** 31:
             return 0
-        if R < 12288 and "MMFM_FUSED" not in os.environ:
+        if R < 12288 and sw.fused is None:
             # a row-owner pass is 128 rows: below ~100 passes per launch the grid cannot fill 256 CUs.  Since round 4 the forward-type linears
             # split N into column blocks there (rowgemm.hip), which makes the LayerNorm-fed linears and out_proj worth fusing at the reference's
             # batch of 16 too; the MLP kernels (chained products, no column split) stay off.  ms/step un-fused / 11 / 15: B=16 4.45 / 4.08 / 4.19,
             # B=32 4.85 / 4.71 / -, B=64 5.46 / 5.50 / 5.48 (R = 12,800: the default 15)
             return 11
-        return int(os.environ.get("MMFM_FUSED", "15")) & 15        # default: everything fused, the fastest end to end (DESIGN.md §3b: 35.6 vs 36.3 ms)
+        return (15 if sw.fused is None else sw.fused) & 15        # default: everything fused, the fastest end to end (DESIGN.md §3b: 35.6 vs 36.3 ms)
 
     # ------------------------------------------------------------------ bf16 transposes for the compute-bound dX products
-    def _w_transposed(self, wname, N, Kd, Mr):
+    def _w_transposed(self, wname, N, Kd, Mr, sw=None):
         """W^T [Kd, N] (bf16) of an nn.Linear weight [N, Kd] when its dX = dY[Mr, N] . W belongs to the 256-tile GEMM (csrc/gemm_big.hip:
         reduction N a multiple of 64 and >= 512; d_model-512 configurations and any layer this wide): that kernel wants both operands
         reduction-contiguous.  The views are refreshed by ONE mmfm_prep_weights launch at the top of every training step."""
-        if os.environ.get("MMFM_GEMM_BIG", "1") == "0" or N < 512 or N % 64 or Kd % 8 or Kd < 128 or Mr < 1024:
+        if not (sw or read_switches()).gemm_big or N < 512 or N % 64 or Kd % 8 or Kd < 128 or Mr < 1024:
             return None
-        reg = self.__dict__.setdefault("_wt", dict(views={}, entries=[], table=None))
+        reg = self._wt
         if wname not in reg["views"]:
             t = torch.zeros(Kd, N, dtype=torch.bfloat16, device=self.device)
             reg["views"][wname] = t
@@ -390,19 +401,9 @@ class Engine:
         (mmfm_prep_weights); per ScaleNorm-fed linear Wp = bf16(g * W), bp = b (scalar gain); per plain linear only the bf16
         transpose (the dX products read K-contiguous rows).  A bias-free linear behind a LayerNorm keeps bp = W beta (beta is folded
         into the linear either way); behind a ScaleNorm it has no bp at all (None: the consuming kernel adds nothing)."""
-        if getattr(self, "_prep", None) is not None:
+        if self._prep is not None:
             return self._prep
-        c = self.cfg
-        sites = []
-        for i in range(c.n_enc):
-            p = f"encoder.{i}"
-            sites += [(p + ".attn.qkv", p + ".ln1"), (p + ".attn.out_proj", None), (p + ".mlp.up_proj", p + ".ln2"), (p + ".mlp.down_proj", None)]
-        sites.append(("decoder_proj_context", "encoder_norm"))
-        for i in range(c.n_dec):
-            p = f"decoder.{i}"
-            sites += [(p + ".attn.qkv", p + ".ln1"), (p + ".attn.out_proj", None), (p + ".cross_attn.query", p + ".query_norm"),
-                      (p + ".cross_attn.kv", p + ".context_norm"), (p + ".cross_attn.out_proj", None), (p + ".mlp.up_proj", p + ".ln2"),
-                      (p + ".mlp.down_proj", None)]
+        sites = [(l.name, l.norm) for l in self.linears]
         nW = sum(self.Pf(w + ".weight").numel() for w, _ in sites)
         nWp = sum(self.Pf(w + ".weight").numel() for w, ln in sites if ln)
         has_bp = {w: self.Pb(w) is not None or not self.is_sn(ln) for w, ln in sites if ln}
@@ -442,7 +443,7 @@ class Engine:
         return self._prep
 
     # ------------------------------------------------------------------ plan construction
-    def _dw_split(self, M, N, R, ldn=None):
+    def _dw_split(self, M, N, R, ldn=None, sw=None):
         """Split-K factor for a dW GEMM ([M,N] output, reduction over R tokens).
         bf16 shapes the streaming kernel takes (csrc/gemm_dw.hip: 16-B aligned rows of dY [R, M] and X [R, ldn]): ONE (tile, K-slab) item per CU - the slab
         traffic is items x 64 KB, so fewer, longer items beat filling the chip three times over.
@@ -450,7 +451,7 @@ class Engine:
         kernel (256 CUs x 3 workgroups) exactly once - measured against 512 items at B = 1024: qkv dW 182 -> 155 us, token-embed
         dW 639 -> 508 us - capped at 128 slabs (the slab reduction costs S x M x N x 4 bytes)."""
         tiles = -(-M // 128) * -(-N // 128)
-        stream = self.code == L.BF16 and M % 8 == 0 and (ldn or N) % 8 == 0 and os.environ.get("MMFM_GEMM_DW", "1") != "0"
+        stream = self.code == L.BF16 and M % 8 == 0 and (ldn or N) % 8 == 0 and (sw or read_switches()).gemm_dw
         if stream:
             tiles = L.lib().mmfm_gemm_dw_tiles(M, N, R)
         if R <= 8192:                     # launch-bound regime (reference batch 16 -> R = 3200): <= 15 slabs = one-stage reduce
@@ -463,539 +464,13 @@ class Engine:
         return -(-R // kchunk), kchunk
 
     def _plan(self, B, T, training, grad=True):
-        """grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward."""
+        """The cached step plan of (batch shape, mode); built by plan.PlanBuilder the first time.
+        grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward."""
         key = (B, T, bool(training), bool(grad))
         self._select_pool(B, T)
-        if key in self.plans:
-            return self.plans[key]
-        c = self.cfg
-        H, I, heads = c.hidden, c.inter, c.heads
-        act_fwd, act_grad = K.GEMM_ACTS[c.act[0]]       # the un-fused MLP's mmfm_gemm act codes (beta: c.act[1])
-        dh = H // heads
-        M = len(c.mods)
-        Lq = M * T
-        R, BT = B * Lq, B * T
-        dp = c.dropout if training else 0.0
-        dpe = c.embed_dropout if training else 0.0
-        f32, i64, u8 = torch.float32, torch.int64, torch.uint8
-        buf = self._buf
-        fwd, bwd_tail = [], []
-        code = self.code
-
-        # ---- static inputs
-        for m, (mod, n) in enumerate(c.mods):
-            # input rows padded to 16 B (zeros): the tokeniser's weight-gradient GEMM streams them by LDS-DMA (csrc/gemm_dw.hip)
-            buf(f"in/{m}", (BT, _align(n, 8)), zero=True); buf(f"tgt/{m}", (BT, n), f32); buf(f"mask/{m}", (B, T), i64)
-        ts, attn = buf("ts", (B, T), i64), buf("attn", (B, T), i64)
-        tokmask, keypad = buf("tokmask", (B, Lq), u8), buf("keypad", (B, Lq), u8)
-        keep0, mod_id, count = buf("keep0", (Lq,), u8), buf("mod_id", (Lq,), u8), buf("count", (M,), i64)
-        loss_sum = buf("loss_sum", (M,), f32)
-
-        # ---- workspaces
-        max_slab = 1
-        for _, n in c.mods:
-            # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
-            # streaming kernel and with it another split count)
-            for (mm, nn, ldn) in ((n * c.mult, n, _align(n, 8)), (H, n * c.mult, None), (n, H, None)):
-                S, _ = self._dw_split(mm, nn, BT, ldn=ldn)
-                max_slab = max(max_slab, S * _align(mm * nn + mm))
-        for (mm, nn) in ((3 * H, H), (H, H), (2 * H, H), (I, H), (H, I)):
-            S, _ = self._dw_split(mm, nn, R)
-            max_slab = max(max_slab, S * _align(mm * nn + mm))
-        slab = buf("ws/slab", (max_slab,), f32)
-        slab2 = buf("ws/slab2", (max_slab,), f32)          # a deferred weight-gradient GEMM's slabs, paired with the next one (mmfm_gemm_pair)
-
-        def slab_fits(t, S, stride, what):
-            if S * stride > t.numel():
-                raise RuntimeError(f"engine: {what}: {S} slabs x {stride} floats exceed the {t.numel()}-float slab workspace")
-            return t
-        # launch-bound regime (R <= 8192, the reference's batch of 16): every dW GEMM keeps its own slab region and ONE
-        # mmfm_reduce_slabs_multi per backward segment sums them all (66 reductions of ~7 us each otherwise)
-        batch_red = R <= 8192 and os.environ.get("MMFM_BATCH_REDUCE", "1") != "0"
-        pend: list = []
-        slabm_off = [0]
-        if batch_red:
-            # regions are handed out per backward segment and reused by the next one (close_segment resets the offset behind the segment's
-            # reduction): the largest segment's parameters bound the need, not the whole model's
-            s_max = max(1, min(R // 256, 15))
-            seg_max = max(e - s0 for _, s0, e in self.layout.segments)
-            slabm = buf("ws/slabm", (s_max * (seg_max + 128 * 64),), f32)
-
-        def slab_region(S, stride):
-            o = slabm_off[0]
-            slabm_off[0] = o + S * stride
-            if slabm_off[0] > slabm.numel():
-                raise RuntimeError(f"engine: ws/slabm holds {slabm.numel()} floats, the plan's slab regions need {slabm_off[0]}")
-            return slabm[o:o + S * stride]
-        maxN = max([3 * H, I] + [n * c.mult for _, n in c.mods])
-        ws_col = buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
-        ws_ln = buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
-        ws_st = buf("ws/stitch", (max(1, L.lib().mmfm_stitch_bwd_workspace(code, B, T, Lq, H, c.max_F) // 4),), f32)
-
-        def loss_of(mod):        # (kind, param, flags) of the modality's loss
-            return c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
-
-        def two_kind(mod):       # PoissonNLL(log_input) / MSE without a flag: the two-kind entry points, call for call the plan it always was
-            kind, _, flags = loss_of(mod)
-            return kind in (L.LOSS_POISSON_LOG, L.LOSS_MSE) and flags == 0
-
-        ws_loss = buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
-
-        def lin(plan, X, wname, Y, Mr, N, Kd, ldx=None, **kw):
-            K.gemm(X, self.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.Pb(wname),
-                   dtype=code, plan=plan, **kw)
-
-        used_wt: list = []
-
-        # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
-        # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
-        # parked one alone.  Each product then makes half as many K-slabs (csrc/gemm_dw.hip).
-        pair_ok = code == L.BF16 and not batch_red and os.environ.get("MMFM_DW_PAIR", "1") != "0" and os.environ.get("MMFM_GEMM_DW", "1") != "0"
-        deferred: list = []
-
-        def pair_splits(Na, Ka, Nb, Kb, Mr):
-            ta, tb = L.lib().mmfm_gemm_dw_tiles(Na, Ka, Mr), L.lib().mmfm_gemm_dw_tiles(Nb, Kb, Mr)
-            ia = 256 * (Na + Ka) / (Na + Ka + Nb + Kb)
-            Sa = max(1, int(ia) // ta)
-            while Sa > 1 and (ta * Sa) % 8:
-                Sa -= 1
-            Sb = max(1, (256 - ta * Sa) // tb)
-            out = []
-            for S in (Sa, Sb):
-                kchunk = _align(-(-Mr // max(1, min(S, Mr // 512))), 64)
-                out += [-(-Mr // kchunk), kchunk]
-            return out
-
-        def flush_deferred(plan):
-            if deferred:
-                a = deferred.pop()
-                dlin(plan, a["dY"], a["X"], a["wname"], a["Mr"], a["N"], a["Kd"])
-
-        def dlin(plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, **kw):
-            """Backward of Y[Mr,N] = X[Mr,Kd] @ W[N,Kd]^T + b:  dW, db into G;  dX = dY @ W (optional, fused epilogue).
-            ldx = row stride of X when its rows are padded."""
-            S, kchunk = self._dw_split(N, Kd, Mr, ldn=ldx)
-            ldx = ldx or Kd
-            gw, gb = self.Gv(wname + ".weight"), self.Gb(wname)
-            # bf16: the bias gradient (column sums of dY) rides on the dW GEMM (mmfm_gemm_desc.colsum); when the bias
-            # gradient sits right behind the weight gradient in the flat buffer one slab reduction finishes both.
-            # A bias-free linear (gb None) has no column sum anywhere: the GEMM runs without colsum, its slabs hold the weight gradient only
-            fused = code == L.BF16 and gb is not None
-            adjacent = fused and gb.data_ptr() == gw.data_ptr() + 4 * N * Kd
-            if defer and pair_ok and S > 1 and (adjacent or gb is None) and dX is None and ldx == Kd:
-                flush_deferred(plan)
-                deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd, nb=N if gb is not None else 0))
-                return
-            if S == 1:
-                K.gemm(dY, X, gw, N, Kd, Mr, lda=N, ldb=ldx, ldc=Kd, a_kcontig=0, b_kcontig=0, dtype=code, c_f32=1,
-                       colsum=gb if fused else None, plan=plan)
-            elif adjacent:
-                stride = _align(N * Kd + N)
-                sl = slab_region(S, stride) if batch_red else slab_fits(slab, S, stride, wname)
-                K.gemm(dY, X, sl, N, Kd, Mr, lda=N, ldb=ldx, ldc=Kd, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=stride, dtype=code, c_f32=1, colsum=sl.data_ptr() + 4 * N * Kd, plan=plan)
-                if batch_red:
-                    pend.append((gw, sl, N * Kd + N, S, stride, False))
-                else:
-                    K.reduce_slabs(gw, sl, N * Kd + N, S, stride, plan=plan)
-            else:
-                sl = slab_region(S, N * Kd) if batch_red else slab_fits(slab, S, N * Kd, wname)
-                K.gemm(dY, X, sl, N, Kd, Mr, lda=N, ldb=ldx, ldc=Kd, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=N * Kd, dtype=code, c_f32=1, plan=plan)
-                if batch_red:
-                    pend.append((gw, sl, N * Kd, S, N * Kd, False))
-                else:
-                    K.reduce_slabs(gw, sl, N * Kd, S, N * Kd, plan=plan)
-            if gb is not None and (not fused or (S > 1 and not adjacent)):
-                K.colsum(dY, Mr, N, N, gb, ws_col, plan=plan)
-            if dX is not None:
-                wT = self._w_transposed(wname, N, Kd, Mr) if code == L.BF16 else None
-                if wT is not None:      # reduction >= 512: the 256-tile kernel (csrc/gemm_big.hip) against the K-contiguous transpose W^T [Kd, N]
-                    used_wt.append(wname)
-                    K.gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
-                else:
-                    K.gemm(dY, self.W(wname + ".weight"), dX, Mr, Kd, N, lda=N, ldb=Kd, ldc=Kd, b_kcontig=0, dtype=code, plan=plan, **kw)
-
-        def ln_f(plan, X, name, Y, tag, **kw):
-            if self.is_sn(name):
-                K.scalenorm_fwd(X, self.Pf(name + ".scale"), Y, buf(tag + "/rstd", (R,), f32), R, H, plan=plan)
-                return
-            K.layernorm_fwd(X, self.Pf(name + ".weight"), self.Pf(name + ".bias"), Y, buf(tag + "/mean", (R,), f32),
-                            buf(tag + "/rstd", (R,), f32), R, H, plan=plan, **kw)
-
-        def ln_b(plan, dY, X, name, tag, dres, dX, **kw):
-            if self.is_sn(name):       # (ws/ln, sized for the LayerNorm backward, covers the ScaleNorm's per-block partials)
-                K.scalenorm_bwd(dY, X, self.b[tag + "/rstd"], self.Pf(name + ".scale"), dres, dX, self.Gv(name + ".scale"), R, H, ws_ln,
-                                plan=plan)
-                return
-            K.layernorm_bwd(dY, X, self.b[tag + "/mean"], self.b[tag + "/rstd"], self.Pf(name + ".weight"), dres, dX,
-                            self.Gv(name + ".weight"), self.Gv(name + ".bias"), R, H, ws_ln, plan=plan, **kw)
-
-        es = 4 if self.dtype == "fp32" else 2
-        scale = 1.0 / math.sqrt(dh)
-
-        # keep decisions of the attention-probability dropout: one bit tile set per attention site, written by the forward (generator
-        # kernel in front of it), read by the backward (csrc/attention_fast.hip; 51 MB per site at B = 1024).  MMFM_ATTN_KEEPBITS=0: hash.
-        use_keep = self.code == L.BF16 and dp > 0 and grad and os.environ.get("MMFM_ATTN_KEEPBITS", "1") != "0"
-
-        def attn_desc(tag, q, ldq, kv, ldkv, koff, voff, o, flags, d_o=None, dq=None, dkv=None, lddq=0, lddkv=0, dkoff=0, dvoff=0):
-            keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), u8) if use_keep else None
-            return K.attn_desc(code, B, heads, Lq, Lq, dh, q.data_ptr(), kv.data_ptr() + koff * es, kv.data_ptr() + voff * es, ldq, ldkv, ldkv,
-                               o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), f32), keypad, mod_id, flags, scale,
-                               drop_p=self._drop(tag + "/p", dp), drop_o=self._drop(tag + "/o", dp),
-                               d_o=None if d_o is None else d_o.data_ptr(), lddo=H,
-                               dq=None if dq is None else dq.data_ptr(),
-                               dk=None if dkv is None else dkv.data_ptr() + dkoff * es,
-                               dv=None if dkv is None else dkv.data_ptr() + dvoff * es, lddq=lddq, lddk=lddkv, lddv=lddkv, keepbits=keep)
-
-        fm = self._fused_mask(R)
-        F_QKV, F_LNL, F_MLP, F_OUT = bool(fm & 1), bool(fm & 2), bool(fm & 4), bool(fm & 8)
-        prep = self._build_prep() if fm else None
-        if fm:
-            K.prep_weights(prep["table"], prep["n"], prep["tiles"], plan=fwd)
-            gdb = buf("ws/gdb", (max(_align(mm * nn + mm) for mm, nn in ((3 * H, H), (2 * H, H), (I, H), (H, H))),), f32)
-            if "ws/lng" not in self.b:
-                self.b["ws/lng"] = K.ln_linear_grad_workspace(H, self.device)          # zeroed once; the kernel re-arms its tickets
-            ws_lng = self.b["ws/lng"]
-
-        def ln_lin(plan, Xin, lnname, wname, Yout, N, tag, residual=None, alias=None):
-            """LayerNorm (or ScaleNorm) + the linear it feeds in one launch; x_hat / rstd saved for the backward when training.
-            alias = tag of an earlier call on the SAME input: x_hat / rstd do not depend on the norm's affine / gain (it is folded
-            into the prepared weights), so the earlier call's saved tensors serve this site's backward too and nothing is stored."""
-            pw = prep["v"][wname]
-            if alias is not None and grad:
-                self.b[tag + "/xh"], self.b[tag + "/rs"] = self.b[alias + "/xh"], self.b[alias + "/rs"]
-                xh = rs = None
-            else:
-                xh = buf(tag + "/xh", (R, H)) if grad else None
-                rs = buf(tag + "/rs", (R,), f32) if grad else None
-            K.rowgemm(Xin, pw["Wp"], Yout, R, N, H, bias=pw["bp"], ln=2 if self.is_sn(lnname) else 1, xhat=xh, rstd=rs, residual=residual,
-                      ldr=H if residual is not None else 0, stream_out=True, plan=plan)
-
-        late_lng: list = []
-
-        def lin_norm_grad(plan, Gdb, wname, lnname, N):
-            """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]
-            (bias-free: dbias None; behind a ScaleNorm Gdb then has no colsum block, db_cols)."""
-            if self.is_sn(lnname):
-                K.sn_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".scale"), N, H, self.Gv(wname + ".weight"),
-                                 self.Gb(wname), self.Gv(lnname + ".scale"), ws_lng, plan=plan)
-                return
-            K.ln_linear_grad(Gdb, self.Pf(wname + ".weight"), self.Pf(lnname + ".weight"), self.Pf(lnname + ".bias"), N, H,
-                             self.Gv(wname + ".weight"), self.Gb(wname), self.Gv(lnname + ".weight"), self.Gv(lnname + ".bias"),
-                             ws_lng, plan=plan)
-
-        def db_cols(wname, lnname, N):
-            """Width of the colsum block behind G in a norm-fed linear's Gdb: N, or 0 for a bias-free linear behind a ScaleNorm.
-            Behind a LayerNorm db = colsum dY stays even without a bias: dW and dbeta need it (beta is folded into the linear)."""
-            return N if (self.Gb(wname) is not None or not self.is_sn(lnname)) else 0
-
-        def dlin_ln(plan, dYt, tag, wname, lnname, N):
-            """Gradients of a LayerNorm-fed linear and of that LayerNorm's affine from G = dY^T x_hat (mmfm_ln_linear_grad)."""
-            S, kchunk = self._dw_split(N, H, R)
-            xh = self.b[tag + "/xh"]
-            nb = db_cols(wname, lnname, N)          # colsum block behind G (0: bias-free behind a ScaleNorm, nobody reads db)
-
-            def cs(t):
-                return t.data_ptr() + 4 * N * H if nb else None
-            if deferred and S > 1 and deferred[-1]["Mr"] == R:
-                a = deferred.pop()
-                Na, Ka, nba = a["N"], a["Kd"], a["nb"]
-                Sa, kca, Sb, kcb = pair_splits(Na, Ka, N, H, R)
-                stra, strb = _align(Na * Ka + nba), _align(N * H + nb)
-                slab_fits(slab2, Sa, stra, a["wname"]); slab_fits(slab, Sb, strb, wname)
-                da = K.gemm_desc(a["dY"], a["X"], slab2, Na, Ka, R, lda=Na, ldb=Ka, ldc=Ka, a_kcontig=0, b_kcontig=0, splits=Sa, kchunk=kca,
-                                 slab_stride=stra, dtype=code, c_f32=1, colsum=slab2.data_ptr() + 4 * Na * Ka if nba else None)
-                db_ = K.gemm_desc(dYt, xh, slab, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=Sb, kchunk=kcb,
-                                  slab_stride=strb, dtype=code, c_f32=1, colsum=cs(slab))
-                K.gemm_pair(da, db_, plan=plan)
-                K.reduce_slabs(self.Gv(a["wname"] + ".weight"), slab2, Na * Ka + nba, Sa, stra, plan=plan)
-                K.reduce_slabs(gdb, slab, N * H + nb, Sb, strb, plan=plan)
-            elif S == 1:
-                K.gemm(dYt, xh, gdb, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, dtype=code, c_f32=1,
-                       colsum=cs(gdb), plan=plan)
-            elif batch_red:
-                # launch-bound regime: the slabs join the segment's ONE reduction launch (own region, own reduced buffer per site) and
-                # mmfm_ln_linear_grad runs behind it at the end of the segment (close_segment) - one reduction launch per site less
-                stride = _align(N * H + nb)
-                sl = slab_region(S, stride)
-                g_site = buf(f"ws/gdb/{len(late_lng)}", (gdb.numel(),), f32)
-                K.gemm(dYt, xh, sl, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=stride, dtype=code, c_f32=1, colsum=cs(sl), plan=plan)
-                pend.append((g_site, sl, N * H + nb, S, stride, False))
-                late_lng.append((g_site, wname, lnname, N))
-                return
-            else:
-                stride = _align(N * H + nb)
-                slab_fits(slab, S, stride, wname)
-                K.gemm(dYt, xh, slab, N, H, R, lda=N, ldb=H, ldc=H, a_kcontig=0, b_kcontig=0, splits=S, kchunk=kchunk,
-                       slab_stride=stride, dtype=code, c_f32=1, colsum=cs(slab), plan=plan)
-                K.reduce_slabs(gdb, slab, N * H + nb, S, stride, plan=plan)
-            lin_norm_grad(plan, gdb, wname, lnname, N)
-
-        def dx_ln(plan, dYt, Kd, tag, wname, lnname, dres, dXout):
-            """dX of a norm-fed linear with the norm's backward (and the residual gradient) in its epilogue."""
-            K.rowgemm(dYt, prep["v"][wname]["WpT"], dXout, R, H, Kd, ldw=Kd, residual=dres, ldr=H if dres is not None else 0,
-                      ln_bwd=2 if self.is_sn(lnname) else 1, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
-
-        enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
-        # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
-        # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
-        dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)
-
-        # ============================================================ forward
-        K.mask_prep(B, T, [self.b[f"mask/{m}"] for m in range(M)], [1] * M, attn, [n for _, n in c.mods], tokmask, keypad, keep0,
-                    mod_id, count, plan=fwd)
-        tok_tmp = buf("tok_tmp", (BT, H))
-        x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
-        for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
-            for m, (mod, n) in enumerate(c.mods):
-                p = f"{side}_embeddings.{mod}.embedder"
-                n2 = n * c.mult
-                a = buf(f"{side}/a/{m}", (BT, n2))
-                # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
-                # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
-                z = None if code == L.BF16 else buf(f"{side}/z/{m}", (BT, n2))
-                lin(fwd, self.b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=L.ACT_SOFTSIGN, act_scale=c.embed_scale)
-                lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=self._drop(f"{side}/embdrop/{m}", dpe))
-                mod_row = self.Pf(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m]
-                K.stitch_fwd(tok_tmp, mod_row, self.Pf(p + ".pos_embed.weight"), ts, keep0, xs, es_, B, T, Lq, m, H, c.max_F, plan=fwd)
-
-        def out_proj(plan, a, wname, Xres, Xout):
-            if F_OUT:
-                K.rowgemm(a, self.W(wname + ".weight"), Xout, R, H, H, bias=self.Pb(wname), residual=Xres, ldr=H, plan=plan)
-            else:
-                lin(plan, a, wname, Xout, R, H, H, residual=Xres, ldr=H)
-
-        def self_block(plan, X, p, tag, flags):
-            """x + attn(ln1(x))  (encoder_embeddings.py:112, decoder_embeddings.py:141)."""
-            qkv, a, Xa = buf(tag + "/qkv", (R, 3 * H)), buf(tag + "/a", (R, H)), buf(tag + "/xa", (R, H))
-            if F_QKV:
-                ln_lin(plan, X, p + ".ln1", p + ".attn.qkv", qkv, 3 * H, tag + "/ln1")
-            else:
-                h = buf(tag + "/h1", (R, H))
-                ln_f(plan, X, p + ".ln1", h, tag + "/ln1")
-                lin(plan, h, p + ".attn.qkv", qkv, R, 3 * H, H)
-            K.attn_fwd(attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, a, flags), plan=plan)
-            out_proj(plan, a, p + ".attn.out_proj", X, Xa)
-            return Xa
-
-
-        def mlp_block(plan, X, p, tag):
-            """x + mlp(ln2(x))  (encoder_embeddings.py:114; mm_utils.py:50-52)."""
-            Xb = buf(tag + "/xb", (R, H))
-            if F_MLP:
-                pu = prep["v"][p + ".mlp.up_proj"]
-                d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=prep["v"][p + ".mlp.down_proj"]["WpP"],
-                                b_down=self.Pb(p + ".mlp.down_proj"), drop=self._drop(tag + "/mlpdrop", dp), y=Xb,
-                                xhat=buf(tag + "/ln2/xh", (R, H)) if grad else None,
-                                rstd=buf(tag + "/ln2/rs", (R,), f32) if grad else None, scalenorm=self.is_sn(p + ".ln2"),
-                                act=c.act[0], act_beta=c.act[1])
-                K.mlp_fwd(d_, plan=plan)
-                return Xb
-            h, u, g = buf(tag + "/h2", (R, H)), buf(tag + "/u", (R, I)), buf(tag + "/g", (R, I))
-            ln_f(plan, X, p + ".ln2", h, tag + "/ln2")
-            lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=act_fwd, act_scale=c.act[1])
-            lin(plan, g, p + ".mlp.down_proj", Xb, R, H, I, drop=self._drop(tag + "/mlpdrop", dp), residual=X, ldr=H)
-            return Xb
-
-        X = x_enc
-        stream_in = {}
-        for i in range(c.n_enc):
-            p, tag = f"encoder.{i}", f"enc{i}"
-            stream_in[tag] = X
-            Xa = self_block(fwd, X, p, tag, enc_flags)
-            X = mlp_block(fwd, Xa, p, tag)
-        enc_last = X
-        enc_out, context = buf("enc_out", (R, H)), buf("context", (R, H))
-        if F_LNL:
-            ln_lin(fwd, X, "encoder_norm", "decoder_proj_context", context, H, "encnorm", residual=emb_enc)
-        else:
-            ln_f(fwd, X, "encoder_norm", enc_out, "encnorm")
-            lin(fwd, enc_out, "decoder_proj_context", context, R, H, H, residual=emb_enc, ldr=H)       # mm.py:292
-        Y = x_dec
-        for i in range(c.n_dec):
-            p, tag = f"decoder.{i}", f"dec{i}"
-            stream_in[tag] = Y
-            Ya = self_block(fwd, Y, p, tag, dec_flags)
-            qc, kvc, a2, Yb = buf(tag + "/qc", (R, H)), buf(tag + "/kvc", (R, 2 * H)), buf(tag + "/a2", (R, H)), buf(tag + "/yb", (R, H))
-            if F_LNL:
-                ln_lin(fwd, Ya, p + ".query_norm", p + ".cross_attn.query", qc, H, tag + "/qn")
-                # every decoder layer normalises the same context rows: the statistics are saved by the first layer only
-                ln_lin(fwd, context, p + ".context_norm", p + ".cross_attn.kv", kvc, 2 * H, tag + "/cn", alias=None if i == 0 else "dec0/cn")
-            else:
-                hq, hc = buf(tag + "/hq", (R, H)), buf(tag + "/hc", (R, H))
-                ln_f(fwd, Ya, p + ".query_norm", hq, tag + "/qn")
-                ln_f(fwd, context, p + ".context_norm", hc, tag + "/cn")
-                lin(fwd, hq, p + ".cross_attn.query", qc, R, H, H)
-                lin(fwd, hc, p + ".cross_attn.kv", kvc, R, 2 * H, H)
-            K.attn_fwd(attn_desc(tag + "/xa", qc, H, kvc, 2 * H, 0, H, a2, enc_flags), plan=fwd)   # xa_mask = encoder mask
-            out_proj(fwd, a2, p + ".cross_attn.out_proj", Ya, Yb)
-            Y = mlp_block(fwd, Yb, p, tag)
-        dec_last = Y
-        ydec = buf("ydec", (R, H))                         # de-stitched: [M][B*T][H]
-        ln_f(fwd, Y, "decoder_norm", ydec, "decnorm", ds_L=Lq, ds_T=T)
-        for m, (mod, n) in enumerate(c.mods):
-            pred = buf(f"pred/{m}", (BT, n))
-            lin(fwd, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
-            loss_args = (pred, self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n, loss_sum[m:m + 1], ws_loss)
-            if two_kind(mod):
-                K.masked_loss_fwd(c.loss_kind[mod], *loss_args, plan=fwd)
-            else:
-                K.masked_loss_kind_fwd(*loss_of(mod), *loss_args, plan=fwd)
-        K.loss_finalize(loss_sum, count, M, self.b["loss"], self.b["inv_n"], plan=fwd)
-
-        if not grad:
-            plan = dict(fwd=fwd, bwd=None, B=B, T=T, training=bool(training), M=M, R=R, BT=BT, runs=dict(fwd=0, bwd=0), graphs={}, b=self.b)
-            self.plans[key] = plan
-            return plan
-        # ============================================================ backward (segments fire DDP hooks)
-        bwd: List[Tuple[str, list]] = []
-        cur: list = []
-
-        def close_segment(name):
-            nonlocal cur
-            if pend:                          # the segment's weight-gradient slabs, all in one launch, before its DDP hook fires
-                K.reduce_slabs_multi(list(pend), self.device, plan=cur)
-                pend.clear()
-            for g_site, wname, lnname, N in late_lng:
-                lin_norm_grad(cur, g_site, wname, lnname, N)
-            late_lng.clear()
-            slabm_off[0] = 0                  # the reduction has consumed the regions (stream order): the next segment reuses them
-            bwd.append((name, cur))
-            cur = []
-
-        dY = buf("d/stream", (R, H))
-        dydec = buf("d/ydec", (R, H))
-        t1, t2, dh_ = buf("d/t1", (R, H)), buf("d/t2", (R, H)), buf("d/h", (R, H))
-        du, dqkv, dctx = buf("d/u", (R, I)), buf("d/qkv", (R, 3 * H)), buf("d/ctx", (R, H))
-        for m, (mod, n) in enumerate(c.mods):
-            dpred = buf(f"d/pred/{m}", (BT, n))
-            loss_args = (self.b[f"pred/{m}"], self.b[f"tgt/{m}"], tokmask[:, m * T:], Lq, T, BT, n, self.b["gout"], self.b["inv_n"], dpred)
-            if two_kind(mod):
-                K.masked_loss_bwd(c.loss_kind[mod], *loss_args, plan=cur)
-            else:
-                K.masked_loss_kind_bwd(*loss_of(mod), *loss_args, plan=cur)
-            dlin(cur, dpred, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[m * BT:(m + 1) * BT])
-        ln_b(cur, dydec, dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
-        close_segment("head")
-
-        def mlp_back(plan, dS, p, tag, X_in):
-            """dS: running gradient of the residual stream (in place).  X_in = the stream value that fed ln2."""
-            if F_MLP:
-                pu, pdn = prep["v"][p + ".mlp.up_proj"], prep["v"][p + ".mlp.down_proj"]
-                t1b, gb, dub = buf("d/t1m", (R, H)), buf("d/g", (R, I)), buf("d/du", (R, I))
-                # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step.  A ScaleNorm ln2 always splits (the one-launch kernel has no ScaleNorm epilogue)
-                split = os.environ.get("MMFM_MLP_BWD_SPLIT", "1") == "1" or self.is_sn(p + ".ln2")
-                d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=self._drop(tag + "/mlpdrop", dp), xhat=self.b[tag + "/ln2/xh"],
-                                rstd=self.b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
-                                dx=None if split else dS, scalenorm=self.is_sn(p + ".ln2"), act=c.act[0], act_beta=c.act[1])
-                K.mlp_bwd(d_, plan=plan)
-                if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
-                    dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
-                dlin(plan, t1b, gb, p + ".mlp.down_proj", R, H, I, defer=True)     # dW_down = t1^T g, db_down = colsum t1
-                dlin_ln(plan, dub, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", I)
-                flush_deferred(plan)
-                return
-            dSd = dS
-            if dp > 0:                                                       # mm_utils.py:52 dropout(down_proj(.))
-                K.dropout_apply(dS, t1, R, H, self._drop(tag + "/mlpdrop", dp), plan=plan)
-                dSd = t1
-            dlin(plan, dSd, self.b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, act=act_grad, act_scale=c.act[1],
-                 gradmul_pre=self.b[tag + "/u"])
-            dlin(plan, du, self.b[tag + "/h2"], p + ".mlp.up_proj", R, I, H, dX=dh_)
-            ln_b(plan, dh_, X_in, p + ".ln2", tag + "/ln2", dS, dS)
-
-        def out_proj_back(plan, dS, a, wname):
-            """dW, db of an attention out_proj and d(attention output) -> t2."""
-            if F_OUT:
-                dlin(plan, dS, a, wname, R, H, H, defer=True)        # leaves with the next LayerNorm-fed linear's weight gradient
-                K.rowgemm(dS, prep["v"][wname]["WpT"], t2, R, H, H, plan=plan)
-            else:
-                dlin(plan, dS, a, wname, R, H, H, dX=t2)
-
-        def self_back(plan, dS, p, tag, X_in, flags):
-            out_proj_back(plan, dS, self.b[tag + "/a"], p + ".attn.out_proj")
-            qkv = self.b[tag + "/qkv"]
-            K.attn_bwd(attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, self.b[tag + "/a"], flags, d_o=t2, dq=dqkv, dkv=dqkv,
-                                 lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), plan=plan)
-            if F_QKV:
-                dlin_ln(plan, dqkv, tag + "/ln1", p + ".attn.qkv", p + ".ln1", 3 * H)
-                flush_deferred(plan)
-                dx_ln(plan, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", dS, dS)
-            else:
-                flush_deferred(plan)
-                dlin(plan, dqkv, self.b[tag + "/h1"], p + ".attn.qkv", R, 3 * H, H, dX=dh_)
-                ln_b(plan, dh_, X_in, p + ".ln1", tag + "/ln1", dS, dS)
-
-        dqc, dkvc = buf("d/qc", (R, H)), buf("d/kvc", (R, 2 * H))
-        first_ctx = True
-        for i in reversed(range(c.n_dec)):
-            p, tag = f"decoder.{i}", f"dec{i}"
-            mlp_back(cur, dY, p, tag, self.b[tag + "/yb"])
-            # cross attention (decoder_embeddings.py:143): query side -> stream, context side -> dctx
-            out_proj_back(cur, dY, self.b[tag + "/a2"], p + ".cross_attn.out_proj")
-            K.attn_bwd(attn_desc(tag + "/xa", self.b[tag + "/qc"], H, self.b[tag + "/kvc"], 2 * H, 0, H, self.b[tag + "/a2"], enc_flags,
-                                 d_o=t2, dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=cur)
-            if F_LNL:
-                dlin_ln(cur, dqc, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", H)
-                flush_deferred(cur)
-                dx_ln(cur, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", dY, dY)
-                dlin_ln(cur, dkvc, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", 2 * H)
-                dx_ln(cur, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", None if first_ctx else dctx, dctx)
-            else:
-                flush_deferred(cur)
-                dlin(cur, dqc, self.b[tag + "/hq"], p + ".cross_attn.query", R, H, H, dX=dh_)
-                ln_b(cur, dh_, self.b[tag + "/xa"], p + ".query_norm", tag + "/qn", dY, dY)
-                dlin(cur, dkvc, self.b[tag + "/hc"], p + ".cross_attn.kv", R, 2 * H, H, dX=dh_)
-                ln_b(cur, dh_, context, p + ".context_norm", tag + "/cn", None if first_ctx else dctx, dctx)
-            first_ctx = False
-            self_back(cur, dY, p, tag, stream_in[tag], dec_flags)
-            close_segment(p)
-        if c.n_dec == 0:
-            raise NotImplementedError("n_dec == 0")
-        # now dY = d(dec_tokens + dec_emb) and dctx = d(context); context = ctx_proj(enc_out) + encoder_emb (mm.py:292)
-        dX = buf("d/xstream", (R, H))
-        if F_LNL:
-            dlin_ln(cur, dctx, "encnorm", "decoder_proj_context", "encoder_norm", H)
-            dx_ln(cur, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", None, dX)
-        else:
-            dlin(cur, dctx, enc_out, "decoder_proj_context", R, H, H, dX=dh_)
-            ln_b(cur, dh_, enc_last, "encoder_norm", "encnorm", None, dX)
-        close_segment("bridge")
-        for i in reversed(range(c.n_enc)):
-            p, tag = f"encoder.{i}", f"enc{i}"
-            mlp_back(cur, dX, p, tag, self.b[tag + "/xa"])
-            self_back(cur, dX, p, tag, stream_in[tag], enc_flags)
-            close_segment(p)
-        # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds)
-        for side, dS, dextra, acc_mod in (("decoder", dY, None, False), ("encoder", dX, dctx, True)):
-            for m, (mod, n) in enumerate(c.mods):
-                pS = f"{side}_embeddings.{mod}.embedder"
-                K.stitch_bwd(dS, dextra, ts, keep0, self._drop(f"{side}/embdrop/{m}", dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
-                             self.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], self.Gv(pS + ".pos_embed.weight"),
-                             acc_mod, False, B, T, Lq, m, H, c.max_F, ws_st, plan=cur)
-        for side in ("decoder", "encoder"):
-            for m, (mod, n) in enumerate(c.mods):
-                p = f"{side}_embeddings.{mod}.embedder"
-                n2 = n * c.mult
-                dz = buf(f"d/z/{m}", (BT, n2))
-                if code == L.BF16:
-                    dlin(cur, self.b[f"d/tok/{side}/{m}"], self.b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
-                         act=L.ACT_SOFTSIGN_GRAD_OUT, act_scale=c.embed_scale, gradmul_pre=self.b[f"{side}/a/{m}"])
-                else:
-                    dlin(cur, self.b[f"d/tok/{side}/{m}"], self.b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
-                         act=L.ACT_SOFTSIGN_GRAD, act_scale=c.embed_scale, gradmul_pre=self.b[f"{side}/z/{m}"])
-                dlin(cur, dz, self.b[f"in/{m}"], p + ".token_embed", BT, n2, n, ldx=_align(n, 8))
-        close_segment("embed")
-        if used_wt:                 # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
-            tw = self._wt_table()
-            K.prep_weights(tw["table"], tw["n"], tw["tiles"], plan=fwd)
-            fwd.insert(0, fwd.pop())
-        plan = dict(fwd=fwd, bwd=bwd, B=B, T=T, training=bool(training), M=M, R=R, BT=BT, runs=dict(fwd=0, bwd=0), graphs={}, b=self.b,
-                    fused=fm, use_keep=use_keep)
-        self.plans[key] = plan
-        return plan
+        if key not in self.plans:
+            self.plans[key] = PlanBuilder(self, B, T, training, grad).build()
+        return self.plans[key]
 
     def dropout_sites(self, B, T):
         """Read-only description of the dropout sites of the built training plan of batch shape (B, T), for tests that read the masks

@@ -1,0 +1,525 @@
+"""The step-plan builder: MultiModal forward / backward of one batch shape as lists of pre-bound HIP kernel launches.
+
+`PlanBuilder(engine, B, T, training, grad).build()` returns the plan dict `Engine._plan` caches.  What is mutable while a plan is laid
+out (the launch lists, the parked weight gradient, the pending slab reductions) lives in the builder; parameters, buffer pools, dropout
+sites and the regime decisions (`_fused_mask`, `_dw_split`, `_w_transposed`) stay with the engine.  DESIGN.md §7b: layout, plan signature."""
+from __future__ import annotations
+
+import functools
+import math
+import os
+from collections import namedtuple
+
+import torch
+
+from . import _lib as L
+from . import ops as K
+
+
+def _align(n, a=8):
+    return (n + a - 1) // a * a
+
+
+# The plan-time MMFM_* environment switches, read once when a plan is built.  fused: MMFM_FUSED as an int, None when it is
+# not set (the shape decides: Engine._fused_mask); the others: False where the variable turns the path off
+Switches = namedtuple("Switches", "fused gemm_big gemm_dw batch_reduce dw_pair attn_keepbits mlp_bwd_split")
+
+
+def read_switches() -> Switches:
+    env, on = os.environ, lambda k: os.environ.get(k, "1") != "0"
+    return Switches(fused=int(env["MMFM_FUSED"]) if "MMFM_FUSED" in env else None, gemm_big=on("MMFM_GEMM_BIG"), gemm_dw=on("MMFM_GEMM_DW"),
+                    batch_reduce=on("MMFM_BATCH_REDUCE"), dw_pair=on("MMFM_DW_PAIR"), attn_keepbits=on("MMFM_ATTN_KEEPBITS"),
+                    mlp_bwd_split=env.get("MMFM_MLP_BWD_SPLIT", "1") == "1")
+
+
+class PlanBuilder:
+    def __init__(self, engine, B, T, training, grad=True):
+        e, c = self.e, self.c = engine, engine.cfg
+        self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
+        self.sw = read_switches()
+        self.H, self.I, self.heads, self.M = c.hidden, c.inter, c.heads, len(c.mods)
+        self.Lq, self.R, self.BT = self.M * T, B * self.M * T, B * T
+        self.dp, self.dpe = (c.dropout, c.embed_dropout) if training else (0.0, 0.0)
+        self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
+        self.act_fwd, self.act_grad = K.GEMM_ACTS[c.act[0]]       # the un-fused MLP's mmfm_gemm act codes (beta: c.act[1])
+        self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
+        # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
+        # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
+        self.dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)
+        self.fwd, self.bwd, self.cur = [], [], []      # the forward, the closed backward segments, the open one
+        self.pend: list = []         # batched reduction: the open segment's slab regions, summed by ONE launch in close_segment
+        self.late_lng: list = []     # ... and the norm-fed linears whose mmfm_ln_linear_grad runs behind that launch
+        self.slabm_off = 0           # ... and the floats of ws/slabm the open segment has handed out
+        self.deferred: list = []     # a parked weight gradient, waiting for a partner (mmfm_gemm_pair)
+        self.used_wt: list = []      # weights whose bf16 transpose a dX product reads
+        self.stream_in = {}          # layer tag -> the residual stream that entered it
+
+    def build(self):
+        self.workspaces()
+        self.forward()
+        plan = dict(fwd=self.fwd, bwd=None, B=self.B, T=self.T, training=self.training, M=self.M, R=self.R, BT=self.BT,
+                    runs=dict(fwd=0, bwd=0), graphs={}, b=self.b)
+        if self.grad:
+            self.backward()
+            plan.update(bwd=self.bwd, fused=self.fm, use_keep=self.use_keep)
+        return plan
+
+    # ------------------------------------------------------------------ static inputs, workspaces, the regime of this shape
+    def workspaces(self):
+        e, c, buf, sw = self.e, self.c, self.buf, self.sw
+        B, T, H, R, BT, Lq, M = self.B, self.T, self.H, self.R, self.BT, self.Lq, self.M
+        f32, i64, u8 = torch.float32, torch.int64, torch.uint8
+        for m, (mod, n) in enumerate(c.mods):
+            # input rows padded to 16 B (zeros): the tokeniser's weight-gradient GEMM streams them by LDS-DMA (csrc/gemm_dw.hip)
+            buf(f"in/{m}", (BT, _align(n, 8)), zero=True); buf(f"tgt/{m}", (BT, n), f32); buf(f"mask/{m}", (B, T), i64)
+        buf("ts", (B, T), i64); buf("attn", (B, T), i64); buf("tokmask", (B, Lq), u8); buf("keypad", (B, Lq), u8)
+        buf("keep0", (Lq,), u8); buf("mod_id", (Lq,), u8); buf("count", (M,), i64); buf("loss_sum", (M,), f32)
+        max_slab = 1
+        for _, n in c.mods:
+            # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
+            # streaming kernel and with it another split count)
+            for (mm, nn, ldn) in ((n * c.mult, n, _align(n, 8)), (H, n * c.mult, None), (n, H, None)):
+                max_slab = max(max_slab, e._dw_split(mm, nn, BT, ldn=ldn, sw=sw)[0] * _align(mm * nn + mm))
+        for l in e.linears:
+            max_slab = max(max_slab, e._dw_split(l.N, l.K, R, sw=sw)[0] * _align(l.N * l.K + l.N))
+        self.slab = buf("ws/slab", (max_slab,), f32)
+        self.slab2 = buf("ws/slab2", (max_slab,), f32)          # a deferred weight-gradient GEMM's slabs, paired with the next one (mmfm_gemm_pair)
+        # launch-bound regime (R <= 8192, the reference's batch of 16): every dW GEMM keeps its own slab region and ONE
+        # mmfm_reduce_slabs_multi per backward segment sums them all (66 reductions of ~7 us each otherwise)
+        self.batch_red = R <= 8192 and sw.batch_reduce
+        if self.batch_red:
+            # regions are handed out per backward segment and reused by the next one (close_segment resets the offset behind the segment's
+            # reduction): the largest segment's parameters bound the need, not the whole model's
+            seg_max = max(end - s0 for _, s0, end in e.layout.segments)
+            self.slabm = buf("ws/slabm", (max(1, min(R // 256, 15)) * (seg_max + 128 * 64),), f32)
+        maxN = max([3 * H, self.I] + [n * c.mult for _, n in c.mods])
+        buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
+        buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
+        buf("ws/stitch", (max(1, L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, c.max_F) // 4),), f32)
+        buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
+        # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
+        # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
+        # parked one alone.  Each product then makes half as many K-slabs (csrc/gemm_dw.hip).
+        self.pair_ok = self.code == L.BF16 and not self.batch_red and sw.dw_pair and sw.gemm_dw
+        # keep decisions of the attention-probability dropout: one bit tile set per attention site, written by the forward (generator
+        # kernel in front of it), read by the backward (csrc/attention_fast.hip; 51 MB per site at B = 1024).  MMFM_ATTN_KEEPBITS=0: hash.
+        self.use_keep = self.code == L.BF16 and self.dp > 0 and self.grad and sw.attn_keepbits
+        fm = self.fm = e._fused_mask(R, sw)
+        self.F_QKV, self.F_LNL, self.F_MLP, self.F_OUT = bool(fm & 1), bool(fm & 2), bool(fm & 4), bool(fm & 8)
+        self.prep = e._build_prep() if fm else None
+        if fm:
+            K.prep_weights(self.prep["table"], self.prep["n"], self.prep["tiles"], plan=self.fwd)
+            self.gdb = buf("ws/gdb", (max(_align(l.N * l.K + l.N) for l in e.linears if l.norm),), f32)
+            if "ws/lng" not in self.b:
+                self.b["ws/lng"] = K.ln_linear_grad_workspace(H, e.device)          # zeroed once; the kernel re-arms its tickets
+
+    def slab_region(self, S, stride):
+        o = self.slabm_off
+        self.slabm_off = o + S * stride
+        if self.slabm_off > self.slabm.numel():
+            raise RuntimeError(f"engine: ws/slabm holds {self.slabm.numel()} floats, the plan's slab regions need {self.slabm_off}")
+        return self.slabm[o:o + S * stride]
+
+    # ------------------------------------------------------------------ linears and their gradients
+    def lin(self, plan, X, wname, Y, Mr, N, Kd, ldx=None, **kw):
+        K.gemm(X, self.e.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.e.Pb(wname), dtype=self.code, plan=plan, **kw)
+
+    def wgrad(self, plan, dY, X, dst, N, Kd, Mr, nb, S, kchunk, what, ldx=None, colsum=None, slab=None, paired=False):
+        """THE weight-gradient product: dst[N, Kd], with nb (N or 0) column sums of dY right behind it, = dY[Mr, N]^T X[Mr, Kd].
+        S == 1: one launch straight into dst (`colsum`: where its column sums go when not behind dst).  S > 1: S K-slabs of `stride`
+        floats - in a region of ws/slabm whose reduction joins the segment's ONE launch (batched reduction), else in `slab`, reduced
+        into dst at once.  paired: nothing is launched; returns the descriptor for mmfm_gemm_pair and the reduction for `reduce`."""
+        n = N * Kd + nb
+        if S == 1 and not paired:
+            out, cs, split, red = dst, colsum if colsum is not None else (dst.data_ptr() + 4 * N * Kd if nb else None), {}, None
+        else:
+            stride = _align(n) if nb else n
+            out = self.slab_region(S, stride) if self.batch_red else slab
+            if S * stride > out.numel():
+                raise RuntimeError(f"engine: {what}: {S} slabs x {stride} floats exceed the {out.numel()}-float slab workspace")
+            cs = out.data_ptr() + 4 * N * Kd if nb else None
+            split, red = dict(splits=S, kchunk=kchunk, slab_stride=stride), (dst, out, n, S, stride)
+        emit = K.gemm_desc if paired else functools.partial(K.gemm, plan=plan)
+        d = emit(dY, X, out, N, Kd, Mr, lda=N, ldb=ldx or Kd, ldc=Kd, a_kcontig=0, b_kcontig=0, dtype=self.code, c_f32=1, colsum=cs, **split)
+        if paired:
+            return d, red
+        if red is not None:
+            self.reduce(plan, red)
+
+    def reduce(self, plan, red):
+        if self.batch_red:
+            self.pend.append(red + (False,))
+        else:
+            K.reduce_slabs(*red, plan=plan)
+
+    def pair_splits(self, Na, Ka, Nb, Kb, Mr):
+        ta, tb = L.lib().mmfm_gemm_dw_tiles(Na, Ka, Mr), L.lib().mmfm_gemm_dw_tiles(Nb, Kb, Mr)
+        ia = 256 * (Na + Ka) / (Na + Ka + Nb + Kb)
+        Sa = max(1, int(ia) // ta)
+        while Sa > 1 and (ta * Sa) % 8:
+            Sa -= 1
+        Sb = max(1, (256 - ta * Sa) // tb)
+        out = []
+        for S in (Sa, Sb):
+            kchunk = _align(-(-Mr // max(1, min(S, Mr // 512))), 64)
+            out += [-(-Mr // kchunk), kchunk]
+        return out
+
+    def flush_deferred(self, plan):
+        if self.deferred:
+            a = self.deferred.pop()
+            self.dlin(plan, a["dY"], a["X"], a["wname"], a["Mr"], a["N"], a["Kd"])
+
+    def dlin(self, plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, **kw):
+        """Backward of Y[Mr,N] = X[Mr,Kd] @ W[N,Kd]^T + b:  dW, db into G;  dX = dY @ W (optional, fused epilogue).
+        ldx = row stride of X when its rows are padded."""
+        e, code = self.e, self.code
+        S, kchunk = e._dw_split(N, Kd, Mr, ldn=ldx, sw=self.sw)
+        gw, gb = e.Gv(wname + ".weight"), e.Gb(wname)
+        # bf16: the bias gradient (column sums of dY) rides on the dW GEMM (mmfm_gemm_desc.colsum); when the bias
+        # gradient sits right behind the weight gradient in the flat buffer one slab reduction finishes both.
+        # A bias-free linear (gb None) has no column sum anywhere: the GEMM runs without colsum, its slabs hold the weight gradient only
+        fused = code == L.BF16 and gb is not None
+        adjacent = fused and gb.data_ptr() == gw.data_ptr() + 4 * N * Kd
+        if defer and self.pair_ok and S > 1 and (adjacent or gb is None) and dX is None and ldx in (None, Kd):
+            self.flush_deferred(plan)
+            self.deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd, nb=N if gb is not None else 0))
+            return
+        self.wgrad(plan, dY, X, gw, N, Kd, Mr, N if adjacent and S > 1 else 0, S, kchunk, wname, ldx=ldx, colsum=gb if fused else None, slab=self.slab)
+        if gb is not None and (not fused or (S > 1 and not adjacent)):
+            K.colsum(dY, Mr, N, N, gb, self.b["ws/col"], plan=plan)
+        if dX is not None:
+            wT = e._w_transposed(wname, N, Kd, Mr, sw=self.sw) if code == L.BF16 else None
+            if wT is not None:      # reduction >= 512: the 256-tile kernel (csrc/gemm_big.hip) against the K-contiguous transpose W^T [Kd, N]
+                self.used_wt.append(wname)
+                K.gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
+            else:
+                K.gemm(dY, e.W(wname + ".weight"), dX, Mr, Kd, N, lda=N, ldb=Kd, ldc=Kd, b_kcontig=0, dtype=code, plan=plan, **kw)
+
+    def lin_norm_grad(self, plan, Gdb, wname, lnname, N):
+        """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]
+        (bias-free: dbias None; behind a ScaleNorm Gdb then has no colsum block, dlin_ln)."""
+        e, H, ws = self.e, self.H, self.b["ws/lng"]
+        if e.is_sn(lnname):
+            K.sn_linear_grad(Gdb, e.Pf(wname + ".weight"), e.Pf(lnname + ".scale"), N, H, e.Gv(wname + ".weight"),
+                             e.Gb(wname), e.Gv(lnname + ".scale"), ws, plan=plan)
+            return
+        K.ln_linear_grad(Gdb, e.Pf(wname + ".weight"), e.Pf(lnname + ".weight"), e.Pf(lnname + ".bias"), N, H,
+                         e.Gv(wname + ".weight"), e.Gb(wname), e.Gv(lnname + ".weight"), e.Gv(lnname + ".bias"), ws, plan=plan)
+
+    def dlin_ln(self, plan, dYt, tag, wname, lnname, N):
+        """Gradients of a LayerNorm-fed linear and of that LayerNorm's affine from G = dY^T x_hat (mmfm_ln_linear_grad)."""
+        H, R, deferred = self.H, self.R, self.deferred
+        S, kchunk = self.e._dw_split(N, H, R, sw=self.sw)
+        xh = self.b[tag + "/xh"]
+        # the colsum block behind G: N, or 0 for a bias-free linear behind a ScaleNorm (nobody reads db).  Behind a LayerNorm db = colsum dY
+        # stays even without a bias: dW and dbeta need it (beta is folded into the linear)
+        nb = N if (self.e.Gb(wname) is not None or not self.e.is_sn(lnname)) else 0
+        if deferred and S > 1 and deferred[-1]["Mr"] == R:
+            a = deferred.pop()
+            Sa, kca, Sb, kcb = self.pair_splits(a["N"], a["Kd"], N, H, R)
+            da, ra = self.wgrad(plan, a["dY"], a["X"], self.e.Gv(a["wname"] + ".weight"), a["N"], a["Kd"], R, a["nb"], Sa, kca, a["wname"],
+                                slab=self.slab2, paired=True)
+            db_, rb = self.wgrad(plan, dYt, xh, self.gdb, N, H, R, nb, Sb, kcb, wname, slab=self.slab, paired=True)
+            K.gemm_pair(da, db_, plan=plan)
+            self.reduce(plan, ra)
+            self.reduce(plan, rb)
+        elif self.batch_red and S > 1:
+            # launch-bound regime: the slabs join the segment's ONE reduction launch (own region, own reduced buffer per site) and
+            # mmfm_ln_linear_grad runs behind it at the end of the segment (close_segment) - one reduction launch per site less
+            g_site = self.buf(f"ws/gdb/{len(self.late_lng)}", (self.gdb.numel(),), torch.float32)
+            self.wgrad(plan, dYt, xh, g_site, N, H, R, nb, S, kchunk, wname)
+            self.late_lng.append((g_site, wname, lnname, N))
+            return
+        else:
+            self.wgrad(plan, dYt, xh, self.gdb, N, H, R, nb, S, kchunk, wname, slab=self.slab)
+        self.lin_norm_grad(plan, self.gdb, wname, lnname, N)
+
+    # ------------------------------------------------------------------ norms, norm-fed linears, attention descriptors
+    def ln_f(self, plan, X, name, Y, tag, **kw):
+        e, R, H, f32 = self.e, self.R, self.H, torch.float32
+        if e.is_sn(name):
+            K.scalenorm_fwd(X, e.Pf(name + ".scale"), Y, self.buf(tag + "/rstd", (R,), f32), R, H, plan=plan)
+            return
+        K.layernorm_fwd(X, e.Pf(name + ".weight"), e.Pf(name + ".bias"), Y, self.buf(tag + "/mean", (R,), f32),
+                        self.buf(tag + "/rstd", (R,), f32), R, H, plan=plan, **kw)
+
+    def ln_b(self, plan, dY, X, name, tag, dres, dX, **kw):
+        e, b, R, H = self.e, self.b, self.R, self.H
+        if e.is_sn(name):       # (ws/ln, sized for the LayerNorm backward, covers the ScaleNorm's per-block partials)
+            K.scalenorm_bwd(dY, X, b[tag + "/rstd"], e.Pf(name + ".scale"), dres, dX, e.Gv(name + ".scale"), R, H, b["ws/ln"], plan=plan)
+            return
+        K.layernorm_bwd(dY, X, b[tag + "/mean"], b[tag + "/rstd"], e.Pf(name + ".weight"), dres, dX,
+                        e.Gv(name + ".weight"), e.Gv(name + ".bias"), R, H, b["ws/ln"], plan=plan, **kw)
+
+    def ln_lin(self, plan, Xin, lnname, wname, Yout, N, tag, residual=None, alias=None):
+        """LayerNorm (or ScaleNorm) + the linear it feeds in one launch; x_hat / rstd saved for the backward when training.
+        alias = tag of an earlier call on the SAME input: x_hat / rstd do not depend on the norm's affine / gain (it is folded
+        into the prepared weights), so the earlier call's saved tensors serve this site's backward too and nothing is stored."""
+        b, R, H = self.b, self.R, self.H
+        pw = self.prep["v"][wname]
+        xh = rs = None
+        if alias is not None and self.grad:
+            b[tag + "/xh"], b[tag + "/rs"] = b[alias + "/xh"], b[alias + "/rs"]
+        elif self.grad:
+            xh, rs = self.buf(tag + "/xh", (R, H)), self.buf(tag + "/rs", (R,), torch.float32)
+        K.rowgemm(Xin, pw["Wp"], Yout, R, N, H, bias=pw["bp"], ln=2 if self.e.is_sn(lnname) else 1, xhat=xh, rstd=rs, residual=residual,
+                  ldr=H if residual is not None else 0, stream_out=True, plan=plan)
+
+    def dx_ln(self, plan, dYt, Kd, tag, wname, lnname, dres, dXout):
+        """dX of a norm-fed linear with the norm's backward (and the residual gradient) in its epilogue."""
+        H = self.H
+        K.rowgemm(dYt, self.prep["v"][wname]["WpT"], dXout, self.R, H, Kd, ldw=Kd, residual=dres, ldr=H if dres is not None else 0,
+                  ln_bwd=2 if self.e.is_sn(lnname) else 1, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
+
+    def attn_desc(self, tag, q, ldq, kv, ldkv, koff, voff, o, flags, d_o=None, dq=None, dkv=None, lddq=0, lddkv=0, dkoff=0, dvoff=0):
+        e, b, buf, B, heads, Lq, H, es, dp = self.e, self.b, self.buf, self.B, self.heads, self.Lq, self.H, self.es, self.dp
+        dh = H // heads
+        keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if self.use_keep else None
+        return K.attn_desc(self.code, B, heads, Lq, Lq, dh, q.data_ptr(), kv.data_ptr() + koff * es, kv.data_ptr() + voff * es, ldq, ldkv, ldkv,
+                           o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), torch.float32), b["keypad"], b["mod_id"], flags,
+                           1.0 / math.sqrt(dh), drop_p=e._drop(tag + "/p", dp), drop_o=e._drop(tag + "/o", dp),
+                           d_o=K.P(d_o), lddo=H, dq=K.P(dq), dk=None if dkv is None else dkv.data_ptr() + dkoff * es,
+                           dv=None if dkv is None else dkv.data_ptr() + dvoff * es, lddq=lddq, lddk=lddkv, lddv=lddkv, keepbits=keep)
+
+    def loss(self, plan, mod, two_kind, kind_fn, *args):
+        """A modality's masked loss, forward or backward.  PoissonNLL(log_input) / MSE without a flag go through the two-kind entry
+        points (`two_kind`), call for call the plan it always was; every other kind through `kind_fn` with its float and flags."""
+        c = self.c
+        kind, param, flags = c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
+        if kind in (L.LOSS_POISSON_LOG, L.LOSS_MSE) and flags == 0:
+            two_kind(kind, *args, plan=plan)
+        else:
+            kind_fn(kind, param, flags, *args, plan=plan)
+
+    # ------------------------------------------------------------------ forward blocks
+    def out_proj(self, plan, a, wname, Xres, Xout):
+        R, H = self.R, self.H
+        if self.F_OUT:
+            K.rowgemm(a, self.e.W(wname + ".weight"), Xout, R, H, H, bias=self.e.Pb(wname), residual=Xres, ldr=H, plan=plan)
+        else:
+            self.lin(plan, a, wname, Xout, R, H, H, residual=Xres, ldr=H)
+
+    def self_block(self, plan, X, p, tag, flags):
+        """x + attn(ln1(x))  (encoder_embeddings.py:112, decoder_embeddings.py:141)."""
+        buf, R, H = self.buf, self.R, self.H
+        qkv, a, Xa = buf(tag + "/qkv", (R, 3 * H)), buf(tag + "/a", (R, H)), buf(tag + "/xa", (R, H))
+        if self.F_QKV:
+            self.ln_lin(plan, X, p + ".ln1", p + ".attn.qkv", qkv, 3 * H, tag + "/ln1")
+        else:
+            self.ln_f(plan, X, p + ".ln1", buf(tag + "/h1", (R, H)), tag + "/ln1")
+            self.lin(plan, self.b[tag + "/h1"], p + ".attn.qkv", qkv, R, 3 * H, H)
+        K.attn_fwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, a, flags), plan=plan)
+        self.out_proj(plan, a, p + ".attn.out_proj", X, Xa)
+        return Xa
+
+    def mlp_block(self, plan, X, p, tag):
+        """x + mlp(ln2(x))  (encoder_embeddings.py:114; mm_utils.py:50-52)."""
+        e, c, buf, R, H, I, f32 = self.e, self.c, self.buf, self.R, self.H, self.I, torch.float32
+        Xb = buf(tag + "/xb", (R, H))
+        if self.F_MLP:
+            pu = self.prep["v"][p + ".mlp.up_proj"]
+            d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=self.prep["v"][p + ".mlp.down_proj"]["WpP"],
+                            b_down=e.Pb(p + ".mlp.down_proj"), drop=e._drop(tag + "/mlpdrop", self.dp), y=Xb,
+                            xhat=buf(tag + "/ln2/xh", (R, H)) if self.grad else None,
+                            rstd=buf(tag + "/ln2/rs", (R,), f32) if self.grad else None, scalenorm=e.is_sn(p + ".ln2"),
+                            act=c.act[0], act_beta=c.act[1])
+            K.mlp_fwd(d_, plan=plan)
+            return Xb
+        h, u, g = buf(tag + "/h2", (R, H)), buf(tag + "/u", (R, I)), buf(tag + "/g", (R, I))
+        self.ln_f(plan, X, p + ".ln2", h, tag + "/ln2")
+        self.lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=self.act_fwd, act_scale=c.act[1])
+        self.lin(plan, g, p + ".mlp.down_proj", Xb, R, H, I, drop=e._drop(tag + "/mlpdrop", self.dp), residual=X, ldr=H)
+        return Xb
+
+    # ------------------------------------------------------------------ forward
+    def forward(self):
+        e, c, b, buf, fwd = self.e, self.c, self.b, self.buf, self.fwd
+        B, T, H, R, BT, Lq, M = self.B, self.T, self.H, self.R, self.BT, self.Lq, self.M
+        K.mask_prep(B, T, [b[f"mask/{m}"] for m in range(M)], [1] * M, b["attn"], [n for _, n in c.mods], b["tokmask"], b["keypad"],
+                    b["keep0"], b["mod_id"], b["count"], plan=fwd)
+        tok_tmp = buf("tok_tmp", (BT, H))
+        x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
+        for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
+            for m, (mod, n) in enumerate(c.mods):
+                p = f"{side}_embeddings.{mod}.embedder"
+                n2 = n * c.mult
+                a = buf(f"{side}/a/{m}", (BT, n2))
+                # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
+                # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
+                z = None if self.code == L.BF16 else buf(f"{side}/z/{m}", (BT, n2))
+                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=L.ACT_SOFTSIGN, act_scale=c.embed_scale)
+                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", self.dpe))
+                mod_row = e.Pf(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m]
+                K.stitch_fwd(tok_tmp, mod_row, e.Pf(p + ".pos_embed.weight"), b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, c.max_F, plan=fwd)
+        X = x_enc
+        for i in range(c.n_enc):
+            p, tag = f"encoder.{i}", f"enc{i}"
+            self.stream_in[tag] = X
+            X = self.mlp_block(fwd, self.self_block(fwd, X, p, tag, self.enc_flags), p, tag)
+        self.enc_last = X
+        enc_out, context = buf("enc_out", (R, H)), buf("context", (R, H))
+        if self.F_LNL:
+            self.ln_lin(fwd, X, "encoder_norm", "decoder_proj_context", context, H, "encnorm", residual=emb_enc)
+        else:
+            self.ln_f(fwd, X, "encoder_norm", enc_out, "encnorm")
+            self.lin(fwd, enc_out, "decoder_proj_context", context, R, H, H, residual=emb_enc, ldr=H)       # mm.py:292
+        Y = x_dec
+        for i in range(c.n_dec):
+            p, tag = f"decoder.{i}", f"dec{i}"
+            self.stream_in[tag] = Y
+            Ya = self.self_block(fwd, Y, p, tag, self.dec_flags)
+            qc, kvc, a2, Yb = buf(tag + "/qc", (R, H)), buf(tag + "/kvc", (R, 2 * H)), buf(tag + "/a2", (R, H)), buf(tag + "/yb", (R, H))
+            if self.F_LNL:
+                self.ln_lin(fwd, Ya, p + ".query_norm", p + ".cross_attn.query", qc, H, tag + "/qn")
+                # every decoder layer normalises the same context rows: the statistics are saved by the first layer only
+                self.ln_lin(fwd, context, p + ".context_norm", p + ".cross_attn.kv", kvc, 2 * H, tag + "/cn", alias=None if i == 0 else "dec0/cn")
+            else:
+                hq, hc = buf(tag + "/hq", (R, H)), buf(tag + "/hc", (R, H))
+                self.ln_f(fwd, Ya, p + ".query_norm", hq, tag + "/qn")
+                self.ln_f(fwd, context, p + ".context_norm", hc, tag + "/cn")
+                self.lin(fwd, hq, p + ".cross_attn.query", qc, R, H, H)
+                self.lin(fwd, hc, p + ".cross_attn.kv", kvc, R, 2 * H, H)
+            K.attn_fwd(self.attn_desc(tag + "/xa", qc, H, kvc, 2 * H, 0, H, a2, self.enc_flags), plan=fwd)   # xa_mask = encoder mask
+            self.out_proj(fwd, a2, p + ".cross_attn.out_proj", Ya, Yb)
+            Y = self.mlp_block(fwd, Yb, p, tag)
+        self.dec_last = Y
+        ydec = buf("ydec", (R, H))                         # de-stitched: [M][B*T][H]
+        self.ln_f(fwd, Y, "decoder_norm", ydec, "decnorm", ds_L=Lq, ds_T=T)
+        for m, (mod, n) in enumerate(c.mods):
+            pred = buf(f"pred/{m}", (BT, n))
+            self.lin(fwd, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], b["tokmask"][:, m * T:], Lq, T, BT, n,
+                      b["loss_sum"][m:m + 1], b["ws/loss"])
+        K.loss_finalize(b["loss_sum"], b["count"], M, b["loss"], b["inv_n"], plan=fwd)
+
+    # ------------------------------------------------------------------ backward blocks
+    def close_segment(self, name):
+        if self.pend:                          # the segment's weight-gradient slabs, all in one launch, before its DDP hook fires
+            K.reduce_slabs_multi(list(self.pend), self.e.device, plan=self.cur)
+            self.pend.clear()
+        for g_site, wname, lnname, N in self.late_lng:
+            self.lin_norm_grad(self.cur, g_site, wname, lnname, N)
+        self.late_lng.clear()
+        self.slabm_off = 0                     # the reduction has consumed the regions (stream order): the next segment reuses them
+        self.bwd.append((name, self.cur))
+        self.cur = []
+
+    def mlp_back(self, plan, dS, p, tag, X_in):
+        """dS: running gradient of the residual stream (in place).  X_in = the stream value that fed ln2."""
+        e, c, b, buf, R, H, I, dp = self.e, self.c, self.b, self.buf, self.R, self.H, self.I, self.dp
+        if self.F_MLP:
+            pu, pdn = self.prep["v"][p + ".mlp.up_proj"], self.prep["v"][p + ".mlp.down_proj"]
+            t1b, gb, dub = buf("d/t1m", (R, H)), buf("d/g", (R, I)), buf("d/du", (R, I))
+            # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step.  A ScaleNorm ln2 always splits (the one-launch kernel has no ScaleNorm epilogue)
+            split = self.sw.mlp_bwd_split or e.is_sn(p + ".ln2")
+            d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=e._drop(tag + "/mlpdrop", dp), xhat=b[tag + "/ln2/xh"],
+                            rstd=b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
+                            dx=None if split else dS, scalenorm=e.is_sn(p + ".ln2"), act=c.act[0], act_beta=c.act[1])
+            K.mlp_bwd(d_, plan=plan)
+            if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
+                self.dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
+            self.dlin(plan, t1b, gb, p + ".mlp.down_proj", R, H, I, defer=True)     # dW_down = t1^T g, db_down = colsum t1
+            self.dlin_ln(plan, dub, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", I)
+            self.flush_deferred(plan)
+            return
+        dSd = dS
+        if dp > 0:                                                       # mm_utils.py:52 dropout(down_proj(.))
+            K.dropout_apply(dS, b["d/t1"], R, H, e._drop(tag + "/mlpdrop", dp), plan=plan)
+            dSd = b["d/t1"]
+        self.dlin(plan, dSd, b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=b["d/u"], act=self.act_grad, act_scale=c.act[1], gradmul_pre=b[tag + "/u"])
+        self.norm_lin_back(plan, False, b["d/u"], I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", tag + "/h2", X_in, dS, dS)
+
+    def norm_lin_back(self, plan, fused, dYt, N, tag, wname, lnname, hkey, X_in, dres, dXout):
+        """Backward of a norm-fed linear [N, H] and its norm (input X_in; un-fused: normalised rows saved under `hkey`): the residual
+        stream gradient dXout = dres + norm'(dYt W).  A parked weight gradient leaves with this one's (fused) or alone in front of it."""
+        if fused:
+            self.dlin_ln(plan, dYt, tag, wname, lnname, N)
+            self.flush_deferred(plan)
+            self.dx_ln(plan, dYt, N, tag, wname, lnname, dres, dXout)
+        else:
+            self.flush_deferred(plan)
+            self.dlin(plan, dYt, self.b[hkey], wname, self.R, N, self.H, dX=self.b["d/h"])
+            self.ln_b(plan, self.b["d/h"], X_in, lnname, tag, dres, dXout)
+
+    def out_proj_back(self, plan, dS, a, wname):
+        """dW, db of an attention out_proj and d(attention output) -> d/t2."""
+        R, H, t2 = self.R, self.H, self.b["d/t2"]
+        if self.F_OUT:
+            self.dlin(plan, dS, a, wname, R, H, H, defer=True)        # leaves with the next LayerNorm-fed linear's weight gradient
+            K.rowgemm(dS, self.prep["v"][wname]["WpT"], t2, R, H, H, plan=plan)
+        else:
+            self.dlin(plan, dS, a, wname, R, H, H, dX=t2)
+
+    def self_back(self, plan, dS, p, tag, flags):
+        b, H = self.b, self.H
+        self.out_proj_back(plan, dS, b[tag + "/a"], p + ".attn.out_proj")
+        qkv, dqkv = b[tag + "/qkv"], b["d/qkv"]
+        K.attn_bwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, b[tag + "/a"], flags, d_o=b["d/t2"], dq=dqkv, dkv=dqkv,
+                                  lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), plan=plan)
+        self.norm_lin_back(plan, self.F_QKV, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", tag + "/h1", self.stream_in[tag], dS, dS)
+
+    def cross_back(self, plan, dY, p, tag, dctx_in):
+        """Cross attention (decoder_embeddings.py:143): query side -> the stream dY, context side -> d/ctx (added to `dctx_in`)."""
+        b, H, dqc, dkvc = self.b, self.H, self.b["d/qc"], self.b["d/kvc"]
+        self.out_proj_back(plan, dY, b[tag + "/a2"], p + ".cross_attn.out_proj")
+        K.attn_bwd(self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
+                                  d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=plan)
+        self.norm_lin_back(plan, self.F_LNL, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", tag + "/hq", b[tag + "/xa"], dY, dY)
+        self.norm_lin_back(plan, self.F_LNL, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", tag + "/hc", b["context"],
+                           dctx_in, b["d/ctx"])
+
+    # ------------------------------------------------------------------ backward (segments fire DDP hooks)
+    def backward(self):
+        e, c, b, buf = self.e, self.c, self.b, self.buf
+        B, T, H, I, R, BT, Lq = self.B, self.T, self.H, self.I, self.R, self.BT, self.Lq
+        dY, dydec = buf("d/stream", (R, H)), buf("d/ydec", (R, H))
+        buf("d/t1", (R, H)); buf("d/t2", (R, H)); buf("d/h", (R, H)); buf("d/u", (R, I)); buf("d/qkv", (R, 3 * H)); dctx = buf("d/ctx", (R, H))
+        ydec = b["ydec"]
+        for m, (mod, n) in enumerate(c.mods):
+            dpred = buf(f"d/pred/{m}", (BT, n))
+            self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], b["tokmask"][:, m * T:],
+                      Lq, T, BT, n, b["gout"], b["inv_n"], dpred)
+            self.dlin(self.cur, dpred, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[m * BT:(m + 1) * BT])
+        self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
+        self.close_segment("head")
+        buf("d/qc", (R, H)); buf("d/kvc", (R, 2 * H))
+        for i in reversed(range(c.n_dec)):
+            p, tag = f"decoder.{i}", f"dec{i}"
+            self.mlp_back(self.cur, dY, p, tag, b[tag + "/yb"])
+            self.cross_back(self.cur, dY, p, tag, None if i == c.n_dec - 1 else dctx)     # the last layer writes d/ctx, the others add
+            self.self_back(self.cur, dY, p, tag, self.dec_flags)
+            self.close_segment(p)
+        if c.n_dec == 0:
+            raise NotImplementedError("n_dec == 0")
+        # now dY = d(dec_tokens + dec_emb) and dctx = d(context); context = ctx_proj(enc_out) + encoder_emb (mm.py:292)
+        dX = buf("d/xstream", (R, H))
+        self.norm_lin_back(self.cur, self.F_LNL, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", "enc_out", self.enc_last, None, dX)
+        self.close_segment("bridge")
+        for i in reversed(range(c.n_enc)):
+            p, tag = f"encoder.{i}", f"enc{i}"
+            self.mlp_back(self.cur, dX, p, tag, b[tag + "/xa"])
+            self.self_back(self.cur, dX, p, tag, self.enc_flags)
+            self.close_segment(p)
+        # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds)
+        for side, dS, dextra, acc_mod in (("decoder", dY, None, False), ("encoder", dX, dctx, True)):
+            for m, (mod, n) in enumerate(c.mods):
+                pS = f"{side}_embeddings.{mod}.embedder"
+                K.stitch_bwd(dS, dextra, b["ts"], b["keep0"], e._drop(f"{side}/embdrop/{m}", self.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
+                             e.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], e.Gv(pS + ".pos_embed.weight"),
+                             acc_mod, False, B, T, Lq, m, H, c.max_F, b["ws/stitch"], plan=self.cur)
+        bf16 = self.code == L.BF16       # the softsign gradient from the activation itself, or (fp32) from the saved pre-activation
+        for side in ("decoder", "encoder"):
+            for m, (mod, n) in enumerate(c.mods):
+                p = f"{side}_embeddings.{mod}.embedder"
+                n2 = n * c.mult
+                dz = buf(f"d/z/{m}", (BT, n2))
+                self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
+                          act=L.ACT_SOFTSIGN_GRAD_OUT if bf16 else L.ACT_SOFTSIGN_GRAD, act_scale=c.embed_scale,
+                          gradmul_pre=b[f"{side}/a/{m}" if bf16 else f"{side}/z/{m}"])
+                self.dlin(self.cur, dz, b[f"in/{m}"], p + ".token_embed", BT, n2, n, ldx=_align(n, 8))
+        self.close_segment("embed")
+        if self.used_wt:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
+            tw = e._wt_table()
+            K.prep_weights(tw["table"], tw["n"], tw["tiles"], plan=self.fwd)
+            self.fwd.insert(0, self.fwd.pop())

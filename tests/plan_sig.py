@@ -1,0 +1,213 @@
+"""The signature of a step plan: what a plan launches, on which data, with buffer addresses taken out.
+
+A plan is a list of `(C function, bound arguments, keep)` entries (ops._emit).  Two plans with the same entries launch the same kernels
+on the same data, so a refactor of the plan builder is checked by comparing signatures, not by running steps.  `plan_signature` turns
+every entry into a canonical record - the function's name, every argument typed by `fn.argtypes`, every descriptor struct / ctypes
+array / device table the entry keeps alive, field by field - in which each device pointer is replaced by `[owner, byte offset]`:
+the owner is the engine tensor the pointer lies in (P, G, Pw, rng, a tensor of the plan's buffer pool by its key, a prepared-weight
+or transposed-weight tensor, or the entry's own device table).  The stream argument and the identity of `fn` are left out.
+
+The result holds, per unit (the forward, each backward segment by name), the SHA-256 of the canonical JSON of its records and the
+list of function names; `full=True` adds the records themselves.
+
+CASES is the matrix tests/golden/plan_signatures.json records (scripts/make_plan_goldens.py) and tests/test_plan_identity_gpu.py
+checks: the smallest shapes that select each regime of Engine._fused_mask, the batched slab reduction, weight-gradient pairing and
+the transposed-weight dX path."""
+import bisect
+import ctypes as C
+import hashlib
+import json
+
+import torch
+
+from multi_modal_foundation_model_amd import _lib as L
+
+TABLES = {"mmfm_prep_weights": L.PrepEntry, "mmfm_reduce_slabs_multi": L.ReduceEntry}       # fn name -> row type of its device table
+SWITCHES = ("MMFM_FUSED", "MMFM_GEMM_BIG", "MMFM_GEMM_DW", "MMFM_BATCH_REDUCE", "MMFM_DW_PAIR", "MMFM_ATTN_KEEPBITS", "MMFM_MLP_BWD_SPLIT")
+_FLOATS = (C.c_float, C.c_double)
+
+
+class Owners:
+    """Device address -> (owner name, byte offset).  Owners are added in priority order: of two that start at the same address (two
+    pool keys on one storage, Pw = P in fp32) the first added names the range."""
+
+    def __init__(self):
+        self.start, self.end, self.name = [], [], []
+
+    def add(self, name, t):
+        n = t.numel() * t.element_size()
+        if n == 0:
+            return
+        p = t.data_ptr()
+        i = bisect.bisect_left(self.start, p)
+        if i < len(self.start) and self.start[i] == p:
+            self.end[i] = max(self.end[i], p + n)
+            return
+        self.start.insert(i, p); self.end.insert(i, p + n); self.name.insert(i, name)
+
+    def find(self, p):
+        i = bisect.bisect_right(self.start, p) - 1
+        if i >= 0 and p < self.end[i]:
+            return [self.name[i], p - self.start[i]]
+        return None
+
+
+def engine_owners(engine, plan):
+    own = Owners()
+    for name in ("P", "G", "Pw", "rng"):
+        own.add(name, getattr(engine, name))
+    for key in sorted(plan["b"]):                 # sorted: of two keys on one storage the smallest names it, whatever the creation order
+        own.add("b:" + key, plan["b"][key])
+    prep = getattr(engine, "_prep", None)
+    if prep:
+        for name, t in zip(("WpT", "Wp", "Wpm", "bp"), prep["keep"][:4]):
+            own.add("prep:" + name, t)
+    wt = getattr(engine, "_wt", None)
+    if wt:
+        for wname in sorted(wt["views"]):
+            own.add("wt:" + wname, wt["views"][wname])
+    return own
+
+
+class _Entry:
+    def __init__(self, own, fn, keep):
+        self.own, self.fn = own, fn
+        self.local = Owners()                     # the entry's own device tensors (tables), behind the engine's
+        for i, k in enumerate(keep):
+            if isinstance(k, torch.Tensor):
+                self.local.add(f"keep:{i}", k)
+
+    def ptr(self, p):
+        if p is None or p == 0:
+            return None
+        hit = self.own.find(p) or self.local.find(p)
+        if hit is None:
+            raise LookupError(f"{self.fn.__name__}: pointer {p:#x} lies in no tensor of the engine, the plan's pool or the entry")
+        return hit
+
+    def value(self, v, t):
+        if isinstance(t, type) and issubclass(t, C.Structure):
+            return self.struct(v)
+        if t is C.c_void_p:
+            return self.ptr(v)
+        if t in _FLOATS:
+            return float(t(v).value).hex()
+        return int(v)
+
+    def struct(self, s):
+        return {name: self.value(getattr(s, name), t) for name, t in s._fields_}
+
+    def array(self, a):
+        return [self.value(v, a._type_) for v in a]
+
+    def arg(self, a, t):
+        if isinstance(a, (C.Structure, int, float)) or a is None:
+            return self.value(a, t)
+        return "ref"                              # byref(descriptor) / a ctypes array: its content is recorded from `keep`
+
+    def kept(self, k):
+        if isinstance(k, C.Structure):
+            return self.struct(k)
+        if isinstance(k, C.Array):
+            return self.array(k)
+        if isinstance(k, torch.Tensor):
+            row = TABLES.get(self.fn.__name__)
+            if row is None:
+                return None                       # a workspace the entry only keeps alive (it is an argument as well)
+            raw = k.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
+            return [self.struct(r) for r in (row * (len(raw) // C.sizeof(row))).from_buffer_copy(raw)]
+        raise TypeError(f"{self.fn.__name__}: keep holds a {type(k).__name__}")
+
+
+def entry_record(own, fn, args, keep):
+    types = list(fn.argtypes)[:-1]                # the last argument is the stream
+    if len(types) != len(args):
+        raise TypeError(f"{fn.__name__}: {len(args)} bound arguments for {len(types)} declared")
+    e = _Entry(own, fn, keep)
+    return dict(fn=fn.__name__, args=[e.arg(a, t) for a, t in zip(args, types)], keep=[e.kept(k) for k in keep])
+
+
+def plan_units(plan):
+    return [("fwd", plan["fwd"])] + [("bwd/" + name, seg) for name, seg in (plan["bwd"] or [])]
+
+
+def plan_signature(engine, plan, full=False):
+    own = engine_owners(engine, plan)
+    out = {}
+    for unit, entries in plan_units(plan):
+        recs = [entry_record(own, fn, args, keep) for fn, args, keep in entries]
+        blob = json.dumps(recs, sort_keys=True, separators=(",", ":")).encode()
+        out[unit] = dict(sha256=hashlib.sha256(blob).hexdigest(), names=[r["fn"] for r in recs])
+        if full:
+            out[unit]["records"] = recs
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the recorded matrix
+def _case(name, model, dtype, B, T, flags=(True, True), **env):
+    return dict(name=name, model=model, dtype=dtype, B=B, T=T, flags=flags, env={k: str(v) for k, v in env.items()})
+
+
+_DROP = dict(dropout=0.1)
+_DROP48 = dict(dropout=0.1, emb_dropout=0.1)
+_SN = dict(scalenorm=True, attn_bias=False, mlp_bias=(True, False), act="silu")
+CASES = [
+    _case("default_B64", "default", "bf16", 64, 100),                      # R = 12,800: mask 15, pairing
+    _case("default_B16", "default", "bf16", 16, 100),                      # R = 3,200: mask 11, batched reduction, late_lng
+    _case("drop_B48", _DROP48, "bf16", 48, 100),                           # R = 9,600: mask 11, no batched reduction, pairing, keep bits
+    _case("drop_B48_forward_only", _DROP48, "bf16", 48, 100, (True, False)),
+    _case("drop_B48_eval_grad", _DROP48, "bf16", 48, 100, (False, True)),
+    _case("fp32_B2", _DROP, "fp32", 2, 8),
+    _case("B64_fused0", _DROP, "bf16", 64, 100, MMFM_FUSED=0),             # _w_transposed / used_wt
+    _case("B64_fused3", _DROP, "bf16", 64, 100, MMFM_FUSED=3),
+    _case("B64_fused8", _DROP, "bf16", 64, 100, MMFM_FUSED=8),
+    _case("B64_mlp_bwd_split0", _DROP, "bf16", 64, 100, MMFM_MLP_BWD_SPLIT=0),
+    _case("B64_dw_pair0", _DROP, "bf16", 64, 100, MMFM_DW_PAIR=0),
+    _case("B64_gemm_dw0", _DROP, "bf16", 64, 100, MMFM_GEMM_DW=0),
+    _case("B64_gemm_big0_fused0", _DROP, "bf16", 64, 100, MMFM_GEMM_BIG=0, MMFM_FUSED=0),
+    _case("B64_attn_keepbits0", _DROP, "bf16", 64, 100, MMFM_ATTN_KEEPBITS=0),
+    _case("B16_batch_reduce0", {}, "bf16", 16, 100, MMFM_BATCH_REDUCE=0),
+    _case("B16_fused15", {}, "bf16", 16, 100, MMFM_FUSED=15),
+    _case("scalenorm_biasfree_B64", _SN, "bf16", 64, 100),
+    _case("scalenorm_biasfree_B16", _SN, "bf16", 16, 100),
+    _case("sep_causal_B64", dict(sep=True, causal=True, dropout=0.1), "bf16", 64, 100),
+    _case("dh128_B8", dict(H=512, heads=4, inter=1024), "bf16", 8, 100),   # dh 128, no row-owner path, big-GEMM dX
+    _case("loss_family_fp32", "loss_family", "fp32", None, None),          # B, T: the loss-family test's own
+    _case("loss_family_bf16", "loss_family", "bf16", None, None),
+]
+
+
+def build_case(case):
+    """(engine, plan, seconds the plan build took on the host) of one matrix row.  Builds the model and the plan and launches no kernel
+    of the step.  The caller has set the row's switches (case["env"]) and cleared the other SWITCHES."""
+    import time
+    from helpers import build_model, load_config, model_config
+    B, T = case["B"], case["T"]
+    if case["model"] == "loss_family":
+        import test_loss_family_model_gpu as lf
+        model, B, T = lf.make_model(case["dtype"]), lf.B, lf.T
+    else:
+        mc = load_config().model if case["model"] == "default" else model_config(n_enc=2, n_dec=2, **case["model"])
+        model = build_model(mc, 668, 2, seed=42)
+        model.compute_dtype = case["dtype"]
+        model.cuda()
+    eng = model.engine()
+    t0 = time.perf_counter()
+    plan = eng._plan(B, T, *case["flags"])
+    return eng, plan, time.perf_counter() - t0
+
+
+# ------------------------------------------------------------------------------------------------ the pinned parameter layouts
+# tests/golden/param_layout.json (scripts/make_plan_goldens.py --layout; tests/test_linear_bias_cpu.py): model_config switches per pin
+LAYOUTS = {"default": {}, "scalenorm": dict(scalenorm=True), "encoder_bias_free": dict(attn_bias=(False, True), mlp_bias=(False, True)),
+           "decoder_bias_free": dict(attn_bias=(True, False), mlp_bias=(True, False))}
+
+
+def layout_record(switches):
+    """ParamLayout of the YAML model (channels 668 / 2) under `switches`, as JSON data.  Needs no GPU."""
+    from helpers import model_config
+    from multi_modal_foundation_model_amd.engine import EngineConfig, ParamLayout
+    lay = ParamLayout(EngineConfig.from_model_config(model_config(**switches), [("ap", 668), ("behavior", 2)]))
+    return dict(entries=[[k, off, list(shape)] for k, (off, shape) in lay.entries.items()],
+                alias=[[k, off, list(shape)] for k, (off, shape) in lay.alias.items()],
+                segments=[list(s) for s in lay.segments], n=lay.n)

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_npz
+import plan_sig
+from conftest import load_json, load_npz
 from helpers import build_model, model_config, tiny_config
 from multi_modal_foundation_model_amd.engine import EngineConfig, ParamLayout, _align
 
@@ -151,3 +152,11 @@ def test_ddp_buckets_cover_every_parameter(case):
         assert hi2 == lo
     for name, (off, shape) in layout.entries.items():
         assert sum(lo <= off and off + int(np.prod(shape)) <= hi for _, lo, hi in b) == 1, name
+
+
+@pytest.mark.parametrize("pin", list(plan_sig.LAYOUTS))
+def test_param_layout_is_the_recorded_one(pin):
+    """entries (names, order, offsets, shapes), aliases, segments and n of the YAML model's flat buffer - default, ScaleNorm, bias-free
+    per side - are what tests/golden/param_layout.json recorded (scripts/make_plan_goldens.py --layout) before ParamLayout was
+    rewritten over engine.block_linears."""
+    assert plan_sig.layout_record(plan_sig.LAYOUTS[pin]) == load_json("param_layout.json")[pin]
