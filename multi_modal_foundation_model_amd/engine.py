@@ -36,8 +36,19 @@ HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention
 BLOCK_NORMS = ("ln1", "ln2", "query_norm", "context_norm")     # the sites `use_scalenorm` switches (encoder_norm / decoder_norm stay LayerNorm)
 
 
+# what a side ("encoder" / "decoder") of the model runs with: EngineConfig.side
+SideConfig = namedtuple("SideConfig", "heads inter dropout norm act embed_scale embed_dropout mult max_F attn_bias mlp_bias")
+# The EngineConfig fields that have one value per side (the two YAML sections are independent): each holds ONE value, meaning both
+# sides, or Sides(encoder, decoder).  A plain (encoder, decoder) tuple or list is taken as Sides too - for `act`, whose one value is
+# itself a (kind, beta) pair, a pair of pairs.  __post_init__ folds a pair of equal values into the one value, so a config that names
+# one value equals the config that names it twice, and the default config is field for field what it always was
+PER_SIDE = ("heads", "inter", "dropout", "norm", "act", "embed_scale", "embed_dropout", "mult", "max_F")
+Sides = namedtuple("Sides", "encoder decoder")
+
+
 @dataclass
 class EngineConfig:
+    # (the PER_SIDE fields - heads, inter, max_F, mult, embed_scale, embed_dropout, dropout, norm, act - hold the annotated type or a Sides of it)
     hidden: int
     heads: int
     inter: int
@@ -65,35 +76,71 @@ class EngineConfig:
     enc_mlp_bias: bool = True
     dec_attn_bias: bool = True
     dec_mlp_bias: bool = True
+    # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
+    # `n_modality` (the decoder's mod_emb IS the encoder's tensor, mm.py:84-87).  Read a side's values through `side()`
+
+    def __post_init__(self):
+        for k in PER_SIDE:
+            v = getattr(self, k)
+            pair = isinstance(v, (tuple, list)) and len(v) == 2 and (k != "act" or isinstance(v[0], (tuple, list)))
+            if pair:
+                enc, dec = (tuple(x) for x in v) if k == "act" else v
+                setattr(self, k, enc if enc == dec else Sides(enc, dec))
+
+    def side(self, side: str) -> SideConfig:
+        """The per-side quantities of "encoder" or "decoder"."""
+        if side not in ("encoder", "decoder"):
+            raise ValueError(f"EngineConfig.side({side!r})")
+        vals = (getattr(self, k) for k in PER_SIDE)
+        return SideConfig(*(getattr(v, side) if isinstance(v, Sides) else v for v in vals),
+                          attn_bias=getattr(self, side[:3] + "_attn_bias"), mlp_bias=getattr(self, side[:3] + "_mlp_bias"))
+
+    def is_scalenorm(self, lnname: str) -> bool:
+        """True where the norm named `lnname` is a ScaleNorm: a block norm (BLOCK_NORMS) of a side with use_scalenorm: true.
+        `decoder.{i}.query_norm` and `context_norm` are the decoder's; encoder_norm / decoder_norm are LayerNorms always."""
+        return lnname.rsplit(".", 1)[-1] in BLOCK_NORMS and self.side(lnname.split(".", 1)[0]).norm == "scalenorm"
 
     @staticmethod
-    def from_model_config(mc, mods) -> "EngineConfig":
-        et, ee = mc["encoder"]["transformer"], mc["encoder"]["embedder"]
-        dtf = mc["decoder"]["transformer"]
-        for k in ("hidden_size", "n_heads", "inter_size", "dropout"):
-            if et[k] != dtf[k]:
-                raise ValueError(f"encoder/decoder transformer.{k} differ ({et[k]} vs {dtf[k]}): not supported")
-        if bool(et["use_scalenorm"]) != bool(dtf["use_scalenorm"]):
-            raise NotImplementedError("use_scalenorm differs between encoder and decoder: not built")
-        if et["act"] != dtf["act"]:
-            raise NotImplementedError(f"transformer.act differs between encoder and decoder ({et['act']} vs {dtf['act']}): not built")
-        act = K.mlp_act(et["act"])
-        if ee["act"] != "softsign":
-            raise NotImplementedError("only act=softsign (embedder) is built")
-        hs, nh = int(et["hidden_size"]), int(et["n_heads"])
-        if nh <= 0 or hs % nh:
-            raise ValueError(f"transformer.hidden_size {hs} is not a multiple of n_heads {nh}: the attention kernels take a head dim "
-                             f"in {HEAD_DIMS}")
-        if hs // nh not in HEAD_DIMS:
-            raise ValueError(f"transformer.hidden_size {hs} / n_heads {nh} = head dim {hs // nh}: the attention kernels take a head dim "
-                             f"in {HEAD_DIMS}")
-        scale = et["hidden_size"] ** 0.5 if ee["scale"] is None else ee["scale"]
-        return EngineConfig(hidden=et["hidden_size"], heads=et["n_heads"], inter=et["inter_size"],
-                            n_enc=et["n_layers"], n_dec=dtf["n_layers"], max_F=ee["max_F"], mult=ee["mult"],
-                            n_modality=ee["n_modality"], embed_scale=float(scale), embed_dropout=ee["dropout"],
-                            dropout=et["dropout"], sep_mask=bool(mc["decoder"]["decoder_sep_mask"]),
-                            causal_mask=bool(mc["decoder"]["decoder_causal_mask"]), mods=list(mods),
-                            norm="scalenorm" if et["use_scalenorm"] else "layernorm", act=act,
+    def from_model_config(mc, mods, per_side: bool = False) -> "EngineConfig":
+        """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
+        two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
+        sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
+        always did (the embedder's keys are read per side either way: the decoder's used to be ignored without a word)."""
+        tf = {side: mc[side]["transformer"] for side in ("encoder", "decoder")}
+        em = {side: mc[side]["embedder"] for side in ("encoder", "decoder")}
+        et, dtf, ee = tf["encoder"], tf["decoder"], em["encoder"]
+        if not per_side:
+            for k in ("n_heads", "inter_size", "dropout"):
+                if et[k] != dtf[k]:
+                    raise ValueError(f"encoder/decoder transformer.{k} differ ({et[k]} vs {dtf[k]}): pass per_side=True to read each section for its side")
+            if bool(et["use_scalenorm"]) != bool(dtf["use_scalenorm"]):
+                raise NotImplementedError("use_scalenorm differs between encoder and decoder: pass per_side=True to read each section for its side")
+            if et["act"] != dtf["act"]:
+                raise NotImplementedError(f"transformer.act differs between encoder and decoder ({et['act']} vs {dtf['act']}): pass per_side=True "
+                                          "to read each section for its side")
+        if et["hidden_size"] != dtf["hidden_size"]:
+            raise ValueError(f"encoder/decoder transformer.hidden_size differ ({et['hidden_size']} vs {dtf['hidden_size']}): not supported - "
+                             "decoder_proj_context is hidden -> hidden and cross-attention reads the encoder's rows, so the two "
+                             "stacks share one width")
+        hs, per = int(et["hidden_size"]), {}
+        for side in ("encoder", "decoder"):
+            t, e = tf[side], em[side]
+            if e["act"] != "softsign":
+                raise NotImplementedError("only act=softsign (embedder) is built")
+            nh = int(t["n_heads"])
+            if nh <= 0 or hs % nh:
+                raise ValueError(f"{side}.transformer.hidden_size {hs} is not a multiple of n_heads {nh}: the attention kernels take a "
+                                 f"head dim in {HEAD_DIMS}")
+            if hs // nh not in HEAD_DIMS:
+                raise ValueError(f"{side}.transformer.hidden_size {hs} / n_heads {nh} = head dim {hs // nh}: the attention kernels take "
+                                 f"a head dim in {HEAD_DIMS}")
+            per[side] = dict(heads=t["n_heads"], inter=t["inter_size"], dropout=t["dropout"],
+                             norm="scalenorm" if t["use_scalenorm"] else "layernorm", act=K.mlp_act(t["act"]),
+                             embed_scale=float(hs ** 0.5 if e["scale"] is None else e["scale"]), embed_dropout=e["dropout"],
+                             mult=e["mult"], max_F=e["max_F"])
+        return EngineConfig(hidden=et["hidden_size"], n_enc=et["n_layers"], n_dec=dtf["n_layers"], n_modality=ee["n_modality"],
+                            sep_mask=bool(mc["decoder"]["decoder_sep_mask"]), causal_mask=bool(mc["decoder"]["decoder_causal_mask"]),
+                            mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE},
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]))
 
@@ -106,10 +153,11 @@ def block_linears(cfg: EngineConfig, side: str, i: int) -> List[Lin]:
     """THE description of a block: the linears of encoder / decoder layer i (or of the "bridge" between the two stacks) in forward
     (= parameter) order.  ParamLayout, the prepared weights of the fused path (Engine._build_prep) and the plan's workspace sizing all
     read the model's structure from here."""
-    H, I, p = cfg.hidden, cfg.inter, f"{side}.{i}"
+    H, p = cfg.hidden, f"{side}.{i}"
     if side == "bridge":
         return [Lin("decoder_proj_context", "encoder_norm", H, H, True, None)]
-    ab, mb = (cfg.enc_attn_bias, cfg.enc_mlp_bias) if side == "encoder" else (cfg.dec_attn_bias, cfg.dec_mlp_bias)
+    sc = cfg.side(side)
+    I, ab, mb = sc.inter, sc.attn_bias, sc.mlp_bias
     attn = [Lin(p + ".attn.qkv", p + ".ln1", 3 * H, H, ab, ("query", "key", "value")), Lin(p + ".attn.out_proj", None, H, H, ab, None)]
     cross = [Lin(p + ".cross_attn.query", p + ".query_norm", H, H, ab, None),
              Lin(p + ".cross_attn.kv", p + ".context_norm", 2 * H, H, ab, ("key", "value")),
@@ -127,8 +175,9 @@ class ParamLayout:
     """name -> (offset, shape) in the flat buffer; `groups` are the DDP buckets' atoms."""
 
     def __init__(self, cfg: EngineConfig):
-        if cfg.norm not in ("layernorm", "scalenorm"):
-            raise ValueError(f"EngineConfig.norm = {cfg.norm!r}")
+        for side in ("encoder", "decoder"):
+            if cfg.side(side).norm not in ("layernorm", "scalenorm"):
+                raise ValueError(f"EngineConfig.norm ({side}) = {cfg.side(side).norm!r}")
         H = cfg.hidden
         self.entries: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self.alias: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
@@ -155,7 +204,7 @@ class ParamLayout:
                     add(f"{prefix.rsplit('.', 1)[0]}.{nm}{kind}", (o // len(parts),) + shape[1:])
 
         def ln(prefix):
-            if cfg.norm == "scalenorm" and prefix.rsplit(".", 1)[-1] in BLOCK_NORMS:
+            if cfg.is_scalenorm(prefix):                   # the side that owns the norm decides
                 pad(); add(prefix + ".scale", ())          # ScaleNorm's 0-dim gain, its own aligned slot (mm_utils.py:31-35)
                 return
             pad(); add(prefix + ".weight", (H,)); pad(); add(prefix + ".bias", (H,))
@@ -177,13 +226,14 @@ class ParamLayout:
 
         def embed():
             for side in ("encoder", "decoder"):
+                sc = cfg.side(side)
                 for mod, n in cfg.mods:
                     p = f"{side}_embeddings.{mod}.embedder"
-                    lin(p + ".token_embed", n * cfg.mult, n)
-                    lin(p + ".projection", H, n * cfg.mult)
+                    lin(p + ".token_embed", n * sc.mult, n)
+                    lin(p + ".projection", H, n * sc.mult)
                     if side == "encoder":       # decoder's mod_emb IS this tensor (mm.py:84-87)
                         pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
-                    pad(); add(p + ".pos_embed.weight", (cfg.max_F, H))
+                    pad(); add(p + ".pos_embed.weight", (sc.max_F, H))
 
         def head():
             ln("decoder_norm")
@@ -221,7 +271,7 @@ class _StepFn(torch.autograd.Function):
 
 class Engine:
     def __init__(self, cfg: EngineConfig, device, dtype: str = "fp32", seed: int = 0):
-        if cfg.hidden % cfg.heads:
+        if cfg.hidden % cfg.side("encoder").heads or cfg.hidden % cfg.side("decoder").heads:
             raise ValueError("Hidden dim is not multiple of head size")
         if dtype not in ("fp32", "bf16"):
             raise ValueError(dtype)
@@ -235,7 +285,6 @@ class Engine:
         self.code = L.F32 if dtype == "fp32" else L.BF16
         self.layout = ParamLayout(cfg)
         n = self.layout.n
-        self.scalenorm = cfg.norm == "scalenorm"
         self.P = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.G = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.Pw = self.P if dtype == "fp32" else torch.zeros(n, dtype=torch.bfloat16, device=self.device)
@@ -315,8 +364,8 @@ class Engine:
         return self.Gv(wname + ".bias") if self.layout.has(wname + ".bias") else None
 
     def is_sn(self, lnname):
-        """True where the norm named `lnname` is a ScaleNorm (the block norms of a use_scalenorm model)."""
-        return self.scalenorm and lnname.rsplit(".", 1)[-1] in BLOCK_NORMS
+        """True where the norm named `lnname` is a ScaleNorm (the block norms of a side with use_scalenorm: true)."""
+        return self.cfg.is_scalenorm(lnname)
 
     # ------------------------------------------------------------------ buffers
     def _select_pool(self, B, T):
@@ -362,9 +411,11 @@ class Engine:
     def _fused_mask(self, R, sw=None):
         """Which op groups run as row-owner fused kernels (csrc/rowchain.h): bit 0 ln1+qkv, bit 1 the other LayerNorm-fed
         linears (cross-attention query / key-value, decoder_proj_context), bit 2 the MLP block, bit 3 attention out_proj.
-        MMFM_FUSED overrides (0 = the un-fused kernels of round 1)."""
+        MMFM_FUSED overrides (0 = the un-fused kernels of round 1).  Bits 0, 1 and 3 (K = 256 linears) hold for both sides; bit 2
+        holds for the sides whose inter_size is 512 (`fused_mlp`), the other side runs the un-fused up / down GEMMs.  A model
+        with no such side stays on the un-fused kernels altogether, as it always has."""
         c, sw = self.cfg, sw or read_switches()
-        if self.dtype != "bf16" or c.hidden != 256 or c.inter != 512 or (R + 128) * 1024 * 2 >= 2 ** 31:
+        if self.dtype != "bf16" or c.hidden != 256 or 512 not in (c.side("encoder").inter, c.side("decoder").inter) or (R + 128) * 1024 * 2 >= 2 ** 31:
             return 0
         if R < 12288 and sw.fused is None:
             # a row-owner pass is 128 rows: below ~100 passes per launch the grid cannot fill 256 CUs.  Since round 4 the forward-type linears
@@ -373,6 +424,10 @@ class Engine:
             # B=32 4.85 / 4.71 / -, B=64 5.46 / 5.50 / 5.48 (R = 12,800: the default 15)
             return 11
         return (15 if sw.fused is None else sw.fused) & 15        # default: everything fused, the fastest end to end (35.6 vs 36.3 ms)
+
+    def fused_mlp(self, side, fm):
+        """True where the MLP blocks of `side` run the row-owner MLP kernels under fused mask `fm` (csrc/mlp_fused.hip: inter 512)."""
+        return bool(fm & 4) and self.cfg.side(side).inter == 512
 
     # ------------------------------------------------------------------ bf16 transposes for the compute-bound dX products
     def _w_transposed(self, wname, N, Kd, Mr, sw=None):
@@ -409,7 +464,10 @@ class Engine:
         has_bp = {w: self.Pb(w) is not None or not self.is_sn(ln) for w, ln in sites if ln}
         nb = sum(self.Pf(w + ".weight").shape[0] for w, ln in sites if ln and has_bp[w])
         # unit-permuted copies for the MLP kernels' LDS-DMA weight ring (include/mmfm.h: mmfm_prep_entry.WpP / WpTP)
-        nPm = sum(self.Pf(w + ".weight").numel() for w, _ in sites if w.endswith(".mlp.up_proj") or w.endswith(".mlp.down_proj"))
+        # (only for the sides whose MLP blocks the kernels take: inter 512)
+        mlp_up = {w for w, _ in sites if w.endswith(".mlp.up_proj") and self.fused_mlp(w.split(".", 1)[0], 4)}
+        mlp_down = {w for w, _ in sites if w.endswith(".mlp.down_proj") and self.fused_mlp(w.split(".", 1)[0], 4)}
+        nPm = sum(self.Pf(w + ".weight").numel() for w in mlp_up | mlp_down)
         WpT = torch.zeros(nW + 64, dtype=torch.bfloat16, device=self.device)
         Wp = torch.zeros(nWp + 64, dtype=torch.bfloat16, device=self.device)
         Wpm = torch.zeros(nPm + 64, dtype=torch.bfloat16, device=self.device)
@@ -421,10 +479,10 @@ class Engine:
             e = dict(W=Wm, WpT=WpT[oT:oT + N * Kd].view(Kd, N))
             oT += N * Kd
             v = dict(WpT=e["WpT"])
-            if w.endswith(".mlp.up_proj"):          # backward: d(x_hat) += W_up^T[:, tile] . du, du an accumulator tile
+            if w in mlp_up:                         # backward: d(x_hat) += W_up^T[:, tile] . du, du an accumulator tile
                 e["WpTP"] = v["WpTP"] = Wpm[oP:oP + N * Kd].view(Kd, N)
                 oP += N * Kd
-            elif w.endswith(".mlp.down_proj"):      # forward: y += W_down[:, tile] . g, g an accumulator tile
+            elif w in mlp_down:                     # forward: y += W_down[:, tile] . g, g an accumulator tile
                 e["WpP"] = v["WpP"] = Wpm[oP:oP + N * Kd].view(N, Kd)
                 oP += N * Kd
             if ln:
@@ -483,17 +541,19 @@ class Engine:
         Builds nothing and launches nothing: the plan must exist (one training forward ran at this shape)."""
         plan = self.plans[(B, T, True, True)]
         c = self.cfg
-        H, heads, Lq = c.hidden, c.heads, len(c.mods) * T
+        H, Lq = c.hidden, len(c.mods) * T
         out = []
         for key, site in self._sites.items():
+            side = "encoder" if key.startswith("enc") else "decoder"          # `encoder/embdrop/0`, `enc0/sa/p`, `dec1/mlpdrop`
+            sc = c.side(side)
             if "/embdrop/" in key:
-                d = dict(p=c.embed_dropout, kind="flat", shape=(B * T, H))
+                d = dict(p=sc.embed_dropout, kind="flat", shape=(B * T, H))
             elif key.endswith("/mlpdrop"):
-                d = dict(p=c.dropout, kind="rowdrop" if plan["fused"] & 4 else "flat", shape=(B * Lq, H))
+                d = dict(p=sc.dropout, kind="rowdrop" if self.fused_mlp(side, plan["fused"]) else "flat", shape=(B * Lq, H))
             elif key.endswith("/o"):
-                d = dict(p=c.dropout, kind="flat", shape=(B * Lq, H))
+                d = dict(p=sc.dropout, kind="flat", shape=(B * Lq, H))
             else:
-                d = dict(p=c.dropout, kind="attn", shape=(B, heads, Lq, Lq), dh=H // heads,
+                d = dict(p=sc.dropout, kind="attn", shape=(B, sc.heads, Lq, Lq), dh=H // sc.heads,
                          keepbits=plan["b"].get(key[:-2] + "/keep") if plan["use_keep"] else None)
             out.append(dict(key=key, site=site, **d))
         return out
@@ -532,7 +592,7 @@ class Engine:
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
         plan = self._plan(B, T, training, want_grad)
         self.load_inputs(B, T, inputs, targets, masks, ts, attn)
-        advance = training and (self.cfg.dropout > 0 or self.cfg.embed_dropout > 0)
+        advance = training and any(sc.dropout > 0 or sc.embed_dropout > 0 for sc in map(self.cfg.side, ("encoder", "decoder")))
 
         def fwd_entries():
             if advance:

@@ -32,16 +32,28 @@ def read_switches() -> Switches:
                     mlp_bwd_split=env.get("MMFM_MLP_BWD_SPLIT", "1") == "1")
 
 
+# What a side of the model lays its blocks out with (EngineConfig.side, in this plan's mode): heads, I = inter_size, dp / dpe = the
+# transformer's / the embedder's dropout (0 outside training), act = (MMFM_MLP_* kind, beta) with act_fwd / act_grad the un-fused MLP's
+# mmfm_gemm act codes, the embedder's scale, mult and max_F, and - set by `workspaces` - use_keep (attention dropout of this side runs
+# on keep-bit workspaces) and F_MLP (its MLP blocks run the row-owner MLP kernels)
+class Side:
+    def __init__(self, sc, training):
+        self.heads, self.I, self.act, self.scale, self.mult, self.max_F = sc.heads, sc.inter, sc.act, sc.embed_scale, sc.mult, sc.max_F
+        self.dp, self.dpe = (sc.dropout, sc.embed_dropout) if training else (0.0, 0.0)
+        self.act_fwd, self.act_grad = K.GEMM_ACTS[sc.act[0]]
+        self.use_keep = self.F_MLP = False
+
+
 class PlanBuilder:
     def __init__(self, engine, B, T, training, grad=True):
         e, c = self.e, self.c = engine, engine.cfg
         self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
         self.sw = read_switches()
-        self.H, self.I, self.heads, self.M = c.hidden, c.inter, c.heads, len(c.mods)
+        self.H, self.M = c.hidden, len(c.mods)
         self.Lq, self.R, self.BT = self.M * T, B * self.M * T, B * T
-        self.dp, self.dpe = (c.dropout, c.embed_dropout) if training else (0.0, 0.0)
+        self.sides = {side: Side(c.side(side), training) for side in ("encoder", "decoder")}
+        self.Imax, self.mult_max = max(sd.I for sd in self.sides.values()), max(sd.mult for sd in self.sides.values())
         self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
-        self.act_fwd, self.act_grad = K.GEMM_ACTS[c.act[0]]       # the un-fused MLP's mmfm_gemm act codes (beta: c.act[1])
         self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
         # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
         # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
@@ -54,6 +66,15 @@ class PlanBuilder:
         self.used_wt: list = []      # weights whose bf16 transpose a dX product reads
         self.stream_in = {}          # layer tag -> the residual stream that entered it
 
+    def side(self, name):
+        """The Side a block belongs to, from its parameter prefix (`encoder.3`), its tag (`enc3`, `dec0/xa`) or the side's own name."""
+        return self.sides["encoder" if name.startswith("enc") else "decoder"]
+
+    @staticmethod
+    def rows(t, R, N):
+        """The first R x N elements of workspace `t` as [R, N]: a workspace both sides use is sized by the larger side."""
+        return t if tuple(t.shape) == (R, N) else t.view(-1)[:R * N].view(R, N)
+
     def build(self):
         self.workspaces()
         self.forward()
@@ -61,7 +82,7 @@ class PlanBuilder:
                     runs=dict(fwd=0, bwd=0), graphs={}, b=self.b)
         if self.grad:
             self.backward()
-            plan.update(bwd=self.bwd, fused=self.fm, use_keep=self.use_keep)
+            plan.update(bwd=self.bwd, fused=self.fm, use_keep=any(sd.use_keep for sd in self.sides.values()))
         return plan
 
     # ------------------------------------------------------------------ static inputs, workspaces, the regime of this shape
@@ -78,8 +99,9 @@ class PlanBuilder:
         for _, n in c.mods:
             # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
             # streaming kernel and with it another split count)
-            for (mm, nn, ldn) in ((n * c.mult, n, _align(n, 8)), (H, n * c.mult, None), (n, H, None)):
-                max_slab = max(max_slab, e._dw_split(mm, nn, BT, ldn=ldn, sw=sw)[0] * _align(mm * nn + mm))
+            for mult in sorted({sd.mult for sd in self.sides.values()}):
+                for (mm, nn, ldn) in ((n * mult, n, _align(n, 8)), (H, n * mult, None), (n, H, None)):
+                    max_slab = max(max_slab, e._dw_split(mm, nn, BT, ldn=ldn, sw=sw)[0] * _align(mm * nn + mm))
         for l in e.linears:
             max_slab = max(max_slab, e._dw_split(l.N, l.K, R, sw=sw)[0] * _align(l.N * l.K + l.N))
         self.slab = buf("ws/slab", (max_slab,), f32)
@@ -92,10 +114,10 @@ class PlanBuilder:
             # reduction): the largest segment's parameters bound the need, not the whole model's
             seg_max = max(end - s0 for _, s0, end in e.layout.segments)
             self.slabm = buf("ws/slabm", (max(1, min(R // 256, 15)) * (seg_max + 128 * 64),), f32)
-        maxN = max([3 * H, self.I] + [n * c.mult for _, n in c.mods])
+        maxN = max([3 * H, self.Imax] + [n * self.mult_max for _, n in c.mods])
         buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
         buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
-        buf("ws/stitch", (max(1, L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, c.max_F) // 4),), f32)
+        buf("ws/stitch", (max(1, max(L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, sd.max_F) for sd in self.sides.values()) // 4),), f32)
         buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
         # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
         # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
@@ -103,9 +125,12 @@ class PlanBuilder:
         self.pair_ok = self.code == L.BF16 and not self.batch_red and sw.dw_pair and sw.gemm_dw
         # keep decisions of the attention-probability dropout: one bit tile set per attention site, written by the forward (generator
         # kernel in front of it), read by the backward (csrc/attention_fast.hip; 51 MB per site at B = 1024).  MMFM_ATTN_KEEPBITS=0: hash.
-        self.use_keep = self.code == L.BF16 and self.dp > 0 and self.grad and sw.attn_keepbits
+        # Per side: a side without dropout has no workspace, so its sites launch no generator
         fm = self.fm = e._fused_mask(R, sw)
-        self.F_QKV, self.F_LNL, self.F_MLP, self.F_OUT = bool(fm & 1), bool(fm & 2), bool(fm & 4), bool(fm & 8)
+        self.F_QKV, self.F_LNL, self.F_OUT = bool(fm & 1), bool(fm & 2), bool(fm & 8)
+        for name, sd in self.sides.items():
+            sd.use_keep = self.code == L.BF16 and sd.dp > 0 and self.grad and sw.attn_keepbits
+            sd.F_MLP = e.fused_mlp(name, fm)
         self.prep = e._build_prep() if fm else None
         if fm:
             K.prep_weights(self.prep["table"], self.prep["n"], self.prep["tiles"], plan=self.fwd)
@@ -273,9 +298,12 @@ class PlanBuilder:
                   ln_bwd=2 if self.e.is_sn(lnname) else 1, bwd_xhat=self.b[tag + "/xh"], bwd_rstd=self.b[tag + "/rs"], plan=plan)
 
     def attn_desc(self, tag, q, ldq, kv, ldkv, koff, voff, o, flags, d_o=None, dq=None, dkv=None, lddq=0, lddkv=0, dkoff=0, dvoff=0):
-        e, b, buf, B, heads, Lq, H, es, dp = self.e, self.b, self.buf, self.B, self.heads, self.Lq, self.H, self.es, self.dp
+        """The descriptor of attention site `tag` (`enc{i}/sa`, `dec{i}/sa`, `dec{i}/xa`): head count, head dim, dropout, the keep-bit
+        workspace and the LSE buffer are the site's side's - cross-attention splits the context's keys / values by the decoder's heads."""
+        e, b, buf, B, Lq, H, es, sd = self.e, self.b, self.buf, self.B, self.Lq, self.H, self.es, self.side(tag)
+        heads, dp = sd.heads, sd.dp
         dh = H // heads
-        keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if self.use_keep else None
+        keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if sd.use_keep else None
         return K.attn_desc(self.code, B, heads, Lq, Lq, dh, q.data_ptr(), kv.data_ptr() + koff * es, kv.data_ptr() + voff * es, ldq, ldkv, ldkv,
                            o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), torch.float32), b["keypad"], b["mod_id"], flags,
                            1.0 / math.sqrt(dh), drop_p=e._drop(tag + "/p", dp), drop_o=e._drop(tag + "/o", dp),
@@ -315,21 +343,22 @@ class PlanBuilder:
 
     def mlp_block(self, plan, X, p, tag):
         """x + mlp(ln2(x))  (encoder_embeddings.py:114; mm_utils.py:50-52)."""
-        e, c, buf, R, H, I, f32 = self.e, self.c, self.buf, self.R, self.H, self.I, torch.float32
+        e, buf, R, H, f32, sd = self.e, self.buf, self.R, self.H, torch.float32, self.side(p)
+        I, dp = sd.I, sd.dp
         Xb = buf(tag + "/xb", (R, H))
-        if self.F_MLP:
+        if sd.F_MLP:
             pu = self.prep["v"][p + ".mlp.up_proj"]
             d_ = K.mlp_desc(R, x=X, w_up=pu["Wp"], b_up=pu["bp"], w_down=self.prep["v"][p + ".mlp.down_proj"]["WpP"],
-                            b_down=e.Pb(p + ".mlp.down_proj"), drop=e._drop(tag + "/mlpdrop", self.dp), y=Xb,
+                            b_down=e.Pb(p + ".mlp.down_proj"), drop=e._drop(tag + "/mlpdrop", dp), y=Xb,
                             xhat=buf(tag + "/ln2/xh", (R, H)) if self.grad else None,
                             rstd=buf(tag + "/ln2/rs", (R,), f32) if self.grad else None, scalenorm=e.is_sn(p + ".ln2"),
-                            act=c.act[0], act_beta=c.act[1])
+                            act=sd.act[0], act_beta=sd.act[1])
             K.mlp_fwd(d_, plan=plan)
             return Xb
         h, u, g = buf(tag + "/h2", (R, H)), buf(tag + "/u", (R, I)), buf(tag + "/g", (R, I))
         self.ln_f(plan, X, p + ".ln2", h, tag + "/ln2")
-        self.lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=self.act_fwd, act_scale=c.act[1])
-        self.lin(plan, g, p + ".mlp.down_proj", Xb, R, H, I, drop=e._drop(tag + "/mlpdrop", self.dp), residual=X, ldr=H)
+        self.lin(plan, h, p + ".mlp.up_proj", g, R, I, H, pre_out=u, act=sd.act_fwd, act_scale=sd.act[1])
+        self.lin(plan, g, p + ".mlp.down_proj", Xb, R, H, I, drop=e._drop(tag + "/mlpdrop", dp), residual=X, ldr=H)
         return Xb
 
     # ------------------------------------------------------------------ forward
@@ -341,17 +370,18 @@ class PlanBuilder:
         tok_tmp = buf("tok_tmp", (BT, H))
         x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
         for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
+            sd = self.sides[side]
             for m, (mod, n) in enumerate(c.mods):
                 p = f"{side}_embeddings.{mod}.embedder"
-                n2 = n * c.mult
+                n2 = n * sd.mult
                 a = buf(f"{side}/a/{m}", (BT, n2))
                 # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
                 # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
                 z = None if self.code == L.BF16 else buf(f"{side}/z/{m}", (BT, n2))
-                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=L.ACT_SOFTSIGN, act_scale=c.embed_scale)
-                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", self.dpe))
+                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=L.ACT_SOFTSIGN, act_scale=sd.scale)
+                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe))
                 mod_row = e.Pf(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m]
-                K.stitch_fwd(tok_tmp, mod_row, e.Pf(p + ".pos_embed.weight"), b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, c.max_F, plan=fwd)
+                K.stitch_fwd(tok_tmp, mod_row, e.Pf(p + ".pos_embed.weight"), b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, sd.max_F, plan=fwd)
         X = x_enc
         for i in range(c.n_enc):
             p, tag = f"encoder.{i}", f"enc{i}"
@@ -407,15 +437,16 @@ class PlanBuilder:
 
     def mlp_back(self, plan, dS, p, tag, X_in):
         """dS: running gradient of the residual stream (in place).  X_in = the stream value that fed ln2."""
-        e, c, b, buf, R, H, I, dp = self.e, self.c, self.b, self.buf, self.R, self.H, self.I, self.dp
-        if self.F_MLP:
+        e, b, buf, R, H, sd = self.e, self.b, self.buf, self.R, self.H, self.side(p)
+        I, dp = sd.I, sd.dp
+        if sd.F_MLP:
             pu, pdn = self.prep["v"][p + ".mlp.up_proj"], self.prep["v"][p + ".mlp.down_proj"]
             t1b, gb, dub = buf("d/t1m", (R, H)), buf("d/g", (R, I)), buf("d/du", (R, I))
             # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step.  A ScaleNorm ln2 always splits (the one-launch kernel has no ScaleNorm epilogue)
             split = self.sw.mlp_bwd_split or e.is_sn(p + ".ln2")
             d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=e._drop(tag + "/mlpdrop", dp), xhat=b[tag + "/ln2/xh"],
                             rstd=b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
-                            dx=None if split else dS, scalenorm=e.is_sn(p + ".ln2"), act=c.act[0], act_beta=c.act[1])
+                            dx=None if split else dS, scalenorm=e.is_sn(p + ".ln2"), act=sd.act[0], act_beta=sd.act[1])
             K.mlp_bwd(d_, plan=plan)
             if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
                 self.dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
@@ -427,8 +458,9 @@ class PlanBuilder:
         if dp > 0:                                                       # mm_utils.py:52 dropout(down_proj(.))
             K.dropout_apply(dS, b["d/t1"], R, H, e._drop(tag + "/mlpdrop", dp), plan=plan)
             dSd = b["d/t1"]
-        self.dlin(plan, dSd, b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=b["d/u"], act=self.act_grad, act_scale=c.act[1], gradmul_pre=b[tag + "/u"])
-        self.norm_lin_back(plan, False, b["d/u"], I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", tag + "/h2", X_in, dS, dS)
+        du = self.rows(b["d/u"], R, I)
+        self.dlin(plan, dSd, b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, act=sd.act_grad, act_scale=sd.act[1], gradmul_pre=b[tag + "/u"])
+        self.norm_lin_back(plan, False, du, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", tag + "/h2", X_in, dS, dS)
 
     def norm_lin_back(self, plan, fused, dYt, N, tag, wname, lnname, hkey, X_in, dres, dXout):
         """Backward of a norm-fed linear [N, H] and its norm (input X_in; un-fused: normalised rows saved under `hkey`): the residual
@@ -472,7 +504,7 @@ class PlanBuilder:
     # ------------------------------------------------------------------ backward (segments fire DDP hooks)
     def backward(self):
         e, c, b, buf = self.e, self.c, self.b, self.buf
-        B, T, H, I, R, BT, Lq = self.B, self.T, self.H, self.I, self.R, self.BT, self.Lq
+        B, T, H, I, R, BT, Lq = self.B, self.T, self.H, self.Imax, self.R, self.BT, self.Lq
         dY, dydec = buf("d/stream", (R, H)), buf("d/ydec", (R, H))
         buf("d/t1", (R, H)); buf("d/t2", (R, H)); buf("d/h", (R, H)); buf("d/u", (R, I)); buf("d/qkv", (R, 3 * H)); dctx = buf("d/ctx", (R, H))
         ydec = b["ydec"]
@@ -503,19 +535,21 @@ class PlanBuilder:
             self.close_segment(p)
         # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds)
         for side, dS, dextra, acc_mod in (("decoder", dY, None, False), ("encoder", dX, dctx, True)):
+            sd = self.sides[side]
             for m, (mod, n) in enumerate(c.mods):
                 pS = f"{side}_embeddings.{mod}.embedder"
-                K.stitch_bwd(dS, dextra, b["ts"], b["keep0"], e._drop(f"{side}/embdrop/{m}", self.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
+                K.stitch_bwd(dS, dextra, b["ts"], b["keep0"], e._drop(f"{side}/embdrop/{m}", sd.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
                              e.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], e.Gv(pS + ".pos_embed.weight"),
-                             acc_mod, False, B, T, Lq, m, H, c.max_F, b["ws/stitch"], plan=self.cur)
+                             acc_mod, False, B, T, Lq, m, H, sd.max_F, b["ws/stitch"], plan=self.cur)
         bf16 = self.code == L.BF16       # the softsign gradient from the activation itself, or (fp32) from the saved pre-activation
         for side in ("decoder", "encoder"):
+            sd = self.sides[side]
             for m, (mod, n) in enumerate(c.mods):
                 p = f"{side}_embeddings.{mod}.embedder"
-                n2 = n * c.mult
-                dz = buf(f"d/z/{m}", (BT, n2))
+                n2 = n * sd.mult
+                dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)
                 self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
-                          act=L.ACT_SOFTSIGN_GRAD_OUT if bf16 else L.ACT_SOFTSIGN_GRAD, act_scale=c.embed_scale,
+                          act=L.ACT_SOFTSIGN_GRAD_OUT if bf16 else L.ACT_SOFTSIGN_GRAD, act_scale=sd.scale,
                           gradmul_pre=b[f"{side}/a/{m}" if bf16 else f"{side}/z/{m}"])
                 self.dlin(self.cur, dz, b[f"in/{m}"], p + ".token_embed", BT, n2, n, ldx=_align(n, 8))
         self.close_segment("embed")
