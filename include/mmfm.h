@@ -28,6 +28,10 @@ extern "C" {
  * mmfm_prep_entry, mmfm_rowgemm_desc, mmfm_mlp_desc, mmfm_ln_linear_grad and mmfm_sn_linear_grad hold.  No struct changed its layout and
  * no export was added, so MMFM_VERSION stays: a caller built against the earlier 401 header runs unchanged. */
 #define MMFM_NULL_BIAS 1
+/* Feature macro: the embedder options (embedder.act other than softsign, pos: false, bias: false).  With it defined mmfm_gemm takes the
+ * act codes 12 .. 25 (mmfm_gemm_desc), mmfm_stitch_fwd a NULL pos_emb and mmfm_stitch_bwd a NULL d_pos.  No struct changed its layout and
+ * no export was added: MMFM_VERSION stays, as for MMFM_NULL_BIAS. */
+#define MMFM_EMBED_OPTS 1
 /* activation kinds of mmfm_mlp_desc.act (the fused MLP's transformer.act) */
 #define MMFM_MLP_GELU 0        /* exact-erf GELU (bf16: the polynomial of act 1) */
 #define MMFM_MLP_RELU 1
@@ -76,6 +80,17 @@ int mmfm_rng_advance(void* state, mmfm_stream stream);
  *   act 10: v = 0.5 v (1 + tanh(k (v + 0.044715 v^3))), k = sqrt(2 / pi)  (gelu_new / gelu_pytorch_tanh / gelu_fast)
  *   act 11: v *= 0.5 (1 + t) + 0.5 u (1 - t^2) k (1 + 3 * 0.044715 u^2),  t = tanh(k (u + 0.044715 u^3))
  *   Evaluated with the hardware exp / reciprocal, tanh-GELU as u * sigmoid(2 k (u + 0.044715 u^3)) (error bounds).
+ *   Embedder activations (embedder.act other than softsign; MMFM_EMBED_OPTS), forward / gradient pairs.  act_scale is the embedder's
+ *   `scale` in every one of them (acts 8 / 9 spend it on beta, hence the two sigmoid gates are codes of their own):
+ *     forward (even)   v = f(v) * act_scale
+ *     gradient (odd)   v *= f'(u) * act_scale,  u = gradmul_pre[m*ldc+n] the pre-activation the forward stored via pre_out
+ *   act 12 / 13: f = identity (`identity`, `linear`); 13 reads no gradmul_pre (it may be NULL)
+ *   act 14 / 15: relu                                act 16 / 17: GELU (erf in fp32, the polynomial of act 1 / 3 in bf16)
+ *   act 18 / 19: v sigmoid(v) (silu / swish)         act 20 / 21: v sigmoid(1.702 v) (quick_gelu)
+ *   act 22 / 23: tanh-GELU (as act 10 / 11)          act 24 / 25: tanh, f' = 1 - tanh^2
+ *   The same device functions as acts 1 / 3 / 6-11; tanh as (1 - e) / (1 + e), e = exp(-2 |v|) (ranges and error bounds).
+ *   Not built: gradients of tanh / relu from the activation's output (as act 5 does for softsign), sigmoid, mish, leaky_relu and the
+ *   other ACT2FN names.
  *   v = dropout(v) (counter m*N+n);  v += residual[m*ldr+n];  C[m*ldc+n] = v
  */
 typedef struct {
@@ -237,7 +252,9 @@ int mmfm_mask_prep(int B, int T, int M, const int64_t* const* mask_src, const in
  *   emb[b, m*T+t] = mod_emb[mod_row] + pos_emb[ts[b][t]]
  *   x  [b, m*T+t] = keep0[m*T+t] * tok[b*T+t] + emb[...]
  * called once per modality m; tok is [B*T][H]; x/emb are [B][L][H]; emb may be NULL; pos_emb has
- * max_F rows (time stamps are clamped into [0, max_F) for memory safety). */
+ * max_F rows (time stamps are clamped into [0, max_F) for memory safety).
+ * pos_emb == NULL (embedder.pos: false, MMFM_EMBED_OPTS): emb = mod_emb[mod_row], the same row for every token; ts may be passed and
+ * is not read (it may be NULL too). */
 int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb,
                     const int64_t* ts, const uint8_t* keep0, void* x, void* emb,
                     int B, int T, int L, int m, int H, int max_F, mmfm_stream stream);
@@ -247,7 +264,10 @@ int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const 
  * modality embedding is shared by the encoder and decoder tokenisers, mm.py:84-87, the position
  * tables are not).  Deterministic (no atomics): fp32 mode scatters through per-column LDS tables and reduces the
  * per-chunk partials; bf16 mode (H % 8 == 0) multiplies by a one-hot matrix on the MFMA GEMM ([d_pos; d_mod] = OH^T E,
- * split-K slabs, fixed-order reduction). */
+ * split-K slabs, fixed-order reduction).
+ * d_pos == NULL (embedder.pos: false, MMFM_EMBED_OPTS): d_tok and d_mod_row only; ts is not read, acc_pos is ignored.  fp32 mode runs without
+ * the LDS tables; in bf16 mode the one-hot product degenerates to a column sum over the modality's rows (per-sample-range slabs, summed in
+ * a fixed order: deterministic, no atomics).  Both stay within mmfm_stitch_bwd_workspace(...), which is the same for either form. */
 int64_t mmfm_stitch_bwd_workspace(int dtype, int B, int T, int L, int H, int max_F);
 int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
                     mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,

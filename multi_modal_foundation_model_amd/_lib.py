@@ -23,6 +23,9 @@ ATTN_DIAG, ATTN_CAUSAL, ATTN_SEP = 1, 2, 4
 ACT_NONE, ACT_GELU, ACT_SOFTSIGN, ACT_GELU_GRAD, ACT_SOFTSIGN_GRAD, ACT_SOFTSIGN_GRAD_OUT = 0, 1, 2, 3, 4, 5
 # the other MLP activations (transformer.act): forward / gradient pairs; the sigmoid kind takes beta in act_scale
 ACT_RELU, ACT_RELU_GRAD, ACT_SIGMOID, ACT_SIGMOID_GRAD, ACT_GELU_TANH, ACT_GELU_TANH_GRAD = 6, 7, 8, 9, 10, 11
+# the embedder activations (embedder.act other than softsign): forward / gradient pairs, act_scale = the embedder's scale in all of them
+(ACT_EMB_IDENTITY, ACT_EMB_IDENTITY_GRAD, ACT_EMB_RELU, ACT_EMB_RELU_GRAD, ACT_EMB_GELU, ACT_EMB_GELU_GRAD, ACT_EMB_SILU, ACT_EMB_SILU_GRAD,
+ ACT_EMB_QUICK_GELU, ACT_EMB_QUICK_GELU_GRAD, ACT_EMB_GELU_TANH, ACT_EMB_GELU_TANH_GRAD, ACT_EMB_TANH, ACT_EMB_TANH_GRAD) = range(12, 26)
 # mmfm_mlp_desc.act (MMFM_MLP_*)
 MLP_GELU, MLP_RELU, MLP_SIGMOID, MLP_GELU_TANH = 0, 1, 2, 3
 # masked-loss kinds (MMFM_LOSS_*) and the PoissonNLLLoss(full=True) flag

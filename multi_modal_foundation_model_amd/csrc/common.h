@@ -262,8 +262,10 @@ template <> struct ActAcc<MMFM_MLP_GELU_TANH> {
         return fmaf(2.f * kGeluTanhK * x * h * (1.f - h), fmaf(3.f * kGeluTanhC, x2, 1.f), h);
     }
 };
-// mmfm_gemm act 6 / 7 -> MMFM_MLP_RELU, 8 / 9 -> _SIGMOID, 10 / 11 -> _GELU_TANH (0 for every other act)
-__host__ __device__ __forceinline__ int gemm_act_kind(int act) { return act >= 6 ? (act - 4) >> 1 : 0; }
+// mmfm_gemm act 6 / 7 -> MMFM_MLP_RELU, 8 / 9 -> _SIGMOID, 10 / 11 -> _GELU_TANH, 12 .. 25 (the embedder activations, below) -> kActEmbed
+// (0 for every other act)
+constexpr int kActEmbed = 4, kActEmbedFirst = 12, kActEmbedLast = 25, kActEmbedIdentityGrad = 13;
+__host__ __device__ __forceinline__ int gemm_act_kind(int act) { return act >= kActEmbedFirst ? kActEmbed : (act >= 6 ? (act - 4) >> 1 : 0); }
 
 // bf16-mode (packed, fast) forms: sigmoid(z) = 1 / (1 + 2^(-z log2 e)) through v_exp_f32 and v_rcp_f32 (1 ulp each); 2^x overflows to inf
 // or underflows to 0 at the ends and rcp(inf) = 0, so s is exactly 0 or 1 there.  tanh-GELU uses 0.5 (1 + tanh(z)) = sigmoid(2 z) and
@@ -349,6 +351,85 @@ __device__ __forceinline__ float softsign_grad(float x) { float d = 1.f + fabsf(
 // an absolute error of up to 2^-9 and the factor r^2 a RELATIVE error of about 0.6 % x (1 + |x|) - 5 % at |x| = 8, the whole value beyond |x| ~ 170
 // (y rounds to s, the gradient reads 0 where the true factor is < 4e-5).  Spike-count pre-activations of the tokenisers sit at |x| of a few units.
 __device__ __forceinline__ float softsign_grad_from_out(float y, float inv_s) { const float r = 1.f - fabsf(y) * inv_s; return r * r; }
+
+// ---- the embedder activations (embedder.act other than softsign): mmfm_gemm act 12 .. 25, forward (even) / gradient (odd) pairs
+//   forward  v = f(v) * act_scale            gradient  v *= f'(u) * act_scale,  u = the saved pre-activation (gradmul_pre)
+// f = (act - 12) >> 1:  0 identity (its gradient reads no u), 1 relu, 2 GELU (erf in fp32, the polynomial in bf16, as act 1 / 3),
+// 3 u sigmoid(u) (silu / swish), 4 u sigmoid(1.702 u) (quick_gelu), 5 tanh-GELU, 6 tanh.  act_scale is the embedder's `scale` - acts 6-11
+// spend it on beta - so the two sigmoid gates are codes of their own.  All of them run in ONE kernel instantiation per site (template
+// kind kActEmbed, the function picked by a wave-uniform switch, embed_dispatch): the kernels of every other act keep their code.  They are the functions
+// of acts 1 / 3 / 6-11; only tanh is new: (1 - e) / (1 + e), e = exp(-2 |u|) (fp32 kernels; absolute error ~1e-7) and 2 sigmoid(2 u) - 1
+// in the packed bf16 forms, tanh' = 1 - t^2 = 4 h (1 - h), h = sigmoid(2 u): e / h saturate to exactly 0 / 1, no clamp is needed.
+__device__ __forceinline__ float tanh_acc(float x) {
+    const float e = __expf(-2.f * fabsf(x));
+    return copysignf((1.f - e) * __builtin_amdgcn_rcpf(1.f + e), x);
+}
+// F is a compile-time constant inside the epilogues: embed_dispatch turns the wave-uniform act code into it ONCE per epilogue, outside the
+// unrolled element loops (a switch inside them keeps hipcc from unrolling, and the accumulators it then indexes go to scratch)
+template <int F> struct EmbedF { static constexpr int value = F; };
+template <typename Fn> __device__ __forceinline__ void embed_dispatch(int act, Fn&& fn) {
+    switch ((act - kActEmbedFirst) >> 1) {
+    case 0: fn(EmbedF<0>{}); break;
+    case 1: fn(EmbedF<1>{}); break;
+    case 2: fn(EmbedF<2>{}); break;
+    case 3: fn(EmbedF<3>{}); break;
+    case 4: fn(EmbedF<4>{}); break;
+    case 5: fn(EmbedF<5>{}); break;
+    default: fn(EmbedF<6>{}); break;
+    }
+}
+template <int F> constexpr float embed_beta() { return F == 4 ? 1.702f : 1.f; }
+template <bool POLY, int F> __device__ __forceinline__ float embed_act1(float v) {
+    if constexpr (F == 0) return v;
+    else if constexpr (F == 1) return fmaxf(v, 0.f);
+    else if constexpr (F == 2) return POLY ? gelu_poly(v) : gelu_erf(v);
+    else if constexpr (F == 3 || F == 4) return ActAcc<MMFM_MLP_SIGMOID>::f(v, embed_beta<F>());
+    else if constexpr (F == 5) return ActAcc<MMFM_MLP_GELU_TANH>::f(v, 1.f);
+    else return tanh_acc(v);
+}
+// v * f'(u) (relu: a select, as torch's threshold backward; identity reads no u)
+template <bool POLY, int F> __device__ __forceinline__ float embed_mul_grad1(float v, float u) {
+    if constexpr (F == 0) return v;
+    else if constexpr (F == 1) return u > 0.f ? v : 0.f;
+    else if constexpr (F == 2) return v * (POLY ? gelu_poly_grad(u) : gelu_erf_grad(u));
+    else if constexpr (F == 3 || F == 4) return v * ActAcc<MMFM_MLP_SIGMOID>::grad(u, embed_beta<F>());
+    else if constexpr (F == 5) return v * ActAcc<MMFM_MLP_GELU_TANH>::grad(u, 1.f);
+    else { const float t = tanh_acc(u); return v * fmaf(-t, t, 1.f); }
+}
+// the packed bf16-mode forms on an even-length array: v = f(v) * s in place / v *= f'(u) * s
+template <int N, int F> __device__ __forceinline__ void embed_act_n(float* v, float s) {
+    if constexpr (F == 1) mlp_act_n<MMFM_MLP_RELU, N>(v, 1.f);
+    else if constexpr (F == 2) gelu_n<N>(v);
+    else if constexpr (F == 3 || F == 4) mlp_act_n<MMFM_MLP_SIGMOID, N>(v, embed_beta<F>());
+    else if constexpr (F == 5) mlp_act_n<MMFM_MLP_GELU_TANH, N>(v, 1.f);
+    else if constexpr (F == 6) {
+#pragma unroll
+        for (int i = 0; i < N; i += 2) {
+            mmfm_f32x2 a; a.x = v[i]; a.y = v[i + 1];
+            a = __builtin_elementwise_fma(sigmoid2(a * splat2(2.f)), splat2(2.f), splat2(-1.f));
+            v[i] = a.x; v[i + 1] = a.y;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] *= s;
+}
+template <int N, int F> __device__ __forceinline__ void embed_mul_grad_n(float* v, const float* u, float s) {
+    if constexpr (F == 1) mul_mlp_act_grad_n<MMFM_MLP_RELU, N>(v, u, 1.f);
+    else if constexpr (F == 2) mul_gelu_grad_n<N>(v, u);
+    else if constexpr (F == 3 || F == 4) mul_mlp_act_grad_n<MMFM_MLP_SIGMOID, N>(v, u, embed_beta<F>());
+    else if constexpr (F == 5) mul_mlp_act_grad_n<MMFM_MLP_GELU_TANH, N>(v, u, 1.f);
+    else if constexpr (F == 6) {
+#pragma unroll
+        for (int i = 0; i < N; i += 2) {
+            mmfm_f32x2 a; a.x = u[i]; a.y = u[i + 1];
+            const mmfm_f32x2 h = sigmoid2(a * splat2(2.f));
+            a = splat2(4.f) * h * (splat2(1.f) - h);
+            v[i] *= a.x; v[i + 1] *= a.y;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] *= s;
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

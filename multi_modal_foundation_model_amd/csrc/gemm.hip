@@ -87,21 +87,31 @@ __device__ __forceinline__ void r2s(float* __restrict__ S, const float4 (&r)[4],
     }
 }
 
-// ---- fused epilogue for one element.  AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; every
-// other act runs the AK = 0 kernels, whose code does not change with them
-template <typename TO, int AK = 0>
+// ---- fused epilogue for one element.  AK: the MLP activation kind of act 6-11, or kActEmbed for the embedder activations 12-25
+// (gemm_act_kind), one instantiation per kind; every other act runs the AK = 0 kernels, whose code does not change with them
+template <typename TO, int AK = 0, int EF = 0>
 __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Drop& dr, float v, int m, int n) {
     typedef io<TO> O;
+    constexpr int AKM = (AK && AK != kActEmbed) ? AK : MMFM_MLP_RELU;      // the ActAcc the MLP-kind branches name (dead code in the other kernels)
     if (d.bias) v += d.bias[n];
     if (d.pre_out) O::st(reinterpret_cast<TO*>(d.pre_out) + (size_t)m * d.ldc + n, v);
+    if constexpr (AK == kActEmbed) {
+        if (!(d.act & 1)) v = embed_act1<false, EF>(v) * d.act_scale;                    // EF: the embedder function, embed_dispatch
+        else if (EF == 0) v *= d.act_scale;
+        else v = embed_mul_grad1<false, EF>(v, O::ld(reinterpret_cast<const TO*>(d.gradmul_pre) + (size_t)m * d.ldc + n)) * d.act_scale;
+        v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
+        if (d.residual) v += O::ld(reinterpret_cast<const TO*>(d.residual) + (size_t)m * d.ldr + n);
+        O::st(reinterpret_cast<TO*>(d.C) + (size_t)m * d.ldc + n, v);
+        return;
+    }
     if (d.act == 1) v = gelu_erf(v);
     else if (d.act == 2) v = softsign_f(v) * d.act_scale;
-    else if (AK && !(d.act & 1)) v = ActAcc<AK ? AK : MMFM_MLP_RELU>::f(v, d.act_scale);
+    else if (AK && !(d.act & 1)) v = ActAcc<AKM>::f(v, d.act_scale);
     if (d.gradmul_pre) {
         const float u = O::ld(reinterpret_cast<const TO*>(d.gradmul_pre) + (size_t)m * d.ldc + n);
         // act kinds 3/4 = multiply by gelu'(u) / softsign'(u)*scale (backward through the activation); 7/9/11 the MLP activations'
         if (AK == MMFM_MLP_RELU) v = u > 0.f ? v : 0.f;          // a select, as torch's threshold backward
-        else if (AK) v *= ActAcc<AK ? AK : MMFM_MLP_RELU>::grad(u, d.act_scale);
+        else if (AK) v *= ActAcc<AKM>::grad(u, d.act_scale);
         else v *= (d.act == 3) ? gelu_erf_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
     }
     v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
@@ -181,6 +191,21 @@ __global__ __launch_bounds__(NTHREADS) void gemm_f32_kernel(const mmfm_gemm_desc
         return;
     }
     const Drop dr = drop_init(d.drop);
+    if constexpr (AK == kActEmbed) {
+        embed_dispatch(d.act, [&](auto F) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                        const int n = n0 + wn * 64 + j * 32 + l31;
+                        if (m < d.M && n < d.N) epilogue_store<float, AK, decltype(F)::value>(d, dr, acc[i][j][r], m, n);
+                    }
+        });
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -310,12 +335,13 @@ static int gemm_check(const mmfm_gemm_desc* dp, mmfm_gemm_desc& d) {
     MMFM_REQUIRE(d.ldb >= (d.b_kcontig ? d.K : d.N), "mmfm_gemm: ldb %d too small", d.ldb);
     MMFM_REQUIRE(d.ldc >= d.N, "mmfm_gemm: ldc %d < N %d", d.ldc, d.N);
     MMFM_REQUIRE(!(d.a_kcontig == 0 && d.b_kcontig == 1), "mmfm_gemm: layout (A row-contig, B k-contig) is not built");
-    MMFM_REQUIRE(d.act >= 0 && d.act <= 11, "mmfm_gemm: bad act %d", d.act);
-    // gradient kinds: 3, 4, 5 and the odd codes from 7 on
+    MMFM_REQUIRE(d.act >= 0 && d.act <= kActEmbedLast, "mmfm_gemm: bad act %d", d.act);
+    // gradient kinds: 3, 4, 5 and the odd codes from 7 on; 13 (the embedder's identity) is the one that reads no pre-activation
     const bool grad_act = (d.act >= 3 && d.act <= 5) || (d.act >= 7 && (d.act & 1));
     MMFM_REQUIRE(!d.gradmul_pre || grad_act,
-                 "mmfm_gemm: gradmul_pre needs a gradient act (3 gelu', 4 softsign', 5 softsign' from the output, 7 relu', 9 sigmoid-gate', 11 tanh-gelu')");
-    MMFM_REQUIRE(d.gradmul_pre || !grad_act, "mmfm_gemm: act %d needs gradmul_pre", d.act);
+                 "mmfm_gemm: gradmul_pre needs a gradient act (3 gelu', 4 softsign', 5 softsign' from the output, 7 relu', 9 sigmoid-gate', 11 tanh-gelu', "
+                 "the embedder's 13 identity', 15 relu', 17 gelu', 19 silu', 21 quick_gelu', 23 tanh-gelu', 25 tanh')");
+    MMFM_REQUIRE(d.gradmul_pre || !grad_act || d.act == kActEmbedIdentityGrad, "mmfm_gemm: act %d needs gradmul_pre", d.act);
     if (d.splits <= 1) {
         d.splits = 1;
         d.kchunk = d.K;
@@ -351,6 +377,7 @@ extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
     case MMFM_MLP_RELU: { F32_LAUNCH(MMFM_MLP_RELU) } break;
     case MMFM_MLP_SIGMOID: { F32_LAUNCH(MMFM_MLP_SIGMOID) } break;
     case MMFM_MLP_GELU_TANH: { F32_LAUNCH(MMFM_MLP_GELU_TANH) } break;
+    case kActEmbed: { F32_LAUNCH(kActEmbed) } break;                // the embedder activations 12-25
     default: { F32_LAUNCH(0) }
     }
 #undef F32_LAUNCH

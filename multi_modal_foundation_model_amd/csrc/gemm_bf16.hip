@@ -111,20 +111,30 @@ __device__ __forceinline__ bf16x8v frag(const char* __restrict__ S, int rowbase,
     }
 }
 
-// AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; the AK = 0 kernels run every other act, and
-// their code does not change with these
-template <typename TO, int AK = 0>
+// AK: the MLP activation kind of act 6-11, or kActEmbed for the embedder activations 12-25 (gemm_act_kind), one instantiation per kind;
+// the AK = 0 kernels run every other act, and their code does not change with these
+template <typename TO, int AK = 0, int EF = 0>
 __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Drop& dr, float v, int m, int n) {
     typedef io<uint16_t> I16;
+    constexpr int AKM = AK == kActEmbed ? 0 : AK;           // the MlpAct the MLP-kind branches name (dead code in the kActEmbed kernels)
     if (d.bias) v += d.bias[n];
     if (d.pre_out) I16::st(reinterpret_cast<uint16_t*>(d.pre_out) + (size_t)m * d.ldc + n, v);
+    if constexpr (AK == kActEmbed) {                          // the embedder activations 12-25 (common.h)
+        if (!(d.act & 1)) v = embed_act1<true, EF>(v) * d.act_scale;                     // EF: the embedder function, embed_dispatch
+        else if (EF == 0) v *= d.act_scale;
+        else v = embed_mul_grad1<true, EF>(v, I16::ld(reinterpret_cast<const uint16_t*>(d.gradmul_pre) + (size_t)m * d.ldc + n)) * d.act_scale;
+        v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
+        if (d.residual) v += I16::ld(reinterpret_cast<const uint16_t*>(d.residual) + (size_t)m * d.ldr + n);
+        io<TO>::st(reinterpret_cast<TO*>(d.C) + (size_t)m * d.ldc + n, v);
+        return;
+    }
     if (d.act == 1) v = gelu_poly(v);
     else if (d.act == 2) v = softsign_f(v) * d.act_scale;
-    else if (AK && !(d.act & 1)) v = mlp_act1<AK>(v, d.act_scale);
+    else if (AK && !(d.act & 1)) v = mlp_act1<AKM>(v, d.act_scale);
     if (d.gradmul_pre) {
         const float u = I16::ld(reinterpret_cast<const uint16_t*>(d.gradmul_pre) + (size_t)m * d.ldc + n);
         if (AK == MMFM_MLP_RELU) v = u > 0.f ? v : 0.f;          // a select, as torch's threshold backward
-        else if (AK) v *= mlp_act_grad1<AK>(u, d.act_scale);
+        else if (AK) v *= mlp_act_grad1<AKM>(u, d.act_scale);
         else v *= (d.act == 3) ? gelu_poly_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
     }
     v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
@@ -175,13 +185,14 @@ __device__ __forceinline__ void stg8(uint16_t* p, uint4 v, bool a16, bool hi, bo
 
 // EPI_LOADS = false: the instantiation of the persistent bf16-output kernel, launched only without a saved pre-activation /
 // residual operand (their registers would sit on top of the next tile's prefetched slice)
-template <typename TO, bool EPI_LOADS = true, int AK = 0>
+template <typename TO, bool EPI_LOADS = true, int AK = 0, int EF = 0>
 __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&acc)[2][2], char* smem, int m0, int n0, int z, int vec_epi,
                                               int t, int wm, int wn, int kh, int l31) {
     // ---- epilogue.  Fast path (row-aligned shapes): the fp32 tile is staged through LDS half a tile at a time
     // (64 rows x 128 cols x 4 B = 32 KB, reusing the operand buffers) so that each thread owns 8 consecutive
     // columns of a row: bias/pre-activation/residual/output move as 16-B (bf16) or 2x16-B (fp32) accesses.
     const bool split = d.splits > 1;
+    constexpr int AKM = AK == kActEmbed ? 0 : AK;           // as in epilogue_store
     float* Cf = reinterpret_cast<float*>(d.C) + (split ? (size_t)z * d.slab_stride : 0);
     const Drop dr = drop_init(d.drop);
     if (vec_epi & 1) {
@@ -253,19 +264,26 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
                     continue;
                 }
                 if (d.pre_out) stg8(reinterpret_cast<uint16_t*>(d.pre_out) + off, __builtin_bit_cast(uint4, pack8f(v)), a16, hi, (vec_epi & 8192) != 0);
-                if (d.act == 1) gelu_n<8>(v);
+                if constexpr (AK == kActEmbed) {              // the embedder activations 12-25 (13, identity', has no gradmul_pre: gu = 0)
+                    if (!(d.act & 1)) embed_act_n<8, EF>(v, d.act_scale);
+                    else {
+                        float u[8];
+                        unpack8(gu[c], u);
+                        embed_mul_grad_n<8, EF>(v, u, d.act_scale);
+                    }
+                } else if (d.act == 1) gelu_n<8>(v);
                 else if (d.act == 2) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = softsign_f(v[e]) * d.act_scale;
                 } else if (AK && !(d.act & 1)) mlp_act_n<AK, 8>(v, d.act_scale);
-                if (EPI_LOADS && d.gradmul_pre) {
+                if (AK != kActEmbed && EPI_LOADS && d.gradmul_pre) {
                     float u[8];
                     unpack8(gu[c], u);
                     if (d.act == 3) mul_gelu_grad_n<8>(v, u);
                     else if (d.act == 4) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] *= softsign_grad(u[e]) * d.act_scale;
-                    } else if (AK) mul_mlp_act_grad_n<AK, 8>(v, u, d.act_scale);
+                    } else if (AK) mul_mlp_act_grad_n<AKM, 8>(v, u, d.act_scale);
                     else {
                         const float inv_s = 1.f / d.act_scale;
 #pragma unroll
@@ -309,7 +327,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const int n = n0 + wn * 64 + j * 32 + l31;
-                if (m < d.M && n < d.N) epilogue_store<TO, AK>(d, dr, acc[i][j][r], m, n);
+                if (m < d.M && n < d.N) epilogue_store<TO, AK, EF>(d, dr, acc[i][j][r], m, n);
             }
 }
 
@@ -420,7 +438,12 @@ __global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(c
                 d.colsum[(d.splits > 1 ? (size_t)z * d.slab_stride : 0) + m0 + t] = sum;
             }
         }
-        epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
+        if constexpr (AK == kActEmbed)             // the embedder activations: one epilogue per function, picked once per tile
+            embed_dispatch(d.act, [&](auto F) {
+                epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK, decltype(F)::value>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
+            });
+        else
+            epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
         if (!more) break;
         w = wn_; m0 = m0n; n0 = n0n; z = zn; kbeg = kbegn; kend = kendn;
     }
@@ -493,6 +516,7 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     if (ak == MMFM_MLP_RELU) { LAUNCH_AK(ARC, BRC, MMFM_MLP_RELU) }                                                \
     else if (ak == MMFM_MLP_SIGMOID) { LAUNCH_AK(ARC, BRC, MMFM_MLP_SIGMOID) }                                     \
     else if (ak == MMFM_MLP_GELU_TANH) { LAUNCH_AK(ARC, BRC, MMFM_MLP_GELU_TANH) }                                 \
+    else if (ak == kActEmbed) { LAUNCH_AK(ARC, BRC, kActEmbed) }                                                   \
     else if (BKsel == 128) { LAUNCH2(ARC, BRC, 128) } else { LAUNCH2(ARC, BRC, 64) }
     if (d.a_kcontig && d.b_kcontig) { LAUNCH(false, false) }
     else if (d.a_kcontig && !d.b_kcontig) { LAUNCH(false, true) }

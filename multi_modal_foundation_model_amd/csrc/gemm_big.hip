@@ -66,8 +66,8 @@ __device__ __forceinline__ void issue_ktile(char* buf, const uint16_t* const (&p
 #define LDS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define LDS_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
-// AK: the MLP activation kind of act 6-11 (gemm_act_kind), one instantiation per kind; the AK = 0 kernel runs every other act, and
-// its code does not change with these
+// AK: the MLP activation kind of act 6-11, or kActEmbed for the embedder activations 12-25 (gemm_act_kind), one instantiation per kind;
+// the AK = 0 kernel runs every other act, and its code does not change with these
 template <int AK = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -201,7 +201,24 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
                     if (a.nt_pre) flush_lines<true>(stg, Pb, wrow0, ldcb, (uint32_t)ncol0 * 2u, lane, nchunk);
                     else flush_lines<false>(stg, Pb, wrow0, ldcb, (uint32_t)ncol0 * 2u, lane, nchunk);
                 }
-                if (d.act == 1) { gelu16(acc[2 * ip][j]); gelu16(acc[2 * ip + 1][j]); }
+                if constexpr (AK == kActEmbed) {                  // the embedder activations 12-25 (common.h)
+                    const bool fwd = !(d.act & 1), pre = !fwd && d.act != kActEmbedIdentityGrad;
+                    if (pre) stage_lines(stg, fetch_lines(Gb, wrow0, ldcb, (uint32_t)ncol0 * 2u, lane), lane);
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        float uu[16], vv[16];
+                        f32x16& v = acc[2 * ip + e][j];
+                        const f32x16 u = pre ? unstage_tile(stg, e, m, h) : zero16();
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) { uu[r] = u[r]; vv[r] = v[r]; }
+                        embed_dispatch(d.act, [&](auto F) {
+                            if (fwd) embed_act_n<16, decltype(F)::value>(vv, d.act_scale);
+                            else embed_mul_grad_n<16, decltype(F)::value>(vv, uu, d.act_scale);
+                        });
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) v[r] = vv[r];
+                    }
+                } else if (d.act == 1) { gelu16(acc[2 * ip][j]); gelu16(acc[2 * ip + 1][j]); }
                 else if (d.act == 2) {
 #pragma unroll
                     for (int e = 0; e < 2; ++e)
@@ -308,6 +325,7 @@ int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     const void* kern = ak == MMFM_MLP_RELU ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_RELU>)
                      : ak == MMFM_MLP_SIGMOID ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_SIGMOID>)
                      : ak == MMFM_MLP_GELU_TANH ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_GELU_TANH>)
+                     : ak == kActEmbed ? reinterpret_cast<const void*>(gemm_big_kernel<kActEmbed>)
                      : reinterpret_cast<const void*>(gemm_big_kernel<0>);
     if (int rc = mmfm_lds_opt_in(kern, LDS_ALL, "mmfm_gemm(bf16, 256 tile)")) return rc;
     static const int nt_env = [] { const char* e = getenv("MMFM_GEMM_NT"); return e ? atoi(e) : 3; }();
@@ -321,6 +339,7 @@ int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     if (ak == MMFM_MLP_RELU) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_RELU>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
     else if (ak == MMFM_MLP_SIGMOID) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_SIGMOID>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
     else if (ak == MMFM_MLP_GELU_TANH) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_GELU_TANH>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    else if (ak == kActEmbed) hipLaunchKernelGGL(gemm_big_kernel<kActEmbed>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
     else hipLaunchKernelGGL(gemm_big_kernel<0>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
     MMFM_LAUNCH_CHECK("mmfm_gemm(bf16, 256 tile)");
     return 0;

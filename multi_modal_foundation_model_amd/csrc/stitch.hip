@@ -64,9 +64,12 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
         const int b = (int)(r / Tn), t = (int)(r % Tn);
         const int l = m * Tn + t;
         const float4 mr = *reinterpret_cast<const float4*>(mod_row + c);
-        const int tsv = (int)min((int64_t)(max_F - 1), max((int64_t)0, ts[r]));     // memory-safe even for bad stamps
-        const float4 pr = *reinterpret_cast<const float4*>(pos + (size_t)tsv * H + c);
-        float4 e = make_float4(mr.x + pr.x, mr.y + pr.y, mr.z + pr.z, mr.w + pr.w);
+        float4 e = mr;                                  // pos == NULL (embedder.pos: false): the modality row alone, ts is not read
+        if (pos) {
+            const int tsv = (int)min((int64_t)(max_F - 1), max((int64_t)0, ts[r]));     // memory-safe even for bad stamps
+            const float4 pr = *reinterpret_cast<const float4*>(pos + (size_t)tsv * H + c);
+            e = make_float4(mr.x + pr.x, mr.y + pr.y, mr.z + pr.z, mr.w + pr.w);
+        }
         const size_t o = ((size_t)b * L + l) * H + c;
         if (emb) io<T>::st4(emb + o, e);
         if (keep0[l]) {
@@ -77,8 +80,9 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
     }
 }
 
-// block = CW threads (one column each); grid = (H/CW, nchunks); LDS table [max_F][CW]
-template <typename T>
+// block = CW threads (one column each); grid = (H/CW, nchunks); LDS table [max_F][CW].  POS = false (d_pos == NULL, embedder.pos: false):
+// no table, no time stamps - a chunk's partial is its d_mod row alone (the caller passes max_F = 0)
+template <typename T, bool POS>
 __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict__ dextra, const int64_t* __restrict__ ts,
                                   const uint8_t* __restrict__ keep0, mmfm_dropout dropa, T* __restrict__ d_tok,
                                   float* __restrict__ part, int B, int Tn, int L, int m, int H, int max_F, int bper) {
@@ -96,8 +100,10 @@ __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict_
             float e = g;
             if (dextra) e += io<T>::ld(dextra + o);
             const int64_t r = (int64_t)b * Tn + t;
-            const int tsv = (int)min((int64_t)(max_F - 1), max((int64_t)0, ts[r]));
-            tab[tsv * CW + j] += e;                   // a thread owns its column: no race, fixed order
+            if (POS) {
+                const int tsv = (int)min((int64_t)(max_F - 1), max((int64_t)0, ts[r]));
+                tab[tsv * CW + j] += e;               // a thread owns its column: no race, fixed order
+            }
             macc += e;
             if (d_tok) io<T>::st(d_tok + (size_t)r * H + col, keep0[l] ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
         }
@@ -128,6 +134,39 @@ __global__ __launch_bounds__(256) void onehot_kernel(const int64_t* __restrict__
                 if (c0 + j == tsv || c0 + j == max_F) w[j >> 1] |= 0x3F80u << (16 * (j & 1));      // bf16 1.0
         }
         *reinterpret_cast<uint4*>(oh + row * ohc + c0) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// ---- bf16 path without a position table (d_pos == NULL): OH has the one column of ones, the product is the column sum of the modality's
+// rows of E = dx + dextra.  grid (ceil(H / 256), S): slab s sums the rows (b, t) of samples [s * bper, (s + 1) * bper) - a thread owns 4
+// columns, the block's 4 row lanes meet in LDS in a fixed order - and mmfm_reduce_slabs adds the S slabs: deterministic, no atomics.
+__global__ __launch_bounds__(256) void stitch_modsum_kernel(const uint16_t* __restrict__ dx, const uint16_t* __restrict__ dextra,
+                                                            float* __restrict__ part, int B, int Tn, int L, int m, int H, int bper) {
+    __shared__ float4 red[4][64];
+    const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int c = blockIdx.x * 256 + lane * 4;
+    const int b0 = blockIdx.y * bper, b1 = min(B, b0 + bper);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < H) {
+        for (int64_t r = (int64_t)b0 * Tn + rl; r < (int64_t)b1 * Tn; r += 4) {
+            const size_t o = ((size_t)(r / Tn) * L + (size_t)m * Tn + (size_t)(r % Tn)) * H + c;
+            float4 e = io<uint16_t>::ld4(dx + o);
+            if (dextra) {
+                const float4 x = io<uint16_t>::ld4(dextra + o);
+                e.x += x.x; e.y += x.y; e.z += x.z; e.w += x.w;
+            }
+            acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += e.w;
+        }
+    }
+    red[rl][lane] = acc;
+    __syncthreads();
+    if (rl == 0 && c < H) {
+        float4 o;
+        o.x = (red[0][lane].x + red[1][lane].x) + (red[2][lane].x + red[3][lane].x);
+        o.y = (red[0][lane].y + red[1][lane].y) + (red[2][lane].y + red[3][lane].y);
+        o.z = (red[0][lane].z + red[1][lane].z) + (red[2][lane].z + red[3][lane].z);
+        o.w = (red[0][lane].w + red[1][lane].w) + (red[2][lane].w + red[3][lane].w);
+        *reinterpret_cast<float4*>(part + (size_t)blockIdx.y * H + c) = o;
     }
 }
 
@@ -265,7 +304,7 @@ extern "C" int mmfm_collate_csr(int B, int max_T, int max_N, float pad_value, co
 
 extern "C" int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
                                const uint8_t* keep0, void* x, void* emb, int B, int T, int L, int m, int H, int max_F, mmfm_stream stream) {
-    MMFM_REQUIRE(tok && mod_emb_row && pos_emb && ts && keep0 && x, "mmfm_stitch_fwd: null pointer");
+    MMFM_REQUIRE(tok && mod_emb_row && (ts || !pos_emb) && keep0 && x, "mmfm_stitch_fwd: null pointer");       // pos_emb NULL: no position table
     MMFM_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && m >= 0 && (m + 1) * T <= L && max_F > 0, "mmfm_stitch_fwd: bad shape");
     const int64_t n = (int64_t)B * T * (H / 4);
     dim3 grid((int)std::min<int64_t>(4096, (n + 255) / 256)), block(256);
@@ -294,7 +333,7 @@ extern "C" int64_t mmfm_stitch_bwd_workspace(int dtype, int B, int T, int L, int
 extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
                                mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
                                int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
-    MMFM_REQUIRE(dx && ts && keep0 && d_mod_row && d_pos, "mmfm_stitch_bwd: null pointer");
+    MMFM_REQUIRE(dx && (ts || !d_pos) && keep0 && d_mod_row, "mmfm_stitch_bwd: null pointer");                 // d_pos NULL: no position table
     MMFM_REQUIRE(B > 0 && T > 0 && H > 0 && max_F > 0 && m >= 0 && (m + 1) * T <= L, "mmfm_stitch_bwd: bad shape");
     if (oh_path(dtype, H)) {
         const OhGeo g = oh_geo(B, L, H, max_F);
@@ -302,6 +341,22 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
         MMFM_REQUIRE((uintptr_t)dx % 16 == 0 && (!dextra || (uintptr_t)dextra % 16 == 0) && (!d_tok || (uintptr_t)d_tok % 16 == 0) &&
                      (uintptr_t)workspace % 16 == 0, "mmfm_stitch_bwd: bf16 tensors must be 16-byte aligned");
         hipStream_t st = (hipStream_t)stream;
+        if (!d_pos) {
+            // the column sum: as many slabs of H floats as samples, at most 256, and no more than the workspace bound of the one-hot
+            // product holds (mmfm_stitch_bwd_workspace does not know which form it sizes; it holds at least 2 (max_F + 1) such slabs)
+            const int64_t room = mmfm_stitch_bwd_workspace(dtype, B, T, L, H, max_F) / ((int64_t)H * (int64_t)sizeof(float));
+            const int S = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(B, 256), room));
+            const int bper = (B + S - 1) / S, nsl = (B + bper - 1) / bper;
+            if (d_tok) {
+                const int64_t n = (int64_t)B * T * (H / 8);
+                hipLaunchKernelGGL(stitch_dtok_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, st, (const uint16_t*)dx, keep0,
+                                   drop, (uint16_t*)d_tok, B, T, L, m, H);
+            }
+            hipLaunchKernelGGL(stitch_modsum_kernel, dim3(cdiv(H, 256), nsl), dim3(256), 0, st, (const uint16_t*)dx, (const uint16_t*)dextra,
+                               (float*)workspace, B, T, L, m, H, bper);
+            MMFM_LAUNCH_CHECK("mmfm_stitch_bwd(column sum)");
+            return mmfm_reduce_slabs(d_mod_row, (const float*)workspace, H, nsl, H, acc_mod, stream);
+        }
         uint16_t* oh = reinterpret_cast<uint16_t*>(workspace);
         float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + g.oh_bytes);
         const int64_t nch = (int64_t)B * L * (g.ohc / 8);
@@ -338,14 +393,24 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
     dim3 grid(H / cw, nch), block(cw);
     const size_t lds = (size_t)max_F * cw * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
+    MMFM_REQUIRE(dtype == MMFM_F32 || dtype == MMFM_BF16, "mmfm_stitch_bwd: bad dtype %d", dtype);
+    if (!d_pos) {
+        // no position table: the same column slabs and chunks (so the same workspace bound), each chunk's partial one row of H floats
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((stitch_bwd_kernel<float, false>), grid, block, 0, st, (const float*)dx, (const float*)dextra, ts, keep0, drop,
+                               (float*)d_tok, (float*)workspace, B, T, L, m, H, 0, bper);
+        else
+            hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, false>), grid, block, 0, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, drop,
+                               (uint16_t*)d_tok, (float*)workspace, B, T, L, m, H, 0, bper);
+        MMFM_LAUNCH_CHECK("mmfm_stitch_bwd(no table)");
+        return mmfm_reduce_slabs(d_mod_row, (const float*)workspace, H, nch, H, acc_mod, stream);
+    }
     if (dtype == MMFM_F32)
-        hipLaunchKernelGGL(stitch_bwd_kernel<float>, grid, block, lds, st, (const float*)dx, (const float*)dextra, ts, keep0, drop, (float*)d_tok,
+        hipLaunchKernelGGL((stitch_bwd_kernel<float, true>), grid, block, lds, st, (const float*)dx, (const float*)dextra, ts, keep0, drop, (float*)d_tok,
                            (float*)workspace, B, T, L, m, H, max_F, bper);
-    else if (dtype == MMFM_BF16)
-        hipLaunchKernelGGL(stitch_bwd_kernel<uint16_t>, grid, block, lds, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, drop,
-                           (uint16_t*)d_tok, (float*)workspace, B, T, L, m, H, max_F, bper);
     else
-        return mmfm_set_error(-1, "mmfm_stitch_bwd: bad dtype %d", dtype);
+        hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, true>), grid, block, lds, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, drop,
+                           (uint16_t*)d_tok, (float*)workspace, B, T, L, m, H, max_F, bper);
     MMFM_LAUNCH_CHECK("mmfm_stitch_bwd");
     const int64_t stride = (int64_t)(max_F + 1) * H;
     if (int rc = mmfm_reduce_slabs(d_pos, (const float*)workspace, (int64_t)max_F * H, nch, stride, acc_pos, stream)) return rc;

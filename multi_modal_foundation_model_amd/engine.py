@@ -22,7 +22,7 @@ import itertools
 import math
 import os
 from collections import namedtuple
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field, fields
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -37,12 +37,15 @@ BLOCK_NORMS = ("ln1", "ln2", "query_norm", "context_norm")     # the sites `use_
 
 
 # what a side ("encoder" / "decoder") of the model runs with: EngineConfig.side
-SideConfig = namedtuple("SideConfig", "heads inter dropout norm act embed_scale embed_dropout mult max_F attn_bias mlp_bias")
+SideConfig = namedtuple("SideConfig", "heads inter dropout norm act embed_scale embed_dropout mult max_F embed_act embed_pos embed_bias attn_bias mlp_bias")
 # The EngineConfig fields that have one value per side (the two YAML sections are independent): each holds ONE value, meaning both
 # sides, or Sides(encoder, decoder).  A plain (encoder, decoder) tuple or list is taken as Sides too - for `act`, whose one value is
 # itself a (kind, beta) pair, a pair of pairs.  __post_init__ folds a pair of equal values into the one value, so a config that names
 # one value equals the config that names it twice, and the default config is field for field what it always was
 PER_SIDE = ("heads", "inter", "dropout", "norm", "act", "embed_scale", "embed_dropout", "mult", "max_F")
+# The embedder options (embedder.act / pos / bias), per side in the same way.  They are constructor keywords and attributes of the config but
+# not dataclass fields (InitVar): the field list, asdict() and the constructor calls from before they existed are what they were
+PER_SIDE_EMBED = ("embed_act", "embed_pos", "embed_bias")
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -76,22 +79,35 @@ class EngineConfig:
     enc_mlp_bias: bool = True
     dec_attn_bias: bool = True
     dec_mlp_bias: bool = True
+    # the embedder options, per side like the fields above (one value or Sides): embedder.act (a name of ops.EMBED_ACTS), embedder.pos
+    # (False: no pos_embed table, emb = mod_emb row) and embedder.bias (False: token_embed is nn.Linear(bias=False))
+    embed_act: InitVar[str] = "softsign"
+    embed_pos: InitVar[bool] = True
+    embed_bias: InitVar[bool] = True
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
     # `n_modality` (the decoder's mod_emb IS the encoder's tensor, mm.py:84-87).  Read a side's values through `side()`
 
-    def __post_init__(self):
-        for k in PER_SIDE:
+    def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True):
+        self.embed_act, self.embed_pos, self.embed_bias = embed_act, embed_pos, embed_bias
+        for k in PER_SIDE + PER_SIDE_EMBED:
             v = getattr(self, k)
             pair = isinstance(v, (tuple, list)) and len(v) == 2 and (k != "act" or isinstance(v[0], (tuple, list)))
             if pair:
                 enc, dec = (tuple(x) for x in v) if k == "act" else v
                 setattr(self, k, enc if enc == dec else Sides(enc, dec))
 
+    def __eq__(self, other):
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED)
+
+    __hash__ = None
+
     def side(self, side: str) -> SideConfig:
         """The per-side quantities of "encoder" or "decoder"."""
         if side not in ("encoder", "decoder"):
             raise ValueError(f"EngineConfig.side({side!r})")
-        vals = (getattr(self, k) for k in PER_SIDE)
+        vals = (getattr(self, k) for k in PER_SIDE + PER_SIDE_EMBED)
         return SideConfig(*(getattr(v, side) if isinstance(v, Sides) else v for v in vals),
                           attn_bias=getattr(self, side[:3] + "_attn_bias"), mlp_bias=getattr(self, side[:3] + "_mlp_bias"))
 
@@ -101,11 +117,14 @@ class EngineConfig:
         return lnname.rsplit(".", 1)[-1] in BLOCK_NORMS and self.side(lnname.split(".", 1)[0]).norm == "scalenorm"
 
     @staticmethod
-    def from_model_config(mc, mods, per_side: bool = False) -> "EngineConfig":
+    def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False) -> "EngineConfig":
         """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
         two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
         sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
-        always did (the embedder's keys are read per side either way: the decoder's used to be ignored without a word)."""
+        always did (the embedder's keys are read per side either way: the decoder's used to be ignored without a word).
+        embedder_opts = True (what MultiModal passes): embedder.act, pos and bias are read per side too (embed_act / embed_pos /
+        embed_bias; an act without a kernel raises NotImplementedError naming the accepted ones).  Without it the call keeps the
+        contract it had: any act but softsign, pos: false and bias: false raise NotImplementedError."""
         tf = {side: mc[side]["transformer"] for side in ("encoder", "decoder")}
         em = {side: mc[side]["embedder"] for side in ("encoder", "decoder")}
         et, dtf, ee = tf["encoder"], tf["decoder"], em["encoder"]
@@ -125,8 +144,13 @@ class EngineConfig:
         hs, per = int(et["hidden_size"]), {}
         for side in ("encoder", "decoder"):
             t, e = tf[side], em[side]
-            if e["act"] != "softsign":
-                raise NotImplementedError("only act=softsign (embedder) is built")
+            if embedder_opts:
+                K.embed_act(e["act"])
+            elif e["act"] != "softsign":
+                raise NotImplementedError(f"{side}.embedder.act={e['act']!r}: only act=softsign (embedder) is read by this call; pass "
+                                          "embedder_opts=True for the other embedder activations")
+            elif not e["pos"] or not e["bias"]:
+                raise NotImplementedError(f"{side}.embedder.pos / bias = false: pass embedder_opts=True to read the embedder's act, pos and bias")
             nh = int(t["n_heads"])
             if nh <= 0 or hs % nh:
                 raise ValueError(f"{side}.transformer.hidden_size {hs} is not a multiple of n_heads {nh}: the attention kernels take a "
@@ -137,10 +161,10 @@ class EngineConfig:
             per[side] = dict(heads=t["n_heads"], inter=t["inter_size"], dropout=t["dropout"],
                              norm="scalenorm" if t["use_scalenorm"] else "layernorm", act=K.mlp_act(t["act"]),
                              embed_scale=float(hs ** 0.5 if e["scale"] is None else e["scale"]), embed_dropout=e["dropout"],
-                             mult=e["mult"], max_F=e["max_F"])
+                             mult=e["mult"], max_F=e["max_F"], embed_act=str(e["act"]), embed_pos=bool(e["pos"]), embed_bias=bool(e["bias"]))
         return EngineConfig(hidden=et["hidden_size"], n_enc=et["n_layers"], n_dec=dtf["n_layers"], n_modality=ee["n_modality"],
                             sep_mask=bool(mc["decoder"]["decoder_sep_mask"]), causal_mask=bool(mc["decoder"]["decoder_causal_mask"]),
-                            mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE},
+                            mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE + (PER_SIDE_EMBED if embedder_opts else ())},
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]))
 
@@ -229,11 +253,12 @@ class ParamLayout:
                 sc = cfg.side(side)
                 for mod, n in cfg.mods:
                     p = f"{side}_embeddings.{mod}.embedder"
-                    lin(p + ".token_embed", n * sc.mult, n)
+                    lin(p + ".token_embed", n * sc.mult, n, bias=sc.embed_bias)
                     lin(p + ".projection", H, n * sc.mult)
                     if side == "encoder":       # decoder's mod_emb IS this tensor (mm.py:84-87)
                         pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
-                    pad(); add(p + ".pos_embed.weight", (sc.max_F, H))
+                    if sc.embed_pos:            # embedder.pos: false builds no pos_embed module
+                        pad(); add(p + ".pos_embed.weight", (sc.max_F, H))
 
         def head():
             ln("decoder_norm")

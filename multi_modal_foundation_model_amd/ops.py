@@ -276,6 +276,28 @@ GEMM_ACTS = {L.MLP_GELU: (L.ACT_GELU, L.ACT_GELU_GRAD), L.MLP_RELU: (L.ACT_RELU,
              L.MLP_SIGMOID: (L.ACT_SIGMOID, L.ACT_SIGMOID_GRAD), L.MLP_GELU_TANH: (L.ACT_GELU_TANH, L.ACT_GELU_TANH_GRAD)}
 
 
+# embedder.act (a `transformers` ACT2FN name, or `identity`) -> the mmfm_gemm act codes of its forward and of its gradient.  softsign's
+# gradient code is the fp32 one (from the saved pre-activation); the bf16 plan takes it from the output instead (ACT_SOFTSIGN_GRAD_OUT)
+EMBED_ACTS = {
+    "softsign": (L.ACT_SOFTSIGN, L.ACT_SOFTSIGN_GRAD),
+    "identity": (L.ACT_EMB_IDENTITY, L.ACT_EMB_IDENTITY_GRAD), "linear": (L.ACT_EMB_IDENTITY, L.ACT_EMB_IDENTITY_GRAD),
+    "relu": (L.ACT_EMB_RELU, L.ACT_EMB_RELU_GRAD),
+    "gelu": (L.ACT_EMB_GELU, L.ACT_EMB_GELU_GRAD),
+    "silu": (L.ACT_EMB_SILU, L.ACT_EMB_SILU_GRAD), "swish": (L.ACT_EMB_SILU, L.ACT_EMB_SILU_GRAD),
+    "quick_gelu": (L.ACT_EMB_QUICK_GELU, L.ACT_EMB_QUICK_GELU_GRAD),
+    "gelu_new": (L.ACT_EMB_GELU_TANH, L.ACT_EMB_GELU_TANH_GRAD), "gelu_pytorch_tanh": (L.ACT_EMB_GELU_TANH, L.ACT_EMB_GELU_TANH_GRAD),
+    "gelu_fast": (L.ACT_EMB_GELU_TANH, L.ACT_EMB_GELU_TANH_GRAD),
+    "tanh": (L.ACT_EMB_TANH, L.ACT_EMB_TANH_GRAD),
+}
+
+
+def embed_act(name):
+    """(forward code, gradient code) of an embedder.act name; NotImplementedError for names without a kernel."""
+    if name not in EMBED_ACTS:
+        raise NotImplementedError(f"embedder act {name!r} has no kernel; accepted: {', '.join(EMBED_ACTS)}")
+    return EMBED_ACTS[name]
+
+
 def mlp_act(name):
     """(kind, beta) of a transformer.act name; NotImplementedError for names without a kernel."""
     if name not in MLP_ACTS:

@@ -34,13 +34,17 @@ def read_switches() -> Switches:
 
 # What a side of the model lays its blocks out with (EngineConfig.side, in this plan's mode): heads, I = inter_size, dp / dpe = the
 # transformer's / the embedder's dropout (0 outside training), act = (MMFM_MLP_* kind, beta) with act_fwd / act_grad the un-fused MLP's
-# mmfm_gemm act codes, the embedder's scale, mult and max_F, and - set by `workspaces` - use_keep (attention dropout of this side runs
+# mmfm_gemm act codes, the embedder's scale, mult, max_F, activation codes (emb_fwd / emb_grad) and pos, and - set by `workspaces` - use_keep (attention dropout of this side runs
 # on keep-bit workspaces) and F_MLP (its MLP blocks run the row-owner MLP kernels)
 class Side:
     def __init__(self, sc, training):
         self.heads, self.I, self.act, self.scale, self.mult, self.max_F = sc.heads, sc.inter, sc.act, sc.embed_scale, sc.mult, sc.max_F
         self.dp, self.dpe = (sc.dropout, sc.embed_dropout) if training else (0.0, 0.0)
         self.act_fwd, self.act_grad = K.GEMM_ACTS[sc.act[0]]
+        # the embedder's options: its activation's mmfm_gemm codes (ops.EMBED_ACTS), pos (False: no position table) and whether
+        # token_embed has a bias (the layout decides what the launches get: Engine.Pb / Gb)
+        self.emb_act, self.pos = sc.embed_act, sc.embed_pos
+        self.emb_fwd, self.emb_grad = K.embed_act(sc.embed_act)
         self.use_keep = self.F_MLP = False
 
 
@@ -65,6 +69,15 @@ class PlanBuilder:
         self.deferred: list = []     # a parked weight gradient, waiting for a partner (mmfm_gemm_pair)
         self.used_wt: list = []      # weights whose bf16 transpose a dX product reads
         self.stream_in = {}          # layer tag -> the residual stream that entered it
+
+    def embed_saved(self, sd):
+        """What the backward of a tokeniser's activation reads (DESIGN.md 3o): "z", the token_embed pre-activation, stored by the forward;
+        "a", the activation itself (softsign in bf16 mode, act 5: nothing extra is stored); None for the identity."""
+        if sd.emb_fwd == L.ACT_EMB_IDENTITY:
+            return None
+        if sd.emb_fwd == L.ACT_SOFTSIGN and self.code == L.BF16:
+            return "a"
+        return "z"
 
     def side(self, name):
         """The Side a block belongs to, from its parameter prefix (`encoder.3`), its tag (`enc3`, `dec0/xa`) or the side's own name."""
@@ -377,11 +390,13 @@ class PlanBuilder:
                 a = buf(f"{side}/a/{m}", (BT, n2))
                 # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
                 # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
-                z = None if self.code == L.BF16 else buf(f"{side}/z/{m}", (BT, n2))
-                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=L.ACT_SOFTSIGN, act_scale=sd.scale)
+                # every other activation but the identity stores z in both modes (2 bytes x B T x mult N in bf16)
+                z = buf(f"{side}/z/{m}", (BT, n2)) if self.embed_saved(sd) == "z" else None
+                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=sd.emb_fwd, act_scale=sd.scale)
                 self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe))
                 mod_row = e.Pf(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m]
-                K.stitch_fwd(tok_tmp, mod_row, e.Pf(p + ".pos_embed.weight"), b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, sd.max_F, plan=fwd)
+                pos = e.Pf(p + ".pos_embed.weight") if sd.pos else None            # embedder.pos: false -> emb = the modality row
+                K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, sd.max_F, plan=fwd)
         X = x_enc
         for i in range(c.n_enc):
             p, tag = f"encoder.{i}", f"enc{i}"
@@ -539,18 +554,19 @@ class PlanBuilder:
             for m, (mod, n) in enumerate(c.mods):
                 pS = f"{side}_embeddings.{mod}.embedder"
                 K.stitch_bwd(dS, dextra, b["ts"], b["keep0"], e._drop(f"{side}/embdrop/{m}", sd.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
-                             e.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], e.Gv(pS + ".pos_embed.weight"),
+                             e.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
                              acc_mod, False, B, T, Lq, m, H, sd.max_F, b["ws/stitch"], plan=self.cur)
-        bf16 = self.code == L.BF16       # the softsign gradient from the activation itself, or (fp32) from the saved pre-activation
+        # the softsign gradient from the activation itself (bf16), or from the saved pre-activation (fp32, and every other activation)
         for side in ("decoder", "encoder"):
             sd = self.sides[side]
+            saved = self.embed_saved(sd)
             for m, (mod, n) in enumerate(c.mods):
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
                 dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)
                 self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
-                          act=L.ACT_SOFTSIGN_GRAD_OUT if bf16 else L.ACT_SOFTSIGN_GRAD, act_scale=sd.scale,
-                          gradmul_pre=b[f"{side}/a/{m}" if bf16 else f"{side}/z/{m}"])
+                          act=L.ACT_SOFTSIGN_GRAD_OUT if saved == "a" else sd.emb_grad, act_scale=sd.scale,
+                          gradmul_pre=b[f"{side}/{saved}/{m}"] if saved else None)
                 self.dlin(self.cur, dz, b[f"in/{m}"], p + ".token_embed", BT, n2, n, ldx=_align(n, 8))
         self.close_segment("embed")
         if self.used_wt:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)

@@ -14,12 +14,12 @@ DEFAULT_CONFIG = "src/configs/multi_modal/mm.yaml"
 
 
 class TokeniserLayer(nn.Module):
-    """x = proj(softsign(tok(inputs)) * scale);  emb = mod_emb[modality] + pos_embed[timestamp]."""
+    """x = proj(act(tok(inputs)) * scale);  emb = mod_emb[modality] (+ pos_embed[timestamp] unless embedder.pos is false).
+    act: an embedder.act name with a kernel (ops.EMBED_ACTS); token_embed has no bias under embedder.bias: false."""
 
     def __init__(self, hidden_size, n_channels, config: DictConfig):
         super().__init__()
-        if config.act != "softsign":
-            raise NotImplementedError(f"embedder act '{config.act}': only softsign has a kernel")
+        self.act_codes = K.embed_act(config.act)       # NotImplementedError (naming the accepted ones) for an act without a kernel
         self.bias = config.bias
         self.n_channels = n_channels
         self.input_dim = n_channels * config.mult
@@ -28,10 +28,9 @@ class TokeniserLayer(nn.Module):
         self.scale = hidden_size ** 0.5 if config.scale is None else config.scale
         self.mod_emb = nn.Embedding(config.n_modality, hidden_size)
         self.pos = config.pos
-        if self.pos:
+        self.max_F = config.max_F
+        if self.pos:                                   # no module (and no draw from the generator) otherwise, as upstream
             self.pos_embed = nn.Embedding(config.max_F, hidden_size)
-        else:
-            raise NotImplementedError("embedder.pos=false is not built")
         self.dropout = nn.Dropout(config.dropout)
 
     def forward(self, d):
@@ -41,14 +40,17 @@ class TokeniserLayer(nn.Module):
         inputs, ts, mod = d["inputs"], d["inputs_timestamp"], int(d["inputs_modality"])
         B, T, _ = inputs.shape
         H = self.projection.weight.shape[0]
-        a = hip_linear(inputs, self.token_embed, act=L.ACT_SOFTSIGN)
-        if self.scale != 1:
-            a = a * self.scale
+        if self.act_codes[0] == L.ACT_SOFTSIGN:
+            a = hip_linear(inputs, self.token_embed, act=L.ACT_SOFTSIGN)
+            if self.scale != 1:
+                a = a * self.scale
+        else:
+            a = hip_linear(inputs, self.token_embed, act=self.act_codes[0], act_scale=float(self.scale))
         tok = hip_linear(a, self.projection).view(B * T, H)
         x, emb = torch.empty(B, T, H, device=inputs.device), torch.empty(B, T, H, device=inputs.device)
         keep = torch.ones(T, dtype=torch.uint8, device=inputs.device)
-        K.stitch_fwd(tok, self.mod_emb.weight.detach()[mod].contiguous(), self.pos_embed.weight.detach().contiguous(),
-                     ts.contiguous(), keep, x, emb, B, T, T, 0, H, self.pos_embed.weight.shape[0])
+        pos = self.pos_embed.weight.detach().contiguous() if self.pos else None
+        K.stitch_fwd(tok, self.mod_emb.weight.detach()[mod].contiguous(), pos, ts.contiguous(), keep, x, emb, B, T, T, 0, H, self.max_F)
         return x - emb, emb
 
 

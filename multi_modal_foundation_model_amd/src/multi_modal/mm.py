@@ -160,7 +160,7 @@ class MultiModal(nn.Module):
                     raise NotImplementedError("encoder/decoder channel counts differ")
                 if m not in self.loss_mod:
                     raise Exception("Modality not implemented yet.")
-            cfg = EngineConfig.from_model_config(self._model_config, mods, per_side=True)
+            cfg = EngineConfig.from_model_config(self._model_config, mods, per_side=True, embedder_opts=True)
             specs = {m: _loss_spec(self.loss_mod[m]) for m, _ in mods}
             cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
             cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
