@@ -229,23 +229,9 @@ def default_batch():
 
 
 def fx_default_scalars():
-    cfg = ref_config()
-    model = build_model(cfg.model, 668, 2, seed=42)
-    model.eval()
-    batch = default_batch()
-    res = {}
-    for obj in ("encoding", "decoding", "token_masking"):
-        model.zero_grad(set_to_none=True)
-        torch.manual_seed(1)
-        out = model(make_mod_dict(batch, obj))
-        out.loss.backward()
-        res[obj] = dict(
-            loss=float(out.loss),
-            mod_loss={m: float(v) for m, v in out.mod_loss.items()},
-            n={m: int(v) for m, v in out.mod_n_examples.items()},
-            pred_abssum={m: float(v.double().abs().sum()) for m, v in out.mod_preds.items()},
-            grad_norm={k: float(p.grad.double().norm()) for k, p in model.named_parameters()})
-        print("   ", obj, res[obj]["loss"], res[obj]["n"])
+    res = default_scalars(build_model(ref_config().model, 668, 2, seed=42))
+    for obj, r in res.items():
+        print("   ", obj, r["loss"], r["n"])
     save_json("default_scalars.json", res)
 
 
@@ -381,6 +367,116 @@ def run_curve(model, steps, B, T, n_ap, n_beh, total_steps):
         losses.append(float(out.loss))
         objs.append(obj)
     return losses, objs
+
+
+# --------------------------------------------------------------------------- shared by scripts/make_*_goldens.py
+OBJECTIVES = ("encoding", "decoding", "token_masking")
+TINY = dict(B=2, T=8, n_ap=12, n_beh=2)          # the tiny fixtures' batch shape; model seed 7, data seed 3, masker seed 11
+
+
+def with_sides(mcfg, switches):
+    """`mcfg` with each side's sections updated: switches[side][section] = {key: value}."""
+    m = plain(mcfg)
+    for side, secs in switches.items():
+        for sec, upd in secs.items():
+            m[side][sec].update(upd)
+    return DictConfig(m)
+
+
+def init_by_hash(arrs, meta, case, model):
+    """meta state / params of `case`, and its initial parameters in full: cases that draw the same stream share their tensors, so one
+    array per distinct content (init/<hash>; meta init: case -> key -> hash)."""
+    import hashlib
+    meta["state"][case] = [[k, list(v.shape)] for k, v in model.state_dict().items()]
+    meta["params"][case] = [k for k, _ in model.named_parameters()]
+    meta["init"][case] = {}
+    for k, v in model.state_dict().items():
+        a = npify(v)
+        h = hashlib.sha256(str((a.dtype, a.shape)).encode() + a.tobytes()).hexdigest()[:16]
+        arrs[f"init/{h}"] = a
+        meta["init"][case][k] = h
+
+
+def init_digest(model):
+    """Key, shape, dtype, sum and content hash of every state-dict tensor (the mlp_act / scalenorm fixtures' meta init)."""
+    import hashlib
+    return [dict(key=k, shape=list(v.shape), dtype=str(v.dtype), sum=float(v.double().sum()),
+                 sha256=hashlib.sha256(npify(v).tobytes()).hexdigest()[:16]) for k, v in model.state_dict().items()]
+
+
+def record_step(arrs, model, batch, p, obj, keep_grad):
+    """One forward / backward of the reference under prefix `p`: loss, per-modality n / loss / preds / masks, the norm of every
+    gradient in named_parameters order, and the gradient tensors keep_grad(name) asks for."""
+    model.zero_grad(set_to_none=True)
+    torch.manual_seed(11)
+    md = make_mod_dict(batch, obj)
+    out = model(md)
+    out.loss.backward()
+    arrs[f"{p}/loss"] = npify(out.loss)
+    for mod in ("ap", "behavior"):
+        arrs[f"{p}/mod_loss/{mod}"] = npify(out.mod_loss[mod])
+        arrs[f"{p}/n/{mod}"] = npify(out.mod_n_examples[mod])
+        arrs[f"{p}/preds/{mod}"] = npify(out.mod_preds[mod])
+        arrs[f"{p}/mask/{mod}"] = npify(md[mod]["inputs_mask"])
+    arrs[f"{p}/grad_norm"] = np.array([float(prm.grad.double().norm()) for _, prm in model.named_parameters()])
+    for k, prm in model.named_parameters():
+        if keep_grad(k):
+            arrs[f"{p}/grad/{k}"] = npify(prm.grad)
+    print("   ", p, float(out.loss))
+
+
+def fx_case_fwd_bwd(name, cases, config_of, meta, record_init):
+    """tests/golden/<name>: the tiny batch, then per case (config_of(case) is its reference model config) what record_init stores of
+    the initial model and record_step of the three objectives, with every gradient tensor for meta["full_grad"] (of the cases in
+    meta["full_grad_cases"], where the fixture names any).  `meta` is the caller's, in the key order the file keeps."""
+    arrs = {}
+    batch = synth_batch(seed=3, **TINY)
+    for k, v in batch.items():
+        arrs[f"batch/{k}"] = npify(v)
+    for case in cases:
+        model = build_model(config_of(case), TINY["n_ap"], TINY["n_beh"], seed=7)
+        model.train()
+        record_init(arrs, meta, case, model)
+        for obj in OBJECTIVES:
+            full = obj == meta["full_grad"] and case in meta.get("full_grad_cases", cases)
+            record_step(arrs, model, batch, f"{case}/{obj}", obj, lambda k: full)
+            meta["cases"].append(f"{case}/{obj}")
+    arrs["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    save_npz(name, **arrs)
+
+
+def tiny_curve(model, what, model_seed=7, **shape):
+    """The 50-step curve record of `model` at the tiny batch shape (or `shape`)."""
+    shape = shape or TINY
+    l, o = run_curve(model, 50, shape["B"], shape["T"], shape["n_ap"], shape["n_beh"], total_steps=50)
+    print("    tiny curve", what, l[:2], "...", l[-1])
+    return dict(loss=l, objective=o, model_seed=model_seed, **shape, total_steps=50)
+
+
+def default_scalars(model):
+    """Per objective on default_batch(), eval mode: loss, per-modality loss / n / sum |pred|, every gradient norm."""
+    model.eval()
+    batch = default_batch()
+    res = {}
+    for obj in OBJECTIVES:
+        model.zero_grad(set_to_none=True)
+        torch.manual_seed(1)
+        out = model(make_mod_dict(batch, obj))
+        out.loss.backward()
+        res[obj] = dict(
+            loss=float(out.loss), mod_loss={m: float(v) for m, v in out.mod_loss.items()},
+            n={m: int(v) for m, v in out.mod_n_examples.items()},
+            pred_abssum={m: float(v.double().abs().sum()) for m, v in out.mod_preds.items()},
+            grad_norm={k: float(p.grad.double().norm()) for k, p in model.named_parameters()})
+    return res
+
+
+def no_dropout_default_cfg():
+    cfg = plain(ref_config()["model"])
+    for side in ("encoder", "decoder"):
+        cfg[side]["embedder"]["dropout"] = 0.0
+        cfg[side]["transformer"]["dropout"] = 0.0
+    return DictConfig(cfg)
 
 
 def fx_loss_curve():

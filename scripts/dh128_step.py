@@ -9,20 +9,11 @@
         alternating in rounds; per model the step time, the attention kernels' device time per step (torch.profiler, kernels whose name
         contains "attn") and their achieved TF/s on the algorithmic 4 (forward) + 10 (backward) B heads L^2 dh flops per attention site.
 """
-import json
 import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "multi_modal_foundation_model_amd", "src"), os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-import torch  # noqa: E402
-
-from multi_modal_foundation_model_amd.builders import build_model, make_optimizer, model_config  # noqa: E402
-from oracle import mm_oracle as O  # noqa: E402
+from step_timer import emit, make_runner, summarise, time_rounds, torch
+from multi_modal_foundation_model_amd.builders import model_config
 
 MODE = sys.argv[1] if len(sys.argv) > 1 else "default"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else (1024 if MODE == "default" else 64)
@@ -32,35 +23,13 @@ N_AP, N_BEH = (668, 2) if MODE == "default" else (96, 2)
 WIDE = dict(H=1024, heads=8, inter=2048, n_enc=5, n_dec=5)
 
 
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-    return md
-
-
 def make(kw, keepbits):
-    os.environ["MMFM_ATTN_KEEPBITS"] = keepbits          # read whenever the engine builds a step plan: set again before every step
-    model = build_model(model_config(**kw), N_AP, N_BEH, seed=42)
-    model.compute_dtype = "bf16"
-    model.cuda().train()
-    opt, sch = make_optimizer(model, 10000)
-    md = to_dev(O.make_mod_dict(O.synth_batch(B, T, N_AP, N_BEH, seed=0), "encoding"))
-
-    def step():
-        os.environ["MMFM_ATTN_KEEPBITS"] = keepbits
-        out = model({m: dict(d) for m, d in md.items()})
-        out.loss.backward()
-        opt.step(); sch.step(); opt.zero_grad()
-        return out.loss
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    plan = model._engine._last
-    calls = dict(fwd=len(plan["fwd"]), bwd=sum(len(seg) for _, seg in plan["bwd"]))
-    sites = [s for s in model._engine.dropout_sites(B, T) if s["kind"] == "attn"]
-    return dict(model=model, step=step, calls=calls, ms=[], sites=len(sites), dh=sites[0]["dh"] if sites else None)
+    def export():
+        os.environ["MMFM_ATTN_KEEPBITS"] = keepbits          # read whenever the engine builds a step plan: set again before every step
+    export()
+    r = make_runner(model_config(**kw), N_AP, N_BEH, B, T, pre_step=export)
+    sites = [s for s in r["model"]._engine.dropout_sites(B, T) if s["kind"] == "attn"]
+    return dict(r, sites=len(sites), dh=sites[0]["dh"] if sites else None)
 
 
 def keepbit_workspaces(r):
@@ -83,19 +52,10 @@ if MODE == "default":
     runs = {"default": make({}, "1")}
 else:
     runs = {"keepbits": make(WIDE, "1"), "general": make(WIDE, "0")}
-for _ in range(ROUNDS):
-    for name, r in runs.items():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(STEPS):
-            loss = r["step"]()
-        torch.cuda.synchronize()
-        r["ms"].append((time.perf_counter() - t0) / STEPS * 1e3)
-        r["loss"] = float(loss)
+time_rounds(runs, STEPS, ROUNDS)
 res = dict(mode=MODE, B=B, T=T, L=2 * T, dtype="bf16", steps_per_round=STEPS, rounds=ROUNDS, device=torch.cuda.get_device_name(0))
 for name, r in runs.items():
-    res[name] = dict(ms_per_step_median=statistics.median(r["ms"]), ms_per_step_rounds=r["ms"], ms_per_step_spread=max(r["ms"]) - min(r["ms"]),
-                     plan_calls=r["calls"], last_loss=r["loss"], attention_sites=r["sites"], dh=r["dh"], keepbit_workspaces=keepbit_workspaces(r))
+    res[name] = dict(summarise(r, spread=True), attention_sites=r["sites"], dh=r["dh"], keepbit_workspaces=keepbit_workspaces(r))
     if MODE != "default":
         att = attention_ms(r["step"])
         flops = 14.0 * B * WIDE["heads"] * (2 * T) ** 2 * r["dh"] * r["sites"]
@@ -103,8 +63,4 @@ for name, r in runs.items():
 if MODE != "default":
     assert res["keepbits"]["keepbit_workspaces"] and not res["general"]["keepbit_workspaces"], "the two runs took the same attention path"
     res["keepbits_over_general"] = res["keepbits"]["ms_per_step_median"] / res["general"]["ms_per_step_median"]
-print(json.dumps(res, indent=1))
-if OUT:
-    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
-    with open(OUT, "w") as f:
-        json.dump(res, f, indent=1)
+emit(res, OUT)

@@ -11,21 +11,12 @@ Build PARENT_LIB from the parent commit (`make -C multi_modal_foundation_model_a
 checkout of it).  Acceptance: this library's medians lie within the span of the parent's own rounds (or below it).
 """
 import ctypes as C
-import json
-import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "multi_modal_foundation_model_amd", "src")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-import torch  # noqa: E402
-
-from multi_modal_foundation_model_amd import _lib as L  # noqa: E402
-from multi_modal_foundation_model_amd.builders import build_model, make_optimizer, model_config  # noqa: E402
-from oracle import mm_oracle as O  # noqa: E402
+from step_timer import emit, make_runner, summarise, time_rounds, torch
+from multi_modal_foundation_model_amd import _lib as L
+from multi_modal_foundation_model_amd.builders import model_config
 
 PARENT = sys.argv[1]
 OUT = sys.argv[2] if len(sys.argv) > 2 else None
@@ -98,39 +89,7 @@ for k in ("fwd", "bwd"):
 del pred, tgt, dpred
 
 # ---- the whole default step
-model = build_model(model_config(), 668, 2, seed=42)
-model.compute_dtype = "bf16"
-model.cuda().train()
-opt, sch = make_optimizer(model, 10000)
-md = O.make_mod_dict(O.synth_batch(B, T, 668, 2, seed=0), "encoding")
-for d in md.values():
-    for k, v in list(d.items()):
-        if isinstance(v, torch.Tensor):
-            d[k] = v.cuda()
-
-
-def step():
-    o = model({m: dict(d) for m, d in md.items()})
-    o.loss.backward()
-    opt.step(); sch.step(); opt.zero_grad()
-    return o.loss
-
-
-for _ in range(3):
-    step()
-torch.cuda.synchronize()
-ms = []
-for _ in range(5):
-    t0 = time.perf_counter()
-    for _ in range(STEPS):
-        loss = step()
-    torch.cuda.synchronize()
-    ms.append((time.perf_counter() - t0) / STEPS * 1e3)
-plan = model._engine._last
-res["step"] = dict(ms_per_step_median=statistics.median(ms), ms_per_step_rounds=ms, steps_per_round=STEPS, last_loss=float(loss),
-                   plan_calls=dict(fwd=len(plan["fwd"]), bwd=sum(len(seg) for _, seg in plan["bwd"])))
-print(json.dumps(res, indent=1))
-if OUT:
-    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
-    with open(OUT, "w") as f:
-        json.dump(res, f, indent=1)
+runs = {"step": make_runner(model_config(), 668, 2, B, T)}
+time_rounds(runs, STEPS, 5)
+res["step"] = dict(summarise(runs["step"]), steps_per_round=STEPS)
+emit(res, OUT)

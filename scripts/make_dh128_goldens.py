@@ -79,10 +79,8 @@ def fx_fwd_bwd():
 
 def fx_curve():
     model = G.build_model(G.tiny_model_cfg(dropout=0.0, emb_dropout=0.0, **CFG), N_AP, N_BEH, seed=MODEL_SEED)
-    l, o = G.run_curve(model, 50, B, T, N_AP, N_BEH, total_steps=50)
-    res = dict(loss=l, objective=o, model_seed=MODEL_SEED, B=B, T=T, n_ap=N_AP, n_beh=N_BEH, total_steps=50,
+    res = dict(G.tiny_curve(model, "dh128", model_seed=MODEL_SEED, B=B, T=T, n_ap=N_AP, n_beh=N_BEH),
                n_state_keys=len(model.state_dict()), final_norm={k: float(v.double().norm()) for k, v in model.state_dict().items()}, **CFG)
-    print("    dh128 curve", l[:2], "...", l[-1])
     G.save_json("dh128_curve.json", res)
 
 

@@ -179,13 +179,22 @@ def collect_step_multipliers(ops, engine, B, T):
     return out
 
 
+# csrc/attention_long.hip at dh 128: image rows of 272 B, two 128-row chunk images and eight 32-row tiles (139,328 B with the flags),
+# plus per padded key 4 B of bias - and, under CAUSAL / SEP, 4 B of second bias row, 1 B of mod_id and the tile / chunk votes
+# (4 B per 32 and per 128 keys, 16 B) - within 160 KB.  The MASKED need is the larger one: 139,328 + 9.16 LkP <= 163,840 up to LkP = 2656.
+DH128_MAX_LK = 2656
+
+
 def keepbit_path(dh, Lq, Lk):
     """Shapes whose drop_p decisions live in the keep-bit workspace when one is passed (include/mmfm.h: mmfm_attn_desc.keepbits), for
-    the dense and CAUSAL / SEP self-attention launches of the engine (bf16, aligned operands, Lq == Lk)."""
+    the dense and CAUSAL / SEP self-attention launches of the engine (bf16, aligned operands, Lq == Lk): bit groups of 8 queries / keys,
+    and per head dim the limit its kernels' LDS sets."""
     if Lq % 8 or Lk % 8:
         return False
     if dh == 32:
         return Lq <= 256 and Lk <= 224 and (Lk + 31) // 32 <= (Lq + 31) // 32
+    if dh == 128:
+        return Lk <= DH128_MAX_LK
     return dh == 64 and Lk <= 9800
 
 

@@ -131,3 +131,22 @@ def masked_loss_bwd(kind, pred, target, rowmask, grad_out, inv_n, param=0.0):
     g = loss_grad(kind, f64(pred), f64(target), param)
     g = torch.where(mk != 0, g, torch.zeros_like(g))        # an un-masked row's own NaN / inf does not pass the mask
     return (f64(grad_out).reshape(()) * f64(inv_n).reshape(())) * mk * g
+
+
+# ------------------------------------------------------------------------------------------------ the loss-family model
+# tests/test_loss_family_model_gpu.py's three-modality model and batch shape; tests/plan_sig.py pins its step plans
+FAMILY_MODS = [("ap", 12), ("behavior", 2), ("choice", 3)]
+FAMILY_B, FAMILY_T = 2, 8
+
+
+def make_family_model(dtype):
+    import torch.nn as nn
+    from helpers import build_model_mods, tiny_config
+    model = build_model_mods(tiny_config(n_modality=3), FAMILY_MODS, seed=0)
+    model.loss_mod["ap"] = nn.PoissonNLLLoss(log_input=False, full=True, reduction="none")
+    model.loss_mod["behavior"] = nn.HuberLoss(reduction="none", delta=0.5)
+    model.loss_mod["choice"] = nn.BCEWithLogitsLoss(reduction="none")
+    with torch.no_grad():                      # a rate head: predictions must be positive for the reference itself to be finite
+        model.decoder_embeddings["ap"].out.bias.fill_(4.0)
+    model.compute_dtype = dtype
+    return model.cuda()

@@ -184,8 +184,8 @@ def build_case(case):
     from helpers import build_model, load_config, model_config
     B, T = case["B"], case["T"]
     if case["model"] == "loss_family":
-        import test_loss_family_model_gpu as lf
-        model, B, T = lf.make_model(case["dtype"]), lf.B, lf.T
+        import loss_refs as lf
+        model, B, T = lf.make_family_model(case["dtype"]), lf.FAMILY_B, lf.FAMILY_T
     else:
         mc = load_config().model if case["model"] == "default" else model_config(n_enc=2, n_dec=2, **case["model"])
         model = build_model(mc, 668, 2, seed=42)

@@ -8,21 +8,12 @@ import torch
 
 from conftest import load_json
 from helpers import build_model, make_optimizer, model_config
+from model_checks import cosine, to_dev
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 CASES = ["causal", "sep", "causal_sep"]
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
 
 
 def fixture_model(meta, case, dtype="fp32", dropout=0.0):
@@ -33,13 +24,8 @@ def fixture_model(meta, case, dtype="fp32", dropout=0.0):
     return model.cuda()
 
 
-def fixture_batch(meta):
+def synth_fixture_batch(meta):
     return O.synth_batch(meta["B"], meta["T"], meta["n_ap"], meta["n_beh"], seed=meta["data_seed"], pad=meta["pad"])
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -48,7 +34,7 @@ def test_fp32_scalars_vs_reference_fixture(case):
     g = load_json("decoder_mask_scalars.json")
     meta = g["meta"]
     model = fixture_model(meta, case).eval()
-    batch = fixture_batch(meta)
+    batch = synth_fixture_batch(meta)
     for obj in ("encoding", "decoding", "token_masking"):
         c = g["cases"][case][obj]
         model.zero_grad(set_to_none=True)
@@ -70,7 +56,7 @@ def test_bf16_tracks_fixture_and_fp32_engine(case):
     g = load_json("decoder_mask_scalars.json")
     meta = g["meta"]
     model, ref = fixture_model(meta, case, "bf16").eval(), fixture_model(meta, case).eval()
-    batch = fixture_batch(meta)
+    batch = synth_fixture_batch(meta)
     for obj in ("encoding", "decoding"):
         c = g["cases"][case][obj]
         for m in (model, ref):
@@ -97,7 +83,7 @@ def test_bf16_training_step_draws_keep_bits_for_decoder_self_attention(case):
     meta = load_json("decoder_mask_scalars.json")["meta"]
     model = fixture_model(meta, case, "bf16", dropout=0.4).train()
     opt, sch = make_optimizer(model, 10)
-    batch = fixture_batch(meta)
+    batch = synth_fixture_batch(meta)
 
     def step():
         torch.manual_seed(meta["mask_seed"])

@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-import dh128_refs as R128
-import test_dropout_step_gpu as DS
+import dropout_refs as DR
 from conftest import load_json, load_npz
-from helpers import build_model, make_optimizer, model_config
+from helpers import build_model, model_config
+from model_checks import bf16_stats, check_bf16, check_fixture_outputs, engine_step_and_oracle, run_curve, to_dev
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -54,21 +54,9 @@ def test_fp32_forward_backward_vs_reference_fixture(case):
     for k, v in model.state_dict().items():                          # the seed gives the reference's initial parameters
         np.testing.assert_array_equal(sample(v.numpy(), meta["sample"]), z[f"init/{k}"], err_msg=k)
         assert float(v.double().sum()) == pytest.approx(float(z[f"init_stat/{k}"][0]), rel=1e-9, abs=1e-9), k
-    model.cuda().train()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith("batch/")}
-    torch.manual_seed(meta["mask_seed"])
-    md = DS.to_dev(O.make_mod_dict(batch, meta["objective"]))
-    out = model(md)
-    out.loss.backward()
+    check_fixture_outputs(model, z, case, meta["objective"], seed=meta["mask_seed"])
     eng = model._engine
     assert eng.cfg.hidden // eng.cfg.heads == 128
-    print(case, "loss", out.loss.item(), "reference", float(z[f"{case}/loss"]))
-    assert out.loss.item() == pytest.approx(float(z[f"{case}/loss"]), rel=2e-5)
-    for m in ("ap", "behavior"):
-        assert int(out.mod_n_examples[m]) == int(z[f"{case}/n/{m}"])
-        np.testing.assert_array_equal(md[m]["inputs_mask"].cpu().numpy(), z[f"{case}/mask/{m}"])
-        assert out.mod_loss[m].item() == pytest.approx(float(z[f"{case}/mod_loss/{m}"]), rel=5e-5, abs=1e-6)
-        np.testing.assert_allclose(out.mod_preds[m].cpu().numpy(), z[f"{case}/preds/{m}"], rtol=1e-4, atol=2e-5)
     named = dict(model.named_parameters())
     assert list(named) == meta["params"]
     for k in meta["params"]:
@@ -91,18 +79,7 @@ def test_fp32_loss_curve_50_steps_vs_reference_fixture():
                       emb_dropout=0.0)
     model = build_model(mc, g["n_ap"], g["n_beh"], seed=g["model_seed"]).cuda()
     assert len(model.state_dict()) == g["n_state_keys"]
-    opt, sch = make_optimizer(model, g["total_steps"])
-    model.train()
-    torch.manual_seed(1234)
-    losses = []
-    for s in range(50):
-        out = model(DS.to_dev(O.make_mod_dict(O.synth_batch(g["B"], g["T"], g["n_ap"], g["n_beh"], seed=s), g["objective"][s])))
-        out.loss.backward()
-        opt.step()
-        sch.step()
-        opt.zero_grad()
-        losses.append(out.loss.detach())
-    losses = [x.item() for x in losses]
+    losses = run_curve(model, 50, g["B"], g["T"], g["n_ap"], g["n_beh"], g["total_steps"], g["objective"])
     print("max relative gap", float(np.max(np.abs(np.array(losses) / np.array(g["loss"]) - 1))))
     np.testing.assert_allclose(losses, g["loss"], rtol=1e-4)
     worst = 0.0
@@ -124,18 +101,18 @@ def test_bf16_dh128_dropout_step_vs_oracle_fed_the_steps_masks(T):
       T = 70: L = 140 crosses a 128-row chunk; 140 is no multiple of 8, so the launches hand the workspace back and run the general
               tiled kernels of csrc/attention_bf16.hip with hash dropout (the read-out of tests/dropout_refs.py follows that rule).
       T = 72: L = 144, the keep-bit kernels of csrc/attention_long.hip; the masks are the bits of the engine's workspaces.
-    Both go through tests/dh128_refs.py, which knows the launcher's rule at dh 128."""
+    Both are read out under tests/dropout_refs.keepbit_path, the launcher's rule restated."""
     mc = model_config(H=256, heads=2, inter=512, n_enc=1, n_dec=1, max_F=T, causal=True, sep=True)
     batch = O.synth_batch(4, T, 12, 2, seed=6, pad=[0, 10, 0, 37])
-    out, named, ref, grads, eng = R128.engine_step_and_oracle(mc, 12, 2, batch, "encoding", "bf16", 3)
+    out, named, ref, grads, eng = engine_step_and_oracle(mc, 12, 2, batch, "encoding", "bf16", 3)
     sites = eng.dropout_sites(4, T)
     attn = [s for s in sites if s["kind"] == "attn"]
     assert len(attn) == 3 and all(s["dh"] == 128 and s["keepbits"] is not None and s["shape"] == (4, 2, 2 * T, 2 * T) for s in attn)
     nbits = 4 * 2 * ((2 * T + 31) // 32) ** 2 * 128
     wrote = [bool(s["keepbits"][:nbits].any()) for s in attn]
     # (the engine does not clear its workspaces: where the launches hash, L = 140, their bytes say nothing)
-    assert all(wrote) or not R128.keepbit_path(128, 2 * T, 2 * T), "the keep-bit kernels fill every site's bit tiles"
-    DS.check_bf16(DS.bf16_stats(out, named, ref, grads), f"bf16 dh 128, T {T}, dropout on")
+    assert all(wrote) or not DR.keepbit_path(128, 2 * T, 2 * T), "the keep-bit kernels fill every site's bit tiles"
+    check_bf16(bf16_stats(out, named, ref, grads), f"bf16 dh 128, T {T}, dropout on")
 
 
 # ---------------------------------------------------------------------------------------------- hidden 1024
@@ -145,7 +122,7 @@ def test_width_1024_step_fp32_vs_oracle_and_bf16():
     finite and within the bf16 step bound (2e-2) of the fp32 one."""
     mc = model_config(H=1024, heads=8, inter=2048, n_enc=1, n_dec=1, max_F=8, dropout=0.0, emb_dropout=0.0)
     batch = O.synth_batch(2, 8, 12, 2, seed=4, pad=[0, 2])
-    out, named, ref, grads, eng = DS.engine_step_and_oracle(mc, 12, 2, batch, "token_masking", "fp32", 0)
+    out, named, ref, grads, eng = engine_step_and_oracle(mc, 12, 2, batch, "token_masking", "fp32", 0)
     assert eng.cfg.hidden == 1024 and eng.cfg.hidden // eng.cfg.heads == 128
     l32 = out.loss.item()
     assert l32 == pytest.approx(ref["loss"].item(), rel=2e-5)
@@ -162,7 +139,7 @@ def test_width_1024_step_fp32_vs_oracle_and_bf16():
     model.compute_dtype = "bf16"
     model.cuda().train()
     torch.manual_seed(5)
-    o16 = model(DS.to_dev(O.make_mod_dict(batch, "token_masking")))
+    o16 = model(to_dev(O.make_mod_dict(batch, "token_masking")))
     o16.loss.backward()
     l16 = o16.loss.item()
     print("fp32", l32, "bf16", l16, "relative gap", abs(l16 - l32) / abs(l32))

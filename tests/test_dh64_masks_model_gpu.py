@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from helpers import build_model_mods, make_optimizer, model_config
+from model_checks import to_dev
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -14,16 +15,6 @@ pytestmark = pytest.mark.gpu
 MODS = [("ap", 24), ("behavior", 2), ("lfp", 8)]
 B, T = 4, 40
 CASES = {"causal": dict(causal=True), "sep": dict(sep=True), "causal_sep": dict(causal=True, sep=True)}
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
 
 
 def make(**kw):

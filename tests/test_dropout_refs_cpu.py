@@ -112,3 +112,4 @@ def test_survivor_scale_is_the_fp32_quotient():
     assert DR.survivor_scale(0.4) == float(torch.tensor(1.0) / (torch.tensor(1.0) - torch.tensor(0.4)))
     assert DR.survivor_scale(0.25) == 4.0 / 3.0 or abs(DR.survivor_scale(0.25) - 4.0 / 3.0) < 1e-7
     assert DR.keepbit_path(32, 200, 200) and DR.keepbit_path(64, 600, 600) and not DR.keepbit_path(32, 264, 264) and not DR.keepbit_path(32, 204, 204)
+    assert DR.keepbit_path(128, 200, 200) and DR.keepbit_path(128, 2656, 2656) and not DR.keepbit_path(128, 2664, 2664) and not DR.keepbit_path(128, 204, 204)

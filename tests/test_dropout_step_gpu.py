@@ -11,67 +11,16 @@ survivor scale applied twice or not at all, or a row-keyed hash off by a row eac
 fail here."""
 import numpy as np
 import pytest
-import torch
 
 import dropout_refs as DR
-from helpers import build_model, model_config, tiny_config
+from helpers import model_config, tiny_config
+from model_checks import bf16_stats, check_bf16, engine_step_and_oracle
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 VARIANTS = {"base": (dict(), None), "pad": (dict(), [0, 3, 1]), "sep": (dict(sep=True), [0, 2, 0]), "causal": (dict(causal=True), [1, 0, 0]),
             "deep": (dict(n_enc=2, n_dec=2), [0, 0, 5])}
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
-
-
-def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed):
-    """One training step of the HIP engine, then the fp64 oracle (on the GPU, plain torch) with the step's token masks and dropout
-    multipliers.  Returns the model output, {name: grad}, the oracle's output dict, {name: oracle grad} and the engine."""
-    from multi_modal_foundation_model_amd import ops as K
-    model = build_model(mc, n_ap, n_beh, seed=model_seed)
-    model.compute_dtype = dtype
-    model.engine_seed = 77
-    model.cuda().train()
-    torch.manual_seed(5)
-    md = to_dev(O.make_mod_dict(batch, objective))
-    out = model(md)
-    out.loss.backward()
-    torch.cuda.synchronize()
-    eng = model._engine
-    B, T = batch["spikes_data"].shape[:2]
-    mults = {k: v.cuda() for k, v in DR.collect_step_multipliers(K, eng, B, T).items()}
-    cfg = O.OracleCfg.from_model_config(mc, {"ap": n_ap, "behavior": n_beh})
-    sd = O.share_mod_emb({k: v.detach().double().clone() for k, v in model.state_dict().items()}, cfg)
-    keys = O.trainable_keys(sd, cfg)
-    for k in keys:
-        sd[k].requires_grad_(True)
-    ref_md = O.make_mod_dict(batch, objective)
-    for m, d in ref_md.items():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda().double() if v.is_floating_point() else v.cuda()
-        d["eval_mask"] = md[m]["inputs_mask"][:, :, None].to(torch.int64)          # the token masks the step ran with
-    used = set()
-    ref = O.forward(sd, ref_md, cfg, training=True, dropout_fn=DR.oracle_dropout_fn(mults, used))
-    assert used == set(mults), sorted(set(mults) ^ used)                           # every site of the engine is a site of the model
-    grads = dict(zip(keys, torch.autograd.grad(ref["loss"], [sd[k] for k in keys])))
-    named = {k: p.grad for k, p in model.named_parameters()}
-    assert set(named) == set(keys)
-    return out, named, ref, grads, eng
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
@@ -95,34 +44,6 @@ def test_fp32_dropout_step_vs_oracle_fed_the_steps_masks(variant, objective):
     for k, g in named.items():
         r = grads[k].cpu().numpy()
         np.testing.assert_allclose(g.cpu().numpy(), r, rtol=2e-3, atol=3e-6 + 1e-4 * np.abs(r).max(), err_msg=k)
-
-
-def bf16_stats(out, named, ref, grads):
-    """Worst loss error, gradient cosine (tensors of >= 256 / < 256 elements) and norm ratio error over all tensors but key.bias
-    (softmax is invariant to a key bias: its true gradient is 0)."""
-    st = dict(loss=abs(out.loss.item() / ref["loss"].item() - 1), cos_big=1.0, cos_small=1.0, norm=0.0)
-    for k, g in named.items():
-        r = grads[k]
-        if k.endswith("key.bias"):
-            continue
-        if float(r.abs().max()) == 0:
-            assert float(g.abs().max()) == 0, k
-            continue
-        c = cosine(g, r)
-        which = "cos_big" if r.numel() >= 256 else "cos_small"
-        if c < st[which]:
-            st[which], st[which + "_at"] = c, k
-        n = abs(g.double().norm().item() / r.norm().item() - 1)
-        if n > st["norm"]:
-            st["norm"], st["norm_at"] = n, k
-    return st
-
-
-def check_bf16(st, what):
-    print(f"{what}: {st}")
-    assert st["loss"] < 2e-2, (what, st)
-    assert st["cos_big"] > 0.995 and st["cos_small"] > 0.98, (what, st)
-    assert st["norm"] < 5e-2, (what, st)
 
 
 @pytest.mark.parametrize("dropout", ["off", "on"])

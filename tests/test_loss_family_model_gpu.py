@@ -8,35 +8,14 @@ import torch.nn as nn
 
 import edge_refs as E
 import loss_refs as R
-from helpers import build_model, build_model_mods, load_config, tiny_config
+from helpers import build_model, load_config
+from model_checks import to_dev
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-MODS = [("ap", 12), ("behavior", 2), ("choice", 3)]
-B, T = 2, 8
+MODS, B, T, make_model = R.FAMILY_MODS, R.FAMILY_B, R.FAMILY_T, R.make_family_model
 SPECS = {"ap": (R.POISSON_RATE, 1e-8, R.FULL), "behavior": (R.HUBER, 0.5, 0), "choice": (R.BCE_LOGITS, 0.0, 0)}
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
-
-
-def make_model(dtype):
-    model = build_model_mods(tiny_config(n_modality=3), MODS, seed=0)
-    model.loss_mod["ap"] = nn.PoissonNLLLoss(log_input=False, full=True, reduction="none")
-    model.loss_mod["behavior"] = nn.HuberLoss(reduction="none", delta=0.5)
-    model.loss_mod["choice"] = nn.BCEWithLogitsLoss(reduction="none")
-    with torch.no_grad():                      # a rate head: predictions must be positive for the reference itself to be finite
-        model.decoder_embeddings["ap"].out.bias.fill_(4.0)
-    model.compute_dtype = dtype
-    return model.cuda()
 
 
 def make_batch():

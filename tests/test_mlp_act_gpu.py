@@ -1,14 +1,13 @@
 """transformer.act = relu / silu / quick_gelu / gelu_new on the MI355X: the GEMM epilogues (fp32, bf16 128-tile, bf16 256-tile), the
 fused MLP kernels (forward, one-launch backward, front half + rowgemm) against fp64 torch, and whole models against the reference's
 own forward / backward (tests/golden/mlp_act_*, scripts/make_mlp_act_goldens.py)."""
-import random
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_json, load_npz
 from helpers import build_model, make_optimizer, model_config, tiny_config
+from model_checks import check_fixture_case, cosine, resume_roundtrip, run_curve, to_dev
 from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd import ops as K
 from oracle import mm_oracle as O
@@ -33,21 +32,6 @@ def df_ref(kind, beta, u):
     u = u.double().clone().requires_grad_(True)
     f_ref(kind, beta, u).backward(torch.ones_like(u))
     return u.grad
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-300))
 
 
 def bf(t):
@@ -273,45 +257,7 @@ def fixture():
 @pytest.mark.parametrize("objective", ["encoding", "decoding", "token_masking"])
 def test_tiny_forward_backward_vs_reference_fixture(act, objective):
     z, meta = fixture()
-    model = build_model(tiny_config(act=act), meta["n_ap"], meta["n_beh"], seed=meta["model_seed"])
-    model.cuda().train()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith("batch/")}
-    torch.manual_seed(11)
-    md = to_dev(O.make_mod_dict(batch, objective))
-    out = model(md)
-    out.loss.backward()
-    p = f"{act}/{objective}"
-    assert out.loss.item() == pytest.approx(float(z[f"{p}/loss"]), rel=2e-5)
-    for m in ("ap", "behavior"):
-        assert int(out.mod_n_examples[m]) == int(z[f"{p}/n/{m}"])
-        np.testing.assert_array_equal(md[m]["inputs_mask"].cpu().numpy(), z[f"{p}/mask/{m}"])
-        assert out.mod_loss[m].item() == pytest.approx(float(z[f"{p}/mod_loss/{m}"]), rel=5e-5, abs=1e-6)
-        np.testing.assert_allclose(out.mod_preds[m].cpu().numpy(), z[f"{p}/preds/{m}"], rtol=1e-4, atol=2e-5)
-    names = meta["params"][act]
-    named = dict(model.named_parameters())
-    assert list(named) == names
-    for k, gn in zip(names, z[f"{p}/grad_norm"]):
-        assert float(named[k].grad.double().norm()) == pytest.approx(float(gn), rel=5e-3, abs=1e-8), k
-    stored = [k for k in names if f"{p}/grad/{k}" in z.files]
-    assert (objective != meta["full_grad"]) or len(stored) == len(names)
-    for k in stored:
-        g, ref = named[k].grad.cpu().numpy(), z[f"{p}/grad/{k}"]
-        np.testing.assert_allclose(g, ref, rtol=2e-3, atol=3e-6 + 1e-4 * np.abs(ref).max(), err_msg=k)
-
-
-def run_curve(model, steps, B, T, n_ap, n_beh, total_steps, objectives):
-    opt, sch = make_optimizer(model, total_steps)
-    model.train()
-    torch.manual_seed(1234)
-    losses = []
-    for s in range(steps):
-        out = model(to_dev(O.make_mod_dict(O.synth_batch(B, T, n_ap, n_beh, seed=s), objectives[s])))
-        out.loss.backward()
-        opt.step()
-        sch.step()
-        opt.zero_grad()
-        losses.append(out.loss.detach())
-    return [x.item() for x in losses]
+    check_fixture_case(build_model(tiny_config(act=act), meta["n_ap"], meta["n_beh"], seed=meta["model_seed"]), z, meta, act, objective)
 
 
 @pytest.mark.parametrize("act", list(KINDS))
@@ -402,48 +348,4 @@ def test_bf16_drift_against_fp32_over_12_steps(monkeypatch, act):
 # ---------------------------------------------------------------------------------------------- resume
 def test_silu_resume_from_train_state_is_bit_identical(tmp_path):
     """6 steps in one go == 3 steps, save_model + train state, fresh objects restored from the files, 3 more steps (bf16, dropout on)."""
-    from trainer.make import make_multimodal_trainer
-    from multi_modal_foundation_model_amd.ddp import Accelerator
-    from helpers import load_config
-    B, T, n_ap, n_beh = 4, 8, 12, 2
-    mc = tiny_config(n_enc=2, n_dec=2, dropout=0.4, emb_dropout=0.2, act="silu")
-
-    def batches(lo, hi):
-        out = []
-        for i in range(lo, hi):
-            b = O.synth_batch(B, T, n_ap, n_beh, seed=i)
-            b["eid"] = ["synthetic"] * B
-            b["neuron_regions"] = [["XX"] * B for _ in range(n_ap)]
-            out.append(b)
-        return out
-
-    def make(model, loader, log_dir):
-        model.compute_dtype = "bf16"
-        acc = Accelerator()
-        model = acc.prepare(model)
-        opt, sch = make_optimizer(model, 40, lr=1e-3)
-        tr = make_multimodal_trainer(model=model, train_dataloader=loader, eval_dataloader=[], optimizer=opt, log_dir=str(log_dir),
-                                     accelerator=acc, lr_scheduler=sch, avail_mod=["ap", "behavior"], config=load_config(),
-                                     modal_filter=dict(input=["ap", "behavior"], output=["ap", "behavior"]), mixed_training=True,
-                                     num_neurons=[n_ap])
-        return model, opt, sch, tr
-
-    m0 = build_model(mc, n_ap, n_beh, seed=7); m0.engine_seed = 5
-    m0, opt0, sch0, tr0 = make(m0, batches(0, 6), tmp_path / "a")
-    random.seed(42); torch.manual_seed(99)
-    tr0.train_epoch(0)
-    want = {k: v.detach().clone() for k, v in m0.state_dict().items()}
-    m1 = build_model(mc, n_ap, n_beh, seed=7); m1.engine_seed = 5
-    (tmp_path / "b").mkdir()
-    m1, opt1, sch1, tr1 = make(m1, batches(0, 3), tmp_path / "b")
-    random.seed(42); torch.manual_seed(99)
-    tr1.train_epoch(0)
-    tr1.save_model(name="last", epoch=0)
-    del m1, opt1, sch1, tr1
-    random.seed(0); torch.manual_seed(0)
-    ck = torch.load(tmp_path / "b" / "model_last.pt", weights_only=False)
-    m2, opt2, sch2, tr2 = make(ck["model"], batches(3, 6), tmp_path / "b")
-    assert tr2.load_train_state(name="last") == 0
-    tr2.train_epoch(1)
-    for k, v in m2.state_dict().items():
-        assert torch.equal(v, want[k]), k
+    resume_roundtrip(tmp_path, tiny_config(n_enc=2, n_dec=2, dropout=0.4, emb_dropout=0.2, act="silu"), dtype="bf16")

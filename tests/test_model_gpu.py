@@ -11,21 +11,12 @@ import torch
 
 from conftest import load_json, load_npz
 from helpers import build_model, build_model_mods, load_config, make_optimizer, model_config, tiny_config
+from model_checks import check_fixture_outputs, check_stored_grads, cosine, fixture_batch, resume_roundtrip, run_curve, to_dev
 from oracle import mm_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 VARIANT_KW = {"base": {}, "pad": {}, "sep": dict(sep=True), "causal": dict(causal=True), "deep": dict(n_enc=2, n_dec=2)}
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
 
 
 @pytest.mark.parametrize("variant", list(VARIANT_KW))
@@ -36,25 +27,12 @@ def test_tiny_forward_backward_vs_reference_fixture(variant, objective):
     pre = f"{variant}/sd/"
     sd = {k[len(pre):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(pre)}
     model.load_state_dict(sd)
-    model.cuda().train()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{variant}/batch/")}
-    torch.manual_seed(11)
-    md = to_dev(O.make_mod_dict(batch, objective))
-    out = model(md)
-    out.loss.backward()
     p = f"{variant}/{objective}"
-    assert out.loss.item() == pytest.approx(float(z[f"{p}/loss"]), rel=2e-5)
-    for m in ("ap", "behavior"):
-        assert int(out.mod_n_examples[m]) == int(z[f"{p}/n/{m}"])                                  # exact
-        np.testing.assert_array_equal(md[m]["inputs_mask"].cpu().numpy(), z[f"{p}/mask/{m}"])     # exact
-        assert out.mod_loss[m].item() == pytest.approx(float(z[f"{p}/mod_loss/{m}"]), rel=5e-5, abs=1e-6)
-        np.testing.assert_allclose(out.mod_preds[m].cpu().numpy(), z[f"{p}/preds/{m}"], rtol=1e-4, atol=2e-5)
-    eng = model._engine
-    B, T = batch["spikes_data"].shape[:2]
-    np.testing.assert_allclose(eng.b["enc_out"].view(B, 2 * T, -1).cpu().numpy(), z[f"{p}/enc_out"], rtol=1e-4, atol=2e-5)
-    for k, prm in model.named_parameters():
-        g, ref = prm.grad.cpu().numpy(), z[f"{p}/grad/{k}"]
-        np.testing.assert_allclose(g, ref, rtol=2e-3, atol=3e-6 + 1e-4 * np.abs(ref).max(), err_msg=k)
+    check_fixture_outputs(model, z, p, objective, prefix=f"{variant}/batch/")
+    B, T = z[f"{variant}/batch/spikes_data"].shape[:2]
+    np.testing.assert_allclose(model._engine.b["enc_out"].view(B, 2 * T, -1).cpu().numpy(), z[f"{p}/enc_out"], rtol=1e-4, atol=2e-5)
+    named = dict(model.named_parameters())
+    assert check_stored_grads(named, z, p, list(named)) == list(named)           # the fixture keeps every gradient tensor
 
 
 _MM_CASES = list(range(10))
@@ -74,7 +52,7 @@ def test_masker_modes_through_engine_vs_reference_fixture(cid):
     for k, v in c["set"].items():
         setattr(model.masker, k, v)
     model.cuda().train()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith("batch/")}
+    batch = fixture_batch(z)
     torch.manual_seed(31 + cid)
     random.seed(41 + cid)
     md = O.make_mod_dict(batch, "token_masking")
@@ -208,21 +186,6 @@ def test_config5_bf16_drift_against_fp32_engine_and_dropout_run():
     assert np.isfinite(ld).all()
     assert ld[0] == pytest.approx(l16[0], rel=0.3)
     assert any(k.endswith("/keep") for k in md._engine.b), "the keep-bit attention workspaces were not allocated: dropout ran on the hash path"
-
-
-def run_curve(model, steps, B, T, n_ap, n_beh, total_steps, objectives):
-    opt, sch = make_optimizer(model, total_steps)
-    model.train()
-    torch.manual_seed(1234)
-    losses = []
-    for s in range(steps):
-        out = model(to_dev(O.make_mod_dict(O.synth_batch(B, T, n_ap, n_beh, seed=s), objectives[s])))
-        out.loss.backward()
-        opt.step()
-        sch.step()
-        opt.zero_grad()
-        losses.append(out.loss.detach())
-    return [x.item() for x in losses]
 
 
 def test_loss_curve_tiny_50_steps_vs_reference_fixture():
@@ -443,11 +406,6 @@ def test_checkpoint_pickle_roundtrip(tmp_path):
 
 
 # ------------------------------------------------------------------------------------ bf16 throughput mode
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
-
-
 def test_bf16_mode_tracks_fp32_reference_fixture():
     """bf16 storage / fp32 accumulate vs the fp32 reference numbers: stated tolerance 2e-2 on the loss,
     gradient direction cosine >= 0.99 per large tensor (bf16 has 8 significant bits)."""
@@ -605,53 +563,10 @@ def test_resume_from_train_state_is_bit_identical(tmp_path, dtype):
     """6 steps in one go == 3 steps, save_model (module pickle + train state), brand-new model / optimiser /
     scheduler / trainer objects restored from the files, 3 more steps.  Dropout is on (engine RNG), objectives are sampled
     (Python RNG) and token_masking draws masks (torch RNG): all three streams must continue exactly."""
-    from trainer.make import make_multimodal_trainer
-    from multi_modal_foundation_model_amd.ddp import Accelerator
-    B, T, n_ap, n_beh = 4, 8, 12, 2
-    mc = tiny_config(n_enc=2, n_dec=2, dropout=0.4, emb_dropout=0.2)
+    def after_restore(m2, opt2, sch2):
+        assert opt2._t == 3 and sch2.last_epoch == 3
 
-    def batches(lo, hi):
-        out = []
-        for i in range(lo, hi):
-            b = O.synth_batch(B, T, n_ap, n_beh, seed=i)
-            b["eid"] = ["synthetic"] * B
-            b["neuron_regions"] = [["XX"] * B for _ in range(n_ap)]
-            out.append(b)
-        return out
-
-    def make(model, loader, log_dir):
-        model.compute_dtype = dtype
-        acc = Accelerator()
-        model = acc.prepare(model)
-        opt, sch = make_optimizer(model, 40, lr=1e-3)
-        tr = make_multimodal_trainer(model=model, train_dataloader=loader, eval_dataloader=[], optimizer=opt, log_dir=str(log_dir),
-                                     accelerator=acc, lr_scheduler=sch, avail_mod=["ap", "behavior"], config=load_config(),
-                                     modal_filter=dict(input=["ap", "behavior"], output=["ap", "behavior"]), mixed_training=True,
-                                     num_neurons=[n_ap])
-        return model, opt, sch, tr
-
-    # reference run: 6 steps
-    m0 = build_model(mc, n_ap, n_beh, seed=7); m0.engine_seed = 5
-    m0, opt0, sch0, tr0 = make(m0, batches(0, 6), tmp_path / "a")
-    random.seed(42); torch.manual_seed(99)
-    tr0.train_epoch(0)
-    want = {k: v.detach().clone() for k, v in m0.state_dict().items()}
-    # interrupted run: 3 steps, save, fresh objects, 3 more
-    m1 = build_model(mc, n_ap, n_beh, seed=7); m1.engine_seed = 5
-    (tmp_path / "b").mkdir()
-    m1, opt1, sch1, tr1 = make(m1, batches(0, 3), tmp_path / "b")
-    random.seed(42); torch.manual_seed(99)
-    tr1.train_epoch(0)
-    tr1.save_model(name="last", epoch=0)
-    del m1, opt1, sch1, tr1
-    random.seed(0); torch.manual_seed(0)                                  # scramble every host stream
-    ck = torch.load(tmp_path / "b" / "model_last.pt", weights_only=False)  # our own file (whole-module pickle, like the reference)
-    m2, opt2, sch2, tr2 = make(ck["model"], batches(3, 6), tmp_path / "b")
-    assert tr2.load_train_state(name="last") == 0
-    assert opt2._t == 3 and sch2.last_epoch == 3
-    tr2.train_epoch(1)
-    for k, v in m2.state_dict().items():
-        assert torch.equal(v, want[k]), k
+    resume_roundtrip(tmp_path, tiny_config(n_enc=2, n_dec=2, dropout=0.4, emb_dropout=0.2), dtype=dtype, after_restore=after_restore)
 
 
 def test_optimizer_step_without_backward_is_a_noop():

@@ -2,35 +2,20 @@
 forward / backward and 50-step curves (tests/golden/side_config_*, scripts/make_side_config_goldens.py); a bf16 model whose encoder runs
 the row-owner MLP kernels (8 heads, inter 512) and whose decoder the un-fused GEMMs (4 heads = dh 64, inter 1024, relu) against the fp32
 engine and against the un-fused kernels, with the launches read off the plan; dropout per side; checkpoint resume and hipGraph replay."""
-import random
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_json
-from helpers import build_model, make_optimizer
+from helpers import build_model
+from model_checks import (check_fixture_case, cosine, fixture_batch, graph_replay_matches_eager, resume_roundtrip, run_curve,
+                          to_dev)
 from oracle import mm_oracle as O
 from side_config import CASES, OBJECTIVES, case_config, fixture, sides
 
 pytestmark = pytest.mark.gpu
 B, T, N_AP, N_BEH = 4, 100, 48, 2          # the bf16 tests' batch: R = 800 rows of H = 256
 MIXED = dict(dec=dict(n_heads=4, inter_size=1024, act="relu"), n_enc=2, n_dec=2)      # on the YAML's encoder: 8 heads, inter 512, gelu
-
-
-def to_dev(md):
-    for d in md.values():
-        for k, v in list(d.items()):
-            if isinstance(v, torch.Tensor):
-                d[k] = v.cuda()
-        d["targets_modality"] = d["inputs_modality"]
-        d["targets_timestamp"] = d["inputs_timestamp"]
-    return md
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-300))
 
 
 def attn_descs(plan, which="fwd"):
@@ -47,32 +32,7 @@ def test_tiny_forward_backward_vs_reference_fixture(case, objective):
     """Loss, counts (exact), predictions, every gradient norm and (ALL / token_masking) every gradient tensor; the tolerances of
     test_linear_bias_model_gpu.py::test_tiny_forward_backward_vs_reference_fixture."""
     z, meta = fixture()
-    model = build_model(case_config(case), meta["n_ap"], meta["n_beh"], seed=meta["model_seed"])
-    model.cuda().train()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith("batch/")}
-    torch.manual_seed(11)
-    md = to_dev(O.make_mod_dict(batch, objective))
-    out = model(md)
-    out.loss.backward()
-    p = f"{case}/{objective}"
-    print(p, "loss", out.loss.item(), "reference", float(z[f"{p}/loss"]))
-    assert out.loss.item() == pytest.approx(float(z[f"{p}/loss"]), rel=2e-5)
-    for m in ("ap", "behavior"):
-        assert int(out.mod_n_examples[m]) == int(z[f"{p}/n/{m}"])
-        np.testing.assert_array_equal(md[m]["inputs_mask"].cpu().numpy(), z[f"{p}/mask/{m}"])
-        assert out.mod_loss[m].item() == pytest.approx(float(z[f"{p}/mod_loss/{m}"]), rel=5e-5, abs=1e-6)
-        np.testing.assert_allclose(out.mod_preds[m].cpu().numpy(), z[f"{p}/preds/{m}"], rtol=1e-4, atol=2e-5)
-    names = meta["params"][case]
-    named = dict(model.named_parameters())
-    assert list(named) == names
-    assert list(model.state_dict()) == [k for k, _ in meta["state"][case]]
-    for k, gn in zip(names, z[f"{p}/grad_norm"]):
-        assert float(named[k].grad.double().norm()) == pytest.approx(float(gn), rel=5e-3, abs=1e-8), k
-    stored = [k for k in names if f"{p}/grad/{k}" in z.files]
-    assert len(stored) == (len(names) if objective == meta["full_grad"] and case in meta["full_grad_cases"] else 0)
-    for k in stored:
-        g, ref = named[k].grad.cpu().numpy(), z[f"{p}/grad/{k}"]
-        np.testing.assert_allclose(g, ref, rtol=2e-3, atol=3e-6 + 1e-4 * np.abs(ref).max(), err_msg=k)
+    check_fixture_case(build_model(case_config(case), meta["n_ap"], meta["n_beh"], seed=meta["model_seed"]), z, meta, case, objective)
 
 
 def test_drop0_control_is_the_unmixed_model():
@@ -80,7 +40,7 @@ def test_drop0_control_is_the_unmixed_model():
     model's, bit for bit."""
     from helpers import tiny_config
     z, meta = fixture()
-    batch = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith("batch/")}
+    batch = fixture_batch(z)
     res = []
     for mc in (case_config("DROP0"), tiny_config()):
         model = build_model(mc, meta["n_ap"], meta["n_beh"], seed=meta["model_seed"]).cuda().train()
@@ -91,21 +51,6 @@ def test_drop0_control_is_the_unmixed_model():
     (c0, l0, g0), (c1, l1, g1) = res
     assert c0 == c1 and l0 == l1 and list(g0) == list(g1)
     assert all(torch.equal(g0[k], g1[k]) for k in g0)
-
-
-def run_curve(model, steps, Bc, Tc, n_ap, n_beh, total_steps, objectives):
-    opt, sch = make_optimizer(model, total_steps)
-    model.train()
-    torch.manual_seed(1234)
-    losses = []
-    for s in range(steps):
-        out = model(to_dev(O.make_mod_dict(O.synth_batch(Bc, Tc, n_ap, n_beh, seed=s), objectives[s])))
-        out.loss.backward()
-        opt.step()
-        sch.step()
-        opt.zero_grad()
-        losses.append(out.loss.detach())
-    return [x.item() for x in losses]
 
 
 @pytest.mark.parametrize("case", ["ALL", "HEADS"])
@@ -256,68 +201,19 @@ def test_no_dropout_anywhere_is_deterministic_and_decoder_embedder_dropout_is_re
 def test_all_case_resume_from_train_state_is_bit_identical(tmp_path):
     """The ALL tiny model in fp32: 6 steps in one go == 3 steps, save_model + save_train_state, fresh objects restored from the files
     (load_train_state), 3 more steps."""
-    from trainer.make import make_multimodal_trainer
-    from multi_modal_foundation_model_amd.ddp import Accelerator
-    from helpers import load_config
-    Bc, Tc, n_ap, n_beh = 2, 8, 12, 2
-    mc = case_config("ALL", n_enc=2, n_dec=2)
+    def after_save(ck):
+        keys = list(ck["model"].state_dict())
+        assert "encoder.1.ln1.scale" in keys and "decoder.1.ln1.weight" in keys
 
-    def batches(lo, hi):
-        out = []
-        for i in range(lo, hi):
-            b = O.synth_batch(Bc, Tc, n_ap, n_beh, seed=i)
-            b["eid"] = ["synthetic"] * Bc
-            b["neuron_regions"] = [["XX"] * Bc for _ in range(n_ap)]
-            out.append(b)
-        return out
+    def after_restore(m2, opt2, sch2):
+        enc, dec = (m2._engine.cfg.side(s) for s in ("encoder", "decoder"))
+        assert (enc.heads, dec.heads, enc.inter, dec.inter, enc.norm, dec.norm) == (4, 2, 64, 128, "scalenorm", "layernorm")
 
-    def make(model, loader, log_dir):
-        model.compute_dtype = "fp32"
-        acc = Accelerator()
-        model = acc.prepare(model)
-        opt, sch = make_optimizer(model, 40, lr=1e-3)
-        tr = make_multimodal_trainer(model=model, train_dataloader=loader, eval_dataloader=[], optimizer=opt, log_dir=str(log_dir),
-                                     accelerator=acc, lr_scheduler=sch, avail_mod=["ap", "behavior"], config=load_config(),
-                                     modal_filter=dict(input=["ap", "behavior"], output=["ap", "behavior"]), mixed_training=True,
-                                     num_neurons=[n_ap])
-        return model, opt, sch, tr
-
-    m0 = build_model(mc, n_ap, n_beh, seed=7); m0.engine_seed = 5
-    m0, opt0, sch0, tr0 = make(m0, batches(0, 6), tmp_path / "a")
-    random.seed(42); torch.manual_seed(99)
-    tr0.train_epoch(0)
-    want = {k: v.detach().clone() for k, v in m0.state_dict().items()}
-    m1 = build_model(mc, n_ap, n_beh, seed=7); m1.engine_seed = 5
-    (tmp_path / "b").mkdir()
-    m1, opt1, sch1, tr1 = make(m1, batches(0, 3), tmp_path / "b")
-    random.seed(42); torch.manual_seed(99)
-    tr1.train_epoch(0)
-    tr1.save_model(name="last", epoch=0)
-    del m1, opt1, sch1, tr1
-    random.seed(0); torch.manual_seed(0)
-    ck = torch.load(tmp_path / "b" / "model_last.pt", weights_only=False)
-    keys = list(ck["model"].state_dict())
-    assert "encoder.1.ln1.scale" in keys and "decoder.1.ln1.weight" in keys
-    m2, opt2, sch2, tr2 = make(ck["model"], batches(3, 6), tmp_path / "b")
-    assert tr2.load_train_state(name="last") == 0
-    enc, dec = (m2._engine.cfg.side(s) for s in ("encoder", "decoder"))
-    assert (enc.heads, dec.heads, enc.inter, dec.inter, enc.norm, dec.norm) == (4, 2, 64, 128, "scalenorm", "layernorm")
-    tr2.train_epoch(1)
-    assert list(m2.state_dict()) == list(want)
-    for k, v in m2.state_dict().items():
-        assert torch.equal(v, want[k]), k
+    resume_roundtrip(tmp_path, case_config("ALL", n_enc=2, n_dec=2), B=2, after_save=after_save, after_restore=after_restore)
 
 
 def test_all_case_graph_replay_gives_the_eager_losses(monkeypatch):
     """The ALL tiny model, 5 optimiser steps in fp32: with hipGraph replay (the plan runs eagerly once, is captured on the second step and
     replayed from the third) the losses are the ones of MMFM_GRAPH=0, bit for bit."""
     g = load_json("side_config_curve.json")["ALL"]
-    res = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("MMFM_GRAPH", mode)
-        model = build_model(case_config("ALL"), g["n_ap"], g["n_beh"], seed=g["model_seed"]).cuda()
-        res[mode] = run_curve(model, 5, g["B"], g["T"], g["n_ap"], g["n_beh"], g["total_steps"], ["token_masking"] * 5)
-        plan = model._engine._last
-        assert (set(plan["graphs"]) == {"fwd", "bwd"}) == (mode == "1") and plan["runs"]["fwd"] == 5
-    print("eager", res["0"], "graph", res["1"])
-    assert res["0"] == res["1"] and all(np.isfinite(res["0"]))
+    graph_replay_matches_eager(monkeypatch, lambda: build_model(case_config("ALL"), g["n_ap"], g["n_beh"], seed=g["model_seed"]), g)
