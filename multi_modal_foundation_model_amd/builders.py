@@ -57,34 +57,34 @@ def tiny_config(**kw):
     return model_config(**base)
 
 
-def build_model(mcfg, n_ap, n_beh, seed=None):
-    """train_multi_modal.py:160-189 (construction order = RNG contract)."""
-    from multi_modal.mm import MultiModal
-    from multi_modal.encoder_embeddings import EncoderEmbedding
-    from multi_modal.decoder_embeddings import DecoderEmbedding
-    if seed is not None:
-        torch.manual_seed(seed)
-    enc, dec = {}, {}
-    for mod in ("ap", "behavior"):
-        enc[mod] = EncoderEmbedding(hidden_size=mcfg.encoder.transformer.hidden_size, n_channel=n_ap if mod == "ap" else n_beh,
-                                    config=mcfg.encoder)
-    for mod in ("ap", "behavior"):
-        dec[mod] = DecoderEmbedding(hidden_size=mcfg.decoder.transformer.hidden_size, n_channel=n_ap if mod == "ap" else n_beh,
-                                    output_channel=n_ap if mod == "ap" else n_beh, config=mcfg.decoder)
-    return MultiModal(enc, dec, avail_mod=["ap", "behavior"], config=mcfg, share_modality_embeddings=True)
+def _filtered(mods, modal_filter):
+    """(encoder modalities, decoder modalities) of `modal_filter` = dict(input=[...], output=[...]) (train_multi_modal.py), each in the
+    order the filter names them - the construction order, which is the RNG contract; None: every modality on both sides."""
+    if modal_filter is None:
+        return list(mods), list(mods)
+    chan = dict(mods)
+    return [(m, chan[m]) for m in modal_filter["input"]], [(m, chan[m]) for m in modal_filter["output"]]
 
 
-def build_model_mods(mcfg, mods, seed=None):
+def build_model(mcfg, n_ap, n_beh, seed=None, modal_filter=None, share_modality_embeddings=True):
+    """train_multi_modal.py:160-189 (construction order = RNG contract).  modal_filter: dict(input=[...], output=[...]), the
+    modalities the encoder / the decoder gets tokenisers for (None: both get both)."""
+    return build_model_mods(mcfg, [("ap", n_ap), ("behavior", n_beh)], seed=seed, modal_filter=modal_filter,
+                            share_modality_embeddings=share_modality_embeddings)
+
+
+def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_embeddings=True):
     """Same construction order for an arbitrary modality list [(name, channels)] (BASELINE configs[4]: 3 modalities)."""
     from multi_modal.mm import MultiModal
     from multi_modal.encoder_embeddings import EncoderEmbedding
     from multi_modal.decoder_embeddings import DecoderEmbedding
     if seed is not None:
         torch.manual_seed(seed)
-    H = mcfg.encoder.transformer.hidden_size
-    enc = {m: EncoderEmbedding(hidden_size=H, n_channel=n, config=mcfg.encoder) for m, n in mods}
-    dec = {m: DecoderEmbedding(hidden_size=H, n_channel=n, output_channel=n, config=mcfg.decoder) for m, n in mods}
-    return MultiModal(enc, dec, avail_mod=[m for m, _ in mods], config=mcfg, share_modality_embeddings=True)
+    enc_mods, dec_mods = _filtered(mods, modal_filter)
+    enc = {m: EncoderEmbedding(hidden_size=mcfg.encoder.transformer.hidden_size, n_channel=n, config=mcfg.encoder) for m, n in enc_mods}
+    dec = {m: DecoderEmbedding(hidden_size=mcfg.decoder.transformer.hidden_size, n_channel=n, output_channel=n, config=mcfg.decoder)
+           for m, n in dec_mods}
+    return MultiModal(enc, dec, avail_mod=[m for m, _ in mods], config=mcfg, share_modality_embeddings=share_modality_embeddings)
 
 
 def make_optimizer(model, total_steps, lr=1e-4, wd=0.01, eps=1e-8):

@@ -46,6 +46,9 @@ PER_SIDE = ("heads", "inter", "dropout", "norm", "act", "embed_scale", "embed_dr
 # The embedder options (embedder.act / pos / bias), per side in the same way.  They are constructor keywords and attributes of the config but
 # not dataclass fields (InitVar): the field list, asdict() and the constructor calls from before they existed are what they were
 PER_SIDE_EMBED = ("embed_act", "embed_pos", "embed_bias")
+# The modality sets of the two sides (modal_filter) and whether their tokenisers share mod_emb tables: constructor keywords and attributes
+# like the embedder options, and like them no dataclass fields
+MODAL = ("enc_mods", "dec_mods", "share_mod_emb")
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -84,11 +87,30 @@ class EngineConfig:
     embed_act: InitVar[str] = "softsign"
     embed_pos: InitVar[bool] = True
     embed_bias: InitVar[bool] = True
+    # modal_filter (train_multi_modal.py): the modalities the encoder / the decoder has tokenisers (and the decoder heads) for, names out
+    # of `mods`; None = all of them.  Held in `mods` order, whatever order they were named in; a list that names every modality is
+    # folded into None, so the config that names them all equals the config that names none.  share_mod_emb
+    # (share_modality_embeddings): a decoder tokeniser of a modality the encoder has too reads the ENCODER's mod_emb table (mm.py:84-87);
+    # False, or a modality the encoder lacks: the decoder tokeniser owns its table.  Read through `side_mods` / `mod_emb_owner`
+    enc_mods: InitVar[Optional[List[str]]] = None
+    dec_mods: InitVar[Optional[List[str]]] = None
+    share_mod_emb: InitVar[bool] = True
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
-    # `n_modality` (the decoder's mod_emb IS the encoder's tensor, mm.py:84-87).  Read a side's values through `side()`
+    # `n_modality` (a shared mod_emb is one tensor, mm.py:84-87, and the row is the modality's index in `mods` on either side).  Read a
+    # side's values through `side()`
 
-    def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True):
+    def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True):
         self.embed_act, self.embed_pos, self.embed_bias = embed_act, embed_pos, embed_bias
+        names = [m for m, _ in self.mods]
+        for k, v in (("enc_mods", enc_mods), ("dec_mods", dec_mods)):
+            if v is not None:
+                v = list(v)
+                unknown = [m for m in v if m not in names]
+                if unknown or not v or len(set(v)) != len(v):
+                    raise ValueError(f"EngineConfig.{k} = {v}: a non-empty list of distinct names out of mods {names}")
+                v = [m for m in names if m in v]
+            setattr(self, k, None if v == names else v)
+        self.share_mod_emb = bool(share_mod_emb)
         for k in PER_SIDE + PER_SIDE_EMBED:
             v = getattr(self, k)
             pair = isinstance(v, (tuple, list)) and len(v) == 2 and (k != "act" or isinstance(v[0], (tuple, list)))
@@ -99,7 +121,7 @@ class EngineConfig:
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED)
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL)
 
     __hash__ = None
 
@@ -111,20 +133,37 @@ class EngineConfig:
         return SideConfig(*(getattr(v, side) if isinstance(v, Sides) else v for v in vals),
                           attn_bias=getattr(self, side[:3] + "_attn_bias"), mlp_bias=getattr(self, side[:3] + "_mlp_bias"))
 
+    def side_mods(self, side: str) -> List[Tuple[int, str, int]]:
+        """The modalities "encoder" or "decoder" has tokenisers for, in `mods` order: (index in `mods`, name, channels).  The index is the
+        modality's mod_emb row (mod_to_indx) and names its buffers; its place in this list is its slot in the side's stitched sequence."""
+        if side not in ("encoder", "decoder"):
+            raise ValueError(f"EngineConfig.side_mods({side!r})")
+        own = self.enc_mods if side == "encoder" else self.dec_mods
+        return [(m, mod, n) for m, (mod, n) in enumerate(self.mods) if own is None or mod in own]
+
+    def mod_emb_owner(self, side: str, mod: str) -> str:
+        """The side whose tokeniser of `mod` owns the mod_emb table the tokeniser of `side` reads: the encoder's for a decoder tokeniser
+        that shares it (mm.py:84-87), else `side` itself."""
+        if side == "decoder" and self.share_mod_emb and (self.enc_mods is None or mod in self.enc_mods):
+            return "encoder"
+        return side
+
     def is_scalenorm(self, lnname: str) -> bool:
         """True where the norm named `lnname` is a ScaleNorm: a block norm (BLOCK_NORMS) of a side with use_scalenorm: true.
         `decoder.{i}.query_norm` and `context_norm` are the decoder's; encoder_norm / decoder_norm are LayerNorms always."""
         return lnname.rsplit(".", 1)[-1] in BLOCK_NORMS and self.side(lnname.split(".", 1)[0]).norm == "scalenorm"
 
     @staticmethod
-    def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False) -> "EngineConfig":
+    def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False, enc_mods=None, dec_mods=None,
+                          share_mod_emb: bool = True) -> "EngineConfig":
         """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
         two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
         sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
         always did (the embedder's keys are read per side either way: the decoder's used to be ignored without a word).
         embedder_opts = True (what MultiModal passes): embedder.act, pos and bias are read per side too (embed_act / embed_pos /
         embed_bias; an act without a kernel raises NotImplementedError naming the accepted ones).  Without it the call keeps the
-        contract it had: any act but softsign, pos: false and bias: false raise NotImplementedError."""
+        contract it had: any act but softsign, pos: false and bias: false raise NotImplementedError.
+        enc_mods / dec_mods / share_mod_emb: the config's fields of those names (modal_filter, share_modality_embeddings)."""
         tf = {side: mc[side]["transformer"] for side in ("encoder", "decoder")}
         em = {side: mc[side]["embedder"] for side in ("encoder", "decoder")}
         et, dtf, ee = tf["encoder"], tf["decoder"], em["encoder"]
@@ -166,7 +205,8 @@ class EngineConfig:
                             sep_mask=bool(mc["decoder"]["decoder_sep_mask"]), causal_mask=bool(mc["decoder"]["decoder_causal_mask"]),
                             mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE + (PER_SIDE_EMBED if embedder_opts else ())},
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
-                            dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]))
+                            dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]),
+                            enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb)
 
 
 # a block's linear: name, the norm that feeds it (None: plain), weight [N, K], has a bias, the adjacent nn.Linear's a fused projection aliases
@@ -251,18 +291,20 @@ class ParamLayout:
         def embed():
             for side in ("encoder", "decoder"):
                 sc = cfg.side(side)
-                for mod, n in cfg.mods:
+                for _, mod, n in cfg.side_mods(side):       # (a side has no slot for a modality it has no tokeniser for)
                     p = f"{side}_embeddings.{mod}.embedder"
                     lin(p + ".token_embed", n * sc.mult, n, bias=sc.embed_bias)
                     lin(p + ".projection", H, n * sc.mult)
-                    if side == "encoder":       # decoder's mod_emb IS this tensor (mm.py:84-87)
+                    # a decoder tokeniser's mod_emb IS the encoder's tensor where the two share it (mm.py:84-87): no slot.  One of a
+                    # modality the encoder lacks, or of an unshared model, owns its table
+                    if cfg.mod_emb_owner(side, mod) == side:
                         pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
                     if sc.embed_pos:            # embedder.pos: false builds no pos_embed module
                         pad(); add(p + ".pos_embed.weight", (sc.max_F, H))
 
         def head():
             ln("decoder_norm")
-            for mod, n in cfg.mods:
+            for _, mod, n in cfg.side_mods("decoder"):
                 lin(f"decoder_embeddings.{mod}.out", n, H)
 
         segment("embed", embed)
@@ -566,7 +608,7 @@ class Engine:
         Builds nothing and launches nothing: the plan must exist (one training forward ran at this shape)."""
         plan = self.plans[(B, T, True, True)]
         c = self.cfg
-        H, Lq = c.hidden, len(c.mods) * T
+        H, Lq = c.hidden, len(c.side_mods("encoder")) * T
         out = []
         for key, site in self._sites.items():
             side = "encoder" if key.startswith("enc") else "decoder"          # `encoder/embdrop/0`, `enc0/sa/p`, `dec1/mlpdrop`
@@ -605,9 +647,11 @@ class Engine:
     # ------------------------------------------------------------------ data in
     def load_inputs(self, B, T, inputs, targets, masks, ts, attn):
         """Copy one batch into the static input buffers (device tensors or host tensors)."""
-        for m in range(len(self.cfg.mods)):
+        dec = {m for m, _, _ in self.cfg.side_mods("decoder")}
+        for m in sorted(dec | {m for m, _, _ in self.cfg.side_mods("encoder")}):      # (a modality no side has is not staged)
             self.b[f"in/{m}"].view(B, T, -1)[..., :inputs[m].shape[-1]].copy_(inputs[m], non_blocking=True)
-            self.b[f"tgt/{m}"].view(B, T, -1).copy_(targets[m], non_blocking=True)
+            if m in dec:
+                self.b[f"tgt/{m}"].view(B, T, -1).copy_(targets[m], non_blocking=True)
             self.b[f"mask/{m}"].copy_(masks[m], non_blocking=True)
         self.b["ts"].copy_(ts, non_blocking=True)
         self.b["attn"].copy_(attn, non_blocking=True)
@@ -628,10 +672,11 @@ class Engine:
         self._token += 1
         self._fwd_token = self._token
         self._last = plan
-        M = plan["M"]
-        out = dict(mod_loss=[self.b["loss_sum"][m].clone() for m in range(M)],
-                   mod_n=[self.b["count"][m].clone() for m in range(M)],
-                   preds=[self.b[f"pred/{m}"].view(B, T, -1) for m in range(M)])
+        # per decoder modality, in the decoder's order (all of `mods` unless dec_mods says otherwise)
+        dec, count = self.cfg.side_mods("decoder"), self.b[plan["count"]]
+        out = dict(mod_loss=[self.b["loss_sum"][j].clone() for j in range(len(dec))],
+                   mod_n=[count[j].clone() for j in range(len(dec))],
+                   preds=[self.b[f"pred/{m}"].view(B, T, -1) for m, _, _ in dec])
         if want_grad:
             out["loss"] = _StepFn.apply(anchor, self, self._token)
         else:

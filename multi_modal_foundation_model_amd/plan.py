@@ -53,8 +53,19 @@ class PlanBuilder:
         e, c = self.e, self.c = engine, engine.cfg
         self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
         self.sw = read_switches()
-        self.H, self.M = c.hidden, len(c.mods)
+        # each side's modalities (EngineConfig.side_mods: index in cfg.mods, name, channels).  A modality's place in its side's list is
+        # its slot in that side's stitched sequence; its index in cfg.mods names its buffers and is its mod_emb row.  M counts a side's
+        # modalities: both sides have as many (cross-attention pairs the two sequences position for position, mm.py:152-158, 210)
+        self.mods_of = {side: c.side_mods(side) for side in ("encoder", "decoder")}
+        self.H, self.M = c.hidden, len(self.mods_of["encoder"])
+        if len(self.mods_of["decoder"]) != self.M:
+            raise RuntimeError(f"engine: the encoder's sequence has {self.M * T} tokens ({self.M} modalities x {T}), the decoder's "
+                               f"{len(self.mods_of['decoder']) * T}: cross-attention needs the two lengths equal")
         self.Lq, self.R, self.BT = self.M * T, B * self.M * T, B * T
+        # the mask products (tokmask / keypad / keep0 / mod_id / count) come from the side's own modalities' masks: one buffer set while
+        # the two sides have the same modalities, else the decoder's own under "dec/"
+        self.split_masks = [m for m, _, _ in self.mods_of["encoder"]] != [m for m, _, _ in self.mods_of["decoder"]]
+        self.staged = sorted({m for side in self.mods_of.values() for m, _, _ in side})      # modalities some side uses
         self.sides = {side: Side(c.side(side), training) for side in ("encoder", "decoder")}
         self.Imax, self.mult_max = max(sd.I for sd in self.sides.values()), max(sd.mult for sd in self.sides.values())
         self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
@@ -79,6 +90,10 @@ class PlanBuilder:
             return "a"
         return "z"
 
+    def mk(self, side, name):
+        """The key of mask product `name` of `side` ("encoder" / "decoder")."""
+        return "dec/" + name if self.split_masks and side == "decoder" else name
+
     def side(self, name):
         """The Side a block belongs to, from its parameter prefix (`encoder.3`), its tag (`enc3`, `dec0/xa`) or the side's own name."""
         return self.sides["encoder" if name.startswith("enc") else "decoder"]
@@ -92,7 +107,7 @@ class PlanBuilder:
         self.workspaces()
         self.forward()
         plan = dict(fwd=self.fwd, bwd=None, B=self.B, T=self.T, training=self.training, M=self.M, R=self.R, BT=self.BT,
-                    runs=dict(fwd=0, bwd=0), graphs={}, b=self.b)
+                    runs=dict(fwd=0, bwd=0), graphs={}, b=self.b, count=self.mk("decoder", "count"))
         if self.grad:
             self.backward()
             plan.update(bwd=self.bwd, fused=self.fm, use_keep=any(sd.use_keep for sd in self.sides.values()))
@@ -103,13 +118,20 @@ class PlanBuilder:
         e, c, buf, sw = self.e, self.c, self.buf, self.sw
         B, T, H, R, BT, Lq, M = self.B, self.T, self.H, self.R, self.BT, self.Lq, self.M
         f32, i64, u8 = torch.float32, torch.int64, torch.uint8
-        for m, (mod, n) in enumerate(c.mods):
+        dec = {m for m, _, _ in self.mods_of["decoder"]}
+        chans = [c.mods[m][1] for m in self.staged]
+        for m in self.staged:
+            n = c.mods[m][1]
             # input rows padded to 16 B (zeros): the tokeniser's weight-gradient GEMM streams them by LDS-DMA (csrc/gemm_dw.hip)
-            buf(f"in/{m}", (BT, _align(n, 8)), zero=True); buf(f"tgt/{m}", (BT, n), f32); buf(f"mask/{m}", (B, T), i64)
-        buf("ts", (B, T), i64); buf("attn", (B, T), i64); buf("tokmask", (B, Lq), u8); buf("keypad", (B, Lq), u8)
-        buf("keep0", (Lq,), u8); buf("mod_id", (Lq,), u8); buf("count", (M,), i64); buf("loss_sum", (M,), f32)
+            buf(f"in/{m}", (BT, _align(n, 8)), zero=True); buf(f"mask/{m}", (B, T), i64)
+            if m in dec:            # targets: decoder modalities only
+                buf(f"tgt/{m}", (BT, n), f32)
+        buf("ts", (B, T), i64); buf("attn", (B, T), i64); buf("loss_sum", (M,), f32)
+        for pre in ("", "dec/") if self.split_masks else ("",):
+            buf(pre + "tokmask", (B, Lq), u8); buf(pre + "keypad", (B, Lq), u8)
+            buf(pre + "keep0", (Lq,), u8); buf(pre + "mod_id", (Lq,), u8); buf(pre + "count", (M,), i64)
         max_slab = 1
-        for _, n in c.mods:
+        for n in chans:
             # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
             # streaming kernel and with it another split count)
             for mult in sorted({sd.mult for sd in self.sides.values()}):
@@ -127,7 +149,7 @@ class PlanBuilder:
             # reduction): the largest segment's parameters bound the need, not the whole model's
             seg_max = max(end - s0 for _, s0, end in e.layout.segments)
             self.slabm = buf("ws/slabm", (max(1, min(R // 256, 15)) * (seg_max + 128 * 64),), f32)
-        maxN = max([3 * H, self.Imax] + [n * self.mult_max for _, n in c.mods])
+        maxN = max([3 * H, self.Imax] + [n * self.mult_max for n in chans])
         buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
         buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
         buf("ws/stitch", (max(1, max(L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, sd.max_F) for sd in self.sides.values()) // 4),), f32)
@@ -315,10 +337,13 @@ class PlanBuilder:
         workspace and the LSE buffer are the site's side's - cross-attention splits the context's keys / values by the decoder's heads."""
         e, b, buf, B, Lq, H, es, sd = self.e, self.b, self.buf, self.B, self.Lq, self.H, self.es, self.side(tag)
         heads, dp = sd.heads, sd.dp
+        # whose mask products: the encoder's for its self-attention and for cross-attention (xa_mask IS the encoder's mask, mm.py:210),
+        # the decoder's (its mod_id under CAUSAL / SEP) for the decoder's self-attention
+        ms = "decoder" if tag.startswith("dec") and tag.endswith("/sa") else "encoder"
         dh = H // heads
         keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if sd.use_keep else None
         return K.attn_desc(self.code, B, heads, Lq, Lq, dh, q.data_ptr(), kv.data_ptr() + koff * es, kv.data_ptr() + voff * es, ldq, ldkv, ldkv,
-                           o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), torch.float32), b["keypad"], b["mod_id"], flags,
+                           o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), torch.float32), b[self.mk(ms, "keypad")], b[self.mk(ms, "mod_id")], flags,
                            1.0 / math.sqrt(dh), drop_p=e._drop(tag + "/p", dp), drop_o=e._drop(tag + "/o", dp),
                            d_o=K.P(d_o), lddo=H, dq=K.P(dq), dk=None if dkv is None else dkv.data_ptr() + dkoff * es,
                            dv=None if dkv is None else dkv.data_ptr() + dvoff * es, lddq=lddq, lddk=lddkv, lddv=lddkv, keepbits=keep)
@@ -378,13 +403,15 @@ class PlanBuilder:
     def forward(self):
         e, c, b, buf, fwd = self.e, self.c, self.b, self.buf, self.fwd
         B, T, H, R, BT, Lq, M = self.B, self.T, self.H, self.R, self.BT, self.Lq, self.M
-        K.mask_prep(B, T, [b[f"mask/{m}"] for m in range(M)], [1] * M, b["attn"], [n for _, n in c.mods], b["tokmask"], b["keypad"],
-                    b["keep0"], b["mod_id"], b["count"], plan=fwd)
+        mk = self.mk
+        for side in ("encoder", "decoder") if self.split_masks else ("encoder",):       # mm.py:147-149 / 169-171: each side's own masks
+            K.mask_prep(B, T, [b[f"mask/{m}"] for m, _, _ in self.mods_of[side]], [1] * M, b["attn"], [n for _, _, n in self.mods_of[side]],
+                        b[mk(side, "tokmask")], b[mk(side, "keypad")], b[mk(side, "keep0")], b[mk(side, "mod_id")], b[mk(side, "count")], plan=fwd)
         tok_tmp = buf("tok_tmp", (BT, H))
         x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
         for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
             sd = self.sides[side]
-            for m, (mod, n) in enumerate(c.mods):
+            for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
                 a = buf(f"{side}/a/{m}", (BT, n2))
@@ -394,9 +421,10 @@ class PlanBuilder:
                 z = buf(f"{side}/z/{m}", (BT, n2)) if self.embed_saved(sd) == "z" else None
                 self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=sd.emb_fwd, act_scale=sd.scale)
                 self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe))
-                mod_row = e.Pf(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m]
+                # row mod_to_indx[mod] of the table this tokeniser reads: its own, or the encoder's where the two share it
+                mod_row = e.Pf(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m]
                 pos = e.Pf(p + ".pos_embed.weight") if sd.pos else None            # embedder.pos: false -> emb = the modality row
-                K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b["keep0"], xs, es_, B, T, Lq, m, H, sd.max_F, plan=fwd)
+                K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
         X = x_enc
         for i in range(c.n_enc):
             p, tag = f"encoder.{i}", f"enc{i}"
@@ -431,12 +459,13 @@ class PlanBuilder:
         self.dec_last = Y
         ydec = buf("ydec", (R, H))                         # de-stitched: [M][B*T][H]
         self.ln_f(fwd, Y, "decoder_norm", ydec, "decnorm", ds_L=Lq, ds_T=T)
-        for m, (mod, n) in enumerate(c.mods):
+        tokmask = b[mk("decoder", "tokmask")]
+        for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             pred = buf(f"pred/{m}", (BT, n))
-            self.lin(fwd, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
-            self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], b["tokmask"][:, m * T:], Lq, T, BT, n,
-                      b["loss_sum"][m:m + 1], b["ws/loss"])
-        K.loss_finalize(b["loss_sum"], b["count"], M, b["loss"], b["inv_n"], plan=fwd)
+            self.lin(fwd, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], tokmask[:, j * T:], Lq, T, BT, n,
+                      b["loss_sum"][j:j + 1], b["ws/loss"])
+        K.loss_finalize(b["loss_sum"], b[mk("decoder", "count")], M, b["loss"], b["inv_n"], plan=fwd)
 
     # ------------------------------------------------------------------ backward blocks
     def close_segment(self, name):
@@ -523,11 +552,12 @@ class PlanBuilder:
         dY, dydec = buf("d/stream", (R, H)), buf("d/ydec", (R, H))
         buf("d/t1", (R, H)); buf("d/t2", (R, H)); buf("d/h", (R, H)); buf("d/u", (R, I)); buf("d/qkv", (R, 3 * H)); dctx = buf("d/ctx", (R, H))
         ydec = b["ydec"]
-        for m, (mod, n) in enumerate(c.mods):
+        tokmask = b[self.mk("decoder", "tokmask")]
+        for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             dpred = buf(f"d/pred/{m}", (BT, n))
-            self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], b["tokmask"][:, m * T:],
+            self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, j * T:],
                       Lq, T, BT, n, b["gout"], b["inv_n"], dpred)
-            self.dlin(self.cur, dpred, ydec[m * BT:(m + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[m * BT:(m + 1) * BT])
+            self.dlin(self.cur, dpred, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[j * BT:(j + 1) * BT])
         self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
         self.close_segment("head")
         buf("d/qc", (R, H)); buf("d/kvc", (R, 2 * H))
@@ -548,19 +578,23 @@ class PlanBuilder:
             self.mlp_back(self.cur, dX, p, tag, b[tag + "/xa"])
             self.self_back(self.cur, dX, p, tag, self.enc_flags)
             self.close_segment(p)
-        # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds)
-        for side, dS, dextra, acc_mod in (("decoder", dY, None, False), ("encoder", dX, dctx, True)):
+        # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds).  The encoder side adds
+        # only where a decoder tokeniser really wrote that row: a table no decoder tokeniser shares gets its gradient by overwriting,
+        # and a table the decoder owns gets its own
+        shared = {mod for _, mod, _ in self.mods_of["decoder"] if c.mod_emb_owner("decoder", mod) == "encoder"}
+        for side, dS, dextra in (("decoder", dY, None), ("encoder", dX, dctx)):
             sd = self.sides[side]
-            for m, (mod, n) in enumerate(c.mods):
+            for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 pS = f"{side}_embeddings.{mod}.embedder"
-                K.stitch_bwd(dS, dextra, b["ts"], b["keep0"], e._drop(f"{side}/embdrop/{m}", sd.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
-                             e.Gv(f"encoder_embeddings.{mod}.embedder.mod_emb.weight")[m], e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
-                             acc_mod, False, B, T, Lq, m, H, sd.max_F, b["ws/stitch"], plan=self.cur)
+                K.stitch_bwd(dS, dextra, b["ts"], b[self.mk(side, "keep0")], e._drop(f"{side}/embdrop/{m}", sd.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
+                             e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
+                             e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
+                             side == "encoder" and mod in shared, False, B, T, Lq, slot, H, sd.max_F, b["ws/stitch"], plan=self.cur)
         # the softsign gradient from the activation itself (bf16), or from the saved pre-activation (fp32, and every other activation)
         for side in ("decoder", "encoder"):
             sd = self.sides[side]
             saved = self.embed_saved(sd)
-            for m, (mod, n) in enumerate(c.mods):
+            for m, mod, n in self.mods_of[side]:
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
                 dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)

@@ -6,6 +6,10 @@ Behavioural notes kept from the reference on purpose:
   * `forward` mutates `mod_dict` in place (inputs_mask, targets_mask, *_attn_mask, gt, preds);
   * tokens are zeroed at the positions where SAMPLE 0 is masked, for every sample (mm.py:147-149);
   * the loss is sum(mod_loss)/sum(n_examples) and is NaN when nothing is masked (mm.py:237);
+  * `encoder_embeddings` / `decoder_embeddings` may hold subsets of `avail_mod` (the entry script's `modal_filter`): `mod_dict` still
+    carries every modality, the masker is still called once per modality in that order, and each side keeps the modalities it has
+    tokenisers for (mm.py:277-287); the outputs hold the decoder's modalities.  Two sets of different size fail in cross-attention
+    upstream (the [B, Le, Le] encoder mask cannot be expanded to [B, h, Ld, Le]); here `forward` raises before any launch;
   * `masking_mode` (mask_type: input) fails exactly like upstream (`mask` is never bound, mm.py:256-272).
 """
 import os
@@ -108,10 +112,10 @@ class MultiModal(nn.Module):
         self.encoder_embeddings = nn.ModuleDict(encoder_embeddings)
         self.decoder_modalities = set(decoder_embeddings.keys())
         self.decoder_embeddings = nn.ModuleDict(decoder_embeddings)
+        # False: every decoder tokeniser keeps its own mod_emb parameter (the engine lays it out and trains it: EngineConfig.share_mod_emb)
+        self._share_mod_emb = bool(share_modality_embeddings)
         if share_modality_embeddings:
             self.share_modality_embeddings()
-        elif self.encoder_modalities & self.decoder_modalities:
-            raise NotImplementedError("share_modality_embeddings=False is not built (the entry script passes True)")
 
         self.mask = config.masker.force_active
         if self.mask:
@@ -154,14 +158,22 @@ class MultiModal(nn.Module):
             raise RuntimeError("MultiModal runs on an MI355X through libmmfm_hip.so; move the model to the GPU first "
                                "(there is deliberately no CPU fallback; the CPU restatement is oracle/, test-only)")
         if self._engine is None or self._engine.device != dev or self._engine.dtype != self.compute_dtype:
-            mods = [(m, self.encoder_embeddings[m].n_channel) for m in self.avail_mod]
-            for m, n in mods:
-                if self.decoder_embeddings[m].n_channel != n or self.decoder_embeddings[m].output_channel != n:
+            mods = []
+            for m in self.avail_mod:
+                sides = [d[m] for d in (self.encoder_embeddings, self.decoder_embeddings) if m in d]
+                # (a modality neither side has a tokeniser for keeps its place in avail_mod - its index is the others' mod_emb row -
+                # and is never staged: 0 channels)
+                n = sides[0].n_channel if sides else 0
+                if any(t.n_channel != n for t in sides) or (m in self.decoder_embeddings and self.decoder_embeddings[m].output_channel != n):
                     raise NotImplementedError("encoder/decoder channel counts differ")
-                if m not in self.loss_mod:
+                if m in self.decoder_embeddings and m not in self.loss_mod:
                     raise Exception("Modality not implemented yet.")
-            cfg = EngineConfig.from_model_config(self._model_config, mods, per_side=True, embedder_opts=True)
-            specs = {m: _loss_spec(self.loss_mod[m]) for m, _ in mods}
+                mods.append((m, n))
+            cfg = EngineConfig.from_model_config(self._model_config, mods, per_side=True, embedder_opts=True,
+                                                 enc_mods=[m for m in self.avail_mod if m in self.encoder_embeddings],
+                                                 dec_mods=[m for m in self.avail_mod if m in self.decoder_embeddings],
+                                                 share_mod_emb=getattr(self, "_share_mod_emb", True))      # (a module pickled before the flag existed shares)
+            specs = {m: _loss_spec(self.loss_mod[m]) for m in self.avail_mod if m in self.decoder_embeddings}
             cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
             cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
             cfg.loss_flags = {m: sp[2] for m, sp in specs.items()}
@@ -213,11 +225,16 @@ class MultiModal(nn.Module):
                 if d[key] is not ref and not torch.equal(d[key], ref):
                     raise NotImplementedError(f"per-modality {key} differ: the stitched sequence assumes shared bins")
         B, T, _ = first['inputs'].shape
+        enc_mods, dec_mods = ([m for m in mods if m in emb] for emb in (self.encoder_embeddings, self.decoder_embeddings))
+        if len(enc_mods) != len(dec_mods):
+            raise RuntimeError(f"encoder sequence length {len(enc_mods) * T} ({len(enc_mods)} modalities x {T} bins) != decoder sequence "
+                               f"length {len(dec_mods) * T} ({len(dec_mods)} x {T}): cross-attention masks the decoder's queries with the "
+                               "encoder's [B, Le, Le] mask (mm.py:152-158, 210), so the two sides need equally many modalities")
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
                           training=self.training, anchor=self.decoder_norm.weight)
         mod_loss, mod_n, preds, targets = {}, {}, {}, {}
-        for i, mod in enumerate(mods):
+        for i, mod in enumerate(dec_mods):      # the engine's outputs are the decoder's modalities, in this order
             mod_loss[mod], mod_n[mod] = out["mod_loss"][i], out["mod_n"][i]
             # bf16 engine: the fp32 copy of the predictions (68 M elements for 'ap' at B = 1024: a 410 MB cast kernel per step) is made
             # where somebody reads them - evaluation; in training mode (the trainer's train_epoch only reads the loss) mod_preds
