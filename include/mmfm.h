@@ -125,6 +125,34 @@ int mmfm_gemm(const mmfm_gemm_desc* d, mmfm_stream stream);
  * the slabs it would make alone.  The weight gradients of two linears whose dY are both at hand (MLP up / down, attention qkv / out_proj). */
 int mmfm_gemm_pair(const mmfm_gemm_desc* a, const mmfm_gemm_desc* b, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- live rows (MMFM_LIVE_ROWS)
+ * The model zeroes a token of EVERY sample at each position where SAMPLE 0 is masked (mm.py:147-149, 169-171; keep0 of mmfm_mask_prep),
+ * so the tokeniser rows of such a time bin are dead: nobody reads their output and their gradient is zero.  The live-bin record of one
+ * modality slot says which bins are live, on the device (nothing is read back; launches keep fixed grids):
+ *   rec[0]         = T_live, the number of bins t with keep0[t] != 0            (rec[1..3]: reserved, 0)
+ *   rec[4 + j]     = live_t[j], the original bin of the j-th live bin, ascending (j < T_live)
+ *   rec[4 + T + t] = rank[t], the place of bin t among the live bins, -1 for a dead bin
+ * Dead bins are the same for every sample: row (b, t) of a [B*T] row space sits at compact row b * T_live + rank[t].
+ * mmfm_live_bins: keep0 is u8 [M][T], rec int32 [M][MMFM_LIVE_REC_INTS(T)] - one record per modality slot, one launch. */
+#define MMFM_LIVE_ROWS 1
+#define MMFM_LIVE_REC_INTS(T) (2 * (T) + 4)
+int mmfm_live_bins(const uint8_t* keep0, int T, int M, int32_t* rec, mmfm_stream stream);
+/* dst[b * T_live + j][:] = src[b * T + live_t[j]][:] for rows of row_bytes bytes (a multiple of 4; 16-B accesses when rows and both
+ * pointers are 16-B aligned).  Rows of dst beyond B * T_live are not written. */
+int mmfm_gather_live_rows(const void* src, void* dst, int B, int T, int64_t row_bytes, const int32_t* rec, mmfm_stream stream);
+/* mmfm_gemm (dtype bf16) over the compact row space of `live`.  The descriptor is the one of the full row space (B * T rows: the launch
+ * geometry and the kernel choice come from it, so the grid is fixed) and the kernels read the row count B * T_live off the record:
+ *   a_kcontig == 1 (x.W^T, dY.W): M = B * T_live.  Tiles beyond it exit before any load; rows of C / pre_out beyond it are not written;
+ *     the dropout counter of compact row m' stays that of its original row, (m' / T_live) * T + live_t[m' % T_live], times N, plus n.
+ *   a_kcontig == 0 (dY^T.X, with colsum): K = B * T_live.  The split count stays; with K_live == K the split ranges are the
+ *     descriptor's, else kchunk = ceil(K_live / splits) rounded up to 64, so the live rows stay spread over all splits; a split with an
+ *     empty range writes zeros for its slab and colsum. */
+typedef struct {
+    const int32_t* rec;   /* the record of mmfm_live_bins */
+    int B, T;             /* d->M (or d->K) == B * T */
+} mmfm_live_rows;
+int mmfm_gemm_live(const mmfm_gemm_desc* d, const mmfm_live_rows* live, mmfm_stream stream);
+
 /* dst[i] (+)= sum_s src[s*slab_stride + i], fp32, deterministic order.  `src` is scratch: it may be
  * clobbered (a tall-skinny reduction first sums groups of slabs in place). */
 /* Work items per K-split that a bf16 weight-gradient launch (a_kcontig == b_kcontig == 0, fp32 output, 16-B aligned rows) over K rows is
@@ -273,6 +301,16 @@ int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t
                     mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
                     int B, int T, int L, int m, int H, int max_F,
                     void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+/* The same with tok / d_tok over the compact row space of the slot's live-bin record `rec` (mmfm_live_bins; keep0 is the one it was made
+ * from): the forward reads tok at row b * T_live + rank[t], the backward writes d_tok for live rows only, at their compact rows (the
+ * dropout counter stays the original row's).  Everything else - emb, d_mod_row, d_pos - covers all rows as above. */
+int mmfm_stitch_fwd_live(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb,
+                         const int64_t* ts, const uint8_t* keep0, const int32_t* rec, void* x, void* emb,
+                         int B, int T, int L, int m, int H, int max_F, mmfm_stream stream);
+int mmfm_stitch_bwd_live(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, const int32_t* rec,
+                         mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
+                         int B, int T, int L, int m, int H, int max_F,
+                         void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
 /* ---------------------------------------------------------------------------------- loader collate
  * BaseDataset._preprocess_ibl_data + get_binned_spikes_from_sparse (loader/base.py:304-450,

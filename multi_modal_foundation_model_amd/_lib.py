@@ -53,6 +53,16 @@ class GemmDesc(C.Structure):
                 ("ldr", C.c_int), ("colsum", C.c_void_p)]
 
 
+class LiveRows(C.Structure):
+    """mmfm_live_rows: the live-bin record of a modality slot (int32 [live_rec_ints(T)], mmfm_live_bins) and the row space B * T it compacts."""
+    _fields_ = [("rec", C.c_void_p), ("B", C.c_int), ("T", C.c_int)]
+
+
+def live_rec_ints(T):
+    """MMFM_LIVE_REC_INTS: T_live + 3 reserved, live_t[T], rank[T]."""
+    return 2 * T + 4
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("Lq", C.c_int), ("Lk", C.c_int), ("dh", C.c_int),
                 ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("ldq", C.c_int), ("ldk", C.c_int),
@@ -98,6 +108,9 @@ _PROTOS = {
     "mmfm_rng_advance": (C.c_int, [_vp, _vp]),
     "mmfm_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "mmfm_gemm_pair": (C.c_int, [_vp, _vp, _vp]),
+    "mmfm_gemm_live": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(LiveRows), _vp]),
+    "mmfm_live_bins": (C.c_int, [_vp, _i, _i, _vp, _vp]),
+    "mmfm_gather_live_rows": (C.c_int, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
     "mmfm_gemm_dw_tiles": (C.c_int, [_i, _i, _i]),
     "mmfm_reduce_slabs": (C.c_int, [_vp, _vp, _i64, _i, _i64, _i, _vp]),
     "mmfm_reduce_slabs_multi": (C.c_int, [_vp, _i, _i, _vp]),
@@ -116,6 +129,8 @@ _PROTOS = {
     "mmfm_mask_prep": (C.c_int, [_i, _i, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_collate_csr": (C.c_int, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_stitch_fwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmfm_stitch_fwd_live": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmfm_stitch_bwd_live": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mmfm_stitch_bwd_workspace": (C.c_int64, [_i, _i, _i, _i, _i, _i]),
     "mmfm_stitch_bwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mmfm_masked_loss_workspace": (C.c_int64, [_i64, _i]),

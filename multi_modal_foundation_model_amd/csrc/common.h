@@ -34,6 +34,31 @@ int mmfm_lds_opt_in(const void* kern, size_t bytes, const char* what);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ------------------------------------------------------------------ live rows (mmfm_gemm_live; include/mmfm.h)
+// What a GEMM kernel gets beside its descriptor: rec == NULL is the plain launch.  kdim: the record sizes the reduction (dY^T.X), else M.
+struct LiveArg {
+    const int32_t* rec;
+    int B, T, kdim;
+};
+static const LiveArg kNoLive = {nullptr, 0, 0, 0};
+// the descriptor of the compact row space: M, or K with the split ranges, from the record (uniform: scalar loads)
+__device__ __forceinline__ void live_patch(mmfm_gemm_desc& d, const LiveArg& lv) {
+    if (!lv.rec) return;
+    const int rows = lv.B * lv.rec[0];
+    if (!lv.kdim) {
+        d.M = rows;
+    } else if (rows != d.K) {
+        d.kchunk = d.splits > 1 ? ((rows + d.splits - 1) / d.splits + 63) / 64 * 64 : rows;      // the host's rounding (Engine._dw_split)
+        d.K = rows;
+    }
+}
+// the original row of compact row m (m < B * T_live): what the dropout counter is made of
+__device__ __forceinline__ int live_orig_row(const LiveArg& lv, int m) {
+    if (!lv.rec) return m;
+    const int tl = lv.rec[0], b = m / tl;
+    return b * lv.T + lv.rec[4 + m - b * tl];
+}
+
 // ------------------------------------------------------------------ bf16 <-> f32
 __device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {

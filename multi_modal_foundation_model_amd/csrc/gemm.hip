@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const T* __restrict__ x, i
 
 }  // namespace
 
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* d, hipStream_t st);  // gemm_bf16.hip
+int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* d, hipStream_t st, const LiveArg& lv);  // gemm_bf16.hip
 
 // argument checks and normalisation shared by mmfm_gemm and mmfm_gemm_pair (d = *dp on success)
 static int gemm_check(const mmfm_gemm_desc* dp, mmfm_gemm_desc& d) {
@@ -363,7 +363,7 @@ extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
     mmfm_gemm_desc d;
     if (int rc = gemm_check(dp, d)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (d.dtype == MMFM_BF16) return mmfm_gemm_bf16_launch(&d, st);
+    if (d.dtype == MMFM_BF16) return mmfm_gemm_bf16_launch(&d, st, kNoLive);
 
     const int tiles = cdiv(d.M, BM) * cdiv(d.N, BN);
     const int vecA = (d.lda % 4 == 0) && ((uintptr_t)d.A % 16 == 0);
@@ -383,6 +383,18 @@ extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
 #undef F32_LAUNCH
     MMFM_LAUNCH_CHECK("mmfm_gemm(f32)");
     return 0;
+}
+
+// mmfm_gemm over the compact row space of a live-bin record (include/mmfm.h): the same kernels, chosen and launched for the full row space
+extern "C" int mmfm_gemm_live(const mmfm_gemm_desc* dp, const mmfm_live_rows* live, mmfm_stream stream) {
+    mmfm_gemm_desc d;
+    if (int rc = gemm_check(dp, d)) return rc;
+    MMFM_REQUIRE(d.dtype == MMFM_BF16, "mmfm_gemm_live: bf16 only (the fp32 parity path keeps the full row space)");
+    MMFM_REQUIRE(live && live->rec && live->B > 0 && live->T > 0, "mmfm_gemm_live: bad live-row record");
+    const LiveArg lv = {live->rec, live->B, live->T, d.a_kcontig ? 0 : 1};
+    MMFM_REQUIRE((int64_t)live->B * live->T == (lv.kdim ? d.K : d.M), "mmfm_gemm_live: B * T = %lld is not the descriptor's %s = %d",
+                 (long long)live->B * live->T, lv.kdim ? "K" : "M", lv.kdim ? d.K : d.M);
+    return mmfm_gemm_bf16_launch(&d, (hipStream_t)stream, lv);
 }
 
 // Two independent GEMMs.  Two bf16 weight-gradient launches that the streaming kernel takes run as ONE launch, each on its share of the

@@ -114,7 +114,7 @@ __device__ __forceinline__ bf16x8v frag(const char* __restrict__ S, int rowbase,
 // AK: the MLP activation kind of act 6-11, or kActEmbed for the embedder activations 12-25 (gemm_act_kind), one instantiation per kind;
 // the AK = 0 kernels run every other act, and their code does not change with these
 template <typename TO, int AK = 0, int EF = 0>
-__device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Drop& dr, float v, int m, int n) {
+__device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const LiveArg& lv, const Drop& dr, float v, int m, int n) {
     typedef io<uint16_t> I16;
     constexpr int AKM = AK == kActEmbed ? 0 : AK;           // the MlpAct the MLP-kind branches name (dead code in the kActEmbed kernels)
     if (d.bias) v += d.bias[n];
@@ -123,7 +123,7 @@ __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Dr
         if (!(d.act & 1)) v = embed_act1<true, EF>(v) * d.act_scale;                     // EF: the embedder function, embed_dispatch
         else if (EF == 0) v *= d.act_scale;
         else v = embed_mul_grad1<true, EF>(v, I16::ld(reinterpret_cast<const uint16_t*>(d.gradmul_pre) + (size_t)m * d.ldc + n)) * d.act_scale;
-        v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
+        if (dr.on()) v = dr.apply(v, (uint64_t)live_orig_row(lv, m) * (uint64_t)d.N + (uint64_t)n);
         if (d.residual) v += I16::ld(reinterpret_cast<const uint16_t*>(d.residual) + (size_t)m * d.ldr + n);
         io<TO>::st(reinterpret_cast<TO*>(d.C) + (size_t)m * d.ldc + n, v);
         return;
@@ -137,7 +137,7 @@ __device__ __forceinline__ void epilogue_store(const mmfm_gemm_desc& d, const Dr
         else if (AK) v *= mlp_act_grad1<AKM>(u, d.act_scale);
         else v *= (d.act == 3) ? gelu_poly_grad(u) : (d.act == 4 ? softsign_grad(u) : softsign_grad_from_out(u, 1.f / d.act_scale)) * d.act_scale;
     }
-    v = dr.apply(v, (uint64_t)m * (uint64_t)d.N + (uint64_t)n);
+    if (dr.on()) v = dr.apply(v, (uint64_t)live_orig_row(lv, m) * (uint64_t)d.N + (uint64_t)n);
     if (d.residual) v += I16::ld(reinterpret_cast<const uint16_t*>(d.residual) + (size_t)m * d.ldr + n);
     io<TO>::st(reinterpret_cast<TO*>(d.C) + (size_t)m * d.ldc + n, v);
 }
@@ -186,7 +186,7 @@ __device__ __forceinline__ void stg8(uint16_t* p, uint4 v, bool a16, bool hi, bo
 // EPI_LOADS = false: the instantiation of the persistent bf16-output kernel, launched only without a saved pre-activation /
 // residual operand (their registers would sit on top of the next tile's prefetched slice)
 template <typename TO, bool EPI_LOADS = true, int AK = 0, int EF = 0>
-__device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&acc)[2][2], char* smem, int m0, int n0, int z, int vec_epi,
+__device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, const LiveArg& lv, f32x16 (&acc)[2][2], char* smem, int m0, int n0, int z, int vec_epi,
                                               int t, int wm, int wn, int kh, int l31) {
     // ---- epilogue.  Fast path (row-aligned shapes): the fp32 tile is staged through LDS half a tile at a time
     // (64 rows x 128 cols x 4 B = 32 KB, reusing the operand buffers) so that each thread owns 8 consecutive
@@ -291,7 +291,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
                     }
                 }
                 if (dr.on()) {
-                    const uint64_t base = (uint64_t)m * (uint64_t)d.N + (uint64_t)n;
+                    const uint64_t base = (uint64_t)live_orig_row(lv, m) * (uint64_t)d.N + (uint64_t)n;
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) dr.apply2(v[e], v[e + 1], base + e);      // n and N are even here, so base is
                 }
@@ -327,7 +327,7 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const int n = n0 + wn * 64 + j * 32 + l31;
-                if (m < d.M && n < d.N) epilogue_store<TO, AK, EF>(d, dr, acc[i][j][r], m, n);
+                if (m < d.M && n < d.N) epilogue_store<TO, AK, EF>(d, lv, dr, acc[i][j][r], m, n);
             }
 }
 
@@ -340,8 +340,13 @@ __device__ __forceinline__ void epilogue_tile(const mmfm_gemm_desc& d, f32x16 (&
 // pre-activation) are issued after the prefetch and vmcnt retires in order, so the epilogue would wait for the whole
 // prefetch; hoisting those loads above the prefetch costs 40 VGPRs, spills, and measured 30 % slower (194 -> 261 us).
 template <bool ARC, bool BRC, typename TO, int BK, bool PERSIST = (sizeof(TO) == 4), int AK = 0>
-__global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(const mmfm_gemm_desc d, const int alignA, const int alignB,
-                                                                              const int vec_epi, const int total_items) {
+__global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(const mmfm_gemm_desc d_full, const int alignA, const int alignB,
+                                                                              const int vec_epi, const int items_full, const LiveArg lv) {
+    // a live-row launch (mmfm_gemm_live): M, or K with the split ranges, and the item count come from the device record; the grid was
+    // sized for all rows and the workgroups beyond the live items leave at once
+    mmfm_gemm_desc d = d_full;
+    live_patch(d, lv);
+    const int total_items = (lv.rec && !lv.kdim) ? ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN) : items_full;
     constexpr int TILE_BYTES = Geo<BK>::TILE_BYTES;
     __shared__ __attribute__((aligned(16))) char smem[2 * TILE_BYTES];
     char* As = smem;
@@ -440,10 +445,10 @@ __global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(c
         }
         if constexpr (AK == kActEmbed)             // the embedder activations: one epilogue per function, picked once per tile
             embed_dispatch(d.act, [&](auto F) {
-                epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK, decltype(F)::value>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
+                epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK, decltype(F)::value>(d, lv, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
             });
         else
-            epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK>(d, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
+            epilogue_tile<TO, !(PERSIST && sizeof(TO) == 2), AK>(d, lv, acc, smem, m0, n0, z, vec_epi, t, wm, wn, kh, l31);
         if (!more) break;
         w = wn_; m0 = m0n; n0 = n0n; z = zn; kbeg = kbegn; kend = kendn;
     }
@@ -457,15 +462,16 @@ int align_of(const void* p, int ld) {
 
 }  // namespace
 
-int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st);   // gemm_big.hip: 256 x 256 tiles for the compute-bound shapes
-int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st);    // gemm_dw.hip: the HBM-bound weight-gradient stream
+int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);   // gemm_big.hip: 256 x 256 tiles for the compute-bound shapes
+int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);    // gemm_dw.hip: the HBM-bound weight-gradient stream
 
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
+// lv: kNoLive, or the live-row record of mmfm_gemm_live - every choice below is made from the descriptor of the full row space
+int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
     const mmfm_gemm_desc d = *dp;
     {
-        const int rb = mmfm_gemm_big_launch(dp, st);
+        const int rb = mmfm_gemm_big_launch(dp, st, lv);
         if (rb != -1000) return rb;
-        const int rw = mmfm_gemm_dw_launch(dp, st);
+        const int rw = mmfm_gemm_dw_launch(dp, st, lv);
         if (rw != -1000) return rw;
     }
     MMFM_REQUIRE(d.splits == 1 || d.kchunk % 64 == 0, "mmfm_gemm(bf16): kchunk %d must be a multiple of 64", d.kchunk);
@@ -506,12 +512,12 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     // occupancy probe: unused dynamic LDS bytes per workgroup (60000 -> one workgroup per CU less, 100000 -> one per CU)
     static const int pad_lds = [] { const char* e = getenv("MMFM_GEMM_PAD_LDS"); return e ? atoi(e) : 0; }();
 #define LAUNCH2(ARC, BRC, BKV)                                                                                    \
-    if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);  \
-    else if (pb) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV, true>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items); \
-    else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);
+    if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items, lv);  \
+    else if (pb) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV, true>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items, lv); \
+    else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, BKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items, lv);
 #define LAUNCH_AK(ARC, BRC, AKV)                                                                                  \
-    if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, 64, true, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items); \
-    else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, 64, false, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items);
+    if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, float, 64, true, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items, lv); \
+    else hipLaunchKernelGGL((gemm_bf16_kernel<ARC, BRC, uint16_t, 64, false, AKV>), grid, block, pad_lds, st, d, aA, aB, vecf, total_items, lv);
 #define LAUNCH(ARC, BRC)                                                                                          \
     if (ak == MMFM_MLP_RELU) { LAUNCH_AK(ARC, BRC, MMFM_MLP_RELU) }                                                \
     else if (ak == MMFM_MLP_SIGMOID) { LAUNCH_AK(ARC, BRC, MMFM_MLP_SIGMOID) }                                     \

@@ -69,8 +69,12 @@ __device__ __forceinline__ void issue_ktile(char* buf, const uint16_t* const (&p
 // AK: the MLP activation kind of act 6-11, or kActEmbed for the embedder activations 12-25 (gemm_act_kind), one instantiation per kind;
 // the AK = 0 kernel runs every other act, and its code does not change with these
 template <int AK = 0>
-__global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
+__global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a_full, const LiveArg lv) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // a live-row launch (mmfm_gemm_live): M and the tile count come from the device record; workgroups without a live tile leave at once
+    BigArgs a = a_full;
+    live_patch(a.d, lv);
+    if (lv.rec) a.ntiles = ((a.d.M + TB - 1) / TB) * a.tiles_n;
     const mmfm_gemm_desc& d = a.d;
     const int t = threadIdx.x, lane = t & 63, m = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -272,12 +276,13 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
                     }
                 }
                 if (dr.on()) {
+                    const int drow = row < (uint32_t)d.M ? live_orig_row(lv, (int)row) : (int)row;       // the counter's row: the original one
 #pragma unroll
                     for (int e = 0; e < 2; ++e)
 #pragma unroll
                         for (int r = 0; r < 16; r += 2) {
                             float v0 = acc[2 * ip + e][j][r], v1 = acc[2 * ip + e][j][r + 1];
-                            dr.apply2(v0, v1, (uint64_t)row * (uint64_t)d.N + (uint64_t)(ncol0 + 32 * e + 8 * (r >> 2) + 4 * h + (r & 3)));
+                            dr.apply2(v0, v1, (uint64_t)drow * (uint64_t)d.N + (uint64_t)(ncol0 + 32 * e + 8 * (r >> 2) + 4 * h + (r & 3)));
                             acc[2 * ip + e][j][r] = v0; acc[2 * ip + e][j][r + 1] = v1;
                         }
                 }
@@ -305,11 +310,11 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a) {
 }  // namespace
 
 // returns -1000 when the shape belongs to the 128 x 128 kernel
-int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
+int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
     const mmfm_gemm_desc& d = *dp;
     static const int on = [] { const char* e = getenv("MMFM_GEMM_BIG"); return e ? atoi(e) : 1; }();
     static const int kmin = [] { const char* e = getenv("MMFM_GEMM_BIG_KMIN"); return e ? atoi(e) : 512; }();
-    if (!on || d.dtype != MMFM_BF16 || d.c_f32 || d.splits > 1 || !d.a_kcontig || !d.b_kcontig || d.colsum) return -1000;
+    if (!on || d.dtype != MMFM_BF16 || d.c_f32 || d.splits > 1 || !d.a_kcontig || !d.b_kcontig || d.colsum || (lv.rec && lv.kdim)) return -1000;
     if (d.K % BK || d.K < kmin || d.N < 128 || d.M < 1024 || d.N % 8) return -1000;
     // too few 256-wide tiles to occupy the chip (the reference's batch of 16: M = 3,200 rows x N = 256 = 13 tiles, 23-34 us against ~15 us
     // for the 50 tiles of the 128-tile kernel)
@@ -336,11 +341,11 @@ int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
     a.nk = d.K / BK;
     a.nt_c = nt_env & 1;
     a.nt_pre = (nt_env >> 1) & 1;
-    if (ak == MMFM_MLP_RELU) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_RELU>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
-    else if (ak == MMFM_MLP_SIGMOID) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_SIGMOID>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
-    else if (ak == MMFM_MLP_GELU_TANH) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_GELU_TANH>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
-    else if (ak == kActEmbed) hipLaunchKernelGGL(gemm_big_kernel<kActEmbed>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
-    else hipLaunchKernelGGL(gemm_big_kernel<0>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a);
+    if (ak == MMFM_MLP_RELU) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_RELU>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a, lv);
+    else if (ak == MMFM_MLP_SIGMOID) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_SIGMOID>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a, lv);
+    else if (ak == MMFM_MLP_GELU_TANH) hipLaunchKernelGGL(gemm_big_kernel<MMFM_MLP_GELU_TANH>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a, lv);
+    else if (ak == kActEmbed) hipLaunchKernelGGL(gemm_big_kernel<kActEmbed>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a, lv);
+    else hipLaunchKernelGGL(gemm_big_kernel<0>, dim3(std::min(a.ntiles, 256)), dim3(NT), LDS_ALL, st, a, lv);
     MMFM_LAUNCH_CHECK("mmfm_gemm(bf16, 256 tile)");
     return 0;
 }

@@ -82,7 +82,7 @@ struct DwPair {
 };
 
 template <int TN, int BK>
-__global__ __launch_bounds__(DNT) void gemm_dw_kernel(const DwPair pr) {
+__global__ __launch_bounds__(DNT) void gemm_dw_kernel(const DwPair pr, const LiveArg lv) {
     const bool second = pr.first > 0 && (int)blockIdx.x >= pr.first;
     const DwArgs& a = second ? pr.b : pr.a;
     const int w0 = second ? (int)blockIdx.x - pr.first : (int)blockIdx.x;
@@ -91,7 +91,10 @@ __global__ __launch_bounds__(DNT) void gemm_dw_kernel(const DwPair pr) {
     constexpr int NLW = 4;                                       // every wave issues its quarter of the DMA loads
     constexpr int NST = G::NST, NJ = G::NJ, RBB = TN * 2;       // B image row bytes
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const mmfm_gemm_desc& d = a.d;
+    // a live-row launch (mmfm_gemm_live): K and the split ranges come from the device record; a split with an empty range requests
+    // nothing but zero-fill and stores zeros
+    mmfm_gemm_desc d = a.d;
+    live_patch(d, lv);
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave >> 1, wn = wave & 1;
@@ -252,7 +255,7 @@ DwArgs make_args(const mmfm_gemm_desc& d) {
 }
 
 template <int TN, int BK>
-int launch(const mmfm_gemm_desc& d, const mmfm_gemm_desc* d2, hipStream_t st) {
+int launch(const mmfm_gemm_desc& d, const mmfm_gemm_desc* d2, hipStream_t st, const LiveArg& lv) {
     typedef Geo<TN, BK> G;
     if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(gemm_dw_kernel<TN, BK>), G::LDS, "mmfm_gemm(bf16, dW stream)")) return rc;
     DwPair p;
@@ -265,7 +268,7 @@ int launch(const mmfm_gemm_desc& d, const mmfm_gemm_desc* d2, hipStream_t st) {
         p.first = p.a.items;
         grid = p.a.items + p.b.items;
     }
-    hipLaunchKernelGGL((gemm_dw_kernel<TN, BK>), dim3(grid), dim3(DNT), G::LDS, st, p);
+    hipLaunchKernelGGL((gemm_dw_kernel<TN, BK>), dim3(grid), dim3(DNT), G::LDS, st, p, lv);
     MMFM_LAUNCH_CHECK("mmfm_gemm(bf16, dW stream)");
     return 0;
 }
@@ -297,10 +300,10 @@ static bool dw_eligible(const mmfm_gemm_desc& d) {
 }
 
 // returns -1000 when the launch belongs to the general kernel of gemm_bf16.hip
-int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st) {
+int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
     const mmfm_gemm_desc& d = *dp;
-    if (!dw_eligible(d)) return -1000;
-    return dw_wide(d.N, d.K) ? launch<256, 32>(d, nullptr, st) : launch<128, 32>(d, nullptr, st);
+    if (!dw_eligible(d) || (lv.rec && !lv.kdim)) return -1000;
+    return dw_wide(d.N, d.K) ? launch<256, 32>(d, nullptr, st, lv) : launch<128, 32>(d, nullptr, st, lv);
 }
 
 // both descriptors in one launch when both belong to the streaming kernel with the same tile width, every item fits the grid once and the
@@ -312,5 +315,5 @@ int mmfm_gemm_dw_pair_launch(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp,
     if (wide != dw_wide(b.N, b.K)) return -1000;
     const int ia = mmfm_gemm_dw_tiles(a.M, a.N, a.K) * std::max(1, a.splits), ib = mmfm_gemm_dw_tiles(b.M, b.N, b.K) * std::max(1, b.splits);
     if (ia % 8 || ia + ib > 512) return -1000;
-    return wide ? launch<256, 32>(a, &b, st) : launch<128, 32>(a, &b, st);
+    return wide ? launch<256, 32>(a, &b, st, kNoLive) : launch<128, 32>(a, &b, st, kNoLive);
 }

@@ -54,8 +54,8 @@ __global__ void zero_u64_kernel(unsigned long long* p, int n) {
 template <typename T>
 __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ tok, const float* __restrict__ mod_row,
                                                          const float* __restrict__ pos, const int64_t* __restrict__ ts,
-                                                         const uint8_t* __restrict__ keep0, T* __restrict__ x, T* __restrict__ emb,
-                                                         int B, int Tn, int L, int m, int H, int max_F) {
+                                                         const uint8_t* __restrict__ keep0, const int32_t* __restrict__ rec, T* __restrict__ x,
+                                                         T* __restrict__ emb, int B, int Tn, int L, int m, int H, int max_F) {
     const int C4 = H / 4;
     const int64_t total = (int64_t)B * Tn * C4;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -73,7 +73,9 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
         const size_t o = ((size_t)b * L + l) * H + c;
         if (emb) io<T>::st4(emb + o, e);
         if (keep0[l]) {
-            const float4 tv = io<T>::ld4(tok + (size_t)r * H + c);
+            // rec (mmfm_stitch_fwd_live): tok holds the live rows only, (b, t) at b * T_live + rank[t]
+            const int64_t tr = rec ? (int64_t)b * rec[0] + rec[4 + Tn + t] : r;
+            const float4 tv = io<T>::ld4(tok + (size_t)tr * H + c);
             e.x += tv.x; e.y += tv.y; e.z += tv.z; e.w += tv.w;
         }
         io<T>::st4(x + o, e);
@@ -84,8 +86,8 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
 // no table, no time stamps - a chunk's partial is its d_mod row alone (the caller passes max_F = 0)
 template <typename T, bool POS>
 __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict__ dextra, const int64_t* __restrict__ ts,
-                                  const uint8_t* __restrict__ keep0, mmfm_dropout dropa, T* __restrict__ d_tok,
-                                  float* __restrict__ part, int B, int Tn, int L, int m, int H, int max_F, int bper) {
+                                  const uint8_t* __restrict__ keep0, const int32_t* __restrict__ rec, mmfm_dropout dropa,
+                                  T* __restrict__ d_tok, float* __restrict__ part, int B, int Tn, int L, int m, int H, int max_F, int bper) {
     extern __shared__ __attribute__((aligned(16))) float tab[];
     const int CW = blockDim.x, j = threadIdx.x, col = blockIdx.x * CW + j;
     const Drop dr = drop_init(dropa);
@@ -105,7 +107,9 @@ __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict_
                 tab[tsv * CW + j] += e;               // a thread owns its column: no race, fixed order
             }
             macc += e;
-            if (d_tok) io<T>::st(d_tok + (size_t)r * H + col, keep0[l] ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
+            if (d_tok && !rec) io<T>::st(d_tok + (size_t)r * H + col, keep0[l] ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
+            else if (d_tok && keep0[l])        // live rows only, at their compact rows; the counter stays the original row's
+                io<T>::st(d_tok + ((size_t)b * rec[0] + rec[4 + Tn + t]) * H + col, dr.apply(g, (uint64_t)r * H + col));
         }
     }
     float* out = part + (size_t)blockIdx.y * (max_F + 1) * H;
@@ -171,7 +175,8 @@ __global__ __launch_bounds__(256) void stitch_modsum_kernel(const uint16_t* __re
 }
 
 // d_tok[b*T+t][:] = keep0[m*T+t] ? dropout'(dx[b][m*T+t][:]) : 0      (bf16, 16-B accesses; H % 8 == 0)
-__global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __restrict__ dx, const uint8_t* __restrict__ keep0, mmfm_dropout dropa,
+__global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __restrict__ dx, const uint8_t* __restrict__ keep0,
+                                                          const int32_t* __restrict__ rec, mmfm_dropout dropa,
                                                           uint16_t* __restrict__ d_tok, int B, int Tn, int L, int m, int H) {
     const Drop dr = drop_init(dropa);
     const int C8 = H / 8;
@@ -181,6 +186,9 @@ __global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __rest
         const int c = (int)(idx % C8) * 8;
         const int b = (int)(r / Tn), l = m * Tn + (int)(r % Tn);
         uint4 o = make_uint4(0u, 0u, 0u, 0u);
+        // rec (mmfm_stitch_bwd_live): live rows only, at their compact rows; the dropout counter stays the original row's
+        if (rec && !keep0[l]) continue;
+        const int64_t orow = rec ? (int64_t)b * rec[0] + rec[4 + Tn + (int)(r % Tn)] : r;
         if (keep0[l]) {
             const uint4 g = *reinterpret_cast<const uint4*>(dx + ((size_t)b * L + l) * H + c);
             if (dr.on()) {
@@ -197,7 +205,7 @@ __global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __rest
                 o = g;
             }
         }
-        *reinterpret_cast<uint4*>(d_tok + (size_t)r * H + c) = o;
+        *reinterpret_cast<uint4*>(d_tok + (size_t)orow * H + c) = o;
     }
 }
 
@@ -264,7 +272,7 @@ bool oh_path(int dtype, int H) { return dtype == MMFM_BF16 && H % 8 == 0; }
 }  // namespace
 
 extern "C" int mmfm_reduce_slabs(float*, const float*, int64_t, int, int64_t, int, mmfm_stream);
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st);       // gemm_bf16.hip
+int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);       // gemm_bf16.hip
 
 extern "C" int mmfm_mask_prep(int B, int T, int M, const int64_t* const* mask_src, const int64_t* mask_stride,
                               const int64_t* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad,
@@ -302,21 +310,32 @@ extern "C" int mmfm_collate_csr(int B, int max_T, int max_N, float pad_value, co
     return 0;
 }
 
-extern "C" int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
-                               const uint8_t* keep0, void* x, void* emb, int B, int T, int L, int m, int H, int max_F, mmfm_stream stream) {
+static int stitch_fwd_impl(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
+                           const uint8_t* keep0, const int32_t* rec, void* x, void* emb, int B, int T, int L, int m, int H, int max_F,
+                           mmfm_stream stream) {
     MMFM_REQUIRE(tok && mod_emb_row && (ts || !pos_emb) && keep0 && x, "mmfm_stitch_fwd: null pointer");       // pos_emb NULL: no position table
     MMFM_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && m >= 0 && (m + 1) * T <= L && max_F > 0, "mmfm_stitch_fwd: bad shape");
     const int64_t n = (int64_t)B * T * (H / 4);
     dim3 grid((int)std::min<int64_t>(4096, (n + 255) / 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMFM_F32)
-        hipLaunchKernelGGL(stitch_fwd_kernel<float>, grid, block, 0, st, (const float*)tok, mod_emb_row, pos_emb, ts, keep0, (float*)x, (float*)emb, B, T, L, m, H, max_F);
+        hipLaunchKernelGGL(stitch_fwd_kernel<float>, grid, block, 0, st, (const float*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (float*)x, (float*)emb, B, T, L, m, H, max_F);
     else if (dtype == MMFM_BF16)
-        hipLaunchKernelGGL(stitch_fwd_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)tok, mod_emb_row, pos_emb, ts, keep0, (uint16_t*)x, (uint16_t*)emb, B, T, L, m, H, max_F);
+        hipLaunchKernelGGL(stitch_fwd_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (uint16_t*)x, (uint16_t*)emb, B, T, L, m, H, max_F);
     else
         return mmfm_set_error(-1, "mmfm_stitch_fwd: bad dtype %d", dtype);
     MMFM_LAUNCH_CHECK("mmfm_stitch_fwd");
     return 0;
+}
+extern "C" int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
+                               const uint8_t* keep0, void* x, void* emb, int B, int T, int L, int m, int H, int max_F, mmfm_stream stream) {
+    return stitch_fwd_impl(dtype, tok, mod_emb_row, pos_emb, ts, keep0, nullptr, x, emb, B, T, L, m, H, max_F, stream);
+}
+extern "C" int mmfm_stitch_fwd_live(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
+                                    const uint8_t* keep0, const int32_t* rec, void* x, void* emb, int B, int T, int L, int m, int H, int max_F,
+                                    mmfm_stream stream) {
+    MMFM_REQUIRE(rec, "mmfm_stitch_fwd_live: null live-bin record");
+    return stitch_fwd_impl(dtype, tok, mod_emb_row, pos_emb, ts, keep0, rec, x, emb, B, T, L, m, H, max_F, stream);
 }
 
 extern "C" int64_t mmfm_stitch_bwd_workspace(int dtype, int B, int T, int L, int H, int max_F) {
@@ -330,9 +349,9 @@ extern "C" int64_t mmfm_stitch_bwd_workspace(int dtype, int B, int T, int L, int
     return (int64_t)stitch_chunks(B, H, cw) * (max_F + 1) * H * sizeof(float);
 }
 
-extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
-                               mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
-                               int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+static int stitch_bwd_impl(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, const int32_t* rec,
+                           mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
+                           int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
     MMFM_REQUIRE(dx && (ts || !d_pos) && keep0 && d_mod_row, "mmfm_stitch_bwd: null pointer");                 // d_pos NULL: no position table
     MMFM_REQUIRE(B > 0 && T > 0 && H > 0 && max_F > 0 && m >= 0 && (m + 1) * T <= L, "mmfm_stitch_bwd: bad shape");
     if (oh_path(dtype, H)) {
@@ -350,7 +369,7 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
             if (d_tok) {
                 const int64_t n = (int64_t)B * T * (H / 8);
                 hipLaunchKernelGGL(stitch_dtok_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, st, (const uint16_t*)dx, keep0,
-                                   drop, (uint16_t*)d_tok, B, T, L, m, H);
+                                   rec, drop, (uint16_t*)d_tok, B, T, L, m, H);
             }
             hipLaunchKernelGGL(stitch_modsum_kernel, dim3(cdiv(H, 256), nsl), dim3(256), 0, st, (const uint16_t*)dx, (const uint16_t*)dextra,
                                (float*)workspace, B, T, L, m, H, bper);
@@ -364,7 +383,7 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
         if (d_tok) {
             const int64_t n = (int64_t)B * T * (H / 8);
             hipLaunchKernelGGL(stitch_dtok_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, st, (const uint16_t*)dx, keep0,
-                               drop, (uint16_t*)d_tok, B, T, L, m, H);
+                               rec, drop, (uint16_t*)d_tok, B, T, L, m, H);
         }
         MMFM_LAUNCH_CHECK("mmfm_stitch_bwd(one-hot)");
         mmfm_gemm_desc gd = {};
@@ -379,7 +398,7 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
             if (!src) continue;
             gd.B = src;
             gd.C = slabs + (int64_t)nsl * g.slab;
-            if (int rc = mmfm_gemm_bf16_launch(&gd, st)) return rc;
+            if (int rc = mmfm_gemm_bf16_launch(&gd, st, kNoLive)) return rc;
             nsl += g.S;
         }
         if (int rc = mmfm_reduce_slabs(d_pos, slabs, (int64_t)max_F * H, nsl, g.slab, acc_pos, stream)) return rc;
@@ -397,22 +416,91 @@ extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, co
     if (!d_pos) {
         // no position table: the same column slabs and chunks (so the same workspace bound), each chunk's partial one row of H floats
         if (dtype == MMFM_F32)
-            hipLaunchKernelGGL((stitch_bwd_kernel<float, false>), grid, block, 0, st, (const float*)dx, (const float*)dextra, ts, keep0, drop,
+            hipLaunchKernelGGL((stitch_bwd_kernel<float, false>), grid, block, 0, st, (const float*)dx, (const float*)dextra, ts, keep0, rec, drop,
                                (float*)d_tok, (float*)workspace, B, T, L, m, H, 0, bper);
         else
-            hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, false>), grid, block, 0, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, drop,
+            hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, false>), grid, block, 0, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, rec, drop,
                                (uint16_t*)d_tok, (float*)workspace, B, T, L, m, H, 0, bper);
         MMFM_LAUNCH_CHECK("mmfm_stitch_bwd(no table)");
         return mmfm_reduce_slabs(d_mod_row, (const float*)workspace, H, nch, H, acc_mod, stream);
     }
     if (dtype == MMFM_F32)
-        hipLaunchKernelGGL((stitch_bwd_kernel<float, true>), grid, block, lds, st, (const float*)dx, (const float*)dextra, ts, keep0, drop, (float*)d_tok,
+        hipLaunchKernelGGL((stitch_bwd_kernel<float, true>), grid, block, lds, st, (const float*)dx, (const float*)dextra, ts, keep0, rec, drop, (float*)d_tok,
                            (float*)workspace, B, T, L, m, H, max_F, bper);
     else
-        hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, true>), grid, block, lds, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, drop,
+        hipLaunchKernelGGL((stitch_bwd_kernel<uint16_t, true>), grid, block, lds, st, (const uint16_t*)dx, (const uint16_t*)dextra, ts, keep0, rec, drop,
                            (uint16_t*)d_tok, (float*)workspace, B, T, L, m, H, max_F, bper);
     MMFM_LAUNCH_CHECK("mmfm_stitch_bwd");
     const int64_t stride = (int64_t)(max_F + 1) * H;
     if (int rc = mmfm_reduce_slabs(d_pos, (const float*)workspace, (int64_t)max_F * H, nch, stride, acc_pos, stream)) return rc;
     return mmfm_reduce_slabs(d_mod_row, (const float*)workspace + (size_t)max_F * H, H, nch, stride, acc_mod, stream);
+}
+
+extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
+                               mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
+                               int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    return stitch_bwd_impl(dtype, dx, dextra, ts, keep0, nullptr, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L, m, H, max_F,
+                           workspace, workspace_bytes, stream);
+}
+extern "C" int mmfm_stitch_bwd_live(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, const int32_t* rec,
+                                    mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
+                                    int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(rec, "mmfm_stitch_bwd_live: null live-bin record");
+    return stitch_bwd_impl(dtype, dx, dextra, ts, keep0, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L, m, H, max_F,
+                           workspace, workspace_bytes, stream);
+}
+
+// ---- live-bin records and the gather of live input rows (include/mmfm.h, "live rows")
+namespace {
+// one wave per modality slot: ballot + popcount prefix over 64 bins at a time
+__global__ __launch_bounds__(64) void live_bins_kernel(const uint8_t* __restrict__ keep0, int T, int32_t* __restrict__ rec_all) {
+    const uint8_t* k = keep0 + (size_t)blockIdx.x * T;
+    int32_t* rec = rec_all + (size_t)blockIdx.x * MMFM_LIVE_REC_INTS(T);
+    const int lane = threadIdx.x;
+    int base = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool live = t < T && k[t] != 0;
+        const unsigned long long mask = __ballot(live);
+        const int r = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (t < T) rec[4 + T + t] = live ? r : -1;
+        if (live) rec[4 + r] = t;
+        base += __popcll(mask);
+    }
+    if (lane < 4) rec[lane] = lane == 0 ? base : 0;
+}
+
+// V = uint4 / uint32_t pieces, cpr of them per row; the grid is sized for all B * T rows, the loop ends at the live ones
+template <typename V>
+__global__ __launch_bounds__(256) void gather_live_kernel(const V* __restrict__ src, V* __restrict__ dst, int B, int T, int cpr,
+                                                          const int32_t* __restrict__ rec) {
+    const int tl = rec[0];
+    const int64_t total = (int64_t)B * tl * cpr;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = idx / cpr;
+        const int c = (int)(idx - row * cpr), b = (int)(row / tl), j = (int)(row - (int64_t)b * tl);
+        dst[idx] = src[((int64_t)b * T + rec[4 + j]) * cpr + c];
+    }
+}
+}  // namespace
+
+extern "C" int mmfm_live_bins(const uint8_t* keep0, int T, int M, int32_t* rec, mmfm_stream stream) {
+    MMFM_REQUIRE(keep0 && rec && T > 0 && M > 0, "mmfm_live_bins: bad arguments");
+    hipLaunchKernelGGL(live_bins_kernel, dim3(M), dim3(64), 0, (hipStream_t)stream, keep0, T, rec);
+    MMFM_LAUNCH_CHECK("mmfm_live_bins");
+    return 0;
+}
+
+extern "C" int mmfm_gather_live_rows(const void* src, void* dst, int B, int T, int64_t row_bytes, const int32_t* rec, mmfm_stream stream) {
+    MMFM_REQUIRE(src && dst && rec && B > 0 && T > 0 && row_bytes > 0 && row_bytes % 4 == 0 && row_bytes < ((int64_t)1 << 30),
+                 "mmfm_gather_live_rows: bad arguments (rows of a multiple of 4 bytes)");
+    const bool v16 = row_bytes % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    const int cpr = (int)(row_bytes / (v16 ? 16 : 4));
+    const int64_t n = (int64_t)B * T * cpr;
+    dim3 grid((int)std::min<int64_t>(4096, (n + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (v16) hipLaunchKernelGGL(gather_live_kernel<uint4>, grid, block, 0, st, (const uint4*)src, (uint4*)dst, B, T, cpr, rec);
+    else hipLaunchKernelGGL(gather_live_kernel<uint32_t>, grid, block, 0, st, (const uint32_t*)src, (uint32_t*)dst, B, T, cpr, rec);
+    MMFM_LAUNCH_CHECK("mmfm_gather_live_rows");
+    return 0;
 }

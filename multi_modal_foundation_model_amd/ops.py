@@ -70,6 +70,29 @@ def gemm(A, B, Cout, M, N, K, *, plan=None, **kw):
     _emit(plan, L.lib().mmfm_gemm, (C.byref(d),), keep=(d,))
 
 
+def live_rows(rec, B, T):
+    """The mmfm_live_rows of a live-bin record tensor (int32, live_bins) over the row space B * T."""
+    lv = L.LiveRows()
+    lv.rec, lv.B, lv.T = P(rec), B, T
+    lv._keep = rec
+    return lv
+
+
+def gemm_live(A, B, Cout, M, N, K, *, live, plan=None, **kw):
+    """mmfm_gemm_live: the product over the compact row space of `live` (live_rows); M (or, for dY^T.X, K) is the full B * T."""
+    d = gemm_desc(A, B, Cout, M, N, K, **kw)
+    _emit(plan, L.lib().mmfm_gemm_live, (C.byref(d), C.byref(live)), keep=(d, live))
+
+
+def live_bins(keep0, T, M, rec, plan=None):
+    """rec int32 [M][live_rec_ints(T)] <- the live-bin records of keep0 u8 [M][T] (mmfm_live_bins)."""
+    _emit(plan, L.lib().mmfm_live_bins, (P(keep0), T, M, P(rec)))
+
+
+def gather_live_rows(src, dst, B, T, row_bytes, rec, plan=None):
+    _emit(plan, L.lib().mmfm_gather_live_rows, (P(src), P(dst), B, T, row_bytes, P(rec)))
+
+
 def gemm_pair(da, db, plan=None):
     """Two independent products (descriptors from gemm_desc) through mmfm_gemm_pair: two streaming weight-gradient launches become one."""
     _emit(plan, L.lib().mmfm_gemm_pair, (C.byref(da), C.byref(db)), keep=(da, db))
@@ -163,6 +186,16 @@ def mask_prep(B, T, masks, strides, attn, channels, tokmask, keypad, keep0, mod_
 
 def stitch_fwd(tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, m, H, max_F, plan=None):
     _emit(plan, L.lib().mmfm_stitch_fwd, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(x), P(emb), B, T, Lseq, m, H, max_F))
+
+
+def stitch_fwd_live(tok, mod_row, pos, ts, keep0, rec, x, emb, B, T, Lseq, m, H, max_F, plan=None):
+    _emit(plan, L.lib().mmfm_stitch_fwd_live, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(rec), P(x), P(emb), B, T, Lseq, m, H, max_F))
+
+
+def stitch_bwd_live(dx, dextra, ts, keep0, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, m, H, max_F, ws, plan=None):
+    _emit(plan, L.lib().mmfm_stitch_bwd_live, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), P(rec), drop if drop is not None else L.NO_DROP,
+                                               P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, m, H, max_F, P(ws),
+                                               ws.numel() * ws.element_size()))
 
 
 def stitch_bwd(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, m, H, max_F, ws, plan=None):

@@ -32,6 +32,17 @@ def read_switches() -> Switches:
                     mlp_bwd_split=env.get("MMFM_MLP_BWD_SPLIT", "1") == "1")
 
 
+# Live rows: tokeniser rows (B * T per modality) from which a bf16 plan runs the tokeniser chains on the compact row space
+# of the time bins sample 0 leaves unmasked.  Below it the chains are launch-bound and the plan stays what it was.  MMFM_LIVE_ROWS = 0
+# turns the path off, 1 turns it on at any size
+LIVE_ROWS_MIN = 16384
+
+
+def live_rows_on(BT):
+    v = os.environ.get("MMFM_LIVE_ROWS")
+    return v == "1" if v in ("0", "1") else BT >= max(8192, LIVE_ROWS_MIN)
+
+
 # What a side of the model lays its blocks out with (EngineConfig.side, in this plan's mode): heads, I = inter_size, dp / dpe = the
 # transformer's / the embedder's dropout (0 outside training), act = (MMFM_MLP_* kind, beta) with act_fwd / act_grad the un-fused MLP's
 # mmfm_gemm act codes, the embedder's scale, mult, max_F, activation codes (emb_fwd / emb_grad) and pos, and - set by `workspaces` - use_keep (attention dropout of this side runs
@@ -69,6 +80,10 @@ class PlanBuilder:
         self.sides = {side: Side(c.side(side), training) for side in ("encoder", "decoder")}
         self.Imax, self.mult_max = max(sd.I for sd in self.sides.values()), max(sd.mult for sd in self.sides.values())
         self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
+        # the tokeniser chains on the live rows only (bf16; the fp32 parity path keeps the full row space).  lv: (side, slot) -> the
+        # slot's mmfm_live_rows, filled by forward()
+        self.live = self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
+        self.lv = {}
         self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
         # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
         # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
@@ -89,6 +104,21 @@ class PlanBuilder:
         if sd.emb_fwd == L.ACT_SOFTSIGN and self.code == L.BF16:
             return "a"
         return "z"
+
+    def live_bias_ok(self):
+        """The live path lets the bias gradient ride on the weight-gradient launch (mmfm_gemm_desc.colsum): a tokeniser linear whose bias
+        gradient does not sit right behind its weight gradient would need the stand-alone column sum, which knows no live rows."""
+        if not self.grad:
+            return True
+        e = self.e
+        for side, mods in self.mods_of.items():
+            for _, mod, _ in mods:
+                for lin in ("token_embed", "projection"):
+                    w = f"{side}_embeddings.{mod}.embedder.{lin}"
+                    gw, gb = e.Gv(w + ".weight"), e.Gb(w)
+                    if gb is not None and gb.data_ptr() != gw.data_ptr() + 4 * gw.numel():
+                        return False
+        return True
 
     def mk(self, side, name):
         """The key of mask product `name` of `side` ("encoder" / "decoder")."""
@@ -181,10 +211,12 @@ class PlanBuilder:
         return self.slabm[o:o + S * stride]
 
     # ------------------------------------------------------------------ linears and their gradients
-    def lin(self, plan, X, wname, Y, Mr, N, Kd, ldx=None, **kw):
-        K.gemm(X, self.e.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.e.Pb(wname), dtype=self.code, plan=plan, **kw)
+    def lin(self, plan, X, wname, Y, Mr, N, Kd, ldx=None, live=None, **kw):
+        """live: the mmfm_live_rows of the row space Mr (a tokeniser linear of the live path), else None."""
+        gemm = K.gemm if live is None else functools.partial(K.gemm_live, live=live)
+        gemm(X, self.e.W(wname + ".weight"), Y, Mr, N, Kd, lda=ldx or Kd, ldb=Kd, ldc=N, bias=self.e.Pb(wname), dtype=self.code, plan=plan, **kw)
 
-    def wgrad(self, plan, dY, X, dst, N, Kd, Mr, nb, S, kchunk, what, ldx=None, colsum=None, slab=None, paired=False):
+    def wgrad(self, plan, dY, X, dst, N, Kd, Mr, nb, S, kchunk, what, ldx=None, colsum=None, slab=None, paired=False, live=None):
         """THE weight-gradient product: dst[N, Kd], with nb (N or 0) column sums of dY right behind it, = dY[Mr, N]^T X[Mr, Kd].
         S == 1: one launch straight into dst (`colsum`: where its column sums go when not behind dst).  S > 1: S K-slabs of `stride`
         floats - in a region of ws/slabm whose reduction joins the segment's ONE launch (batched reduction), else in `slab`, reduced
@@ -199,7 +231,7 @@ class PlanBuilder:
                 raise RuntimeError(f"engine: {what}: {S} slabs x {stride} floats exceed the {out.numel()}-float slab workspace")
             cs = out.data_ptr() + 4 * N * Kd if nb else None
             split, red = dict(splits=S, kchunk=kchunk, slab_stride=stride), (dst, out, n, S, stride)
-        emit = K.gemm_desc if paired else functools.partial(K.gemm, plan=plan)
+        emit = K.gemm_desc if paired else functools.partial(K.gemm, plan=plan) if live is None else functools.partial(K.gemm_live, live=live, plan=plan)
         d = emit(dY, X, out, N, Kd, Mr, lda=N, ldb=ldx or Kd, ldc=Kd, a_kcontig=0, b_kcontig=0, dtype=self.code, c_f32=1, colsum=cs, **split)
         if paired:
             return d, red
@@ -230,9 +262,10 @@ class PlanBuilder:
             a = self.deferred.pop()
             self.dlin(plan, a["dY"], a["X"], a["wname"], a["Mr"], a["N"], a["Kd"])
 
-    def dlin(self, plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, **kw):
+    def dlin(self, plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, live=None, **kw):
         """Backward of Y[Mr,N] = X[Mr,Kd] @ W[N,Kd]^T + b:  dW, db into G;  dX = dY @ W (optional, fused epilogue).
-        ldx = row stride of X when its rows are padded."""
+        ldx = row stride of X when its rows are padded.  live: the mmfm_live_rows of the row space Mr when dY, X and dX hold the live rows
+        only (the split count and the kernels are those of all Mr rows; the kernels read the live count off the record)."""
         e, code = self.e, self.code
         S, kchunk = e._dw_split(N, Kd, Mr, ldn=ldx, sw=self.sw)
         gw, gb = e.Gv(wname + ".weight"), e.Gb(wname)
@@ -245,16 +278,19 @@ class PlanBuilder:
             self.flush_deferred(plan)
             self.deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd, nb=N if gb is not None else 0))
             return
-        self.wgrad(plan, dY, X, gw, N, Kd, Mr, N if adjacent and S > 1 else 0, S, kchunk, wname, ldx=ldx, colsum=gb if fused else None, slab=self.slab)
+        self.wgrad(plan, dY, X, gw, N, Kd, Mr, N if adjacent and S > 1 else 0, S, kchunk, wname, ldx=ldx, colsum=gb if fused else None, slab=self.slab,
+                   live=live)
         if gb is not None and (not fused or (S > 1 and not adjacent)):
+            assert live is None, wname          # live_bias_ok
             K.colsum(dY, Mr, N, N, gb, self.b["ws/col"], plan=plan)
         if dX is not None:
+            gemm = K.gemm if live is None else functools.partial(K.gemm_live, live=live)
             wT = e._w_transposed(wname, N, Kd, Mr, sw=self.sw) if code == L.BF16 else None
             if wT is not None:      # reduction >= 512: the 256-tile kernel (csrc/gemm_big.hip) against the K-contiguous transpose W^T [Kd, N]
                 self.used_wt.append(wname)
-                K.gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
+                gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
             else:
-                K.gemm(dY, e.W(wname + ".weight"), dX, Mr, Kd, N, lda=N, ldb=Kd, ldc=Kd, b_kcontig=0, dtype=code, plan=plan, **kw)
+                gemm(dY, e.W(wname + ".weight"), dX, Mr, Kd, N, lda=N, ldb=Kd, ldc=Kd, b_kcontig=0, dtype=code, plan=plan, **kw)
 
     def lin_norm_grad(self, plan, Gdb, wname, lnname, N):
         """Weight, bias and norm-parameter gradients of a norm-fed linear from Gdb = [dY^T x_hat | colsum dY]
@@ -407,6 +443,11 @@ class PlanBuilder:
         for side in ("encoder", "decoder") if self.split_masks else ("encoder",):       # mm.py:147-149 / 169-171: each side's own masks
             K.mask_prep(B, T, [b[f"mask/{m}"] for m, _, _ in self.mods_of[side]], [1] * M, b["attn"], [n for _, _, n in self.mods_of[side]],
                         b[mk(side, "tokmask")], b[mk(side, "keypad")], b[mk(side, "keep0")], b[mk(side, "mod_id")], b[mk(side, "count")], plan=fwd)
+            if self.live:
+                # the live-bin records of the side's modality slots, from its keep0 (device side: nothing is read back)
+                rec = buf(mk(side, "live"), (M, L.live_rec_ints(T)), torch.int32)
+                K.live_bins(b[mk(side, "keep0")], T, M, rec, plan=fwd)
+        gathered = set()
         tok_tmp = buf("tok_tmp", (BT, H))
         x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
         for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
@@ -419,12 +460,25 @@ class PlanBuilder:
                 # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
                 # every other activation but the identity stores z in both modes (2 bytes x B T x mult N in bf16)
                 z = buf(f"{side}/z/{m}", (BT, n2)) if self.embed_saved(sd) == "z" else None
-                self.lin(fwd, b[f"in/{m}"], p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=sd.emb_fwd, act_scale=sd.scale)
-                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe))
+                xin, lv = b[f"in/{m}"], None
+                if self.live:
+                    # a, z and tok_tmp hold the live rows only (b * T_live + rank[t]); the input's live rows are gathered once per
+                    # modality and mask set (the two sides share them unless their modalities differ)
+                    rec = b[mk(side, "live")][slot]
+                    lv = self.lv[side, slot] = K.live_rows(rec, B, T)
+                    xin = buf(mk(side, f"in_live/{m}"), (BT, _align(n, 8)))
+                    if mk(side, f"in_live/{m}") not in gathered:
+                        gathered.add(mk(side, f"in_live/{m}"))
+                        K.gather_live_rows(b[f"in/{m}"], xin, B, T, _align(n, 8) * self.es, rec, plan=fwd)
+                self.lin(fwd, xin, p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=sd.emb_fwd, act_scale=sd.scale, live=lv)
+                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), live=lv)
                 # row mod_to_indx[mod] of the table this tokeniser reads: its own, or the encoder's where the two share it
                 mod_row = e.Pf(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m]
                 pos = e.Pf(p + ".pos_embed.weight") if sd.pos else None            # embedder.pos: false -> emb = the modality row
-                K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
+                if lv is not None:
+                    K.stitch_fwd_live(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], lv._keep, xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
+                else:
+                    K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
         X = x_enc
         for i in range(c.n_enc):
             p, tag = f"encoder.{i}", f"enc{i}"
@@ -586,22 +640,27 @@ class PlanBuilder:
             sd = self.sides[side]
             for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 pS = f"{side}_embeddings.{mod}.embedder"
-                K.stitch_bwd(dS, dextra, b["ts"], b[self.mk(side, "keep0")], e._drop(f"{side}/embdrop/{m}", sd.dpe), buf(f"d/tok/{side}/{m}", (BT, H)),
-                             e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
-                             e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
-                             side == "encoder" and mod in shared, False, B, T, Lq, slot, H, sd.max_F, b["ws/stitch"], plan=self.cur)
+                lv = self.lv.get((side, slot))
+                stitch = K.stitch_bwd if lv is None else functools.partial(K.stitch_bwd_live, rec=lv._keep)
+                stitch(dS, dextra, b["ts"], b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), d_tok=buf(f"d/tok/{side}/{m}", (BT, H)),
+                       d_mod_row=e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
+                       d_pos=e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
+                       acc_mod=side == "encoder" and mod in shared, acc_pos=False, B=B, T=T, Lseq=Lq, m=slot, H=H, max_F=sd.max_F, ws=b["ws/stitch"],
+                       plan=self.cur)
         # the softsign gradient from the activation itself (bf16), or from the saved pre-activation (fp32, and every other activation)
         for side in ("decoder", "encoder"):
             sd = self.sides[side]
             saved = self.embed_saved(sd)
-            for m, mod, n in self.mods_of[side]:
+            for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
+                lv = self.lv.get((side, slot))
                 dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)
                 self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
                           act=L.ACT_SOFTSIGN_GRAD_OUT if saved == "a" else sd.emb_grad, act_scale=sd.scale,
-                          gradmul_pre=b[f"{side}/{saved}/{m}"] if saved else None)
-                self.dlin(self.cur, dz, b[f"in/{m}"], p + ".token_embed", BT, n2, n, ldx=_align(n, 8))
+                          gradmul_pre=b[f"{side}/{saved}/{m}"] if saved else None, live=lv)
+                self.dlin(self.cur, dz, b[f"in/{m}"] if lv is None else b[self.mk(side, f"in_live/{m}")], p + ".token_embed", BT, n2, n,
+                          ldx=_align(n, 8), live=lv)
         self.close_segment("embed")
         if self.used_wt:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
             tw = e._wt_table()

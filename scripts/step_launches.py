@@ -1,5 +1,10 @@
 """Every launch of the B=1024 bf16 step plan with its shape, its in-order HIP-event time and its rate against the algorithmic
-bytes / flops of that launch: which launches sit furthest from the ~4.2 TB/s the mixed row-strided patterns reach on this chip."""
+bytes / flops of that launch: which launches sit furthest from the ~4.2 TB/s the mixed row-strided patterns reach on this chip.
+
+    python scripts/step_launches.py [B] [objective]
+
+objective (encoding / decoding / token_masking): every step runs it instead of the trainer's draw.  A live-row launch (mmfm_gemm_live,
+DESIGN.md 3q) is listed as `gemm live` with the shape of its full row space: its bytes / flops, and so its rates, are those of all rows."""
 import os, sys, random, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "multi_modal_foundation_model_amd", "src")):
@@ -12,6 +17,7 @@ from multi_modal_foundation_model_amd.synthetic import synth_batch
 from trainer.make import make_multimodal_trainer
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+OBJECTIVE = sys.argv[2] if len(sys.argv) > 2 else None
 dev = torch.device("cuda", 0)
 cfg = load_config()
 model = build_model(cfg.model, 668, 2, seed=cfg.seed)
@@ -34,6 +40,8 @@ random.seed(42); torch.manual_seed(4242)
 model.train()
 for i in range(3):
     tr._sample_modes()
+    if OBJECTIVE:
+        tr.training_mode = OBJECTIVE
     out = tr._forward_model_outputs(dict(batch), masking_mode=tr.masking_mode, training_mode=tr.training_mode)
     out.loss.backward(); opt.step(); sch.step(); opt.zero_grad()
 torch.cuda.synchronize()
@@ -56,12 +64,12 @@ groups = collections.OrderedDict()
 for i, (fn, args, keep) in enumerate(entries):
     name, us = fn.__name__, acc[i] * 1e3
     by = fl = 0.0
-    if name == "mmfm_gemm":
+    if name in ("mmfm_gemm", "mmfm_gemm_live"):
         d = keep[0]
         kind = "x.W^T" if (d.a_kcontig and d.b_kcontig) else ("dY.W" if d.a_kcontig else "dY^T.X")
         extra = ("+pre" if d.pre_out else "") + ("+res" if d.residual else "") + ("+gm" if d.gradmul_pre else "") + (f"+act{d.act}" if d.act else "") \
             + ("+drop" if d.drop.p > 0 else "") + ("+colsum" if d.colsum else "") + (f" s{d.splits}" if d.splits > 1 else "")
-        key = f"gemm {kind:7s} M={d.M} N={d.N} K={d.K}{extra}"
+        key = f"gemm {'live ' if name.endswith('live') else ''}{kind:7s} M={d.M} N={d.N} K={d.K}{extra}"
         esz = 4 if d.c_f32 else 2
         by = 2.0 * (d.M * d.K + d.K * d.N) + esz * d.M * d.N * max(1, d.splits) + (2.0 * d.M * d.N if d.pre_out else 0) \
             + (2.0 * d.M * d.N if d.residual else 0) + (2.0 * d.M * d.N if d.gradmul_pre else 0)
@@ -87,7 +95,7 @@ for i, (fn, args, keep) in enumerate(entries):
     g[0] += 1; g[1] += us; g[2] += by; g[3] += fl
 
 tot = sum(g[1] for g in groups.values())
-print(f"B={B}: {n} launches, {tot / 1e3:.2f} ms; fused mask {eng._fused_mask(B * 200)}")
+print(f"B={B}{' ' + OBJECTIVE if OBJECTIVE else ''}: {n} launches, {tot / 1e3:.2f} ms; fused mask {eng._fused_mask(B * 200)}")
 print(f"{'launch':78s} {'n':>3s} {'us each':>8s} {'ms tot':>7s} {'TB/s':>6s} {'TF/s':>6s} {'us@4.2TB/s':>10s}")
 for key, g in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     each = g[1] / g[0]
