@@ -473,6 +473,35 @@ typedef struct {
 } mmfm_rowgemm_desc;
 int mmfm_rowgemm(const mmfm_rowgemm_desc* d, mmfm_stream stream);
 
+/* The row-owner linear over up to MMFM_ROWGEMM_MAX_GROUPS weight sets in ONE launch (the context side of cross-attention: every
+ * decoder layer projects the same normalised context rows to its keys / values, and their dX products sum into one gradient).
+ *   ln_bwd == 0 (grouped forward; ln = 1 or 2, K = 256, N in {64, 128, 256, 512, 1024}, groups * N <= 2560):
+ *       x_hat = norm(x[0]) once per row (written to xhat / rstd when non-NULL), then for every group g
+ *       y[g][R][N] = x_hat . w[g][N][K]^T + bias[g]        each y[g] bit-identical to mmfm_rowgemm(ln, x[0], w[g], bias[g]).
+ *   ln_bwd = 1 or 2 (grouped dX + norm backward; N = 256, K = 256 or 512 per group):
+ *       v = sum_g x[g][R][K] . w[g][256][K]^T   (w[g] = WpT of group g's forward linear, fp32 accumulation over all groups)
+ *       y[0] = residual + norm'(v)               exactly mmfm_rowgemm's ln_bwd epilogue on the summed product.
+ * Operands, outputs and weights of all groups share ldx / ldy / ldw; every tensor stays below 2 GiB, and the groups' weight matrices
+ * lie within 2 GiB of each other (they are slices of one prepared-weight tensor).
+ * MMFM_ROWGEMM_MAX_GROUPS is the feature macro for this export (MMFM_VERSION stays, as for MMFM_NULL_BIAS: no existing struct changed). */
+#define MMFM_ROWGEMM_MAX_GROUPS 8
+typedef struct {
+    int64_t R;
+    int K, N;                /* per group */
+    int groups;              /* 1 .. MMFM_ROWGEMM_MAX_GROUPS */
+    const void* x[MMFM_ROWGEMM_MAX_GROUPS]; int ldx;     /* forward: x[0] only */
+    const void* w[MMFM_ROWGEMM_MAX_GROUPS]; int ldw;
+    const float* bias[MMFM_ROWGEMM_MAX_GROUPS];          /* forward; NULL adds nothing */
+    void* y[MMFM_ROWGEMM_MAX_GROUPS]; int ldy;           /* backward: y[0] only */
+    int ln; float eps;
+    void* xhat; float* rstd;
+    const void* residual; int ldr;                       /* backward only */
+    int stream_out, rotate;
+    int ln_bwd;
+    const void* bwd_xhat; const float* bwd_rstd;
+} mmfm_rowgemm_groups_desc;
+int mmfm_rowgemm_groups(const mmfm_rowgemm_groups_desc* d, mmfm_stream stream);
+
 /* The MLP block in one launch (mm_utils.py:42-52 behind ln2, encoder_embeddings.py:114, decoder_embeddings.py:145):
  *   fwd:  y = x + dropout( down( gelu_erf( up( layernorm(x) ) ) ) )        the 512-wide intermediate never leaves the CU
  *         (gelu stands for the activation `act` throughout: GELU unless the trailing field says otherwise)

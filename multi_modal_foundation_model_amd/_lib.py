@@ -90,6 +90,18 @@ class RowGemmDesc(C.Structure):
                 ("stream_out", C.c_int), ("rotate", C.c_int), ("ln_bwd", C.c_int), ("bwd_xhat", C.c_void_p), ("bwd_rstd", C.c_void_p)]
 
 
+ROWGEMM_MAX_GROUPS = 8
+
+
+class RowGemmGroupsDesc(C.Structure):
+    """mmfm_rowgemm_groups_desc: the row-owner linear over up to ROWGEMM_MAX_GROUPS weight sets in one launch."""
+    _fields_ = [("R", C.c_int64), ("K", C.c_int), ("N", C.c_int), ("groups", C.c_int), ("x", C.c_void_p * ROWGEMM_MAX_GROUPS), ("ldx", C.c_int),
+                ("w", C.c_void_p * ROWGEMM_MAX_GROUPS), ("ldw", C.c_int), ("bias", C.c_void_p * ROWGEMM_MAX_GROUPS),
+                ("y", C.c_void_p * ROWGEMM_MAX_GROUPS), ("ldy", C.c_int), ("ln", C.c_int), ("eps", C.c_float), ("xhat", C.c_void_p),
+                ("rstd", C.c_void_p), ("residual", C.c_void_p), ("ldr", C.c_int), ("stream_out", C.c_int), ("rotate", C.c_int),
+                ("ln_bwd", C.c_int), ("bwd_xhat", C.c_void_p), ("bwd_rstd", C.c_void_p)]
+
+
 class MlpDesc(C.Structure):
     _fields_ = [("R", C.c_int64), ("x", C.c_void_p), ("ldx", C.c_int), ("eps", C.c_float), ("w_up", C.c_void_p),
                 ("b_up", C.c_void_p), ("w_down", C.c_void_p), ("b_down", C.c_void_p), ("drop", Dropout), ("y", C.c_void_p),
@@ -144,6 +156,7 @@ _PROTOS = {
     "mmfm_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
+    "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),
     "mmfm_mlp_fwd": (C.c_int, [C.POINTER(MlpDesc), _vp]),
     "mmfm_mlp_bwd": (C.c_int, [C.POINTER(MlpDesc), _vp]),
     "mmfm_ln_linear_grad_workspace": (C.c_int64, [_i]),

@@ -490,6 +490,224 @@ __global__ __launch_bounds__(512) void rowgemm_lnbwd8_kernel(const mmfm_rowgemm_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ grouped launches (mmfm_rowgemm_groups)
+// Up to 8 weight sets against the same rows.  The weights of all groups go through ONE buffer resource (`wbase` + a 32-bit byte offset
+// per group, host-checked); outputs / operands get one bounds-checked resource per group.  The per-group values are picked out of the
+// kernel arguments by a chain of scalar selects.
+constexpr int GROUPS_MAX = MMFM_ROWGEMM_MAX_GROUPS;
+constexpr int GBIAS_MAX = 2560;                     // floats: the biases of all groups stay in LDS (74 KB per workgroup, two per CU)
+struct GroupOff { uint32_t w[GROUPS_MAX]; };
+template <typename T>
+__device__ __forceinline__ T pick8(const T (&a)[GROUPS_MAX], int g) {
+    T r = a[0];
+#pragma unroll
+    for (int i = 1; i < GROUPS_MAX; ++i) r = g == i ? a[i] : r;
+    return r;
+}
+
+// Grouped forward: rowgemm_a_kernel<LN, NTS, 0> whose tile-pair loop walks the groups * N / 64 pairs of all groups (virtual pair vp:
+// group vp >> nps, pair vp & (N / 64 - 1)); the norm prologue and its side outputs run once per row pass.  Every output element sees
+// the statistics and the K = 256 product of the per-group launch, in the same order.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int LN, bool NTS>
+__global__ __launch_bounds__(256, 2) void rowgemm_groups_a_kernel(const mmfm_rowgemm_groups_desc d, const void* wbase, const GroupOff wo, int nps) {
+    constexpr int NT = 256, NW = 4, RING_B = RINGA_SLOTS * CHUNK;
+    extern __shared__ __attribute__((aligned(16))) char smem[];       // RING_B + NW * STG_BYTES + GBIAS_MAX * 4
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), m = lane & 31, h = lane >> 5;
+    // column blocks over the virtual pairs, as in rowgemm_a_kernel; the norm's side outputs are written by column block 0 only
+    const int np_g = d.N >> 6, np_all = np_g * d.groups;
+    const int npb = (np_all + (int)gridDim.y - 1) / (int)gridDim.y, pbase = (int)blockIdx.y * npb;
+    const int npair = min(npb, np_all - pbase), cpp = 2 * npair;
+    const int64_t npass = (d.R + 32 * NW - 1) / (32 * NW);
+    const int my_passes = blockIdx.x < npass ? (int)((npass - 1 - blockIdx.x) / gridDim.x) + 1 : 0;
+    if (my_passes == 0 || npair <= 0) return;
+    const __amdgpu_buffer_rsrc_t rs_w = wbuf(wbase);
+    const uint32_t ldwb = (uint32_t)d.ldw * 2u;
+    const int rot = d.rotate ? (int)(blockIdx.x % npair) : 0;
+    auto src = [&](int g) {
+        const int ti = g % cpp;
+        int vp = (ti >> 1) + rot; vp = pbase + (vp >= npair ? vp - npair : vp);
+        const int pr = vp & (np_g - 1);
+        AChunk c;
+        c.rs = rs_w; c.off = __builtin_amdgcn_readfirstlane(pick8(wo.w, vp >> nps) + (uint32_t)(32 * (2 * pr + (ti & 1))) * ldwb); c.ldb = ldwb; c.kind = 0;
+        return c;
+    };
+    char* stg = smem + RING_B + wave * STG_BYTES;
+    float* lbias = reinterpret_cast<float*>(smem + RING_B + NW * STG_BYTES);
+    for (int g = 0; g < d.groups; ++g) stage_vec(lbias + g * d.N, pick8(d.bias, g), d.N, t, NT);      // visible after the first chunk's barrier
+    const GBuf X = gbuf(d.x[0], d.R * d.ldx * 2);
+    const GBuf XH = gbuf(blockIdx.y == 0 ? d.xhat : nullptr, d.R * 512), RS = gbuf(blockIdx.y == 0 ? d.rstd : nullptr, d.R * 4);
+    const uint32_t ldxb = d.ldx * 2, ldyb = d.ldy * 2;
+    const ALane<NT> ring_al = alane_init<NT>(t, ldwb, 0u);
+    const AFrag fr = afrag_init(m, h);
+    RINGA_DECL(NT);
+    RINGA_START((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem, my_passes * cpp, src);
+    for (int pi = 0; pi < my_passes; ++pi) {
+        const uint32_t wrow0 = (uint32_t)(((int64_t)(blockIdx.x + (int64_t)pi * gridDim.x) * NW + wave) * 32);
+        const bool live = wrow0 < (uint32_t)d.R;          // wave-uniform: a wave without rows only keeps the ring turning
+        opnd x[16];
+        if (live) {
+            load_rows_lines<4>(stg, x, X, wrow0, ldxb, lane, m, h);
+            const float rs = norm_rows<LN>(x, d.eps);
+            store_rows_lines<4, true>(stg, XH, wrow0, 512u, lane, m, h, x);
+            st4f(RS, h == 0 ? (wrow0 + m) * 4u : 0xfffffff0u, rs);
+        }
+        // one tile pair = two ring steps + four line stores: the accounting of rowgemm_a_kernel (EXTRA = 4 behind the pass's first pair)
+        auto pair = [&](int tp, auto first) {
+            constexpr int EX = decltype(first)::value ? 0 : 4;
+            int vp = tp + rot; vp = pbase + (vp >= npair ? vp - npair : vp);
+            const int grp = vp >> nps, pr = vp & (np_g - 1);
+            const GBuf Y = gbuf(pick8(d.y, grp), d.R * d.ldy * 2);
+            const float* gb = lbias + grp * d.N;
+            f32x16 acc[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                uint32_t slot;
+                if (live) vm_wait_n<1024 / NT + EX>(); else vm_wait_n<1024 / NT>();
+                RINGA_SYNC_NOWAIT(src, slot);
+                if (live) {
+                    acc[j] = mma16a<4>(slot, fr, x, zero16(), [&](int g_) { RINGA_PIECE(g_); });
+                    add_vec(acc[j], gb, 2 * pr + j, h);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 1024 / NT; ++q) RINGA_PIECE(q);
+                }
+            }
+            if (!live) return;
+            stage_tile(stg, 0, m, h, acc[0]);
+            stage_tile(stg, 1, m, h, acc[1]);
+            flush_lines<NTS>(stg, Y, wrow0, ldyb, 128u * pr, lane);
+        };
+        pair(0, std::true_type());
+        for (int tp = 1; tp < npair; ++tp) pair(tp, std::false_type());
+    }
+}
+
+// Grouped dX + norm backward: acc[32 rows x 256] = sum over the groups * KP pieces (256 of K each) of x_piece . WpT_piece, then the
+// epilogue of rowgemm_lnbwd_a_kernel.  The operand is STREAMED: one piece (16 operands, 64 registers) is multiplied against the eight
+// persistent accumulator tiles (eight ring steps) while the lines of the next piece - the next pass's first piece behind a pass's last,
+// so every piece issues the same 16 loads - are in flight.  Vector-memory operations retire in order, hence the waits of a piece's steps:
+//   the lines are requested in front of step 0, behind the requests of chunks c and c+1: steps 0 and 1 may leave them in flight (EXTRA = 16);
+//   step 2 waits for chunk c+2, requested behind the lines: they have landed, and are moved into operand layout in front of that step,
+//   where the compiler's own (conservative) wait for them costs nothing the ring's wait would not.
+// (Requesting a whole K = 512 group's lines at once - one exposed round trip per 16 steps instead of 8 - measured the same 406 us at
+// R = 204,800 with five groups and needs 512 registers + 44 bytes of scratch: not kept.)
+// The weight ring's source is a counter pair (piece, tile) advanced once per request: no division by the runtime piece count.
+template <int KP, int NORM>
+__global__ __launch_bounds__(NT) void rowgemm_groups_lnbwd_kernel(const mmfm_rowgemm_groups_desc d, const void* wbase, const GroupOff wo) {
+    constexpr int RING_B = RINGA_SLOTS * CHUNK;
+    extern __shared__ __attribute__((aligned(16))) char smem[];       // RING_B + NW * STG_BYTES + NW * 4 * STG_BYTES
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), m = lane & 31, h = lane >> 5;
+    const int npiece = d.groups * KP;
+    const int64_t npass = (d.R + 32 * NW - 1) / (32 * NW);
+    const int my_passes = blockIdx.x < npass ? (int)((npass - 1 - blockIdx.x) / gridDim.x) + 1 : 0;
+    if (my_passes == 0) return;
+    const __amdgpu_buffer_rsrc_t rs_w = wbuf(wbase);
+    const uint32_t ldwb = (uint32_t)d.ldw * 2u;
+    int src_q = 0, src_t = 0;                           // the next chunk to request: piece, tile
+    auto src = [&](int) {
+        const int g = KP == 1 ? src_q : src_q >> 1, p = KP == 1 ? 0 : src_q & 1;
+        AChunk c;
+        c.rs = rs_w; c.off = __builtin_amdgcn_readfirstlane(pick8(wo.w, g) + (uint32_t)(32 * src_t) * ldwb + 512u * (uint32_t)p); c.ldb = ldwb; c.kind = 0;
+        if (++src_t == 8) { src_t = 0; if (++src_q == npiece) src_q = 0; }
+        return c;
+    };
+    char* stg = smem + RING_B + wave * STG_BYTES;
+    char* xstash = smem + RING_B + NW * STG_BYTES + wave * 4 * STG_BYTES;
+    const GBuf Y = gbuf(d.y[0], d.R * d.ldy * 2), RES = gbuf(d.residual, d.R * d.ldr * 2);
+    const GBuf XH = gbuf(d.bwd_xhat, d.R * 512), RS = gbuf(d.bwd_rstd, d.R * 4);
+    const uint32_t ldxb = d.ldx * 2, ldyb = d.ldy * 2, ldrb = d.ldr * 2;
+    const int64_t xbytes = d.R * d.ldx * 2;
+    const ALane<NT> ring_al = alane_init<NT>(t, ldwb, 0u);
+    const AFrag fr = afrag_init(m, h);
+    RINGA_DECL(NT);
+    RINGA_START((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem, my_passes * 8 * npiece, src);
+    auto row_of = [&](int pi) { return (uint32_t)(((int64_t)(blockIdx.x + (int64_t)pi * gridDim.x) * NW + wave) * 32); };
+    opnd x[16];
+    load_rows_lines<4>(stg, x, gbuf(d.x[0], xbytes), row_of(0), ldxb, lane, m, h);      // piece 0 of the first pass
+    for (int pi = 0; pi < my_passes; ++pi) {
+        const uint32_t wrow0 = row_of(pi);
+        // rows the next pass's first piece comes from; behind the last pass: beyond the tensor (the bounds check returns zeros)
+        const uint32_t nrow0 = pi + 1 < my_passes ? row_of(pi + 1) : (uint32_t)(npass * 32 * NW);
+        {
+            Lines xl[4];
+#pragma unroll
+            for (int tp = 0; tp < 4; ++tp) xl[tp] = fetch_lines(XH, wrow0, 512u, 128u * tp, lane);
+#pragma unroll
+            for (int tp = 0; tp < 4; ++tp) stage_lines(xstash + tp * STG_BYTES, xl[tp], lane);
+        }
+        float rs = ld4f(RS, (wrow0 + m) * 4u);
+        f32x16 acc[8];
+#pragma unroll
+        for (int tt = 0; tt < 8; ++tt) acc[tt] = zero16();
+        for (int q = 0; q < npiece; ++q) {
+            const int nq = q + 1 < npiece ? q + 1 : 0;
+            const uint32_t nrow = q + 1 < npiece ? wrow0 : nrow0;
+            const GBuf XN = gbuf(pick8(d.x, KP == 1 ? nq : nq >> 1), xbytes);
+            const uint32_t ncol = KP == 1 ? 0u : 512u * (uint32_t)(nq & 1);
+            Lines L[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) L[s] = fetch_lines(XN, nrow, ldxb, ncol + 128u * s, lane);
+            opnd xn[16];
+#pragma unroll
+            for (int tt = 0; tt < 8; ++tt) {
+                if (tt == 2) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        stage_lines(stg, L[s], lane);
+#pragma unroll
+                        for (int s4 = 0; s4 < 4; ++s4) xn[4 * s + s4] = unstage_opnd(stg, s4, m, h);
+                    }
+                }
+                uint32_t slot;
+                if (tt < 2) { RINGA_SYNC(src, slot, 16); acc[tt] = mma16a<4>(slot, fr, x, acc[tt], [&](int g_) { RINGA_PIECE(g_); }); }
+                else { RINGA_SYNC(src, slot, 0); acc[tt] = mma16a<4>(slot, fr, x, acc[tt], [&](int g_) { RINGA_PIECE(g_); }); }
+            }
+#pragma unroll
+            for (int s = 0; s < 16; ++s) x[s] = xn[s];
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x16 xt = unstage_tile(xstash + tp * STG_BYTES, j, m, h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { s1 += acc[2 * tp + j][i]; s2 = fmaf(acc[2 * tp + j][i], xt[i], s2); }
+            }
+        }
+        s1 = xhalf(s1);
+        s2 = xhalf(s2);
+        norm_bwd_stats<NORM>(s1, s2, rs);
+        Lines rl4[4];                                   // the residual-gradient lines, requested together
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) rl4[tp] = fetch_lines(RES, wrow0, ldrb, 128u * tp, lane);
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+            const Lines& rl = rl4[tp];
+            f32x16 o[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x16 xt = unstage_tile(xstash + tp * STG_BYTES, j, m, h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[j][i] = rs * (acc[2 * tp + j][i] - s1 - xt[i] * s2);
+            }
+            stage_lines(stg, rl, lane);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x16 r = unstage_tile(stg, j, m, h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[j][i] += r[i];
+            }
+            stage_tile(stg, 0, m, h, o[0]);
+            stage_tile(stg, 1, m, h, o[1]);
+            flush_lines<false>(stg, Y, wrow0, ldyb, 128u * tp, lane);
+        }
+    }
+}
+#pragma clang diagnostic pop
+
 // ------------------------------------------------------------------------------------------------ weight preparation
 // One block per (entry, 32-row tile of W): Wp = bf16(W * gamma[k]) [N][K], WpT = its transpose [K][N] (WpP / WpTP: the same, unit-permuted),
 // bp[n] = bias[n] + sum_k W[n][k] * beta[k]  (the LayerNorm affine folded into the linear it feeds).  scalar_gain: gamma is ONE float g
@@ -638,6 +856,77 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
 #undef RG_LAUNCH
     }
     MMFM_LAUNCH_CHECK("mmfm_rowgemm");
+    return 0;
+}
+
+extern "C" int mmfm_rowgemm_groups(const mmfm_rowgemm_groups_desc* dp, mmfm_stream stream) {
+    const mmfm_rowgemm_groups_desc d = *dp;
+    MMFM_REQUIRE(d.groups >= 1 && d.groups <= GROUPS_MAX && d.R > 0, "mmfm_rowgemm_groups: groups = %d (1 .. %d), R = %lld", d.groups, GROUPS_MAX, (long long)d.R);
+    MMFM_REQUIRE(d.ln >= 0 && d.ln <= 2 && d.ln_bwd >= 0 && d.ln_bwd <= 2 && (d.ln != 0) != (d.ln_bwd != 0),
+                 "mmfm_rowgemm_groups: ln = %d, ln_bwd = %d: exactly one of them must be 1 (LayerNorm) or 2 (ScaleNorm)", d.ln, d.ln_bwd);
+    MMFM_REQUIRE(d.ldx % 8 == 0 && d.ldw % 8 == 0 && d.ldy % 8 == 0 && d.ldx >= d.K && d.ldw >= d.K && d.ldy >= d.N,
+                 "mmfm_rowgemm_groups: leading dimensions (%d, %d, %d) must be multiples of 8 and cover the rows", d.ldx, d.ldw, d.ldy);
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const int nx = d.ln_bwd ? d.groups : 1, ny = d.ln_bwd ? 1 : d.groups;
+    uintptr_t wmin = (uintptr_t)d.w[0];
+    for (int g = 0; g < d.groups; ++g) {
+        MMFM_REQUIRE(d.w[g] && al16(d.w[g]) && al16(d.bias[g]), "mmfm_rowgemm_groups: group %d: weights NULL or operands not 16-byte aligned", g);
+        MMFM_REQUIRE(g >= nx || (d.x[g] && al16(d.x[g])), "mmfm_rowgemm_groups: group %d: x NULL or not 16-byte aligned", g);
+        MMFM_REQUIRE(g >= ny || (d.y[g] && al16(d.y[g])), "mmfm_rowgemm_groups: group %d: y NULL or not 16-byte aligned", g);
+        wmin = std::min(wmin, (uintptr_t)d.w[g]);
+    }
+    MMFM_REQUIRE(al16(d.residual) && al16(d.xhat) && al16(d.bwd_xhat), "mmfm_rowgemm_groups: operands must be 16-byte aligned");
+    GroupOff wo = {};
+    const int64_t wbytes = (int64_t)(d.ln_bwd ? 256 : d.N) * d.ldw * 2;
+    for (int g = 0; g < d.groups; ++g) {
+        const int64_t off = (int64_t)((uintptr_t)d.w[g] - wmin);
+        MMFM_REQUIRE(off + wbytes < (int64_t)1 << 31, "mmfm_rowgemm_groups: group %d: weights more than 2 GiB from the first group's", g);
+        wo.w[g] = (uint32_t)off;
+    }
+    const int64_t maxld = std::max<int64_t>(std::max(d.ldx, d.ldy), std::max(d.ldr, 256));
+    MMFM_REQUIRE((d.R + 256) * maxld * 2 < (int64_t)1 << 31, "mmfm_rowgemm_groups: tensors beyond 2 GiB are not addressable by the 32-bit buffer offsets");
+    static const int per_cu_env = [] { const char* e = getenv("MMFM_ROWGEMM_WG_PER_CU"); return e ? atoi(e) : 0; }();
+    hipStream_t st = (hipStream_t)stream;
+    const void* wbase = (const void*)wmin;
+    if (d.ln_bwd) {
+        MMFM_REQUIRE(d.N == 256 && (d.K == 256 || d.K == 512) && d.bwd_xhat && d.bwd_rstd,
+                     "mmfm_rowgemm_groups: ln_bwd needs N = 256, K = 256 or 512 (got %d, %d), x_hat and rstd", d.N, d.K);
+        MMFM_REQUIRE(!d.residual || (d.ldr % 8 == 0 && d.ldr >= d.N), "mmfm_rowgemm_groups: ldr %d", d.ldr);
+        dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1)), block(NT);
+        constexpr int LDS_L = RINGA_SLOTS * CHUNK + NW * STG_BYTES + NW * 4 * STG_BYTES;
+#define GLNB(KP, NORM)                                                                                                      \
+        {                                                                                                                   \
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_groups_lnbwd_kernel<KP, NORM>), LDS_L, "mmfm_rowgemm_groups")) return rc; \
+            hipLaunchKernelGGL((rowgemm_groups_lnbwd_kernel<KP, NORM>), grid, block, LDS_L, st, d, wbase, wo);              \
+        }
+        if (d.K == 256) { if (d.ln_bwd == 2) GLNB(1, 2) else GLNB(1, 1) }
+        else { if (d.ln_bwd == 2) GLNB(2, 2) else GLNB(2, 1) }
+#undef GLNB
+    } else {
+        MMFM_REQUIRE(d.K == 256, "mmfm_rowgemm_groups: the norm prologue needs K = 256 (got %d)", d.K);
+        MMFM_REQUIRE(d.N >= 64 && d.N <= 1024 && (d.N & (d.N - 1)) == 0, "mmfm_rowgemm_groups: N = %d must be 64, 128, 256, 512 or 1024", d.N);
+        MMFM_REQUIRE(d.groups * d.N <= GBIAS_MAX, "mmfm_rowgemm_groups: groups * N = %d > %d", d.groups * d.N, GBIAS_MAX);
+        MMFM_REQUIRE(!d.residual, "mmfm_rowgemm_groups: the grouped forward takes no residual");
+        int nps = 0;
+        while ((64 << nps) < d.N) ++nps;
+        dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 2, 4)), block(256);
+        constexpr int LDS_A = RINGA_SLOTS * CHUNK + 4 * STG_BYTES + GBIAS_MAX * 4;
+        // fewer row passes than a quarter of the resident slots: column blocks over the pairs of all groups (as mmfm_rowgemm)
+        const int64_t npass = (d.R + 127) / 128;
+        const int np_all = (d.N >> 6) * d.groups;
+        static const int nsplit_env = [] { const char* e = getenv("MMFM_ROWGEMM_NSPLIT"); return e ? atoi(e) : 1; }();
+        const int nyb = (nsplit_env && npass < 128) ? (int)std::max<int64_t>(1, std::min<int64_t>(np_all, 512 / npass)) : 1;
+        grid.y = (unsigned)((np_all + (np_all + nyb - 1) / nyb - 1) / ((np_all + nyb - 1) / nyb));
+#define GFWD(LN, NTS)                                                                                                       \
+        {                                                                                                                   \
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_groups_a_kernel<LN, NTS>), LDS_A, "mmfm_rowgemm_groups")) return rc; \
+            hipLaunchKernelGGL((rowgemm_groups_a_kernel<LN, NTS>), grid, block, LDS_A, st, d, wbase, wo, nps);              \
+        }
+        if (d.ln == 2) { if (d.stream_out) GFWD(2, true) else GFWD(2, false) }
+        else { if (d.stream_out) GFWD(1, true) else GFWD(1, false) }
+#undef GFWD
+    }
+    MMFM_LAUNCH_CHECK("mmfm_rowgemm_groups");
     return 0;
 }
 

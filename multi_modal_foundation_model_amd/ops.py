@@ -297,6 +297,32 @@ def rowgemm(x, w, y, R, N, K, *, ldx=None, ldw=None, ldy=None, bias=None, ln=Fal
     _emit(plan, L.lib().mmfm_rowgemm, (C.byref(d),), keep=(d,))
 
 
+def rowgemm_groups(xs, ws, ys, R, N, K, *, ldx=None, ldw=None, ldy=None, biases=None, ln=False, eps=1e-5, xhat=None, rstd=None,
+                   residual=None, ldr=0, stream_out=False, ln_bwd=False, bwd_xhat=None, bwd_rstd=None, rotate=True, plan=None):
+    """mmfm_rowgemm_groups over len(ws) weight sets.  Forward (ln): xs = [x], ys = one output per group, each what
+    rowgemm(x, ws[g], ys[g], ln=ln, bias=biases[g]) writes, the norm's x_hat / rstd written once.  Backward (ln_bwd): xs = one operand
+    per group, ys = [y] = residual + norm'(sum_g xs[g] . ws[g]^T)."""
+    G = len(ws)
+    if not 1 <= G <= L.ROWGEMM_MAX_GROUPS:
+        raise ValueError(f"rowgemm_groups: {G} groups (1 .. {L.ROWGEMM_MAX_GROUPS})")
+    if len(xs) != (G if ln_bwd else 1) or len(ys) != (1 if ln_bwd else G):
+        raise ValueError("rowgemm_groups: forward takes one x and a y per group, backward an x per group and one y")
+    d = L.RowGemmGroupsDesc()
+    d.R, d.K, d.N, d.groups = R, K, N, G
+    for g in range(G):
+        d.w[g] = P(ws[g])
+        d.bias[g] = P(biases[g]) if biases is not None else None
+    for g, x in enumerate(xs):
+        d.x[g] = P(x)
+    for g, y in enumerate(ys):
+        d.y[g] = P(y)
+    d.ldx, d.ldw, d.ldy = K if ldx is None else ldx, K if ldw is None else ldw, N if ldy is None else ldy
+    d.ln, d.eps, d.xhat, d.rstd = int(ln), eps, P(xhat), P(rstd)
+    d.residual, d.ldr = P(residual), ldr
+    d.stream_out, d.ln_bwd, d.bwd_xhat, d.bwd_rstd, d.rotate = int(stream_out), int(ln_bwd), P(bwd_xhat), P(bwd_rstd), int(rotate)
+    _emit(plan, L.lib().mmfm_rowgemm_groups, (C.byref(d),), keep=(d,))
+
+
 # transformer.act (a `transformers` ACT2FN name) -> (MMFM_MLP_* kind, beta): the MLP activations the kernels build
 MLP_ACTS = {
     "gelu": (L.MLP_GELU, 1.0),

@@ -43,6 +43,18 @@ def live_rows_on(BT):
     return v == "1" if v in ("0", "1") else BT >= max(8192, LIVE_ROWS_MIN)
 
 
+# Grouped context side: rows from which a bf16 plan on the fused norm + linear path projects the context to the keys / values
+# of ALL decoder layers in one launch (mmfm_rowgemm_groups) and sums their dX products behind one norm backward at the head of the bridge
+# segment.  Below it the per-layer launches stay, call for call.  MMFM_CTX_GROUP = 0 turns the path off, 1 turns it on at any size
+CTX_GROUP_MIN = 16384
+CTX_GROUP_BIAS = 2560       # floats of bias the grouped forward keeps in LDS: groups * N of one launch (csrc/rowgemm.hip, GBIAS_MAX)
+
+
+def ctx_group_on(R):
+    v = os.environ.get("MMFM_CTX_GROUP")
+    return v == "1" if v in ("0", "1") else R >= CTX_GROUP_MIN
+
+
 # What a side of the model lays its blocks out with (EngineConfig.side, in this plan's mode): heads, I = inter_size, dp / dpe = the
 # transformer's / the embedder's dropout (0 outside training), act = (MMFM_MLP_* kind, beta) with act_fwd / act_grad the un-fused MLP's
 # mmfm_gemm act codes, the embedder's scale, mult, max_F, activation codes (emb_fwd / emb_grad) and pos, and - set by `workspaces` - use_keep (attention dropout of this side runs
@@ -197,6 +209,8 @@ class PlanBuilder:
             sd.use_keep = self.code == L.BF16 and sd.dp > 0 and self.grad and sw.attn_keepbits
             sd.F_MLP = e.fused_mlp(name, fm)
         self.prep = e._build_prep() if fm else None
+        # the context side of all decoder layers in one launch per direction
+        self.ctx_group = self.F_LNL and self.code == L.BF16 and c.n_dec > 0 and ctx_group_on(R)
         if fm:
             K.prep_weights(self.prep["table"], self.prep["n"], self.prep["tiles"], plan=self.fwd)
             self.gdb = buf("ws/gdb", (max(_align(l.N * l.K + l.N) for l in e.linears if l.norm),), f32)
@@ -491,6 +505,8 @@ class PlanBuilder:
         else:
             self.ln_f(fwd, X, "encoder_norm", enc_out, "encnorm")
             self.lin(fwd, enc_out, "decoder_proj_context", context, R, H, H, residual=emb_enc, ldr=H)       # mm.py:292
+        if self.ctx_group:
+            self.context_kv(fwd, context)
         Y = x_dec
         for i in range(c.n_dec):
             p, tag = f"decoder.{i}", f"dec{i}"
@@ -500,7 +516,8 @@ class PlanBuilder:
             if self.F_LNL:
                 self.ln_lin(fwd, Ya, p + ".query_norm", p + ".cross_attn.query", qc, H, tag + "/qn")
                 # every decoder layer normalises the same context rows: the statistics are saved by the first layer only
-                self.ln_lin(fwd, context, p + ".context_norm", p + ".cross_attn.kv", kvc, 2 * H, tag + "/cn", alias=None if i == 0 else "dec0/cn")
+                if not self.ctx_group:
+                    self.ln_lin(fwd, context, p + ".context_norm", p + ".cross_attn.kv", kvc, 2 * H, tag + "/cn", alias=None if i == 0 else "dec0/cn")
             else:
                 hq, hc = buf(tag + "/hq", (R, H)), buf(tag + "/hc", (R, H))
                 self.ln_f(fwd, Ya, p + ".query_norm", hq, tag + "/qn")
@@ -520,6 +537,40 @@ class PlanBuilder:
             self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], tokmask[:, j * T:], Lq, T, BT, n,
                       b["loss_sum"][j:j + 1], b["ws/loss"])
         K.loss_finalize(b["loss_sum"], b[mk("decoder", "count")], M, b["loss"], b["inv_n"], plan=fwd)
+
+    def ctx_norm_kind(self):
+        """1 / 2: every decoder layer's context_norm is a LayerNorm / a ScaleNorm (the grouped launches norm once for all of them)."""
+        kinds = {self.e.is_sn(f"decoder.{i}.context_norm") for i in range(self.c.n_dec)}
+        assert len(kinds) == 1, "decoder layers with different context_norm kinds"
+        return 2 if kinds.pop() else 1
+
+    def context_kv(self, plan, context):
+        """dec{i}/kvc of every decoder layer from ONE pass over `context`: norm once (x_hat / rstd saved under dec0/cn, which every layer's
+        backward reads), then each layer's prepared cross_attn.kv.  Launches of as many layers as the biases fit in LDS, at most 8."""
+        b, R, H, n_dec = self.b, self.R, self.H, self.c.n_dec
+        per = max(1, min(L.ROWGEMM_MAX_GROUPS, CTX_GROUP_BIAS // (2 * H)))
+        xh = rs = None
+        if self.grad:
+            xh, rs = self.buf("dec0/cn/xh", (R, H)), self.buf("dec0/cn/rs", (R,), torch.float32)
+        for i0 in range(0, n_dec, per):
+            ids = range(i0, min(n_dec, i0 + per))
+            pws = [self.prep["v"][f"decoder.{i}.cross_attn.kv"] for i in ids]
+            K.rowgemm_groups([context], [pw["Wp"] for pw in pws], [self.buf(f"dec{i}/kvc", (R, 2 * H)) for i in ids], R, 2 * H, H,
+                             biases=[pw["bp"] for pw in pws], ln=self.ctx_norm_kind(), xhat=xh if i0 == 0 else None,
+                             rstd=rs if i0 == 0 else None, stream_out=True, plan=plan)
+        if self.grad:
+            for i in range(1, n_dec):
+                b[f"dec{i}/cn/xh"], b[f"dec{i}/cn/rs"] = xh, rs
+
+    def context_back(self, plan, dctx):
+        """d/ctx = norm'( sum_i d/kvc/{i} . W'_i ) in one launch (more than 8 layers: launches of 8 chained through the residual input)."""
+        b, R, H, n_dec = self.b, self.R, self.H, self.c.n_dec
+        order = list(reversed(range(n_dec)))
+        for j0 in range(0, n_dec, L.ROWGEMM_MAX_GROUPS):
+            ids = order[j0:j0 + L.ROWGEMM_MAX_GROUPS]
+            K.rowgemm_groups([b[f"d/kvc/{i}"] for i in ids], [self.prep["v"][f"decoder.{i}.cross_attn.kv"]["WpT"] for i in ids], [dctx], R, H, 2 * H,
+                             ldw=2 * H, residual=dctx if j0 else None, ldr=H if j0 else 0, ln_bwd=self.ctx_norm_kind(),
+                             bwd_xhat=b["dec0/cn/xh"], bwd_rstd=b["dec0/cn/rs"], plan=plan)
 
     # ------------------------------------------------------------------ backward blocks
     def close_segment(self, name):
@@ -591,11 +642,17 @@ class PlanBuilder:
 
     def cross_back(self, plan, dY, p, tag, dctx_in):
         """Cross attention (decoder_embeddings.py:143): query side -> the stream dY, context side -> d/ctx (added to `dctx_in`)."""
-        b, H, dqc, dkvc = self.b, self.H, self.b["d/qc"], self.b["d/kvc"]
+        b, H, dqc = self.b, self.H, self.b["d/qc"]
+        # grouped context side: every layer keeps its own d/kvc until the bridge segment sums their dX products (context_back)
+        dkvc = b["d/kvc/" + tag[3:]] if self.ctx_group else b["d/kvc"]
         self.out_proj_back(plan, dY, b[tag + "/a2"], p + ".cross_attn.out_proj")
         K.attn_bwd(self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
                                   d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=plan)
         self.norm_lin_back(plan, self.F_LNL, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", tag + "/hq", b[tag + "/xa"], dY, dY)
+        if self.ctx_group:       # the weight gradient where it was; no context-side dX here
+            self.dlin_ln(plan, dkvc, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", 2 * H)
+            self.flush_deferred(plan)
+            return
         self.norm_lin_back(plan, self.F_LNL, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", tag + "/hc", b["context"],
                            dctx_in, b["d/ctx"])
 
@@ -614,7 +671,12 @@ class PlanBuilder:
             self.dlin(self.cur, dpred, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[j * BT:(j + 1) * BT])
         self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
         self.close_segment("head")
-        buf("d/qc", (R, H)); buf("d/kvc", (R, 2 * H))
+        buf("d/qc", (R, H))
+        if self.ctx_group:
+            for i in range(c.n_dec):
+                buf(f"d/kvc/{i}", (R, 2 * H))
+        else:
+            buf("d/kvc", (R, 2 * H))
         for i in reversed(range(c.n_dec)):
             p, tag = f"decoder.{i}", f"dec{i}"
             self.mlp_back(self.cur, dY, p, tag, b[tag + "/yb"])
@@ -625,6 +687,8 @@ class PlanBuilder:
             raise NotImplementedError("n_dec == 0")
         # now dY = d(dec_tokens + dec_emb) and dctx = d(context); context = ctx_proj(enc_out) + encoder_emb (mm.py:292)
         dX = buf("d/xstream", (R, H))
+        if self.ctx_group:
+            self.context_back(self.cur, dctx)
         self.norm_lin_back(self.cur, self.F_LNL, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", "enc_out", self.enc_last, None, dX)
         self.close_segment("bridge")
         for i in reversed(range(c.n_enc)):

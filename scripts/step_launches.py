@@ -84,6 +84,14 @@ for i, (fn, args, keep) in enumerate(entries):
         key = f"rowgemm R={d.R} N={d.N} K={d.K}" + (" LN" if d.ln else "") + (" +res" if d.residual else "") + (" LNbwd" if d.ln_bwd else "")
         by = 2.0 * d.R * (d.K + d.N) + (2.0 * d.R * 256 if d.residual else 0) + (2.0 * d.R * 256 if (d.ln and d.xhat) else 0) + (2.0 * d.R * 256 if d.ln_bwd else 0)
         fl = 2.0 * d.R * d.N * d.K
+    elif name == "mmfm_rowgemm_groups":
+        d = keep[0]
+        key = f"rowgemm groups={d.groups} R={d.R} N={d.N} K={d.K}" + (" LN" if d.ln else "") + (" +res" if d.residual else "") + (" LNbwd" if d.ln_bwd else "")
+        if d.ln_bwd:        # every group's operand, x_hat, the optional residual, one output
+            by = 2.0 * d.R * (d.groups * d.K + 256 + d.N) + (2.0 * d.R * 256 if d.residual else 0)
+        else:               # the rows once, x_hat when saved, every group's output
+            by = 2.0 * d.R * (d.K + d.groups * d.N) + (2.0 * d.R * 256 if d.xhat else 0)
+        fl = 2.0 * d.R * d.N * d.K * d.groups
     elif name in ("mmfm_attn_fwd", "mmfm_attn_bwd"):
         d = keep[0]
         key = f"{name[5:]} B={d.B} h={d.heads} Lq={d.Lq} Lk={d.Lk} dh={d.dh} flags={d.flags & 0xff}"
