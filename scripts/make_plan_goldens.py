@@ -6,7 +6,7 @@
 
 Needs the MI355X (an Engine allocates its buffers on the device) but runs no forward and no kernel of the step: per row it builds the
 model, calls `model.engine()` and `engine._plan(B, T, training, grad)` under the row's MMFM_* switches (set and restored per row, the
-other plan-time switches cleared) and hashes what the plan would launch (tests/plan_sig.py).  --full DIR also writes every record of
+other plan-time switches and the size-chosen paths' overrides, plan_sig.AUTO, cleared) and hashes what the plan would launch (tests/plan_sig.py).  --full DIR also writes every record of
 every row to DIR/<row>.json for diffing two builds; those files are never committed.
 
 The committed file is what the plan builder launched BEFORE a change.  A pull request that means to change a launch regenerates it
@@ -25,12 +25,12 @@ import plan_sig as S  # noqa: E402  (tests/plan_sig.py; its helpers import puts 
 
 
 def with_switches(env, fn):
-    saved = {k: os.environ.pop(k, None) for k in S.SWITCHES}
+    saved = {k: os.environ.pop(k, None) for k in S.SWITCHES + S.AUTO}
     os.environ.update(env)
     try:
         return fn()
     finally:
-        for k in S.SWITCHES:
+        for k in S.SWITCHES + S.AUTO:
             os.environ.pop(k, None)
             if saved[k] is not None:
                 os.environ[k] = saved[k]
@@ -61,15 +61,17 @@ def main():
     sigs = {}
     for case in S.CASES:
         def one():
+            torch.cuda.reset_peak_memory_stats()
             eng, plan, secs = S.build_case(case)
-            return S.plan_signature(eng, plan, full=args.full is not None), secs
-        sig, secs = with_switches(case["env"], one)
+            return S.plan_signature(eng, plan, full=args.full is not None), secs, torch.cuda.max_memory_allocated()
+        sig, secs, nbytes = with_switches(case["env"], one)
         if args.full:
             os.makedirs(args.full, exist_ok=True)
             with open(os.path.join(args.full, case["name"] + ".json"), "w") as f:
                 json.dump(sig, f, indent=1, sort_keys=True)
         sigs[case["name"]] = {u: dict(sha256=v["sha256"], names=v["names"]) for u, v in sig.items()}
-        print(f"{case['name']}: {sum(len(v['names']) for v in sig.values())} launches, plan built in {secs * 1e3:.1f} ms", flush=True)
+        print(f"{case['name']}: {sum(len(v['names']) for v in sig.values())} launches, plan built in {secs * 1e3:.1f} ms, "
+              f"{nbytes / 2 ** 30:.2f} GiB allocated", flush=True)
         torch.cuda.empty_cache()
     with open(args.out, "w") as f:
         f.write(dump(sigs))

@@ -161,25 +161,32 @@ def resume_roundtrip(tmp_path, mc, dtype="fp32", B=4, after_save=None, after_res
         assert torch.equal(v, want[k]), k
 
 
-def graph_replay_matches_eager(monkeypatch, make_model, g):
-    """5 optimiser steps in fp32 of make_model() at the curve fixture's shape `g`: with hipGraph replay (the plan runs eagerly once, is
-    captured on the second step and replayed from the third) the losses are the ones of MMFM_GRAPH=0, bit for bit."""
-    res = {}
+def graph_replay_matches_eager(monkeypatch, make_model, g, steps=5, params=False):
+    """`steps` optimiser steps (5, in fp32 unless make_model() sets another compute_dtype) of make_model() at the curve fixture's shape
+    `g`: with hipGraph replay (the plan runs eagerly once, is captured on the second step and replayed from the third) the losses are
+    the ones of MMFM_GRAPH=0, bit for bit; params=True: so is every parameter after the last step."""
+    res, final = {}, {}
     for mode in ("0", "1"):
         monkeypatch.setenv("MMFM_GRAPH", mode)
         model = make_model().cuda()
-        res[mode] = run_curve(model, 5, g["B"], g["T"], g["n_ap"], g["n_beh"], g["total_steps"], ["token_masking"] * 5)
+        res[mode] = run_curve(model, steps, g["B"], g["T"], g["n_ap"], g["n_beh"], g["total_steps"], ["token_masking"] * steps)
         plan = model._engine._last
-        assert (set(plan["graphs"]) == {"fwd", "bwd"}) == (mode == "1") and plan["runs"]["fwd"] == 5
+        assert (set(plan["graphs"]) == {"fwd", "bwd"}) == (mode == "1") and plan["runs"]["fwd"] == steps
+        if params:
+            final[mode] = {k: p.detach().clone() for k, p in model.named_parameters()}
     print("eager", res["0"], "graph", res["1"])
     assert res["0"] == res["1"] and all(np.isfinite(res["0"]))
+    for k, v in final.get("0", {}).items():
+        assert torch.equal(final["1"][k], v), k
 
 
 # ---------------------------------------------------------------------------------------------- one step against the fp64 oracle
-def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed, embed=None):
+def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed, embed=None, oracle_dtype=torch.float64):
     """One training step of the HIP engine, then the fp64 oracle (on the GPU, plain torch) with the step's token masks and dropout
     multipliers (tests/dropout_refs.py); `embed` stands in for oracle.mm_oracle.embed where the model's tokeniser is not the default
-    one.  Returns the model output, {name: grad}, the oracle's output dict, {name: oracle grad} and the engine."""
+    one.  oracle_dtype = torch.float32 runs the oracle itself in single precision on the same inputs, masks and multipliers: what plain
+    fp32 torch is off the fp64 oracle by.  Returns the model output, {name: grad}, the oracle's output dict, {name: oracle grad} and
+    the engine."""
     from multi_modal_foundation_model_amd import ops as K
     model = build_model(mc, n_ap, n_beh, seed=model_seed)
     model.compute_dtype = dtype
@@ -194,7 +201,7 @@ def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed,
     B, T = batch["spikes_data"].shape[:2]
     mults = {k: v.cuda() for k, v in DR.collect_step_multipliers(K, eng, B, T).items()} if eng._sites else {}
     cfg = O.OracleCfg.from_model_config(mc, {"ap": n_ap, "behavior": n_beh})
-    sd = O.share_mod_emb({k: v.detach().double().clone() for k, v in model.state_dict().items()}, cfg)
+    sd = O.share_mod_emb({k: v.detach().to(oracle_dtype).clone() for k, v in model.state_dict().items()}, cfg)
     keys = O.trainable_keys(sd, cfg)
     for k in keys:
         sd[k].requires_grad_(True)
@@ -202,7 +209,7 @@ def engine_step_and_oracle(mc, n_ap, n_beh, batch, objective, dtype, model_seed,
     for m, d in ref_md.items():
         for k, v in list(d.items()):
             if isinstance(v, torch.Tensor):
-                d[k] = v.cuda().double() if v.is_floating_point() else v.cuda()
+                d[k] = v.cuda().to(oracle_dtype) if v.is_floating_point() else v.cuda()
         d["eval_mask"] = md[m]["inputs_mask"][:, :, None].to(torch.int64)          # the token masks the step ran with
     used = set()
     with mock.patch.object(O, "embed", embed) if embed else contextlib.nullcontext():

@@ -12,7 +12,8 @@ list of function names; `full=True` adds the records themselves.
 
 CASES is the matrix tests/golden/plan_signatures.json records (scripts/make_plan_goldens.py) and tests/test_plan_identity_gpu.py
 checks: the smallest shapes that select each regime of Engine._fused_mask, the batched slab reduction, weight-gradient pairing and
-the transposed-weight dX path."""
+the transposed-weight dX path, and the large-batch regime bench.py times (tests/large_regime.py: B_BIG = 343, the smallest batch on the
+benchmark's side of every size gate, and the benchmark's own plan at B = 1024)."""
 import bisect
 import ctypes as C
 import hashlib
@@ -24,6 +25,8 @@ from multi_modal_foundation_model_amd import _lib as L
 
 TABLES = {"mmfm_prep_weights": L.PrepEntry, "mmfm_reduce_slabs_multi": L.ReduceEntry}       # fn name -> row type of its device table
 SWITCHES = ("MMFM_FUSED", "MMFM_GEMM_BIG", "MMFM_GEMM_DW", "MMFM_BATCH_REDUCE", "MMFM_DW_PAIR", "MMFM_ATTN_KEEPBITS", "MMFM_MLP_BWD_SPLIT")
+# paths the plan builder chooses by size, with an override for A/B runs: cleared for every row (the rows record the automatic choice), set by none
+AUTO = ("MMFM_LIVE_ROWS", "MMFM_CTX_GROUP")
 _FLOATS = (C.c_float, C.c_double)
 
 
@@ -88,6 +91,8 @@ class _Entry:
     def value(self, v, t):
         if isinstance(t, type) and issubclass(t, C.Structure):
             return self.struct(v)
+        if isinstance(t, type) and issubclass(t, C.Array):      # an array field of a descriptor (mmfm_rowgemm_groups_desc: x, w, bias, y per group)
+            return self.array(v)
         if t is C.c_void_p:
             return self.ptr(v)
         if t in _FLOATS:
@@ -174,12 +179,18 @@ CASES = [
     _case("dh128_B8", dict(H=512, heads=4, inter=1024), "bf16", 8, 100),   # dh 128, no row-owner path, big-GEMM dX
     _case("loss_family_fp32", "loss_family", "fp32", None, None),          # B, T: the loss-family test's own
     _case("loss_family_bf16", "loss_family", "bf16", None, None),
+    # the large-batch regime (large_regime.B_BIG; R = 68,600, B T = 34,300): live rows, grouped context side, 256-wide dW tiles, large split counts
+    _case("default_B343", "default", "bf16", 343, 100),
+    _case("drop_B343", _DROP48, "bf16", 343, 100),                         # keep bits, every dropout site
+    _case("scalenorm_biasfree_B343", _SN, "bf16", 343, 100),
+    _case("sep_causal_B343", dict(sep=True, causal=True, dropout=0.1), "bf16", 343, 100),
+    _case("default_B1024", "default", "bf16", 1024, 100),                  # the plan bench.py times, built and not run
 ]
 
 
 def build_case(case):
     """(engine, plan, seconds the plan build took on the host) of one matrix row.  Builds the model and the plan and launches no kernel
-    of the step.  The caller has set the row's switches (case["env"]) and cleared the other SWITCHES."""
+    of the step.  The caller has set the row's switches (case["env"]) and cleared the other SWITCHES and AUTO."""
     import time
     from helpers import build_model, load_config, model_config
     B, T = case["B"], case["T"]

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("case", S.CASES, ids=[c["name"] for c in S.CASES])
 def test_plan_signature_is_the_recorded_one(case, monkeypatch):
-    for k in S.SWITCHES:
+    for k in S.SWITCHES + S.AUTO:
         monkeypatch.delenv(k, raising=False)
     for k, v in case["env"].items():
         monkeypatch.setenv(k, v)

@@ -117,6 +117,26 @@ def test_unresolvable_pointer_raises():
         S.plan_signature(eng, plan)
 
 
+def test_array_fields_of_a_descriptor_are_resolved_element_by_element():
+    """mmfm_rowgemm_groups_desc holds its per-group operands as pointer arrays: each is an (owner, offset), NULL stays None, and moving
+    one group's pointer changes the signature."""
+    groups = fn("mmfm_rowgemm_groups", C.POINTER(L.RowGemmGroupsDesc))
+
+    def with_groups(off):
+        eng, plan = make()
+        d = L.RowGemmGroupsDesc()
+        d.R, d.K, d.N, d.groups = 32, 256, 512, 2
+        d.x[0] = plan["b"]["x"].data_ptr()
+        d.w[0], d.w[1] = eng.Pw.data_ptr(), eng.Pw.data_ptr() + off
+        d.y[0], d.y[1] = plan["b"]["out"].data_ptr(), plan["b"]["slab"].data_ptr() + 16
+        plan["fwd"].append((groups, (C.byref(d),), (d,)))
+        return eng, plan
+    rec = S.plan_signature(*with_groups(64), full=True)["fwd"]["records"][-1]["keep"][0]
+    assert rec["w"] == [["Pw", 0], ["Pw", 64]] + [None] * (L.ROWGEMM_MAX_GROUPS - 2) and rec["bias"] == [None] * L.ROWGEMM_MAX_GROUPS
+    assert rec["y"][:2] == [["b:out", 0], ["b:slab", 16]] and rec["x"][0] == ["b:x", 0] and rec["groups"] == 2
+    assert hashes(with_groups(64))["fwd"] != hashes(with_groups(32))["fwd"] and hashes(with_groups(64)) == hashes(with_groups(64))
+
+
 def test_argument_count_is_checked():
     eng, plan = make()
     plan["fwd"].append((NORM, (None, None), ()))
