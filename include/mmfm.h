@@ -265,6 +265,23 @@ int mmfm_attn_bwd(const mmfm_attn_desc* d, mmfm_stream stream);
 int64_t mmfm_attn_keepbits_bytes(int B, int heads, int Lq, int Lk);
 /* the keep probability the keep-bit path applies for a drop probability p */
 float mmfm_attn_keep_prob(float p);
+/* Which kernel family mmfm_attn_fwd (backward == 0) or mmfm_attn_bwd (backward != 0) runs for *d: one of the codes below, or a negative
+ * code with mmfm_last_error set where the launch would refuse.  It launches nothing, reads no tensor (pointers count by being NULL or
+ * not and by their alignment) and makes no HIP call: a machine without a GPU answers it.  A forward and its backward always name the
+ * same family - the families draw the drop_p decisions from different sources - unless the gradient tensors alone keep the backward
+ * off the bf16 kernels (not 16-B aligned, or leading dims % 8 != 0): then it is an error where drop_p is on or the family cannot be
+ * left (KEEPBIT_LONG, BF16_TILED), and the next family down the list otherwise.  A backward on MMFM_ATTN_FAMILY_BF16 that runs the
+ * single-pass kernel instead of the two-phase pair has MMFM_ATTN_FAMILY_BWD_SINGLE or-ed in.
+ * MMFM_ATTN_FAMILY_MASK is the feature macro for this export (MMFM_VERSION stays, as for MMFM_NULL_BIAS: no existing struct changed). */
+#define MMFM_ATTN_FAMILY_KEEPBIT_DH32 1   /* csrc/attention_fast.hip: bf16, dh 32, keep-bit workspace */
+#define MMFM_ATTN_FAMILY_KEEPBIT_LONG 2   /* csrc/attention_long.hip: bf16, dh 64 / 128, keep-bit workspace */
+#define MMFM_ATTN_FAMILY_BF16 3           /* csrc/attention_bf16.hip: bf16 MFMA, the head's images resident in LDS */
+#define MMFM_ATTN_FAMILY_BF16_TILED 4     /* csrc/attention_bf16.hip: bf16 MFMA, chunk-streaming pair */
+#define MMFM_ATTN_FAMILY_F32 5            /* csrc/attention.hip: fp32 compute (fp32 or bf16 storage), LDS-resident */
+#define MMFM_ATTN_FAMILY_F32_TILED 6      /* csrc/attention.hip: fp32 compute, chunk-streaming pair */
+#define MMFM_ATTN_FAMILY_MASK 0xf
+#define MMFM_ATTN_FAMILY_BWD_SINGLE 0x10
+int mmfm_attn_family(const mmfm_attn_desc* d, int backward);
 
 /* ---------------------------------------------------------------------------------- masks / stitch
  * mm.py:245-275 (mask = eval_mask[:,:,0] & attn_mask), :102 (mod_mask), :145,167 (sample-0 ids),

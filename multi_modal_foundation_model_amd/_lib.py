@@ -20,6 +20,10 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmfm.h")
 
 F32, BF16 = 0, 1
 ATTN_DIAG, ATTN_CAUSAL, ATTN_SEP = 1, 2, 4
+# mmfm_attn_family (MMFM_ATTN_FAMILY_*)
+ATTN_FAMILY_KEEPBIT_DH32, ATTN_FAMILY_KEEPBIT_LONG, ATTN_FAMILY_BF16, ATTN_FAMILY_BF16_TILED, ATTN_FAMILY_F32, ATTN_FAMILY_F32_TILED = range(1, 7)
+ATTN_FAMILY_MASK, ATTN_FAMILY_BWD_SINGLE = 0xf, 0x10
+ATTN_KEEPBIT_FAMILIES = (ATTN_FAMILY_KEEPBIT_DH32, ATTN_FAMILY_KEEPBIT_LONG)
 ACT_NONE, ACT_GELU, ACT_SOFTSIGN, ACT_GELU_GRAD, ACT_SOFTSIGN_GRAD, ACT_SOFTSIGN_GRAD_OUT = 0, 1, 2, 3, 4, 5
 # the other MLP activations (transformer.act): forward / gradient pairs; the sigmoid kind takes beta in act_scale
 ACT_RELU, ACT_RELU_GRAD, ACT_SIGMOID, ACT_SIGMOID_GRAD, ACT_GELU_TANH, ACT_GELU_TANH_GRAD = 6, 7, 8, 9, 10, 11
@@ -138,6 +142,7 @@ _PROTOS = {
     "mmfm_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), _vp]),
     "mmfm_attn_keepbits_bytes": (C.c_int64, [_i, _i, _i, _i]),
     "mmfm_attn_keep_prob": (C.c_float, [_f]),
+    "mmfm_attn_family": (C.c_int, [C.POINTER(AttnDesc), _i]),
     "mmfm_mask_prep": (C.c_int, [_i, _i, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_collate_csr": (C.c_int, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_stitch_fwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -12,10 +12,8 @@
 // Backward: recompute P from Q, K and the saved LSE.  Phase A: a wave owns a key tile and keeps
 //   dK^T, dV^T in accumulators over all query tiles.  Phase B: a wave owns a query tile and keeps
 //   dQ^T.  No atomics: results are bitwise reproducible.
-#include "common.h"
+#include "attn_route.h"
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
 namespace {
 
@@ -772,26 +770,6 @@ size_t bwd_lds_bytes(int Lq, int Lk, int dh) {
     return (size_t)(2 * LqP * (dh + 1) + 2 * LkP * (dh + 1) + 2 * LqP + 4 * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16;
 }
 
-// Opt in to > 64 KiB of dynamic LDS once per kernel (not a stream operation; done on the first,
-// un-captured call so later graph captures see no attribute change).
-template <typename K>
-int set_lds(K kern, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_map<uint64_t, size_t> done;             // per (device, kernel)
-    if (bytes <= 65536) return 0;
-    const void* fn = reinterpret_cast<const void*>(kern);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t key = (uint64_t)(uintptr_t)fn ^ ((uint64_t)(dev + 1) << 56);
-    std::lock_guard<std::mutex> g(mu);
-    auto it = done.find(key);
-    if (it != done.end() && it->second >= bytes) return 0;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return mmfm_set_error((int)e, "hipFuncSetAttribute(%zu B LDS): %s", bytes, hipGetErrorString(e));
-    done[key] = 160 * 1024;
-    return 0;
-}
-
 int check_common(const mmfm_attn_desc& d, const char* who) {
     MMFM_REQUIRE(d.dtype == MMFM_F32 || d.dtype == MMFM_BF16, "%s: bad dtype", who);
     MMFM_REQUIRE(d.B > 0 && d.heads > 0 && d.Lq > 0 && d.Lk > 0, "%s: bad shape", who);
@@ -814,7 +792,7 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
 #define ATTN_DISPATCH(KERN, TT, DHV)                                                             \
     {                                                                                            \
         auto kern = KERN<TT, DHV>;                                                               \
-        if (int rc = set_lds(kern, lds)) return rc;                                              \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;  \
         hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(256), lds, (hipStream_t)stream, d);   \
     }
 
@@ -837,14 +815,10 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
         }                                                                        \
     }
 
-int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_bf16.hip (bf16 MFMA)
-int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_fast.hip (bf16, dh 32, L <= 224)
-int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);   // attention_long.hip (bf16, dh 64 / 128, keep-bit workspace)
-
 #define ATTN_TILED(KERN, GY, ...)                                                                                  \
     {                                                                                                              \
         auto kern = KERN<__VA_ARGS__>;                                                                             \
-        if (int rc = set_lds(kern, lds)) return rc;                                                                \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;                    \
         hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(tnw * 64), lds, (hipStream_t)stream, d);            \
     }
 #define ATTN_TILED_ALL(KERN, GY, ...)                                                                              \
@@ -866,79 +840,129 @@ int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         }                                                                                                          \
     }
 
-// One decision per SHAPE for forward and backward together: the bf16-MFMA kernels and the fp32-compute kernels draw their
-// attention-dropout decisions from different hash layouts, so a forward/backward pair must never be split across them,
-// and the untiled/tiled choice must not depend on which of the two passes happens to fit.
-static bool use_tiled(const mmfm_attn_desc& d) {
-    static const bool force = [] { const char* e = getenv("MMFM_ATTN_FORCE_TILED"); return e && atoi(e) != 0; }();
-    return force || fwd_lds_bytes(d.Lq, d.Lk, d.dh) > 160 * 1024 || bwd_lds_bytes(d.Lq, d.Lk, d.dh) > 160 * 1024;
+// The route: ONE decision per descriptor, for forward and backward together.  The families draw their attention-dropout decisions from
+// different sources (keep-bit workspace, the bf16 MFMA kernels' hash layout, the fp32-compute kernels' hash layout), so a
+// forward/backward pair must never be split across them, and the LDS-resident/tiled choice must not depend on which of the two passes
+// happens to fit.  Hence every predicate below reads only what the forward sees, and the backward takes the family its forward took.
+// The one thing only the backward sees is the gradient tensors' alignment, which the bf16 families need: where it is missing the
+// backward moves down the chain when no decision source changes with the move, and is an error otherwise.
+// MMFM_ATTN_FORCE_TILED: 1 = tiled kernels for every shape, 2 = as 1, and bf16 storage runs the fp32-compute kernels.
+static int attn_route(const mmfm_attn_desc& d, bool backward, AttnRoute& r) {
+    static const int force_tiled = [] { const char* e = getenv("MMFM_ATTN_FORCE_TILED"); return e ? atoi(e) : 0; }();
+    const bool bf16 = d.dtype == MMFM_BF16, misaligned = backward && bf16 && !attn_grads_aligned(d), drop = attn_drop_p_on(d);
+    bool fast = bf16 && mmfm_attn_fast_takes(d);
+    if (fast && misaligned) {
+        // the forward of this shape took its decisions from the keep bits; the general backward would hash different ones
+        if (drop) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 32): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 when "
+                                            "attention dropout runs on the keep-bit path (mmfm_attn_desc.keepbits)");
+        fast = false;
+    }
+    if (fast) { r.family = MMFM_ATTN_FAMILY_KEEPBIT_DH32; return 0; }
+    if (bf16 && mmfm_attn_long_takes(d)) {
+        if (misaligned) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 64 / 128): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 on the "
+                                                  "keep-bit path (mmfm_attn_desc.keepbits)");
+        r.family = MMFM_ATTN_FAMILY_KEEPBIT_LONG;
+        return 0;
+    }
+    if (bf16 && force_tiled != 2 && mmfm_attn_bf16_takes(d, force_tiled == 1, r)) {
+        if (!misaligned) return 0;
+        if (r.family == MMFM_ATTN_FAMILY_BF16_TILED)
+            return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, tiled): gradient tensors must be 16-byte aligned with leading dims % 8 == 0");
+        // the forward of this shape ran the bf16-MFMA kernel; the fp32-compute fallback lays its dropout hash out differently,
+        // so falling through would regenerate a DIFFERENT attention-dropout mask in the backward
+        if (drop) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 when "
+                                            "attention dropout is on (the fallback kernel family draws a different mask than the forward did)");
+    }
+    // fp32 compute, on fp32 or bf16 storage
+    if (force_tiled || fwd_lds_bytes(d.Lq, d.Lk, d.dh) > ATTN_LDS_MAX || bwd_lds_bytes(d.Lq, d.Lk, d.dh) > ATTN_LDS_MAX) {
+        const size_t lds = backward ? bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh) : fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+        MMFM_REQUIRE(lds <= ATTN_LDS_MAX, "mmfm_attn_%s: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)",
+                     backward ? "bwd" : "fwd", d.dh, d.Lq, d.Lk, lds);
+        r.family = MMFM_ATTN_FAMILY_F32_TILED;
+    } else {
+        r.family = MMFM_ATTN_FAMILY_F32;
+    }
+    return 0;
+}
+
+// What every entry point does first: the descriptor as the kernels get it, the checks, the route.
+static int attn_prologue(const mmfm_attn_desc* dp, bool backward, const char* who, mmfm_attn_desc& d, AttnRoute& r) {
+    MMFM_REQUIRE(dp, "%s: null descriptor", who);
+    static const int no_remap = [] { const char* e = getenv("MMFM_ATTN_NO_REMAP"); return e ? atoi(e) : 0; }();
+    d = *dp;
+    d.flags = (d.flags & 0xff) | (no_remap ? 0x100 : 0);          // bit 8: plain workgroup order (common.h attn_xcd_remap)
+    if (int rc = check_common(d, who)) return rc;
+    if (backward) {
+        MMFM_REQUIRE(d.d_o && d.dq && d.dk && d.dv, "mmfm_attn_bwd: null gradient tensor");
+        const int hd = d.heads * d.dh;
+        MMFM_REQUIRE(d.lddo >= hd && d.lddq >= hd && d.lddk >= hd && d.lddv >= hd, "mmfm_attn_bwd: gradient leading dim < heads*dh");
+        MMFM_REQUIRE(d.lddo % 4 == 0 && d.lddq % 4 == 0 && d.lddk % 4 == 0 && d.lddv % 4 == 0, "mmfm_attn_bwd: gradient leading dims must be multiples of 4");
+    }
+    return attn_route(d, backward, r);
+}
+
+extern "C" int mmfm_attn_family(const mmfm_attn_desc* dp, int backward) {
+    mmfm_attn_desc d;
+    AttnRoute r;
+    if (int rc = attn_prologue(dp, backward != 0, backward ? "mmfm_attn_bwd" : "mmfm_attn_fwd", d, r)) return rc < 0 ? rc : -1;
+    return r.family | (backward && r.family == MMFM_ATTN_FAMILY_BF16 && r.bwd_single ? MMFM_ATTN_FAMILY_BWD_SINGLE : 0);
 }
 
 extern "C" int mmfm_attn_fwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
-    MMFM_REQUIRE(dp, "mmfm_attn_fwd: null descriptor");
-    static const int no_remap = [] { const char* e = getenv("MMFM_ATTN_NO_REMAP"); return e ? atoi(e) : 0; }();
-    mmfm_attn_desc d_ = *dp;
-    d_.flags = (d_.flags & 0xff) | (no_remap ? 0x100 : 0);          // bit 8: plain workgroup order (common.h attn_xcd_remap)
-    const mmfm_attn_desc d = d_;
-    if (int rc = check_common(d, "mmfm_attn_fwd")) return rc;
-    if (d.dtype == MMFM_BF16) {          // bf16 MFMA kernel; shapes it does not take fall through to fp32 compute on bf16 storage
-        const int rf = mmfm_attn_fast_launch(d, false, (hipStream_t)stream);
-        if (rf != -1000) return rf;
-        const int rl = mmfm_attn_long_launch(d, false, (hipStream_t)stream);
-        if (rl != -1000) return rl;
-        const int rc = mmfm_attn_bf16_launch(d, false, (hipStream_t)stream);
-        if (rc != -1000) return rc;
+    const char* who = "mmfm_attn_fwd";
+    mmfm_attn_desc d_;
+    AttnRoute r;
+    if (int rc = attn_prologue(dp, false, who, d_, r)) return rc;
+    const mmfm_attn_desc& d = d_;
+    switch (r.family) {
+        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, false, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_KEEPBIT_LONG: return mmfm_attn_long_launch(d, false, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_BF16:
+        case MMFM_ATTN_FAMILY_BF16_TILED: return mmfm_attn_bf16_launch(d, r, false, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_F32_TILED: {
+            const size_t lds = fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+            const int tnw = tiled_nw(d.dh), gy = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
+            ATTN_TILED_ALL(attn_fwd_tiled_kernel, gy)
+            MMFM_LAUNCH_CHECK("mmfm_attn_fwd(tiled)");
+            return 0;
+        }
+        default: {
+            const size_t lds = fwd_lds_bytes(d.Lq, d.Lk, d.dh);
+            ATTN_DISPATCH_ALL(attn_fwd_kernel)
+            MMFM_LAUNCH_CHECK("mmfm_attn_fwd");
+            return 0;
+        }
     }
-    if (use_tiled(d)) {
-        const size_t lds = fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
-        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_fwd: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)", d.dh,
-                     d.Lq, d.Lk, lds);
-        const int tnw = tiled_nw(d.dh), gy = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
-        ATTN_TILED_ALL(attn_fwd_tiled_kernel, gy)
-        MMFM_LAUNCH_CHECK("mmfm_attn_fwd(tiled)");
-        return 0;
-    }
-    const size_t lds = fwd_lds_bytes(d.Lq, d.Lk, d.dh);
-    ATTN_DISPATCH_ALL(attn_fwd_kernel)
-    MMFM_LAUNCH_CHECK("mmfm_attn_fwd");
-    return 0;
 }
 
 extern "C" int mmfm_attn_bwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
-    MMFM_REQUIRE(dp, "mmfm_attn_bwd: null descriptor");
-    static const int no_remap = [] { const char* e = getenv("MMFM_ATTN_NO_REMAP"); return e ? atoi(e) : 0; }();
-    mmfm_attn_desc d_ = *dp;
-    d_.flags = (d_.flags & 0xff) | (no_remap ? 0x100 : 0);
-    const mmfm_attn_desc d = d_;
-    if (int rc = check_common(d, "mmfm_attn_bwd")) return rc;
-    MMFM_REQUIRE(d.d_o && d.dq && d.dk && d.dv, "mmfm_attn_bwd: null gradient tensor");
-    const int hd = d.heads * d.dh;
-    MMFM_REQUIRE(d.lddo >= hd && d.lddq >= hd && d.lddk >= hd && d.lddv >= hd, "mmfm_attn_bwd: gradient leading dim < heads*dh");
-    MMFM_REQUIRE(d.lddo % 4 == 0 && d.lddq % 4 == 0 && d.lddk % 4 == 0 && d.lddv % 4 == 0, "mmfm_attn_bwd: gradient leading dims must be multiples of 4");
-    if (d.dtype == MMFM_BF16) {
-        const int rf = mmfm_attn_fast_launch(d, true, (hipStream_t)stream);
-        if (rf != -1000) return rf;
-        const int rl = mmfm_attn_long_launch(d, true, (hipStream_t)stream);
-        if (rl != -1000) return rl;
-        const int rc = mmfm_attn_bf16_launch(d, true, (hipStream_t)stream);
-        if (rc != -1000) return rc;
-    }
-    if (use_tiled(d)) {
-        const size_t lds = bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
-        MMFM_REQUIRE(lds <= 160 * 1024, "mmfm_attn_bwd: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)", d.dh,
-                     d.Lq, d.Lk, lds);
-        const int tnw = tiled_nw(d.dh), gk = ((d.Lk + 31) / 32 + tnw - 1) / tnw, gq = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
+    const char* who = "mmfm_attn_bwd";
+    mmfm_attn_desc d_;
+    AttnRoute r;
+    if (int rc = attn_prologue(dp, true, who, d_, r)) return rc;
+    const mmfm_attn_desc& d = d_;
+    switch (r.family) {
+        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, true, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_KEEPBIT_LONG: return mmfm_attn_long_launch(d, true, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_BF16:
+        case MMFM_ATTN_FAMILY_BF16_TILED: return mmfm_attn_bf16_launch(d, r, true, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_F32_TILED: {
+            const size_t lds = bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+            const int tnw = tiled_nw(d.dh), gk = ((d.Lk + 31) / 32 + tnw - 1) / tnw, gq = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
 #define COMMA_PHASE0 , 0
 #define COMMA_PHASE1 , 1
-        ATTN_TILED_ALL(attn_bwd_tiled_kernel, gk, COMMA_PHASE0)
-        ATTN_TILED_ALL(attn_bwd_tiled_kernel, gq, COMMA_PHASE1)
+            ATTN_TILED_ALL(attn_bwd_tiled_kernel, gk, COMMA_PHASE0)
+            ATTN_TILED_ALL(attn_bwd_tiled_kernel, gq, COMMA_PHASE1)
 #undef COMMA_PHASE0
 #undef COMMA_PHASE1
-        MMFM_LAUNCH_CHECK("mmfm_attn_bwd(tiled)");
-        return 0;
+            MMFM_LAUNCH_CHECK("mmfm_attn_bwd(tiled)");
+            return 0;
+        }
+        default: {
+            const size_t lds = bwd_lds_bytes(d.Lq, d.Lk, d.dh);
+            ATTN_DISPATCH_ALL(attn_bwd_kernel)
+            MMFM_LAUNCH_CHECK("mmfm_attn_bwd");
+            return 0;
+        }
     }
-    const size_t lds = bwd_lds_bytes(d.Lq, d.Lk, d.dh);
-    ATTN_DISPATCH_ALL(attn_bwd_kernel)
-    MMFM_LAUNCH_CHECK("mmfm_attn_bwd");
-    return 0;
 }

@@ -12,10 +12,9 @@
 //   backward: phase A (wave owns 32 keys):  S = Q K^T, dP = dO V^T, dV^T += dO^T P, dK^T += Q^T dS
 //             phase B (wave owns 32 queries): S^T, dP^T, dQ^T += K^T dS^T        (no atomics)
 #include "attn_common.h"
+#include "attn_route.h"
 #include <algorithm>
 #include <stdlib.h>
-#include <mutex>
-#include <unordered_map>
 
 using namespace attn;
 
@@ -1205,89 +1204,59 @@ size_t bwd_lds(int Lq, int Lk, int dh, int nw, int phase) {
     return images + (phase == 0 ? (size_t)4 * LqP * 4 : 0) + (size_t)nw * 32 * RS + LkP + std::max(Lq, Lk) + 64;
 }
 
-// the attribute belongs to the (device, kernel) pair: a process that drives several GPUs must opt in on each
-int opt_in_lds(const void* kern, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_map<uint64_t, bool> done;
-    if (bytes <= 65536) return 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t key = (uint64_t)(uintptr_t)kern ^ ((uint64_t)(dev + 1) << 56);
-    std::lock_guard<std::mutex> g(mu);
-    if (done.count(key)) return 0;
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return mmfm_set_error((int)e, "hipFuncSetAttribute(%zu B LDS): %s", bytes, hipGetErrorString(e));
-    done[key] = true;
-    return 0;
-}
-
 }  // namespace
 
-// returns MMFM_NOT_HANDLED (-1000) if this path does not take the shape (the caller falls back to the generic
-// kernel), 0 on launch, otherwise an error code
-int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
-    if (!(d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128)) return -1000;
-    const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
-                    (uintptr_t)d.k % 16 == 0 && (uintptr_t)d.v % 16 == 0 && (uintptr_t)d.o % 16 == 0;
-    if (!al) return -1000;
-    {   // shape decision shared by forward and backward (see use_tiled in attention.hip): the untiled kernels are used only
-        // if all three fit; otherwise the tiled bf16 kernels take forward AND backward (one dropout hash layout per pair).
-        // MMFM_ATTN_FORCE_TILED: 1 = tiled bf16 kernels for every shape, 2 = hand the call to the fp32-compute tiled kernels.
-        static const int force_env = [] { const char* e = getenv("MMFM_ATTN_FORCE_TILED"); return e ? atoi(e) : 0; }();
-        if (force_env == 2) return -1000;
-        const int nwf = fwd_waves(), nwb = bwd_waves();
-        const bool fits = fwd_lds(d.Lq, d.Lk, d.dh, nwf) <= 160 * 1024 && bwd_lds(d.Lq, d.Lk, d.dh, nwb, 0) <= 160 * 1024 &&
-                          bwd_lds(d.Lq, d.Lk, d.dh, nwb, 1) <= 160 * 1024;
-        // dh 128 has no LDS-resident instantiation (a 200-token head's images alone are 109 KB): every shape goes tiled
-        if (!fits || force_env == 1 || d.dh == 128) {
-            const int gq = ((d.Lq + 31) / 32 + 3) / 4, gk = ((d.Lk + 31) / 32 + 3) / 4;
-#define TILED16(KERN, GY, LDSB)                                                                                   \
-            {                                                                                                     \
-                auto kern = KERN;                                                                                 \
-                if (int rc = opt_in_lds(reinterpret_cast<const void*>(kern), LDSB)) return rc;                    \
-                hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(256), LDSB, st, d);                        \
-            }
-            if (backward) {
-                const bool alb = d.lddo % 8 == 0 && d.lddq % 8 == 0 && d.lddk % 8 == 0 && d.lddv % 8 == 0 && (uintptr_t)d.d_o % 16 == 0 &&
-                                 (uintptr_t)d.dq % 16 == 0 && (uintptr_t)d.dk % 16 == 0 && (uintptr_t)d.dv % 16 == 0;
-                if (!alb) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, tiled): gradient tensors must be 16-byte aligned with leading dims % 8 == 0");
-                const size_t lds = bwd_tiled16_lds(d.Lq, d.Lk, d.dh);
-                if (lds > 160 * 1024) return -1000;
-                if (d.dh == 16) { TILED16((attn_bwd_bf16_tiled_kernel<16, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<16, 1>), gq, lds) }
-                else if (d.dh == 32) { TILED16((attn_bwd_bf16_tiled_kernel<32, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<32, 1>), gq, lds) }
-                else if (d.dh == 64) { TILED16((attn_bwd_bf16_tiled_kernel<64, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<64, 1>), gq, lds) }
-                else { TILED16((attn_bwd_bf16_tiled_kernel<128, 0>), gk, lds) TILED16((attn_bwd_bf16_tiled_kernel<128, 1>), gq, lds) }
-                MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, tiled)");
-            } else {
-                const size_t lds = fwd_tiled16_lds(d.Lq, d.Lk, d.dh);
-                if (lds > 160 * 1024 || bwd_tiled16_lds(d.Lq, d.Lk, d.dh) > 160 * 1024) return -1000;
-                if (d.dh == 16) TILED16((attn_fwd_bf16_tiled_kernel<16>), gq, lds)
-                else if (d.dh == 32) TILED16((attn_fwd_bf16_tiled_kernel<32>), gq, lds)
-                else if (d.dh == 64) TILED16((attn_fwd_bf16_tiled_kernel<64>), gq, lds)
-                else TILED16((attn_fwd_bf16_tiled_kernel<128>), gq, lds)
-                MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, tiled)");
-            }
-#undef TILED16
-            return 0;
+// Shapes the bf16 MFMA kernels take, and which of them: the LDS-resident kernels only if the forward and both backward phases fit;
+// otherwise (or with force_tiled, or at dh 128, which has no LDS-resident instantiation: a 200-token head's images alone are 109 KB)
+// the tiled kernels take forward AND backward.  One answer per shape, whichever direction asks.
+bool mmfm_attn_bf16_takes(const mmfm_attn_desc& d, bool force_tiled, AttnRoute& r) {
+    if (!(d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) || !attn_io_aligned(d)) return false;
+    const int nwb = bwd_waves();
+    const bool fits = fwd_lds(d.Lq, d.Lk, d.dh, fwd_waves()) <= ATTN_LDS_MAX && bwd_lds(d.Lq, d.Lk, d.dh, nwb, 0) <= ATTN_LDS_MAX &&
+                      bwd_lds(d.Lq, d.Lk, d.dh, nwb, 1) <= ATTN_LDS_MAX;
+    if (!fits || force_tiled || d.dh == 128) {
+        r.family = MMFM_ATTN_FAMILY_BF16_TILED;
+        return fwd_tiled16_lds(d.Lq, d.Lk, d.dh) <= ATTN_LDS_MAX && bwd_tiled16_lds(d.Lq, d.Lk, d.dh) <= ATTN_LDS_MAX;
+    }
+    r.family = MMFM_ATTN_FAMILY_BF16;
+    r.fwd_waves = fwd_waves_for(d.Lq);
+    if (r.fwd_waves == 8 && fwd_lds(d.Lq, d.Lk, d.dh, 8) > ATTN_LDS_MAX) r.fwd_waves = 4;
+    r.bwd_single = bwd1_ok(d.Lq, d.Lk, d.dh);
+    return true;
+}
+
+int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, const AttnRoute& r, bool backward, hipStream_t st) {
+    if (r.family == MMFM_ATTN_FAMILY_BF16_TILED) {
+        const int gq = ((d.Lq + 31) / 32 + 3) / 4, gk = ((d.Lk + 31) / 32 + 3) / 4;
+#define TILED16(KERN, GY, LDSB, WHAT)                                                                             \
+        {                                                                                                         \
+            auto kern = KERN;                                                                                     \
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;             \
+            hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(256), LDSB, st, d);                            \
         }
+        if (backward) {
+            const size_t lds = bwd_tiled16_lds(d.Lq, d.Lk, d.dh);
+#define TILED16B(DHV) { TILED16((attn_bwd_bf16_tiled_kernel<DHV, 0>), gk, lds, "mmfm_attn_bwd(bf16, tiled)") TILED16((attn_bwd_bf16_tiled_kernel<DHV, 1>), gq, lds, "mmfm_attn_bwd(bf16, tiled)") }
+            if (d.dh == 16) TILED16B(16) else if (d.dh == 32) TILED16B(32) else if (d.dh == 64) TILED16B(64) else TILED16B(128)
+#undef TILED16B
+            MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, tiled)");
+        } else {
+            const size_t lds = fwd_tiled16_lds(d.Lq, d.Lk, d.dh);
+#define TILED16F(DHV) TILED16((attn_fwd_bf16_tiled_kernel<DHV>), gq, lds, "mmfm_attn_fwd(bf16, tiled)")
+            if (d.dh == 16) TILED16F(16) else if (d.dh == 32) TILED16F(32) else if (d.dh == 64) TILED16F(64) else TILED16F(128)
+#undef TILED16F
+            MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, tiled)");
+        }
+#undef TILED16
+        return 0;
     }
     if (backward) {
-        const bool alb = d.lddo % 8 == 0 && d.lddq % 8 == 0 && d.lddk % 8 == 0 && d.lddv % 8 == 0 && (uintptr_t)d.d_o % 16 == 0 &&
-                         (uintptr_t)d.dq % 16 == 0 && (uintptr_t)d.dk % 16 == 0 && (uintptr_t)d.dv % 16 == 0;
-        if (!alb) {
-            // the forward of this shape ran the bf16-MFMA kernel; the fp32-compute fallback lays its dropout hash out differently,
-            // so falling through would regenerate a DIFFERENT attention-dropout mask in the backward
-            if (d.drop_p.p > 0.f && d.drop_p.state != nullptr)
-                return mmfm_set_error(-1, "mmfm_attn_bwd(bf16): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 when "
-                                          "attention dropout is on (the fallback kernel family draws a different mask than the forward did)");
-            return -1000;
-        }
-        if (bwd1_ok(d.Lq, d.Lk, d.dh)) {
+        if (r.bwd_single) {
             const size_t lds = bwd1_lds(d.Lq, d.Lk, d.dh);
 #define BWD1S(DHV)                                                                                                \
             {                                                                                                     \
-                auto kern = attn_bwd1_bf16_kernel<DHV, (DHV > 32)>;                                                         \
-                if (int rc = opt_in_lds(reinterpret_cast<const void*>(kern), lds)) return rc;                     \
+                auto kern = attn_bwd1_bf16_kernel<DHV, (DHV > 32)>;                                               \
+                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16, single pass)")) return rc; \
                 hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(BW1_NW * 64), lds, st, d);                     \
             }
             if (d.dh == 16) BWD1S(16) else if (d.dh == 32) BWD1S(32) else BWD1S(64)
@@ -1297,12 +1266,11 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         }
         const int nw = bwd_waves();
         const size_t lds0 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 0), lds1 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 1);
-        if (lds0 > 160 * 1024 || lds1 > 160 * 1024) return -1000;
 #define BWD1(DHV, NWV, PH)                                                                                        \
         {                                                                                                         \
             auto kern = attn_bwd_bf16_kernel<DHV, NWV, PH>;                                                       \
             const size_t lds = PH == 0 ? lds0 : lds1;                                                             \
-            if (int rc = opt_in_lds(reinterpret_cast<const void*>(kern), lds)) return rc;                         \
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16)")) return rc; \
             hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(NWV * 64), lds, st, d);                            \
         }
 #define BWD(DHV)                                                                                                  \
@@ -1313,14 +1281,12 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16)");
         return 0;
     }
-    int nw = fwd_waves_for(d.Lq);
-    if (nw == 8 && fwd_lds(d.Lq, d.Lk, d.dh, 8) > 160 * 1024) nw = 4;
+    const int nw = r.fwd_waves;
     const size_t lds = fwd_lds(d.Lq, d.Lk, d.dh, nw);
-    if (lds > 160 * 1024) return -1000;
 #define FWD1(DHV, NWV)                                                                                            \
     {                                                                                                             \
         auto kern = attn_fwd_bf16_kernel<DHV, NWV>;                                                               \
-        if (int rc = opt_in_lds(reinterpret_cast<const void*>(kern), lds)) return rc;                             \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_fwd(bf16)")) return rc; \
         hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(NWV * 64), lds, st, d);                                \
     }
 #define FWD(DHV) if (nw == 8) FWD1(DHV, 8) else FWD1(DHV, 4)

@@ -21,6 +21,7 @@
 // per number of valid 8-row groups, lazy rescaling of the running maximum, one query tile per wave with as many
 // waves as the head has tiles.
 #include "attn_common.h"
+#include "attn_route.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -759,30 +760,25 @@ int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st) {
     return 0;
 }
 
-// Shapes the fast kernels take.  Returns -1000 when the general kernels must run.
-int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
+// Shapes the fast kernels take (MMFM_ATTN_FAST=0: none).
+bool mmfm_attn_fast_takes(const mmfm_attn_desc& d) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_FAST"); return e && atoi(e) == 0; }();
-    if (off || d.dh != 32) return -1000;
+    if (off || d.dh != 32) return false;
     const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
-    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return -1000;
+    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return false;
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32;
-    if (d.Lq % 8 || d.Lk % 8 || nqt > 8 || nkt > B_CW || nkt > nqt) return -1000;
-    const bool drop = d.drop_p.p > 0.f && d.drop_p.state != nullptr;
-    if (drop && d.drop_p.p >= 1.f) return -1000;
+    if (d.Lq % 8 || d.Lk % 8 || nqt > 8 || nkt > B_CW || nkt > nqt) return false;
+    const bool drop = attn_drop_p_on(d);
+    if (drop && d.drop_p.p >= 1.f) return false;
     // with attention dropout the pair needs the keep-bit workspace (one decision source for both directions); without it the general
     // kernels hash, forward and backward alike
-    if (drop && d.keepbits == nullptr) return -1000;
-    const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
-                    (uintptr_t)d.k % 16 == 0 && (uintptr_t)d.v % 16 == 0 && (uintptr_t)d.o % 16 == 0 && (uintptr_t)d.keepbits % 128 == 0;
-    if (!al) return -1000;
-    const bool alb = !backward || (d.lddo % 8 == 0 && d.lddq % 8 == 0 && d.lddk % 8 == 0 && d.lddv % 8 == 0 && (uintptr_t)d.d_o % 16 == 0 &&
-                                   (uintptr_t)d.dq % 16 == 0 && (uintptr_t)d.dk % 16 == 0 && (uintptr_t)d.dv % 16 == 0);
-    if (!alb) {
-        // the forward of this shape took its decisions from the keep bits; the general backward would hash different ones
-        if (drop) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 32): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 when "
-                                            "attention dropout runs on the keep-bit path (mmfm_attn_desc.keepbits)");
-        return -1000;
-    }
+    if (drop && d.keepbits == nullptr) return false;
+    return attn_io_aligned(d) && (uintptr_t)d.keepbits % 128 == 0;
+}
+
+int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
+    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0, drop = attn_drop_p_on(d);
+    const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32;
     const int grid = d.B * d.heads;
     const float keep_scale = drop ? 1.f / mmfm_attn_keep_prob(d.drop_p.p) : 1.f;
     if (!backward) {

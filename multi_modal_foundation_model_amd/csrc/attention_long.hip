@@ -16,6 +16,7 @@
 // The two-phase backward stays (a single pass needs every key tile of a head in one workgroup's registers: 19 tiles x 64 accumulator
 // registers), so S and P are evaluated twice; what changed is what an evaluation costs.
 #include "attn_common.h"
+#include "attn_route.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -730,26 +731,22 @@ size_t dkv_long_lds(int dh, int Lq, bool masked) {
 
 int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st);          // attention_fast.hip
 
-// dh = 64 or 128 with the keep-bit workspace.  Returns -1000 when the general kernels must run.
-int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
+// dh = 64 or 128 with the keep-bit workspace (MMFM_ATTN_LONG=0: never).
+bool mmfm_attn_long_takes(const mmfm_attn_desc& d) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_LONG"); return e && atoi(e) == 0; }();
-    if (off || (d.dh != 64 && d.dh != 128) || d.keepbits == nullptr) return -1000;
+    if (off || (d.dh != 64 && d.dh != 128) || d.keepbits == nullptr) return false;
     const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
-    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return -1000;
-    if (d.Lq % 8 || d.Lk % 8) return -1000;
+    if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return false;
+    if (d.Lq % 8 || d.Lk % 8) return false;
     // the key bias (and the MASKED kernels' second bias row, mod_id bytes and votes) grow with Lk: past what a workgroup can have,
     // the whole shape - forward and backward alike - belongs to the general kernels
-    constexpr size_t LDS_MAX = 160 * 1024;
-    if (fwd_long_lds(d.dh, d.Lk, masked) > LDS_MAX || dq_long_lds(d.dh, d.Lk, masked) > LDS_MAX) return -1000;
-    const bool drop = d.drop_p.p > 0.f && d.drop_p.state != nullptr;
-    if (drop && d.drop_p.p >= 1.f) return -1000;
-    const bool al = d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.q % 16 == 0 &&
-                    (uintptr_t)d.k % 16 == 0 && (uintptr_t)d.v % 16 == 0 && (uintptr_t)d.o % 16 == 0 && (uintptr_t)d.keepbits % 128 == 0;
-    if (!al) return -1000;
-    const bool alb = !backward || (d.lddo % 8 == 0 && d.lddq % 8 == 0 && d.lddk % 8 == 0 && d.lddv % 8 == 0 && (uintptr_t)d.d_o % 16 == 0 &&
-                                   (uintptr_t)d.dq % 16 == 0 && (uintptr_t)d.dk % 16 == 0 && (uintptr_t)d.dv % 16 == 0);
-    if (!alb) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 64 / 128): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 on the "
-                                        "keep-bit path (mmfm_attn_desc.keepbits)");
+    if (fwd_long_lds(d.dh, d.Lk, masked) > ATTN_LDS_MAX || dq_long_lds(d.dh, d.Lk, masked) > ATTN_LDS_MAX) return false;
+    if (attn_drop_p_on(d) && d.drop_p.p >= 1.f) return false;
+    return attn_io_aligned(d) && (uintptr_t)d.keepbits % 128 == 0;
+}
+
+int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
+    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0, drop = attn_drop_p_on(d);
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32, bh = d.B * d.heads;
     const float keep_scale = drop ? 1.f / mmfm_attn_keep_prob(d.drop_p.p) : 1.f;
     // delta / dropout scale per (b, head, query): the tail of the keep-bit workspace, behind the bit tiles

@@ -406,7 +406,7 @@ extern "C" int mmfm_gemm_pair(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp
     hipStream_t st = (hipStream_t)stream;
     if (a.dtype == MMFM_BF16 && b.dtype == MMFM_BF16) {
         const int rc = mmfm_gemm_dw_pair_launch(&a, &b, st);
-        if (rc != -1000) return rc;
+        if (rc != MMFM_GEMM_DECLINED) return rc;
     }
     if (int rc = mmfm_gemm(ap, stream)) return rc;
     return mmfm_gemm(bp, stream);

@@ -470,9 +470,9 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveAr
     const mmfm_gemm_desc d = *dp;
     {
         const int rb = mmfm_gemm_big_launch(dp, st, lv);
-        if (rb != -1000) return rb;
+        if (rb != MMFM_GEMM_DECLINED) return rb;
         const int rw = mmfm_gemm_dw_launch(dp, st, lv);
-        if (rw != -1000) return rw;
+        if (rw != MMFM_GEMM_DECLINED) return rw;
     }
     MMFM_REQUIRE(d.splits == 1 || d.kchunk % 64 == 0, "mmfm_gemm(bf16): kchunk %d must be a multiple of 64", d.kchunk);
     static const int bk_env = [] { const char* e = getenv("MMFM_GEMM_BK"); return e ? atoi(e) : 0; }();

@@ -299,21 +299,21 @@ static bool dw_eligible(const mmfm_gemm_desc& d) {
     return true;
 }
 
-// returns -1000 when the launch belongs to the general kernel of gemm_bf16.hip
+// returns MMFM_GEMM_DECLINED when the launch belongs to the general kernel of gemm_bf16.hip
 int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
     const mmfm_gemm_desc& d = *dp;
-    if (!dw_eligible(d) || (lv.rec && !lv.kdim)) return -1000;
+    if (!dw_eligible(d) || (lv.rec && !lv.kdim)) return MMFM_GEMM_DECLINED;
     return dw_wide(d.N, d.K) ? launch<256, 32>(d, nullptr, st, lv) : launch<128, 32>(d, nullptr, st, lv);
 }
 
 // both descriptors in one launch when both belong to the streaming kernel with the same tile width, every item fits the grid once and the
-// first problem's item count is a multiple of 8; -1000 otherwise (the caller then issues them one after the other)
+// first problem's item count is a multiple of 8; MMFM_GEMM_DECLINED otherwise (the caller then issues them one after the other)
 int mmfm_gemm_dw_pair_launch(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp, hipStream_t st) {
     const mmfm_gemm_desc &a = *ap, &b = *bp;
-    if (!dw_eligible(a) || !dw_eligible(b)) return -1000;
+    if (!dw_eligible(a) || !dw_eligible(b)) return MMFM_GEMM_DECLINED;
     const bool wide = dw_wide(a.N, a.K);
-    if (wide != dw_wide(b.N, b.K)) return -1000;
+    if (wide != dw_wide(b.N, b.K)) return MMFM_GEMM_DECLINED;
     const int ia = mmfm_gemm_dw_tiles(a.M, a.N, a.K) * std::max(1, a.splits), ib = mmfm_gemm_dw_tiles(b.M, b.N, b.K) * std::max(1, b.splits);
-    if (ia % 8 || ia + ib > 512) return -1000;
+    if (ia % 8 || ia + ib > 512) return MMFM_GEMM_DECLINED;
     return wide ? launch<256, 32>(a, &b, st, kNoLive) : launch<128, 32>(a, &b, st, kNoLive);
 }

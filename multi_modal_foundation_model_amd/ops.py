@@ -167,6 +167,15 @@ def attn_keep_prob(p):
     return float(L.lib().mmfm_attn_keep_prob(float(p)))
 
 
+def attn_family(desc, backward=False):
+    """The kernel family (L.ATTN_FAMILY_*) attn_fwd / attn_bwd runs for `desc` (mmfm_attn_family: nothing is launched, no tensor is read,
+    no GPU is needed); raises where the launch would refuse.  A backward on the single-pass bf16 kernel has L.ATTN_FAMILY_BWD_SINGLE set."""
+    fam = L.lib().mmfm_attn_family(C.byref(desc), int(backward))
+    if fam < 0:
+        L.check(fam, "mmfm_attn_family")
+    return fam
+
+
 def attn_fwd(desc, plan=None):
     _emit(plan, L.lib().mmfm_attn_fwd, (C.byref(desc),), keep=(desc,))
 

@@ -151,12 +151,32 @@ def attention_dropout_ref(q, k, v, allowed, scale, mult_p=None, mult_o=None):
 
 
 # ------------------------------------------------------------------------------------ a whole step's masks -> the oracle's hook
+def attn_site_descs(engine, B, T):
+    """{site id: (forward, backward) mmfm_attn_desc the built training plan of batch shape (B, T) launches at that attention drop_p site}."""
+    plan = engine.plans[(B, T, True, True)]
+    by_site = lambda entries, name: {keep[0].drop_p.site: keep[0] for fn, _, keep in entries if fn.__name__ == name and keep[0].drop_p.p > 0}
+    fwd = by_site(plan["fwd"], "mmfm_attn_fwd")
+    bwd = by_site([e for _, seg in plan["bwd"] for e in seg], "mmfm_attn_bwd")
+    assert set(fwd) == set(bwd)
+    return {site: (fwd[site], bwd[site]) for site in fwd}
+
+
+def on_keepbit_kernels(fwd_desc, bwd_desc=None):
+    """Whether the launch of `fwd_desc` draws drop_p from the keep-bit workspace: the library's own answer (ops.attn_family), and the
+    same answer for the backward's descriptor - or the pair would be split."""
+    from multi_modal_foundation_model_amd import _lib as Lb, ops
+    fam = ops.attn_family(fwd_desc)
+    assert bwd_desc is None or ops.attn_family(bwd_desc, backward=True) & Lb.ATTN_FAMILY_MASK == fam
+    return fam in Lb.ATTN_KEEPBIT_FAMILIES
+
+
 def collect_step_multipliers(ops, engine, B, T):
     """{site key: multiplier (fp64, on the GPU, in the shape the oracle's tensor has at that site)} of the training step the engine just ran
     at batch shape (B, T): engine.rng still holds the state that step used, engine.dropout_sites names id, p, kind and shape, and the
     keep-bit sites are read from the engine's own workspaces."""
     out = {}
     M = len(engine.cfg.mods)
+    descs = attn_site_descs(engine, B, T)
     for s in engine.dropout_sites(B, T):
         key, site, p = s["key"], s["site"], s["p"]
         if s["kind"] == "flat":
@@ -168,7 +188,8 @@ def collect_step_multipliers(ops, engine, B, T):
             m = rowdrop_multiplier(ops, engine.rng, site, p, R)
         else:
             Bq, heads, Lq, Lk = s["shape"]
-            if s["keepbits"] is not None and keepbit_path(s["dh"], Lq, Lk):
+            if on_keepbit_kernels(*descs[site]):
+                assert s["keepbits"] is not None
                 m = keepbit_multiplier(ops, s["keepbits"], p, Bq, heads, Lq, Lk)
             else:
                 m = general_attn_multiplier(ops, engine.rng, site, p, engine.adt, s["dh"], Bq, heads, Lq, Lk)
@@ -177,25 +198,6 @@ def collect_step_multipliers(ops, engine, B, T):
         out[key] = m.double()
     assert len(out) == len(engine._sites) and M > 0
     return out
-
-
-# csrc/attention_long.hip at dh 128: image rows of 272 B, two 128-row chunk images and eight 32-row tiles (139,328 B with the flags),
-# plus per padded key 4 B of bias - and, under CAUSAL / SEP, 4 B of second bias row, 1 B of mod_id and the tile / chunk votes
-# (4 B per 32 and per 128 keys, 16 B) - within 160 KB.  The MASKED need is the larger one: 139,328 + 9.16 LkP <= 163,840 up to LkP = 2656.
-DH128_MAX_LK = 2656
-
-
-def keepbit_path(dh, Lq, Lk):
-    """Shapes whose drop_p decisions live in the keep-bit workspace when one is passed (include/mmfm.h: mmfm_attn_desc.keepbits), for
-    the dense and CAUSAL / SEP self-attention launches of the engine (bf16, aligned operands, Lq == Lk): bit groups of 8 queries / keys,
-    and per head dim the limit its kernels' LDS sets."""
-    if Lq % 8 or Lk % 8:
-        return False
-    if dh == 32:
-        return Lq <= 256 and Lk <= 224 and (Lk + 31) // 32 <= (Lq + 31) // 32
-    if dh == 128:
-        return Lk <= DH128_MAX_LK
-    return dh == 64 and Lk <= 9800
 
 
 def oracle_dropout_fn(mults, used=None):

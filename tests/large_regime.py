@@ -9,7 +9,7 @@ the same regime give EQUAL records:
               use_keep per side - read off a PlanBuilder of the plan's own shape, not restated;
   names       the C function names per plan unit (plan_sig.plan_units);
   launches    for every launch whose LAUNCHER chooses by size, the side of each of its gates, restated here ONCE from the launcher's
-              code (source lines at each rule below; tests/dropout_refs.keepbit_path is the precedent) and computed from the
+              code (source lines at each rule below; the attention launches need none: mmfm_attn_family answers) and computed from the
               descriptor the plan holds: mmfm_gemm / mmfm_gemm_live / mmfm_gemm_pair (which kernel: the 256-tile GEMM, the streaming
               weight-gradient kernel with 128- or 256-wide tiles, or the general 128-tile kernel; whether a pair leaves in one launch),
               mmfm_reduce_slabs and mmfm_colsum (one- or two-stage reduction, which branch of colsum_splits), and every row-owner

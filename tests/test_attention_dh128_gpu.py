@@ -72,9 +72,9 @@ def close_bf16(a, b, msg, tol):
     assert err <= tol * scale, f"{msg}: max abs err {err:.3e} vs scale {scale:.3e}"
 
 
-def on_keepbit_kernels(Lq, Lk):
-    """The launcher's rule (csrc/attention_long.hip) for the shapes of this file: bit groups of 8 queries / keys."""
-    return Lq % 8 == 0 and Lk % 8 == 0
+# which (Lq, Lk) of this file the keep-bit kernels take when a workspace is passed (the table of the module docstring: bit groups of 8
+# queries / keys); every launch asks the library (ops.attn_family) and compares its answer with this and with the workspace writes
+KEEPBIT_SHAPES = {(40, 40): True, (129, 129): False, (136, 136): True, (200, 200): True, (72, 129): False, (72, 136): True, (40, 24): True}
 
 
 def run_case(ops, path, Lq, Lk, flags, headpad, p):
@@ -124,11 +124,15 @@ def run_case(ops, path, Lq, Lk, flags, headpad, p):
         kw["drop_p"], kw["drop_o"] = ops.dropout(state, 7, p), ops.dropout(state, 9, p)
     desc = ops.attn_desc(code, B, HEADS, Lq, Lk, DH, qp, kp_, vp, ldq, ldk, ldk, o.data_ptr(), H, lse, kp, mi if flags & 4 else None, flags,
                          DH ** -0.5, d_o=d_o.data_ptr(), lddo=H, dq=dqp, dk=dkp, dv=dvp, lddq=ldq, lddk=ldk, lddv=ldk, **kw)
+    fam = ops.attn_family(desc)
+    on_keepbit = fam == Lb.ATTN_FAMILY_KEEPBIT_LONG
+    assert on_keepbit == (path == "keep" and KEEPBIT_SHAPES[(Lq, Lk)]), f"{path} Lq {Lq} Lk {Lk}: family {fam}"
+    assert ops.attn_family(desc, backward=True) & Lb.ATTN_FAMILY_MASK == fam, "forward and backward on different kernel families"
     ops.attn_fwd(desc)
     mult_p = mult_o = None
     if p > 0:
         am = allowed[:, None].expand(B, HEADS, Lq, Lk)
-        if path == "keep" and on_keepbit_kernels(Lq, Lk):
+        if on_keepbit:
             assert bool(kb[:nbits].any()), "dropout on the keep-bit kernels: the forward writes the bit tiles"
             mult_p = DR.keepbit_multiplier(ops, kb, p, B, HEADS, Lq, Lk)
             keep_p = ops.attn_keep_prob(p)                           # the keep-bit path honours p to 2^-10
@@ -141,12 +145,12 @@ def run_case(ops, path, Lq, Lk, flags, headpad, p):
         print(f"keep rate over {n} allowed elements: {rate:.5f} (keep {keep_p:.5f})")
         assert abs(rate - keep_p) < 5 * math.sqrt(p * (1 - p) / n) + 1e-4, f"keep rate {rate} over {n} allowed elements"
         mult_o = DR.flat_multiplier(ops, state, 9, p, B * Lq, H)
-    elif kb is not None and on_keepbit_kernels(Lq, Lk):
+    elif on_keepbit:
         assert not bool(kb[:nbits].any()), "no dropout: no bit tile is written"
     ops.attn_bwd(desc)
     if kb is not None:                                               # delta / dropout scale per (b, head, query), behind the bit tiles
         tail = kb[nbits:nbits + B * HEADS * Lq * 4]
-        assert bool(tail.any()) == on_keepbit_kernels(Lq, Lk), "only the keep-bit backward writes the workspace's tail"
+        assert bool(tail.any()) == on_keepbit, "only the keep-bit backward writes the workspace's tail"
     leaves = [t.double().contiguous().requires_grad_(True) for t in (q_in, k_in, v_in)]
     Q = leaves[0].view(B, Lq, HEADS, DH).transpose(1, 2)
     K_, V_ = [t.view(B, Lk, HEADS, DH).transpose(1, 2) for t in leaves[1:]]

@@ -7,9 +7,10 @@ read out of the bit tiles the forward leaves in the keep-bit workspace (document
 cases fail wherever CAUSAL / SEP launches still run on the general kernels."""
 import math
 
-import numpy as np
 import pytest
 import torch
+
+import dropout_refs as DR
 
 pytestmark = pytest.mark.gpu
 
@@ -45,21 +46,6 @@ def close_bf16(a, b, msg, tol):
     a, b = a.float().cpu(), b.float().cpu()
     err, scale = (a - b).abs().max().item(), b.abs().max().item() + 1e-6
     assert err <= tol * scale, f"{msg}: max abs err {err:.3e} vs scale {scale:.3e}"
-
-
-def _unpack_keepbits(kb, B, heads, Lq, Lk):
-    """keep[b, h, q, k] out of the documented bit-tile layout (csrc/attention_fast.hip header): words [bh][qt][kt][32], word 2 r + kh
-    of a tile = key 32 kt + (r & 3) + 8 (r >> 2) + 4 kh, bit j = query 32 qt + j."""
-    nqt, nkt = (Lq + 31) // 32, (Lk + 31) // 32
-    w = kb[:B * heads * nqt * nkt * 128].view(torch.int32).view(B * heads, nqt, nkt, 32).cpu().numpy().astype(np.uint32)
-    bits = ((w[..., None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool)          # [bh, qt, kt, word, qbit]
-    widx = np.arange(32)
-    key_of_word = ((widx >> 1) & 3) + 8 * (widx >> 3) + 4 * (widx & 1)
-    keep = np.zeros((B * heads, nqt * 32, nkt * 32), dtype=bool)
-    for qt in range(nqt):
-        for kt in range(nkt):
-            keep[:, 32 * qt:32 * qt + 32, 32 * kt + key_of_word] = bits[:, qt, kt].transpose(0, 2, 1)
-    return torch.from_numpy(keep[:, :Lq, :Lk]).view(B, heads, Lq, Lk)
 
 
 def _mod_id(L, recipe):
@@ -98,11 +84,13 @@ def _run(ops, B, heads, L, recipe, flags, headpad, p):
     desc = ops.attn_desc(Lb.BF16, B, heads, L, L, DH, q.data_ptr(), kv.data_ptr(), kv.data_ptr() + H * 2, H, 2 * H, 2 * H, o.data_ptr(), H, lse,
                          kp, mi, flags, DH ** -0.5, d_o=d_o.data_ptr(), lddo=H, dq=dq.data_ptr(), dk=dkv.data_ptr(), dv=dkv.data_ptr() + H * 2,
                          lddq=H, lddk=2 * H, lddv=2 * H, **kw)
+    for backward in (False, True):                               # the family this file is about, in both directions
+        assert ops.attn_family(desc, backward) == Lb.ATTN_FAMILY_KEEPBIT_DH32
     ops.attn_fwd(desc)
     am = allowed[:, None].expand(B, heads, L, L)
     keep, keep_p = None, 1.0
     if p > 0:
-        keep = _unpack_keepbits(kb, B, heads, L, L).cuda()
+        keep = DR.unpack_keepbits(kb, B, heads, L, L).cuda()
         keep_p = ops.attn_keep_prob(p)
         assert abs(keep_p - (1 - p)) <= 2 ** -11
         n = int(am.sum().item())

@@ -101,7 +101,8 @@ def test_bf16_dh128_dropout_step_vs_oracle_fed_the_steps_masks(T):
       T = 70: L = 140 crosses a 128-row chunk; 140 is no multiple of 8, so the launches hand the workspace back and run the general
               tiled kernels of csrc/attention_bf16.hip with hash dropout (the read-out of tests/dropout_refs.py follows that rule).
       T = 72: L = 144, the keep-bit kernels of csrc/attention_long.hip; the masks are the bits of the engine's workspaces.
-    Both are read out under tests/dropout_refs.keepbit_path, the launcher's rule restated."""
+    Which of the two a site's launches run is the library's own answer for the plan's descriptor (ops.attn_family), here and in the
+    read-out of tests/dropout_refs.py, and is compared with the table above."""
     mc = model_config(H=256, heads=2, inter=512, n_enc=1, n_dec=1, max_F=T, causal=True, sep=True)
     batch = O.synth_batch(4, T, 12, 2, seed=6, pad=[0, 10, 0, 37])
     out, named, ref, grads, eng = engine_step_and_oracle(mc, 12, 2, batch, "encoding", "bf16", 3)
@@ -111,7 +112,10 @@ def test_bf16_dh128_dropout_step_vs_oracle_fed_the_steps_masks(T):
     nbits = 4 * 2 * ((2 * T + 31) // 32) ** 2 * 128
     wrote = [bool(s["keepbits"][:nbits].any()) for s in attn]
     # (the engine does not clear its workspaces: where the launches hash, L = 140, their bytes say nothing)
-    assert all(wrote) or not DR.keepbit_path(128, 2 * T, 2 * T), "the keep-bit kernels fill every site's bit tiles"
+    descs = DR.attn_site_descs(eng, 4, T)
+    on_keepbit = [DR.on_keepbit_kernels(*descs[s["site"]]) for s in attn]
+    assert on_keepbit == [T == 72] * 3, "L = 144 runs the keep-bit kernels, L = 140 the general ones"
+    assert all(wrote) or not any(on_keepbit), "the keep-bit kernels fill every site's bit tiles"
     check_bf16(bf16_stats(out, named, ref, grads), f"bf16 dh 128, T {T}, dropout on")
 
 

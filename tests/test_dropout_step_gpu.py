@@ -67,7 +67,9 @@ def test_bf16_fused_dropout_step_vs_oracle_fed_the_steps_masks(monkeypatch, drop
         kinds = {s["key"]: s["kind"] for s in eng.dropout_sites(16, 100)}
         assert len(kinds) == 4 + 2 * 3 + 2 * 5                         # 4 embdrop; p, o, mlpdrop per encoder layer; 2 x (p, o) + mlpdrop per decoder layer
         assert all(v == "rowdrop" for k, v in kinds.items() if k.endswith("/mlpdrop"))
-        assert all(s["keepbits"] is not None and DR.keepbit_path(32, 200, 200) for s in eng.dropout_sites(16, 100) if s["kind"] == "attn")
+        descs = DR.attn_site_descs(eng, 16, 100)
+        assert all(s["keepbits"] is not None and descs[s["site"]][0].dh == 32 and DR.on_keepbit_kernels(*descs[s["site"]])
+                   for s in eng.dropout_sites(16, 100) if s["kind"] == "attn")
     check_bf16(bf16_stats(out, named, ref, grads), f"bf16 fused, dropout {dropout}")
 
 
@@ -87,5 +89,6 @@ def test_bf16_dh64_dropout_step_vs_oracle_fed_the_steps_masks(dropout):
     if on:
         sites = eng.dropout_sites(4, 100)
         assert len(sites) == 4 + 3 + 5 and all(s["kind"] == "flat" for s in sites if not s["key"].endswith("/p"))
-        assert all(s["dh"] == 64 and s["keepbits"] is not None and DR.keepbit_path(64, 200, 200) for s in sites if s["kind"] == "attn")
+        descs = DR.attn_site_descs(eng, 4, 100)
+        assert all(s["dh"] == 64 and s["keepbits"] is not None and DR.on_keepbit_kernels(*descs[s["site"]]) for s in sites if s["kind"] == "attn")
     check_bf16(bf16_stats(out, named, ref, grads), f"bf16 dh 64, dropout {dropout}")
