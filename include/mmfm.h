@@ -122,7 +122,8 @@ int mmfm_gemm(const mmfm_gemm_desc* d, mmfm_stream stream);
 /* Two independent products, same results as two mmfm_gemm calls.  Two bf16 weight-gradient descriptors (the dY^T X form with split-K
  * slabs) run as ONE launch, each on its share of the CUs: the caller then sizes their split counts so that
  * tiles(a) * splits(a) + tiles(b) * splits(b) = 256 with the first term a multiple of 8 (mmfm_gemm_dw_tiles) - each product makes half
- * the slabs it would make alone.  The weight gradients of two linears whose dY are both at hand (MLP up / down, attention qkv / out_proj). */
+ * the slabs it would make alone.  The weight gradients of two linears whose dY are both at hand (MLP up / down, attention qkv / out_proj).
+ * mmfm_gemm_pair_fused(a, b) says whether a pair leaves as one launch (1) or as two (0), mmfm_gemm_family which kernel each runs on alone. */
 int mmfm_gemm_pair(const mmfm_gemm_desc* a, const mmfm_gemm_desc* b, mmfm_stream stream);
 
 /* ---------------------------------------------------------------------------------- live rows (MMFM_LIVE_ROWS)
@@ -152,6 +153,18 @@ typedef struct {
     int B, T;             /* d->M (or d->K) == B * T */
 } mmfm_live_rows;
 int mmfm_gemm_live(const mmfm_gemm_desc* d, const mmfm_live_rows* live, mmfm_stream stream);
+/* Which kernel family mmfm_gemm (live == NULL) or mmfm_gemm_live runs for *d: one of the codes below, or a negative code with
+ * mmfm_last_error set where the launch would refuse.  mmfm_gemm_pair_fused: 1 where mmfm_gemm_pair(a, b) leaves as one launch, 0 where it
+ * issues a and b one after the other (each on its mmfm_gemm_family), negative where it would refuse.  Neither launches anything, reads a
+ * tensor (pointers count by being NULL or not and by their alignment) or makes a HIP call: a machine without a GPU answers them.
+ * MMFM_GEMM_FAMILY_F32 is the feature macro for both exports (MMFM_VERSION stays: no existing struct changed). */
+#define MMFM_GEMM_FAMILY_F32 1       /* csrc/gemm.hip: fp32 */
+#define MMFM_GEMM_FAMILY_TILE128 2   /* csrc/gemm_bf16.hip: bf16 MFMA, 128 x 128 tiles, every layout and epilogue */
+#define MMFM_GEMM_FAMILY_BIG256 3    /* csrc/gemm_big.hip: bf16 MFMA, 256 x 256 tiles over LDS-DMA, K-contiguous operands */
+#define MMFM_GEMM_FAMILY_DW128 4     /* csrc/gemm_dw.hip: the streaming weight-gradient kernel (dY^T X, fp32 out), 128-wide tiles */
+#define MMFM_GEMM_FAMILY_DW256 5     /* csrc/gemm_dw.hip: the same, 256-wide tiles */
+int mmfm_gemm_family(const mmfm_gemm_desc* d, const mmfm_live_rows* live_or_null);
+int mmfm_gemm_pair_fused(const mmfm_gemm_desc* a, const mmfm_gemm_desc* b);
 
 /* dst[i] (+)= sum_s src[s*slab_stride + i], fp32, deterministic order.  `src` is scratch: it may be
  * clobbered (a tall-skinny reduction first sums groups of slabs in place). */

@@ -24,6 +24,8 @@ ATTN_DIAG, ATTN_CAUSAL, ATTN_SEP = 1, 2, 4
 ATTN_FAMILY_KEEPBIT_DH32, ATTN_FAMILY_KEEPBIT_LONG, ATTN_FAMILY_BF16, ATTN_FAMILY_BF16_TILED, ATTN_FAMILY_F32, ATTN_FAMILY_F32_TILED = range(1, 7)
 ATTN_FAMILY_MASK, ATTN_FAMILY_BWD_SINGLE = 0xf, 0x10
 ATTN_KEEPBIT_FAMILIES = (ATTN_FAMILY_KEEPBIT_DH32, ATTN_FAMILY_KEEPBIT_LONG)
+# mmfm_gemm_family (MMFM_GEMM_FAMILY_*)
+GEMM_FAMILY_F32, GEMM_FAMILY_TILE128, GEMM_FAMILY_BIG256, GEMM_FAMILY_DW128, GEMM_FAMILY_DW256 = range(1, 6)
 ACT_NONE, ACT_GELU, ACT_SOFTSIGN, ACT_GELU_GRAD, ACT_SOFTSIGN_GRAD, ACT_SOFTSIGN_GRAD_OUT = 0, 1, 2, 3, 4, 5
 # the other MLP activations (transformer.act): forward / gradient pairs; the sigmoid kind takes beta in act_scale
 ACT_RELU, ACT_RELU_GRAD, ACT_SIGMOID, ACT_SIGMOID_GRAD, ACT_GELU_TANH, ACT_GELU_TANH_GRAD = 6, 7, 8, 9, 10, 11
@@ -125,6 +127,8 @@ _PROTOS = {
     "mmfm_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "mmfm_gemm_pair": (C.c_int, [_vp, _vp, _vp]),
     "mmfm_gemm_live": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(LiveRows), _vp]),
+    "mmfm_gemm_family": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(LiveRows)]),
+    "mmfm_gemm_pair_fused": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc)]),
     "mmfm_live_bins": (C.c_int, [_vp, _i, _i, _vp, _vp]),
     "mmfm_gather_live_rows": (C.c_int, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
     "mmfm_gemm_dw_tiles": (C.c_int, [_i, _i, _i]),

@@ -32,10 +32,6 @@ int mmfm_set_error(int code, const char* fmt, ...);
 // to the pair, so a process that drives several GPUs opts in on each (api.hip).  `what` names the entry point in the error text.
 int mmfm_lds_opt_in(const void* kern, size_t bytes, const char* what);
 
-// What a GEMM launcher that picks its own shapes (gemm_big.hip, gemm_dw.hip) returns for a launch it leaves to the next one: no HIP error
-// and no library error has this value.
-constexpr int MMFM_GEMM_DECLINED = -(1 << 30);
-
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ------------------------------------------------------------------ live rows (mmfm_gemm_live; include/mmfm.h)

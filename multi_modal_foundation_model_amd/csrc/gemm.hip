@@ -11,7 +11,7 @@
 //   K-contiguous (x[M,K], W[N,K]):    8 lanes x float4 = one 128-B row segment, transposed on the
 //                                     LDS write (ds_write_b32 x4);
 //   row-contiguous (dY^T, W for dX):  32 lanes x float4 = 512 B of one k-row, ds_write_b128.
-#include "common.h"
+#include "gemm_route.h"
 
 namespace {
 
@@ -322,9 +322,7 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const T* __restrict__ x, i
 
 }  // namespace
 
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* d, hipStream_t st, const LiveArg& lv);  // gemm_bf16.hip
-
-// argument checks and normalisation shared by mmfm_gemm and mmfm_gemm_pair (d = *dp on success)
+// argument checks and normalisation shared by every GEMM entry point (d = *dp on success)
 static int gemm_check(const mmfm_gemm_desc* dp, mmfm_gemm_desc& d) {
     MMFM_REQUIRE(dp != nullptr, "mmfm_gemm: null descriptor");
     d = *dp;
@@ -357,14 +355,38 @@ static int gemm_check(const mmfm_gemm_desc* dp, mmfm_gemm_desc& d) {
     return 0;
 }
 
-int mmfm_gemm_dw_pair_launch(const mmfm_gemm_desc* a, const mmfm_gemm_desc* b, hipStream_t st);   // gemm_dw.hip
-
-extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
+// one checked and routed call: the normalised descriptor, the LiveArg of its live-row record (kNoLive: the plain call) and the route
+struct GemmCall {
     mmfm_gemm_desc d;
-    if (int rc = gemm_check(dp, d)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (d.dtype == MMFM_BF16) return mmfm_gemm_bf16_launch(&d, st, kNoLive);
+    LiveArg lv = kNoLive;
+    GemmRoute r;
+};
 
+// The one place that decides which kernel family runs a checked descriptor (gemm_route.h)
+static void gemm_route(GemmCall& c) {
+    bool wide = false;
+    if (c.d.dtype != MMFM_BF16) c.r.family = MMFM_GEMM_FAMILY_F32;
+    else if (mmfm_gemm_big_takes(c.d, c.lv)) c.r.family = MMFM_GEMM_FAMILY_BIG256;
+    else if (mmfm_gemm_dw_takes(c.d, c.lv, wide)) c.r.family = wide ? MMFM_GEMM_FAMILY_DW256 : MMFM_GEMM_FAMILY_DW128;
+    else c.r.family = MMFM_GEMM_FAMILY_TILE128;
+}
+
+// check once, route once, for every entry point below; `live`: mmfm_gemm_live's record and its own checks, NULL for the plain call
+static int gemm_prologue(const mmfm_gemm_desc* dp, const mmfm_live_rows* live, GemmCall& c) {
+    if (int rc = gemm_check(dp, c.d)) return rc;
+    if (live) {
+        const mmfm_gemm_desc& d = c.d;
+        MMFM_REQUIRE(d.dtype == MMFM_BF16, "mmfm_gemm_live: bf16 only (the fp32 parity path keeps the full row space)");
+        MMFM_REQUIRE(live->rec && live->B > 0 && live->T > 0, "mmfm_gemm_live: bad live-row record");
+        c.lv = {live->rec, live->B, live->T, d.a_kcontig ? 0 : 1};
+        MMFM_REQUIRE((int64_t)live->B * live->T == (c.lv.kdim ? d.K : d.M), "mmfm_gemm_live: B * T = %lld is not the descriptor's %s = %d",
+                     (long long)live->B * live->T, c.lv.kdim ? "K" : "M", c.lv.kdim ? d.K : d.M);
+    }
+    gemm_route(c);
+    return 0;
+}
+
+static int gemm_f32_launch(const mmfm_gemm_desc& d, hipStream_t st) {
     const int tiles = cdiv(d.M, BM) * cdiv(d.N, BN);
     const int vecA = (d.lda % 4 == 0) && ((uintptr_t)d.A % 16 == 0);
     const int vecB = (d.ldb % 4 == 0) && ((uintptr_t)d.B % 16 == 0);
@@ -385,31 +407,59 @@ extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
     return 0;
 }
 
+static int gemm_launch(const GemmCall& c, hipStream_t st) {
+    switch (c.r.family) {
+        case MMFM_GEMM_FAMILY_F32: return gemm_f32_launch(c.d, st);
+        case MMFM_GEMM_FAMILY_BIG256: return mmfm_gemm_big_launch(c.d, st, c.lv);
+        case MMFM_GEMM_FAMILY_DW128:
+        case MMFM_GEMM_FAMILY_DW256: return mmfm_gemm_dw_launch(c.d, nullptr, c.r.family == MMFM_GEMM_FAMILY_DW256, st, c.lv);
+        default: return mmfm_gemm_bf16_launch(c.d, st, c.lv);
+    }
+}
+
+int mmfm_gemm_routed(const mmfm_gemm_desc& d, hipStream_t st) {
+    GemmCall c = {d};
+    gemm_route(c);
+    return gemm_launch(c, st);
+}
+
+extern "C" int mmfm_gemm_family(const mmfm_gemm_desc* dp, const mmfm_live_rows* live) {
+    GemmCall c;
+    if (int rc = gemm_prologue(dp, live, c)) return rc;
+    return c.r.family;
+}
+
+extern "C" int mmfm_gemm_pair_fused(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp) {
+    mmfm_gemm_desc a, b;
+    if (int rc = gemm_check(ap, a)) return rc;
+    if (int rc = gemm_check(bp, b)) return rc;
+    return mmfm_gemm_dw_pair_takes(a, b);
+}
+
+extern "C" int mmfm_gemm(const mmfm_gemm_desc* dp, mmfm_stream stream) {
+    GemmCall c;
+    if (int rc = gemm_prologue(dp, nullptr, c)) return rc;
+    return gemm_launch(c, (hipStream_t)stream);
+}
+
 // mmfm_gemm over the compact row space of a live-bin record (include/mmfm.h): the same kernels, chosen and launched for the full row space
 extern "C" int mmfm_gemm_live(const mmfm_gemm_desc* dp, const mmfm_live_rows* live, mmfm_stream stream) {
-    mmfm_gemm_desc d;
-    if (int rc = gemm_check(dp, d)) return rc;
-    MMFM_REQUIRE(d.dtype == MMFM_BF16, "mmfm_gemm_live: bf16 only (the fp32 parity path keeps the full row space)");
-    MMFM_REQUIRE(live && live->rec && live->B > 0 && live->T > 0, "mmfm_gemm_live: bad live-row record");
-    const LiveArg lv = {live->rec, live->B, live->T, d.a_kcontig ? 0 : 1};
-    MMFM_REQUIRE((int64_t)live->B * live->T == (lv.kdim ? d.K : d.M), "mmfm_gemm_live: B * T = %lld is not the descriptor's %s = %d",
-                 (long long)live->B * live->T, lv.kdim ? "K" : "M", lv.kdim ? d.K : d.M);
-    return mmfm_gemm_bf16_launch(&d, (hipStream_t)stream, lv);
+    static const mmfm_live_rows none = {nullptr, 0, 0};          // a NULL record is refused where a bad one is, after the descriptor's checks
+    GemmCall c;
+    if (int rc = gemm_prologue(dp, live ? live : &none, c)) return rc;
+    return gemm_launch(c, (hipStream_t)stream);
 }
 
 // Two independent GEMMs.  Two bf16 weight-gradient launches that the streaming kernel takes run as ONE launch, each on its share of the
 // CUs; anything else is issued one after the other - same results either way.
 extern "C" int mmfm_gemm_pair(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp, mmfm_stream stream) {
-    mmfm_gemm_desc a, b;
-    if (int rc = gemm_check(ap, a)) return rc;
-    if (int rc = gemm_check(bp, b)) return rc;
+    GemmCall a, b;
+    if (int rc = gemm_prologue(ap, nullptr, a)) return rc;
+    if (int rc = gemm_prologue(bp, nullptr, b)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (a.dtype == MMFM_BF16 && b.dtype == MMFM_BF16) {
-        const int rc = mmfm_gemm_dw_pair_launch(&a, &b, st);
-        if (rc != MMFM_GEMM_DECLINED) return rc;
-    }
-    if (int rc = mmfm_gemm(ap, stream)) return rc;
-    return mmfm_gemm(bp, stream);
+    if (mmfm_gemm_dw_pair_takes(a.d, b.d)) return mmfm_gemm_dw_launch(a.d, &b.d, a.r.family == MMFM_GEMM_FAMILY_DW256, st, kNoLive);
+    if (int rc = gemm_launch(a, st)) return rc;
+    return gemm_launch(b, st);
 }
 
 // Several reductions in one launch: block b owns one 256-float chunk of one entry (found by bisection over the entries' chunk0

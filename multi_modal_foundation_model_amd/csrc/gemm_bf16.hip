@@ -11,7 +11,7 @@
 //      XOR ((k & 3) << 6).  The operand needs 8 k-strided values per lane: two ds_read_b64_tr_b16
 //      (hardware 4x16 transpose); the XOR spreads the four k-rows of a read over the four 64-B quarters
 //      of the bank row -> conflict-free.  Global loads stay 16 B/lane along the contiguous axis.
-#include "common.h"
+#include "gemm_route.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -455,32 +455,19 @@ __global__ __launch_bounds__(NTHREADS, BK == 64 ? 3 : 2) void gemm_bf16_kernel(c
 }
 
 int align_of(const void* p, int ld) {
-    if (ld % 8 == 0 && (uintptr_t)p % 16 == 0) return 8;
+    if (gemm_ld8(ld) && gemm_al16(p)) return 8;
     if (ld % 4 == 0 && (uintptr_t)p % 8 == 0) return 4;
     return 1;
 }
 
 }  // namespace
 
-int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);   // gemm_big.hip: 256 x 256 tiles for the compute-bound shapes
-int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);    // gemm_dw.hip: the HBM-bound weight-gradient stream
-
+// the 128-tile kernels: every checked bf16 descriptor runs here (the route sends what the 256-tile and streaming kernels take elsewhere).
 // lv: kNoLive, or the live-row record of mmfm_gemm_live - every choice below is made from the descriptor of the full row space
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
-    const mmfm_gemm_desc d = *dp;
-    {
-        const int rb = mmfm_gemm_big_launch(dp, st, lv);
-        if (rb != MMFM_GEMM_DECLINED) return rb;
-        const int rw = mmfm_gemm_dw_launch(dp, st, lv);
-        if (rw != MMFM_GEMM_DECLINED) return rw;
-    }
-    MMFM_REQUIRE(d.splits == 1 || d.kchunk % 64 == 0, "mmfm_gemm(bf16): kchunk %d must be a multiple of 64", d.kchunk);
+int mmfm_gemm_bf16_launch(const mmfm_gemm_desc& d, hipStream_t st, const LiveArg& lv) {
     static const int bk_env = [] { const char* e = getenv("MMFM_GEMM_BK"); return e ? atoi(e) : 0; }();
-    // deeper k-tiles when the reduction is short (K = 256/512 block GEMMs): fewer serialized load-latency rounds
-    const int kspan = d.splits > 1 ? d.kchunk : d.K;
     // measured on MI355X (scripts/gemm_bench.py): BK = 128 is 0-15 % SLOWER than BK = 64 at 3 workgroups/CU for the
     // K = 256/512 shapes (the kernel is bound by ds_write + L1 + MFMA issue, not by load-latency rounds) -> default 64
-    (void)kspan;
     const int BKsel = bk_env == 128 ? 128 : 64;
     const int tiles = cdiv(d.M, BM) * cdiv(d.N, BN);
     const int aA = align_of(d.A, d.lda), aB = align_of(d.B, d.ldb);
@@ -488,9 +475,9 @@ int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveAr
     static const int wg_per_cu = [] { const char* e = getenv("MMFM_GEMM_WG_PER_CU"); const int v = e ? atoi(e) : 3; return v > 0 ? v : 3; }();
     const bool f32out = d.c_f32 || d.splits > 1;
     // vector epilogue needs 16-B aligned 8-column chunks of every tensor it touches
-    auto al16 = [](const void* p) { return p == nullptr || (uintptr_t)p % 16 == 0; };
-    const int vec8 = (d.N % 8 == 0) && (d.ldc % 8 == 0) && al16(d.C) && al16(d.pre_out) && al16(d.gradmul_pre) && al16(d.bias) &&
-                     (!d.residual || (d.ldr % 8 == 0 && al16(d.residual))) && (!d.splits || d.splits == 1 || d.slab_stride % 4 == 0);
+    const auto al16 = gemm_al16;
+    const int vec8 = (d.N % 8 == 0) && gemm_ld8(d.ldc) && al16(d.C) && al16(d.pre_out) && al16(d.gradmul_pre) && al16(d.bias) &&
+                     (!d.residual || (gemm_ld8(d.ldr) && al16(d.residual))) && (!d.splits || d.splits == 1 || d.slab_stride % 4 == 0);
     // half mode: 4-column granularity (N = 668): bf16 rows are 8-B aligned, fp32 rows 16-B aligned
     auto al8 = [](const void* p) { return p == nullptr || (uintptr_t)p % 8 == 0; };
     const bool f32c = d.c_f32 || d.splits > 1;

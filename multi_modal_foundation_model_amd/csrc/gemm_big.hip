@@ -19,6 +19,7 @@
 //     Wave w owns features 128 (w & 1) .. + 127 and tokens 64 (w >> 1) .. + 63: 4 x 2 accumulator tiles (128 VGPRs), 6 operand
 //     reads per 8 MFMAs.
 #include "rowchain.h"
+#include "gemm_route.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -309,23 +310,24 @@ __global__ __launch_bounds__(NT, 2) void gemm_big_kernel(const BigArgs a_full, c
 
 }  // namespace
 
-// returns MMFM_GEMM_DECLINED when the shape belongs to the 128 x 128 kernel
-int mmfm_gemm_big_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
-    const mmfm_gemm_desc& d = *dp;
+// every clause that keeps a descriptor off this kernel: it then belongs to the 128 x 128 one
+bool mmfm_gemm_big_takes(const mmfm_gemm_desc& d, const LiveArg& lv) {
     static const int on = [] { const char* e = getenv("MMFM_GEMM_BIG"); return e ? atoi(e) : 1; }();
     static const int kmin = [] { const char* e = getenv("MMFM_GEMM_BIG_KMIN"); return e ? atoi(e) : 512; }();
-    if (!on || d.dtype != MMFM_BF16 || d.c_f32 || d.splits > 1 || !d.a_kcontig || !d.b_kcontig || d.colsum || (lv.rec && lv.kdim)) return MMFM_GEMM_DECLINED;
-    if (d.K % BK || d.K < kmin || d.N < 128 || d.M < 1024 || d.N % 8) return MMFM_GEMM_DECLINED;
+    if (!on || d.dtype != MMFM_BF16 || d.c_f32 || d.splits > 1 || !d.a_kcontig || !d.b_kcontig || d.colsum || (lv.rec && lv.kdim)) return false;
+    if (d.K % BK || d.K < kmin || d.N < 128 || d.M < 1024 || d.N % 8) return false;
     // too few 256-wide tiles to occupy the chip (the reference's batch of 16: M = 3,200 rows x N = 256 = 13 tiles, 23-34 us against ~15 us
     // for the 50 tiles of the 128-tile kernel)
     // (MMFM_GEMM_BIG_MIN_TILES is read per call: the kernel's own test lowers it for its small shapes)
     const char* mt = getenv("MMFM_GEMM_BIG_MIN_TILES");
-    if (cdiv(d.M, TB) * cdiv(d.N, TB) < (mt ? atoi(mt) : 96)) return MMFM_GEMM_DECLINED;
-    auto al16 = [](const void* p) { return p == nullptr || (uintptr_t)p % 16 == 0; };
-    if (d.lda % 8 || d.ldb % 8 || d.ldc % 8 || (d.residual && d.ldr % 8) || !al16(d.A) || !al16(d.B) || !al16(d.C) || !al16(d.pre_out) ||
-        !al16(d.gradmul_pre) || !al16(d.residual) || !al16(d.bias))
-        return MMFM_GEMM_DECLINED;
-    if ((int64_t)d.M * std::max(d.ldc, d.ldr) * 2 >= (int64_t)1 << 31) return MMFM_GEMM_DECLINED;        // 32-bit buffer offsets of the epilogue
+    if (cdiv(d.M, TB) * cdiv(d.N, TB) < (mt ? atoi(mt) : 96)) return false;
+    if (!gemm_ld8(d.lda) || !gemm_ld8(d.ldb) || !gemm_ld8(d.ldc) || (d.residual && !gemm_ld8(d.ldr)) || !gemm_al16(d.A) || !gemm_al16(d.B) ||
+        !gemm_al16(d.C) || !gemm_al16(d.pre_out) || !gemm_al16(d.gradmul_pre) || !gemm_al16(d.residual) || !gemm_al16(d.bias))
+        return false;
+    return (int64_t)d.M * std::max(d.ldc, d.ldr) * 2 < (int64_t)1 << 31;        // 32-bit buffer offsets of the epilogue
+}
+
+int mmfm_gemm_big_launch(const mmfm_gemm_desc& d, hipStream_t st, const LiveArg& lv) {
     const int ak = gemm_act_kind(d.act);   // relu / sigmoid gate / tanh-GELU and their gradients: a kernel per kind
     const void* kern = ak == MMFM_MLP_RELU ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_RELU>)
                      : ak == MMFM_MLP_SIGMOID ? reinterpret_cast<const void*>(gemm_big_kernel<MMFM_MLP_SIGMOID>)

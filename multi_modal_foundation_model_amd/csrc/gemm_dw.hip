@@ -24,7 +24,7 @@
 // Tried on top and measured no better (removed): the tiles of a slab walking its k-tiles in rotated order (no concurrent requests
 // for a line), two of the four waves - or a fifth wave - issuing nothing but L2 warm-up loads for the slab's full-width k-tiles
 // 12-20 steps ahead, 128-wide tiles with an 8-stage ring, 64-deep k-tiles.
-#include "common.h"
+#include "gemm_route.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -286,34 +286,29 @@ static bool dw_wide(int N, int K) {
 // number of (tile) items per K-slab the streaming kernel makes of an [M, N] gradient over K rows (the engine sizes the split count with it)
 extern "C" int mmfm_gemm_dw_tiles(int M, int N, int K) { return cdiv(M, TM) * cdiv(N, dw_wide(N, K) ? 256 : 128); }
 
-static bool dw_eligible(const mmfm_gemm_desc& d) {
+// false: the launch belongs to the general kernel of gemm_bf16.hip (split-K ranges are gemm_check's: kchunk a positive multiple of 64)
+bool mmfm_gemm_dw_takes(const mmfm_gemm_desc& d, const LiveArg& lv, bool& wide) {
     static const int on = [] { const char* e = getenv("MMFM_GEMM_DW"); return e ? atoi(e) : 1; }();
     const bool f32out = d.c_f32 || d.splits > 1;
-    if (!on || d.dtype != MMFM_BF16 || !f32out || d.a_kcontig || d.b_kcontig) return false;
+    if (!on || d.dtype != MMFM_BF16 || !f32out || d.a_kcontig || d.b_kcontig || (lv.rec && !lv.kdim)) return false;
     if (d.bias || d.pre_out || d.gradmul_pre || d.residual || d.act || (d.drop.p > 0.f)) return false;
     // 16-B pieces: rows 16-B aligned; a ragged last piece (M or N not a multiple of 8) must still lie inside its row (padded leading dimension) -
     // the columns it adds are computed and dropped
-    if (d.lda % 8 || d.ldb % 8 || d.lda < (d.M + 7) / 8 * 8 || d.ldb < (d.N + 7) / 8 * 8 || ((uintptr_t)d.A & 15) || ((uintptr_t)d.B & 15) || ((uintptr_t)d.C & 3)) return false;
-    if (d.splits > 1 && (d.kchunk % 64 || d.kchunk <= 0)) return false;
+    if (!gemm_ld8(d.lda) || !gemm_ld8(d.ldb) || d.lda < (d.M + 7) / 8 * 8 || d.ldb < (d.N + 7) / 8 * 8 || !gemm_al16(d.A) || !gemm_al16(d.B) || ((uintptr_t)d.C & 3)) return false;
     if (((int64_t)d.K + 9 * 64) * std::max(d.lda, d.ldb) * 2 >= (int64_t)1 << 31) return false;          // 32-bit buffer offsets, ring run-out included
+    wide = dw_wide(d.N, d.K);
     return true;
 }
 
-// returns MMFM_GEMM_DECLINED when the launch belongs to the general kernel of gemm_bf16.hip
-int mmfm_gemm_dw_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv) {
-    const mmfm_gemm_desc& d = *dp;
-    if (!dw_eligible(d) || (lv.rec && !lv.kdim)) return MMFM_GEMM_DECLINED;
-    return dw_wide(d.N, d.K) ? launch<256, 32>(d, nullptr, st, lv) : launch<128, 32>(d, nullptr, st, lv);
+// both descriptors in one launch when both belong to the streaming kernel with the same tile width, every item fits the grid once and the
+// first problem's item count is a multiple of 8; the caller issues them one after the other otherwise
+bool mmfm_gemm_dw_pair_takes(const mmfm_gemm_desc& a, const mmfm_gemm_desc& b) {
+    bool wa, wb;
+    if (!mmfm_gemm_dw_takes(a, kNoLive, wa) || !mmfm_gemm_dw_takes(b, kNoLive, wb) || wa != wb) return false;
+    const int ia = mmfm_gemm_dw_tiles(a.M, a.N, a.K) * std::max(1, a.splits), ib = mmfm_gemm_dw_tiles(b.M, b.N, b.K) * std::max(1, b.splits);
+    return ia % 8 == 0 && ia + ib <= 512;
 }
 
-// both descriptors in one launch when both belong to the streaming kernel with the same tile width, every item fits the grid once and the
-// first problem's item count is a multiple of 8; MMFM_GEMM_DECLINED otherwise (the caller then issues them one after the other)
-int mmfm_gemm_dw_pair_launch(const mmfm_gemm_desc* ap, const mmfm_gemm_desc* bp, hipStream_t st) {
-    const mmfm_gemm_desc &a = *ap, &b = *bp;
-    if (!dw_eligible(a) || !dw_eligible(b)) return MMFM_GEMM_DECLINED;
-    const bool wide = dw_wide(a.N, a.K);
-    if (wide != dw_wide(b.N, b.K)) return MMFM_GEMM_DECLINED;
-    const int ia = mmfm_gemm_dw_tiles(a.M, a.N, a.K) * std::max(1, a.splits), ib = mmfm_gemm_dw_tiles(b.M, b.N, b.K) * std::max(1, b.splits);
-    if (ia % 8 || ia + ib > 512) return MMFM_GEMM_DECLINED;
-    return wide ? launch<256, 32>(a, &b, st, kNoLive) : launch<128, 32>(a, &b, st, kNoLive);
+int mmfm_gemm_dw_launch(const mmfm_gemm_desc& d, const mmfm_gemm_desc* second, bool wide, hipStream_t st, const LiveArg& lv) {
+    return wide ? launch<256, 32>(d, second, st, lv) : launch<128, 32>(d, second, st, lv);
 }

@@ -2,7 +2,7 @@
 // scattered into the concatenated [B, M*T, H] sequence), forward and backward.
 // mm.py:90-110,141-175,245-275; encoder_embeddings.py:56-61; decoder_embeddings.py:56-61.
 // HBM-bound elementwise/gather work; index semantics are bit-exact (sample-0 quirk included).
-#include "common.h"
+#include "gemm_route.h"
 #include <algorithm>
 
 namespace {
@@ -272,7 +272,6 @@ bool oh_path(int dtype, int H) { return dtype == MMFM_BF16 && H % 8 == 0; }
 }  // namespace
 
 extern "C" int mmfm_reduce_slabs(float*, const float*, int64_t, int, int64_t, int, mmfm_stream);
-int mmfm_gemm_bf16_launch(const mmfm_gemm_desc* dp, hipStream_t st, const LiveArg& lv);       // gemm_bf16.hip
 
 extern "C" int mmfm_mask_prep(int B, int T, int M, const int64_t* const* mask_src, const int64_t* mask_stride,
                               const int64_t* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad,
@@ -398,7 +397,7 @@ static int stitch_bwd_impl(int dtype, const void* dx, const void* dextra, const 
             if (!src) continue;
             gd.B = src;
             gd.C = slabs + (int64_t)nsl * g.slab;
-            if (int rc = mmfm_gemm_bf16_launch(&gd, st, kNoLive)) return rc;
+            if (int rc = mmfm_gemm_routed(gd, st)) return rc;
             nsl += g.S;
         }
         if (int rc = mmfm_reduce_slabs(d_pos, slabs, (int64_t)max_F * H, nsl, g.slab, acc_pos, stream)) return rc;

@@ -98,6 +98,23 @@ def gemm_pair(da, db, plan=None):
     _emit(plan, L.lib().mmfm_gemm_pair, (C.byref(da), C.byref(db)), keep=(da, db))
 
 
+def gemm_family(desc, live=None):
+    """The kernel family (L.GEMM_FAMILY_*) gemm - or, with `live` (live_rows), gemm_live - runs for `desc` (mmfm_gemm_family: nothing is
+    launched, no tensor is read, no GPU is needed); raises where the launch would refuse."""
+    fam = L.lib().mmfm_gemm_family(C.byref(desc), None if live is None else C.byref(live))
+    if fam < 0:
+        L.check(fam, "mmfm_gemm_family")
+    return fam
+
+
+def gemm_pair_fused(da, db):
+    """Whether gemm_pair(da, db) leaves as one launch (mmfm_gemm_pair_fused; no GPU is needed); raises where it would refuse."""
+    fused = L.lib().mmfm_gemm_pair_fused(C.byref(da), C.byref(db))
+    if fused < 0:
+        L.check(fused, "mmfm_gemm_pair_fused")
+    return bool(fused)
+
+
 def reduce_slabs(dst, src, n, nslabs, stride, accumulate=False, plan=None):
     _emit(plan, L.lib().mmfm_reduce_slabs, (P(dst), P(src), n, nslabs, stride, int(accumulate)))
 

@@ -8,13 +8,12 @@ the same regime give EQUAL records:
   decisions   what PlanBuilder.workspaces decides for the shape: fm (Engine._fused_mask), batch_red, pair_ok, ctx_group, live rows,
               use_keep per side - read off a PlanBuilder of the plan's own shape, not restated;
   names       the C function names per plan unit (plan_sig.plan_units);
-  launches    for every launch whose LAUNCHER chooses by size, the side of each of its gates, restated here ONCE from the launcher's
-              code (source lines at each rule below; the attention launches need none: mmfm_attn_family answers) and computed from the
-              descriptor the plan holds: mmfm_gemm / mmfm_gemm_live / mmfm_gemm_pair (which kernel: the 256-tile GEMM, the streaming
-              weight-gradient kernel with 128- or 256-wide tiles, or the general 128-tile kernel; whether a pair leaves in one launch),
-              mmfm_reduce_slabs and mmfm_colsum (one- or two-stage reduction, which branch of colsum_splits), and every row-owner
-              launch (column blocks on or off, whether any workgroup walks a second row pass).
-The rules ignore pointer alignment: every operand of a plan is a pool tensor or a row slice of one at a multiple of 16 bytes.
+  launches    for every launch whose LAUNCHER chooses by size, the side of each of its gates, computed from the descriptor the plan
+              holds.  mmfm_gemm / mmfm_gemm_live / mmfm_gemm_pair: the library's own answer (mmfm_gemm_family: the 256-tile GEMM, the
+              streaming weight-gradient kernel with 128- or 256-wide tiles, or the general 128-tile kernel; mmfm_gemm_pair_fused: whether
+              a pair leaves in one launch), as mmfm_attn_family answers for the attention launches.  mmfm_reduce_slabs and mmfm_colsum
+              (one- or two-stage reduction, which branch of colsum_splits) and every row-owner launch (column blocks on or off, whether
+              any workgroup walks a second row pass): restated here ONCE from the launcher's code (source lines at each rule below).
 
 B_BIG is the smallest batch of the default shapes (T = 100, `ap` 668 + `behavior` 2: R = 200 B rows, B T = 100 B tokeniser rows) on the
 B = 1024 side of every gate; `host_gates` states the gates as functions of B and tests/test_large_regime_cpu.py proves the minimum.
@@ -24,9 +23,8 @@ rounded up to 64 rows afterwards and the count that comes out can be smaller - t
 other (same sums, other grouping).  At B = 1024 all three pairs of a block leave together; at 328 .. 342 the [256, 256] + [256, 256] pair
 (cross-attention out_proj + query) does not.  343 is the first batch from 328 on at which all three do.
 No `test_*` module is imported here."""
-import types
-
 from multi_modal_foundation_model_amd import _lib as L
+from multi_modal_foundation_model_amd import ops
 from multi_modal_foundation_model_amd import plan as P
 from plan_sig import plan_units
 
@@ -59,12 +57,12 @@ def host_gates(B, T=T, M=MODS):
         "live_rows": BT >= max(8192, P.LIVE_ROWS_MIN),                    # plan.py live_rows_on
         "rowgemm_column_blocks_off": cdiv(R, 128) >= 128,                 # csrc/rowgemm.hip mmfm_rowgemm / mmfm_rowgemm_groups: `npass < 128`
         "dw_wide_tiles": min(R, BT) >= 32768,                             # csrc/gemm_dw.hip dw_wide: `K >= 32768` (K = R, and B T for the tokenisers)
-        "gemm_big_rows": BT >= 1024 and cdiv(BT, 256) >= 96,              # csrc/gemm_big.hip mmfm_gemm_big_launch: `d.M < 1024`, `< 96` tiles (narrowest output: one tile column)
+        "gemm_big_rows": BT >= 1024 and cdiv(BT, 256) >= 96,              # csrc/gemm_big.hip mmfm_gemm_big_takes: `d.M < 1024`, `< 96` tiles (narrowest output: one tile column)
         "reduce_large_branch": min(R, BT) > 8192,                         # csrc/gemm.hip colsum_splits: `R <= 8192 ? ... : min(256, R / 64)`
         # csrc/rowgemm.hip, csrc/mlp_fused.hip grid_for: min(passes, 256 per_cu) workgroups.  128-row passes at two workgroups per CU
         # (the K = 256 forward) and 256-row passes at one (the MLP backward's front half) are the last to get a second pass
         "second_row_pass_everywhere": cdiv(R, 128) > 2 * CUS and cdiv(R, 256) > CUS,
-        # plan.py PlanBuilder.pair_splits (the product's own, on the host) into csrc/gemm_dw.hip mmfm_gemm_dw_pair_launch: `ia % 8 || ia + ib > 512`
+        # plan.py PlanBuilder.pair_splits (the product's own, on the host) into mmfm_gemm_pair_fused
         "dw_pairs_one_launch": all(pair_one_launch(*pair_descs(a, b, R)) for a, b in DW_PAIRS),
     }
 
@@ -79,39 +77,24 @@ def pair_descs(a, b, R):
 
 
 # ------------------------------------------------------------------------------------------------ the launchers' rules, per descriptor
-def gemm_kernel(d):
-    """Which kernel mmfm_gemm_bf16_launch (csrc/gemm_bf16.hip:469) gives descriptor `d`: "big" (csrc/gemm_big.hip:317-328), "dw256" /
-    "dw128" (csrc/gemm_dw.hip:280-306: dw_eligible, then dw_wide), else "tile128"; fp32 descriptors: "f32" (csrc/gemm.hip:366)."""
-    if d.dtype != L.BF16:
-        return "f32"
-    f32out = bool(d.c_f32) or d.splits > 1
-    epilogue = bool(d.bias or d.pre_out or d.gradmul_pre or d.residual or d.act or d.drop.p > 0)
-    if (not d.c_f32 and d.splits <= 1 and d.a_kcontig and d.b_kcontig and not d.colsum and d.K % 64 == 0 and d.K >= 512 and d.N >= 128
-            and d.M >= 1024 and d.N % 8 == 0 and cdiv(d.M, 256) * cdiv(d.N, 256) >= 96 and d.lda % 8 == 0 and d.ldb % 8 == 0 and d.ldc % 8 == 0
-            and not (d.residual and d.ldr % 8) and d.M * max(d.ldc, d.ldr) * 2 < 2 ** 31):
-        return "big"
-    if (f32out and not d.a_kcontig and not d.b_kcontig and not epilogue and d.lda % 8 == 0 and d.ldb % 8 == 0
-            and d.lda >= cdiv(d.M, 8) * 8 and d.ldb >= cdiv(d.N, 8) * 8 and (d.splits <= 1 or (d.kchunk > 0 and d.kchunk % 64 == 0))
-            and (d.K + 9 * 64) * max(d.lda, d.ldb) * 2 < 2 ** 31):
-        return "dw256" if d.N > 128 and d.K >= 32768 else "dw128"
-    return "tile128"
+KERNEL_NAMES = {L.GEMM_FAMILY_F32: "f32", L.GEMM_FAMILY_TILE128: "tile128", L.GEMM_FAMILY_BIG256: "big", L.GEMM_FAMILY_DW128: "dw128",
+                L.GEMM_FAMILY_DW256: "dw256"}
 
 
-def gemm_gates(d):
+def gemm_kernel(d, live=None):
+    """Which kernel mmfm_gemm - with `live`, mmfm_gemm_live - gives descriptor `d`: the library's answer (mmfm_gemm_family)."""
+    return KERNEL_NAMES[ops.gemm_family(d, live)]
+
+
+def gemm_gates(d, live=None):
     """The size-free identity of a GEMM descriptor (its two widths: a weight gradient reduces over the rows, K) and its gate sides."""
     widths = (d.N, d.K) if d.a_kcontig else (d.M, d.N)
-    return dict(widths=widths, a_kcontig=int(d.a_kcontig), c_f32=int(d.c_f32), split=d.splits > 1, kernel=gemm_kernel(d))
+    return dict(widths=widths, a_kcontig=int(d.a_kcontig), c_f32=int(d.c_f32), split=d.splits > 1, kernel=gemm_kernel(d, live))
 
 
 def pair_one_launch(a, b):
-    """mmfm_gemm_dw_pair_launch (csrc/gemm_dw.hip:311-318): one launch when both stream with the same tile width, the first problem's item
-    count is a multiple of 8 and all items fit 512 workgroups; else the two descriptors leave one after the other."""
-    ka, kb = gemm_kernel(a), gemm_kernel(b)
-    if not ka.startswith("dw") or ka != kb:
-        return False
-    tn = 256 if ka == "dw256" else 128
-    ia, ib = (cdiv(x.M, 128) * cdiv(x.N, tn) * max(1, x.splits) for x in (a, b))
-    return ia % 8 == 0 and ia + ib <= 512
+    """Whether mmfm_gemm_pair issues descriptors `a` and `b` as one launch: the library's answer (mmfm_gemm_pair_fused)."""
+    return ops.gemm_pair_fused(a, b)
 
 
 def two_stage(n, nslabs, stride):
@@ -159,7 +142,7 @@ def launch_gates(fn, args, keep):
     """The gate record of one plan entry, or None for a launch whose launcher does not choose by size."""
     name = fn.__name__
     if name in ("mmfm_gemm", "mmfm_gemm_live"):
-        return dict(fn=name, **gemm_gates(keep[0]))
+        return dict(fn=name, **gemm_gates(*keep[:2]))            # keep: the descriptor, and mmfm_gemm_live's record
     if name == "mmfm_gemm_pair":
         return dict(fn=name, a=gemm_gates(keep[0]), b=gemm_gates(keep[1]), one_launch=pair_one_launch(keep[0], keep[1]))
     if name == "mmfm_reduce_slabs":
@@ -204,8 +187,11 @@ def record_diff(a, b, path=""):
 
 
 def gemm_desc(**kw):
-    """A stand-in descriptor for the rules above (the CPU test): the fields of mmfm_gemm_desc that the launchers' gates read."""
-    base = dict(dtype=L.BF16, c_f32=0, M=0, N=0, K=0, lda=0, ldb=0, ldc=0, a_kcontig=1, b_kcontig=1, splits=1, kchunk=0, bias=None, pre_out=None,
-                act=0, gradmul_pre=None, residual=None, ldr=0, colsum=None, drop=types.SimpleNamespace(p=0.0))
-    base.update(kw)
-    return types.SimpleNamespace(**base)
+    """A mmfm_gemm_desc for the two questions above, no GPU needed: fake, non-null, 16-byte-aligned operands 64 KiB apart (the route
+    reads pointers only for NULL and alignment); split-K slabs of M * ldc floats unless `slab_stride` says otherwise."""
+    d = L.GemmDesc()
+    d.A, d.B, d.C = (0x10000 * (i + 1) for i in range(3))
+    for k, v in dict(dict(dtype=L.BF16, a_kcontig=1, b_kcontig=1, splits=1, act_scale=1.0, slab_stride=kw["M"] * kw["ldc"]), **kw).items():
+        assert hasattr(L.GemmDesc, k), k
+        setattr(d, k, v)
+    return d

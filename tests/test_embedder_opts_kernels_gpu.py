@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from embedder_opts import close, close_bf16
+from gemm_on import gemm_on
 from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd import ops as K
 
@@ -57,8 +58,9 @@ SITES = [
     ("bf16", 70, 4, 2, 8),           # ... its 4-column half mode (N % 8 == 4): the behaviour path
     ("bf16", 70, 6, 12, 16),         # ... its scalar-edge epilogue (N % 4 != 0)
     ("bf16", 300, 264, 64, 64),      # ... 3 x 3 tiles
-    ("big", 1024, 128, 512, 512),    # the 256-tile kernel: the smallest shape mmfm_gemm_big_launch accepts (M >= 1024, N >= 128, K >= 512)
+    ("big", 1024, 128, 512, 512),    # the 256-tile kernel: the smallest shape mmfm_gemm_big_takes accepts (M >= 1024, N >= 128, K >= 512)
 ]
+FAMILY = {"fp32": L.GEMM_FAMILY_F32, "bf16": L.GEMM_FAMILY_TILE128, "big": L.GEMM_FAMILY_BIG256}      # asserted of every launch (gemm_on)
 
 
 @pytest.mark.parametrize("site", SITES, ids=lambda s: f"{s[0]}-{s[1]}x{s[2]}x{s[3]}")
@@ -87,14 +89,14 @@ def test_gemm_embedder_act_codes(monkeypatch, site, name):
         what = f"{name} scale {s} {mode} {M}x{N}x{Kd}"
         C = torch.full((M + 1, N), 9.0, dtype=dt, device="cuda")
         pre = torch.empty(M, N, dtype=dt, device="cuda")
-        K.gemm(x, W, C, M, N, Kd, lda=ld, ldb=Kd, ldc=N, bias=bias, pre_out=pre, act=fwd, act_scale=s, dtype=code)
+        gemm_on(FAMILY[mode], x, W, C, M, N, Kd, lda=ld, ldb=Kd, ldc=N, bias=bias, pre_out=pre, act=fwd, act_scale=s, dtype=code)
         assert torch.all(C[M:] == 9.0), "rows beyond M written"
         assert torch.isfinite(C.float()).all()
         chk(pre, z, what + " pre-activation")
         chk(C[:M], f_ref(name, z) * s, what + " forward")
         u = None if name == "identity" else pre
         D = torch.empty(M, N, dtype=dt, device="cuda")
-        K.gemm(dY, Wg, D, M, N, Kd, lda=Kd, ldb=Kd, ldc=N, act=grad, act_scale=s, gradmul_pre=u, dtype=code)
+        gemm_on(FAMILY[mode], dY, Wg, D, M, N, Kd, lda=Kd, ldb=Kd, ldc=N, act=grad, act_scale=s, gradmul_pre=u, dtype=code)
         assert torch.isfinite(D.float()).all()
         chk(D, g0 * df_ref(name, pre.double()) * s, what + " gradient")
 

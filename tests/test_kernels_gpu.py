@@ -1,5 +1,6 @@
 """Per-kernel parity: every C-ABI entry point against a plain torch fp32 reference of the same op
 (the oracle's functions where one exists).  Runs on the MI355X only."""
+import functools
 import math
 import os
 
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 from conftest import load_npz
+from gemm_on import gemm_on
 from dropout_refs import extract_attn_keep_mask as _extract_attn_keep_mask, unpack_keepbits as _unpack_keepbits
 from oracle import mm_oracle as O
 
@@ -665,6 +667,8 @@ def _gemm_bf16_256_tile_kernel(ops, M, N, K, Kreal):
     two backward-through-activation forms.  Against torch fp64 on the same bf16 inputs; the first rows bit for bit against the
     128 x 128 kernel (MMFM_GEMM_BIG_KMIN keeps short reductions there: here via a K = 64 * 7 = 448 < 512 twin is not possible, so
     the comparison is against fp64 only)."""
+    from multi_modal_foundation_model_amd import _lib as L
+    big = functools.partial(gemm_on, L.GEMM_FAMILY_BIG256)              # every launch below, asserted to be on that kernel
     x = torch.zeros(M, K, device="cuda", dtype=torch.bfloat16)
     w = torch.zeros(N, K, device="cuda", dtype=torch.bfloat16)
     x[:, :Kreal] = bf(rnd(M, Kreal, seed=1))
@@ -673,36 +677,36 @@ def _gemm_bf16_256_tile_kernel(ops, M, N, K, Kreal):
     ref0 = x.double() @ w.double().T + b.double()
     y, pre = torch.full((M + 1, N), 9.0, device="cuda", dtype=torch.bfloat16), torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     # (1) bias + pre_out + softsign
-    ops.gemm(x, w, y, M, N, K, lda=K, ldb=K, ldc=N, bias=b, pre_out=pre, act=2, act_scale=0.7)
+    big(x, w, y, M, N, K, lda=K, ldb=K, ldc=N, bias=b, pre_out=pre, act=2, act_scale=0.7)
     close_bf16(pre, ref0, "256-tile pre-activation")
     close_bf16(y[:M], 0.7 * ref0 / (1 + ref0.abs()), "256-tile softsign")
     assert torch.all(y[M:] == 9.0), "rows beyond M written"
     # (2) GELU
-    ops.gemm(x, w, y, M, N, K, lda=K, ldb=K, ldc=N, bias=b, act=1)
+    big(x, w, y, M, N, K, lda=K, ldb=K, ldc=N, bias=b, act=1)
     close_bf16(y[:M], torch.nn.functional.gelu(ref0), "256-tile gelu")
     # (3) dropout + residual: the mask is the one mmfm_dropout_apply draws for (site, m * N + n)
     state = torch.zeros(2, dtype=torch.int32, device="cuda")
     ops.rng_seed(state, 5)
     res = bf(rnd(M, N, seed=4))
     y0, yd, msk = (torch.empty(M, N, device="cuda", dtype=torch.bfloat16) for _ in range(3))
-    ops.gemm(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, bias=b)
+    big(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, bias=b)
     close_bf16(y0, ref0, "256-tile plain")
-    ops.gemm(x, w, yd, M, N, K, lda=K, ldb=K, ldc=N, bias=b, drop=ops.dropout(state, 9, 0.4), residual=res, ldr=N)
+    big(x, w, yd, M, N, K, lda=K, ldb=K, ldc=N, bias=b, drop=ops.dropout(state, 9, 0.4), residual=res, ldr=N)
     ops.dropout_apply(torch.ones_like(y0), msk, M, N, ops.dropout(state, 9, 0.4))
     keep = (msk != 0)
     assert abs(keep.float().mean().item() - 0.6) < 0.01
     close_bf16(yd, ref0 * keep / 0.6 + res.double(), "256-tile dropout + residual", tol=2e-2)
     # (4) backward through the activations: act 3 (gelu') and act 4 (softsign') multiply by f'(saved pre-activation)
     u = bf(rnd(M, N, seed=6))
-    ops.gemm(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=u, act=3)
+    big(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=u, act=3)
     ud = u.double()
     gp = 0.5 * (1 + torch.erf(ud / math.sqrt(2))) + ud * torch.exp(-0.5 * ud * ud) / math.sqrt(2 * math.pi)
     close_bf16(y0, (x.double() @ w.double().T) * gp, "256-tile gelu'")
-    ops.gemm(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=u, act=4, act_scale=0.7)
+    big(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=u, act=4, act_scale=0.7)
     close_bf16(y0, (x.double() @ w.double().T) * 0.7 / (1 + ud.abs()) ** 2, "256-tile softsign'")
     # act 5: the same derivative from the activation OUTPUT a = 0.7 softsign(u) (what the bf16 engine saves instead of u)
     a_out = bf(0.7 * ud / (1 + ud.abs()))
-    ops.gemm(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=a_out, act=5, act_scale=0.7)
+    big(x, w, y0, M, N, K, lda=K, ldb=K, ldc=N, gradmul_pre=a_out, act=5, act_scale=0.7)
     close_bf16(y0, (x.double() @ w.double().T) * 0.7 * (1 - a_out.double().abs() / 0.7) ** 2, "256-tile softsign' from the output")
     close_bf16(y0, (x.double() @ w.double().T) * 0.7 / (1 + ud.abs()) ** 2, "256-tile softsign' from the output vs exact", tol=2.5e-2)
 
@@ -1107,14 +1111,32 @@ def test_reduce_slabs_multi_matches_single_reductions(ops):
 def test_gemm_pair_two_weight_gradients_in_one_launch(ops):
     """mmfm_gemm_pair: the MLP's two weight gradients (512x256 and 256x512 over R rows, column sums riding along) from ONE launch of the
     streaming kernel, each on its share of the CUs, against the same two products issued separately and against fp64."""
-    R = 51200
-    dy1, x1 = bf(rnd(R, 512, seed=31)), bf(rnd(R, 256, seed=32))
-    dy2, x2 = bf(rnd(R, 256, seed=33)), bf(rnd(R, 512, seed=34))
+    from multi_modal_foundation_model_amd import _lib as L
+    _gemm_pair(ops, 51200, ((512, 256), (256, 512)), (32, 32), L.GEMM_FAMILY_DW256, 128, True)
+
+
+@pytest.mark.parametrize("slab_counts,items,fused", [((2, 2), 8, True), ((3, 2), 12, False)])
+def test_gemm_pair_one_launch_or_two(ops, slab_counts, items, fused):
+    """R = 4,096 rows: 128-wide tiles (256-wide ones start at 32,768 rows), of which the MLP's [512, 256] gradient makes 8 per slab - any
+    slab count gives a multiple of 8.  A [256, 256] gradient in front (attention's out_proj) makes 4: in 2 slabs 8 items, and the pair
+    leaves in one launch; in 3 slabs 12 - no multiple of 8 - and it leaves as two launches, with the same results."""
+    from multi_modal_foundation_model_amd import _lib as L
+    _gemm_pair(ops, 4096, ((256, 256), (256, 512)), slab_counts, L.GEMM_FAMILY_DW128, items, fused)
+
+
+def _gemm_pair(ops, R, widths, slab_counts, family, items, fused):
+    """Two weight gradients [N, K] = dY^T X over R rows through mmfm_gemm_pair and through two mmfm_gemm: bit-identical, and within the fp64
+    bounds.  `family`: the kernel each runs on alone; `items`: the first problem's tiles x slabs; `fused`: whether the pair is one launch."""
+    from multi_modal_foundation_model_amd import _lib as L
+    import ctypes as C
+    (N1, K1), (N2, K2) = widths
+    dy1, x1 = bf(rnd(R, N1, seed=31)), bf(rnd(R, K1, seed=32))
+    dy2, x2 = bf(rnd(R, N2, seed=33)), bf(rnd(R, K2, seed=34))
 
     def run(pair):
         outs = []
         descs = []
-        for dy, x, S in ((dy1, x1, 32), (dy2, x2, 32)):
+        for dy, x, S in ((dy1, x1, slab_counts[0]), (dy2, x2, slab_counts[1])):
             N, K = dy.shape[1], x.shape[1]
             kchunk = (-(-R // S) + 63) // 64 * 64
             S2 = -(-R // kchunk)
@@ -1122,11 +1144,12 @@ def test_gemm_pair_two_weight_gradients_in_one_launch(ops):
             slabs = torch.full((S2, stride), float("nan"), device="cuda")
             kw = dict(lda=N, ldb=K, ldc=K, a_kcontig=0, b_kcontig=0, splits=S2, kchunk=kchunk, slab_stride=stride, c_f32=1, colsum=slabs.data_ptr() + 4 * N * K)
             descs.append((ops.gemm_desc(dy, x, slabs, N, K, R, **kw), slabs, N, K, S2, stride))
+        assert [ops.gemm_family(d[0]) for d in descs] == [family, family]
+        assert descs[0][4] * L.lib().mmfm_gemm_dw_tiles(N1, K1, R) == items
+        assert ops.gemm_pair_fused(descs[0][0], descs[1][0]) == fused
         if pair:
             ops.gemm_pair(descs[0][0], descs[1][0])
         else:
-            from multi_modal_foundation_model_amd import _lib as L
-            import ctypes as C
             for d in descs:
                 assert L.lib().mmfm_gemm(C.byref(d[0]), None) == 0
         for _, slabs, N, K, S2, stride in descs:

@@ -92,7 +92,8 @@ def test_host_gates_against_the_products_own_functions(monkeypatch):
 @pytest.mark.parametrize("B,wide", [(327, False), (328, True), (LR.B_BIG, True), (LR.B_BENCH, True)])
 def test_descriptor_rules_on_the_default_models_shapes(B, wide):
     R, BT = B * LR.MODS * LR.T, B * LR.T
-    dw = dict(a_kcontig=0, b_kcontig=0, c_f32=1, splits=32, kchunk=2112)
+    # slabs long enough for the fewest splits below (29) to cover R rows: the library checks the descriptors it is asked about
+    dw = dict(a_kcontig=0, b_kcontig=0, c_f32=1, splits=32, kchunk=LR.cdiv(LR.cdiv(R, 29), 64) * 64)
     # dW of qkv [768, 256] over R rows and of the ap token embedding [1336, 668] over B T rows (input rows padded to 672)
     qkv = LR.gemm_desc(M=768, N=256, K=R, lda=768, ldb=256, ldc=256, **dw)
     tok = LR.gemm_desc(M=1336, N=668, K=BT, lda=1336, ldb=672, ldc=668, **dw)

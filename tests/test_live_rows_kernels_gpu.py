@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import edge_refs as ER
+from gemm_on import gemm_on
 from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd import ops as K
 
@@ -134,11 +135,11 @@ def test_forward_product_on_the_256_tile_kernel(monkeypatch, live):
     state, drop = drop_desc()
     kw = dict(lda=Kd, ldb=Kd, ldc=N, bias=bias, act=L.ACT_SOFTSIGN, act_scale=1.5, drop=drop, dtype=L.BF16)
     full = torch.full((R, N), SENT, device="cuda", dtype=BF)
-    K.gemm(x, W, full, R, N, Kd, **kw)
+    gemm_on(L.GEMM_FAMILY_BIG256, x, W, full, R, N, Kd, **kw)
     xg = torch.zeros(R, Kd, device="cuda", dtype=BF)
     xg[:Rl] = x[idx]
     out = torch.full((R + 1, N), SENT, device="cuda", dtype=BF)
-    K.gemm_live(xg, W, out, R, N, Kd, live=K.live_rows(rec, B, T), **kw)
+    gemm_on(L.GEMM_FAMILY_BIG256, xg, W, out, R, N, Kd, live=K.live_rows(rec, B, T), **kw)
     torch.cuda.synchronize()
     assert torch.all(out[Rl:] == SENT), "rows beyond B * T_live were written"
     ER.check_exact(ER.bits(out[:Rl]), ER.bits(full[idx]), "live x.W^T on the 256-tile kernel vs the full-row launch, gathered")
@@ -168,17 +169,14 @@ def test_dx_product_with_gradmul_pre(B, T, live, N, Kd):
 
 
 # ---------------------------------------------------------------------------------------------- dY^T.X + colsum
-def run_dw(dY, X, M, N, Kfull, S, kchunk, live=None):
-    """[M, N] = dY^T X with the column sums of dY behind each slab, reduced: (dW, db)."""
+def run_dw(family, dY, X, M, N, Kfull, S, kchunk, live=None):
+    """[M, N] = dY^T X with the column sums of dY behind each slab, reduced: (dW, db); on kernel `family`, asserted."""
     n = M * N + M
     stride = (n + 7) // 8 * 8
     slab = torch.full((S * stride,), SENT, device="cuda")
     kw = dict(lda=M, ldb=X.shape[1], ldc=N, a_kcontig=0, b_kcontig=0, dtype=L.BF16, c_f32=1, colsum=slab.data_ptr() + 4 * M * N,
               splits=S, kchunk=kchunk, slab_stride=stride)
-    if live is None:
-        K.gemm(dY, X, slab, M, N, Kfull, **kw)
-    else:
-        K.gemm_live(dY, X, slab, M, N, Kfull, live=live, **kw)
+    gemm_on(family, dY, X, slab, M, N, Kfull, live=live, **kw)
     dst = torch.empty(n, device="cuda")
     K.reduce_slabs(dst, slab, n, S, stride)
     torch.cuda.synchronize()
@@ -192,8 +190,8 @@ def run_dw(dY, X, M, N, Kfull, S, kchunk, live=None):
 def test_weight_gradient_with_colsum(M, N, t_live):
     B, T, S, kchunk = 16, 100, 8, 256
     Kfull, Kl = B * T, B * t_live
-    stream = (M, N) == (256, 64)
-    assert (M % 8 == 0) == stream and L.lib().mmfm_gemm_dw_tiles(256, 64, Kfull) == 2       # 256 x 64: the streaming kernel's shape; 4 x 2: the generic one's
+    family = L.GEMM_FAMILY_DW128 if (M, N) == (256, 64) else L.GEMM_FAMILY_TILE128            # run_dw asserts it of each launch
+    assert L.lib().mmfm_gemm_dw_tiles(256, 64, Kfull) == 2
     live = tuple(range(0, T, 1))[:t_live] if t_live in (0, 100) else tuple(sorted(torch.randperm(T, generator=torch.Generator().manual_seed(t_live))[:t_live].tolist()))
     _, rec = record(T, live)
     ldn = (N + 7) // 8 * 8
@@ -204,14 +202,14 @@ def test_weight_gradient_with_colsum(M, N, t_live):
     idx = live_index(B, T, live)
     dYg, Xg = torch.full_like(dY, float("nan")), torch.full_like(X, float("nan"))
     dYg[:Kl], Xg[:Kl] = dY[idx], X[idx]
-    dW, db = run_dw(dYg, Xg, M, N, Kfull, S, kchunk, live=K.live_rows(rec, B, T))
+    dW, db = run_dw(family, dYg, Xg, M, N, Kfull, S, kchunk, live=K.live_rows(rec, B, T))
     if t_live == 0:
         assert torch.equal(dW, torch.zeros_like(dW)) and torch.equal(db, torch.zeros_like(db))
         assert not torch.signbit(dW).any() and not torch.signbit(db).any()
         return
     # the parent launch on the gathered operands (zero rows behind them would change nothing: it reads Kl rows)
     Sp = -(-Kl // kchunk)
-    pW, pb = run_dw(dYg[:Kl].contiguous(), Xg[:Kl].contiguous(), M, N, Kl, Sp, kchunk)
+    pW, pb = run_dw(family, dYg[:Kl].contiguous(), Xg[:Kl].contiguous(), M, N, Kl, Sp, kchunk)
     if t_live == T:
         ER.check_exact(dW, pW, "dW, every bin live")
         ER.check_exact(db, pb, "db, every bin live")
