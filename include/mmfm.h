@@ -415,6 +415,70 @@ int mmfm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, mmfm_stream st
 int mmfm_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
                     const float* hyper, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- optimiser over a range table
+ * Param groups, frozen parameters and gradient clipping: the same update over RANGES of the flat buffers, each with its own hyper row.
+ * MMFM_OPTIM_RANGES is the feature macro for everything below (MMFM_VERSION stays, as for MMFM_NULL_BIAS: mmfm_adamw_step and every
+ * existing struct are unchanged).
+ *
+ * A range is [start, end) in elements of p / g / m / v and names a row of hyper[hyper_rows][8] (the layout of mmfm_adamw_step's hyper).
+ * Ranges are HOST memory, non-empty, sorted by start and disjoint; elements outside every range are never read or written.
+ *
+ * The host cuts the ranges at the multiples of MMFM_OPTIM_CHUNK elements (counted from element 0 of the buffer, so that a chunk never
+ * straddles a 16 KiB window and its interior is 16-byte aligned whenever the buffers are): range r becomes the chunks
+ *   [max(start, k * CHUNK), min(end, (k + 1) * CHUNK))   for k = start / CHUNK .. (end - 1) / CHUNK,
+ * in range order.  mmfm_optim_ranges_chunks counts them, mmfm_optim_ranges_table writes the table into HOST memory:
+ *   mmfm_optim_chunk chunk[n_chunks];  int32 first_chunk[n_ranges + 1]     (mmfm_optim_ranges_table_bytes in all)
+ * which the caller copies to the device once per set of ranges (not per step) and passes as `table`.  A workgroup owns whole chunks and
+ * reads range and hyper row from the table; which lane handles which element follows from the element's index alone, so neither grid
+ * size nor occupancy changes any bit of the results.
+ *
+ * Argument checks (NULL pointers; empty, unsorted or overlapping ranges; a range past n; a hyper row outside [0, hyper_rows); an
+ * n_chunks that is not the count of these ranges) return -1 before any HIP call: a machine without a GPU answers them. */
+#define MMFM_OPTIM_RANGES 1
+#define MMFM_OPTIM_CHUNK 4096
+typedef struct {
+    int64_t start, end;      /* [start, end) in elements */
+    int32_t hyper_row;
+    int32_t reserved;
+} mmfm_optim_range;
+typedef struct {
+    int64_t start;           /* first element */
+    int32_t len;             /* 1 .. MMFM_OPTIM_CHUNK, inside one CHUNK-aligned window */
+    int32_t range;           /* index of the range it was cut from */
+    int32_t hyper_row;
+    int32_t reserved;
+} mmfm_optim_chunk;
+/* The device record mmfm_grad_sumsq_ranges leaves at the start of its workspace (workspace = record, double range_sumsq[n_ranges],
+ * double chunk_partial[n_chunks]).  `skipped` is the only field a call reads before writing: zero the workspace once before first use. */
+typedef struct {
+    double total;            /* sum of range_sumsq, added in range order */
+    float clip_coef;         /* min(1, max_norm / (sqrt(total) + 1e-6)), formed in double; 1 where max_norm <= 0, inf or NaN */
+    int32_t nonfinite;       /* 1 where any chunk partial (or the total) is inf or NaN */
+    int64_t skipped;         /* incremented by every call with skip_nonfinite != 0 that set nonfinite */
+    int32_t n_ranges;
+    int32_t reserved;
+} mmfm_optim_record;
+/* Number of chunks of these ranges (>= n_ranges), or -1 with mmfm_last_error set.  HOST only. */
+int64_t mmfm_optim_ranges_chunks(const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows);
+int64_t mmfm_optim_ranges_table_bytes(int64_t n_chunks, int n_ranges);
+/* Writes the table described above into table_host[table_bytes].  HOST only. */
+int mmfm_optim_ranges_table(const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows, void* table_host, int64_t table_bytes);
+/* Bytes of record + per-range sums + per-chunk partials. */
+int64_t mmfm_optim_ranges_workspace(int64_t n_chunks, int n_ranges);
+/* range_sumsq[r] = sum over range r of x^2 with x = g * coef_in rounded to fp32 (what the update forms: pass coef_in = grad_scale), every
+ * product and addition in fp64.  Two launches, no floating-point atomics: one partial per chunk (fixed lane assignment, fixed reduction
+ * tree), then one workgroup adds each range's partials in chunk order, the range sums in range order, and writes the record.
+ * Same inputs, same bits.  max_norm <= 0 or inf: no clipping (clip_coef = 1); a NaN total also gives clip_coef = 1. */
+int mmfm_grad_sumsq_ranges(const float* g, int64_t n, const mmfm_optim_range* ranges, int n_ranges, const void* table, int64_t n_chunks,
+                           float coef_in, float max_norm, int skip_nonfinite, void* workspace, int64_t workspace_bytes,
+                           mmfm_stream stream);
+/* mmfm_adamw_step's update over every chunk with the chunk's hyper row; the gradient is gi = (g * clip_coef) * grad_scale, in that
+ * order, clip_coef read from *record (DEVICE; NULL: 1).  With skip_nonfinite != 0 and record->nonfinite set every workgroup returns
+ * before its first store: p, m, v and p_bf16 keep every byte.  p_bf16 as in mmfm_adamw_step. */
+int mmfm_adamw_step_ranges(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, const mmfm_optim_range* ranges,
+                           int n_ranges, const void* table, int64_t n_chunks, const float* hyper, int hyper_rows,
+                           const mmfm_optim_record* record, int skip_nonfinite, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- evaluation metrics
  * utils/utils.py:107-115 (metrics_list "r2" = torcheval R2Score per series; trainer/base.py:252-262 calls it for 50
  * neurons x every trial on the host):  out[g*C + c] = 1 - sum_s (y-p)^2 / sum_s (y - mean_s y)^2 over the S elements

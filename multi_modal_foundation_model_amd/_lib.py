@@ -64,6 +64,25 @@ class LiveRows(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("B", C.c_int), ("T", C.c_int)]
 
 
+OPTIM_CHUNK = 4096               # MMFM_OPTIM_CHUNK
+
+
+class OptimRange(C.Structure):
+    """mmfm_optim_range: [start, end) in elements of the flat buffers and the row of the hyper table it is updated with."""
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("hyper_row", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimChunk(C.Structure):
+    """mmfm_optim_chunk: one entry of the table mmfm_optim_ranges_table writes."""
+    _fields_ = [("start", C.c_int64), ("len", C.c_int32), ("range", C.c_int32), ("hyper_row", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimRecord(C.Structure):
+    """mmfm_optim_record: what mmfm_grad_sumsq_ranges leaves at the start of its workspace."""
+    _fields_ = [("total", C.c_double), ("clip_coef", C.c_float), ("nonfinite", C.c_int32), ("skipped", C.c_int64),
+                ("n_ranges", C.c_int32), ("reserved", C.c_int32)]
+
+
 def live_rec_ints(T):
     """MMFM_LIVE_REC_INTS: T_live + 3 reserved, live_t[T], rank[T]."""
     return 2 * T + 4
@@ -163,6 +182,12 @@ _PROTOS = {
     "mmfm_dropout_apply": (C.c_int, [_i, _vp, _vp, _i64, _i, Dropout, _vp]),
     "mmfm_cast_f32_to_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mmfm_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mmfm_optim_ranges_chunks": (C.c_int64, [C.POINTER(OptimRange), _i, _i64, _i]),
+    "mmfm_optim_ranges_table_bytes": (C.c_int64, [_i64, _i]),
+    "mmfm_optim_ranges_table": (C.c_int, [C.POINTER(OptimRange), _i, _i64, _i, _vp, _i64]),
+    "mmfm_optim_ranges_workspace": (C.c_int64, [_i64, _i]),
+    "mmfm_grad_sumsq_ranges": (C.c_int, [_vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _f, _f, _i, _vp, _i64, _vp]),
+    "mmfm_adamw_step_ranges": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _vp, _i, _vp, _i, _vp]),
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
     "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),

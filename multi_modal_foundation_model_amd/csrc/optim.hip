@@ -54,7 +54,306 @@ __global__ void cast_bf16_kernel(const float* __restrict__ src, uint16_t* __rest
 
 int ew_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)); }
 
+// ------------------------------------------------------------------ the range-table optimiser (include/mmfm.h, MMFM_OPTIM_RANGES)
+// A workgroup of 256 lanes walks one chunk's CHUNK-aligned window in OPT_QUADS passes; lane t of pass q owns the four elements
+// window + 4 * (256 q + t) .. + 3.  A quad that lies inside the chunk moves as 16 bytes (VEC: every buffer is 16-B aligned, the window
+// is too); a quad the chunk's head or tail cuts, and every quad without VEC, goes element by element.  The assignment depends on the
+// element's index only - never on the grid.
+constexpr int OPT_CHUNK = MMFM_OPTIM_CHUNK;
+constexpr int OPT_QUADS = OPT_CHUNK / (4 * 256);
+static_assert(OPT_CHUNK % (4 * 256) == 0 && (OPT_CHUNK & (OPT_CHUNK - 1)) == 0, "a chunk is a power-of-two number of 256-lane float4 passes");
+static_assert(sizeof(mmfm_optim_chunk) == 24 && sizeof(mmfm_optim_record) == 32 && sizeof(mmfm_optim_range) == 24, "range-table ABI");
+
+struct AdamwHyper {
+    float decay, omb1, b2, omb2, step, bc2s, eps, gs;
+};
+
+// adamw_kernel's update with every rounding written out.  hipcc contracts adamw_kernel's expressions into the fused multiply-adds below
+// (read from its gfx950 code: v = fma(gi, omb2 gi, b2 v); m = fma(omb1, fma(gs, g, -m), m), the inner one on the UNROUNDED gs g;
+// p = fma(decay, p, -(step q))); inlined into another loop the same expressions contract differently, so contraction is off here and
+// the choice is explicit.  The GPU tests compare the two kernels bit for bit.  gx is the gradient before grad_scale.
+__device__ __forceinline__ void adamw_update(const AdamwHyper& h, float gx, float& pi, float& mi, float& vi) {
+#pragma clang fp contract(off)
+    const float gi = gx * h.gs;
+    vi = __builtin_fmaf(gi, h.omb2 * gi, vi * h.b2);
+    mi = __builtin_fmaf(h.omb1, __builtin_fmaf(h.gs, gx, -mi), mi);
+    const float denom = sqrtf(vi) / h.bc2s + h.eps;
+    pi = __builtin_fmaf(h.decay, pi, -(h.step * (mi / denom)));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, uint16_t* __restrict__ pb, int64_t n,
+                                                           const mmfm_optim_chunk* __restrict__ chunks, int64_t n_chunks,
+                                                           const float* __restrict__ hyper, const mmfm_optim_record* __restrict__ rec,
+                                                           int skip) {
+    float clip = 1.0f;
+    if (rec) {
+        if (skip && rec->nonfinite) return;          // uniform over the grid: nobody stores anything
+        clip = rec->clip_coef;
+    }
+    const bool clipped = rec != nullptr;
+    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const mmfm_optim_chunk ch = chunks[c];
+        const float* hr = hyper + 8 * (int64_t)ch.hyper_row;
+        const AdamwHyper h = {hr[0], hr[1], hr[2], hr[3], hr[4], hr[5], hr[6], hr[7]};
+        const int64_t lo = std::max<int64_t>(ch.start, 0), hi = std::min<int64_t>(ch.start + ch.len, n);   // a table never reaches past n
+        const int64_t base = lo & ~(int64_t)(OPT_CHUNK - 1);
+#pragma unroll
+        for (int q = 0; q < OPT_QUADS; ++q) {
+            const int64_t i0 = base + 4 * (q * 256 + (int)threadIdx.x);
+            if (i0 + 4 <= lo || i0 >= hi) continue;
+            if (VEC && i0 >= lo && i0 + 4 <= hi) {
+                const float4 g4 = *reinterpret_cast<const float4*>(g + i0);
+                float4 p4 = *reinterpret_cast<const float4*>(p + i0), m4 = *reinterpret_cast<const float4*>(m + i0),
+                       v4 = *reinterpret_cast<const float4*>(v + i0);
+                const float gr[4] = {g4.x, g4.y, g4.z, g4.w};
+                float pr[4] = {p4.x, p4.y, p4.z, p4.w}, mr[4] = {m4.x, m4.y, m4.z, m4.w}, vr[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) adamw_update(h, clipped ? gr[j] * clip : gr[j], pr[j], mr[j], vr[j]);
+                *reinterpret_cast<float4*>(p + i0) = make_float4(pr[0], pr[1], pr[2], pr[3]);
+                *reinterpret_cast<float4*>(m + i0) = make_float4(mr[0], mr[1], mr[2], mr[3]);
+                *reinterpret_cast<float4*>(v + i0) = make_float4(vr[0], vr[1], vr[2], vr[3]);
+                if (pb)
+                    *reinterpret_cast<uint2*>(pb + i0) = make_uint2((uint32_t)f2bf(pr[0]) | ((uint32_t)f2bf(pr[1]) << 16),
+                                                                    (uint32_t)f2bf(pr[2]) | ((uint32_t)f2bf(pr[3]) << 16));
+            } else {
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t i = i0 + j;
+                    if (i < lo || i >= hi) continue;
+                    float pi = p[i], mi = m[i], vi = v[i];
+                    adamw_update(h, clipped ? g[i] * clip : g[i], pi, mi, vi);
+                    p[i] = pi; m[i] = mi; v[i] = vi;
+                    if (pb) pb[i] = f2bf(pi);
+                }
+            }
+        }
+    }
+}
+
+// one fp64 partial per chunk: x = g * coef in fp32 (the value the update forms), x * x + acc in fp64 from the first addition
+template <bool VEC>
+__global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restrict__ g, int64_t n, const mmfm_optim_chunk* __restrict__ chunks,
+                                                           int64_t n_chunks, float coef, double* __restrict__ partial) {
+    __shared__ double red[4];
+    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const mmfm_optim_chunk ch = chunks[c];
+        const int64_t lo = std::max<int64_t>(ch.start, 0), hi = std::min<int64_t>(ch.start + ch.len, n);
+        const int64_t base = lo & ~(int64_t)(OPT_CHUNK - 1);
+        double acc = 0.0;
+        if (VEC && hi - lo == OPT_CHUNK) {
+            // a whole chunk (nearly all of them): workgroup-uniform, no bounds test, and all four 16-byte loads of the lane are requested
+            // before the first is used.  Same lanes, same elements, same order of additions as the general path below.
+            float4 gq[OPT_QUADS];
+#pragma unroll
+            for (int q = 0; q < OPT_QUADS; ++q) gq[q] = *reinterpret_cast<const float4*>(g + base + 4 * (q * 256 + (int)threadIdx.x));
+#pragma unroll
+            for (int q = 0; q < OPT_QUADS; ++q) {
+                const double x0 = (double)(gq[q].x * coef), x1 = (double)(gq[q].y * coef), x2 = (double)(gq[q].z * coef), x3 = (double)(gq[q].w * coef);
+                acc = fma(x0, x0, acc); acc = fma(x1, x1, acc); acc = fma(x2, x2, acc); acc = fma(x3, x3, acc);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < OPT_QUADS; ++q) {
+                const int64_t i0 = base + 4 * (q * 256 + (int)threadIdx.x);
+                if (i0 + 4 <= lo || i0 >= hi) continue;
+                if (VEC && i0 >= lo && i0 + 4 <= hi) {
+                    const float4 g4 = *reinterpret_cast<const float4*>(g + i0);
+                    const double x0 = (double)(g4.x * coef), x1 = (double)(g4.y * coef), x2 = (double)(g4.z * coef), x3 = (double)(g4.w * coef);
+                    acc = fma(x0, x0, acc); acc = fma(x1, x1, acc); acc = fma(x2, x2, acc); acc = fma(x3, x3, acc);
+                } else {
+                    for (int j = 0; j < 4; ++j) {
+                        const int64_t i = i0 + j;
+                        if (i < lo || i >= hi) continue;
+                        const double x = (double)(g[i] * coef);
+                        acc = fma(x, x, acc);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);     // butterfly: the same tree in every lane
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[c] = ((red[0] + red[1]) + red[2]) + red[3];
+        __syncthreads();                                                            // red is reused by the next chunk
+    }
+}
+
+// one workgroup: each range's partials in chunk order, the range sums in range order, then the record.  Lane t of a group of 256
+// ranges owns range r0 + t; the group's partials are contiguous in the workspace (chunks lie in range order) and pass through LDS in
+// tiles, so the loads are coalesced round trips of the whole workgroup and only the additions - one dependent chain per range, as the
+// order demands - are serial.  Lane 0 adds the group's range sums, in range order, into the running total.
+constexpr int FIN_TILE = 512;
+__global__ __launch_bounds__(256) void sumsq_finish_kernel(const double* __restrict__ partial, const int32_t* __restrict__ first, int n_ranges,
+                                                           float max_norm, int skip, mmfm_optim_record* __restrict__ rec,
+                                                           double* __restrict__ range_sumsq) {
+    __shared__ double tile[FIN_TILE];
+    __shared__ double sums[256];
+    __shared__ int bad;
+    const int t = threadIdx.x;
+    if (t == 0) bad = 0;
+    double total = 0.0;                                  // lane 0's
+    for (int r0 = 0; r0 < n_ranges; r0 += 256) {
+        const int r = r0 + t, r_end = r0 + 256 < n_ranges ? r0 + 256 : n_ranges;
+        const int32_t my_lo = r < n_ranges ? first[r] : 0, my_hi = r < n_ranges ? first[r + 1] : 0;
+        const int32_t span_lo = first[r0], span_hi = first[r_end];
+        double s = 0.0;
+        for (int32_t tb = span_lo; tb < span_hi; tb += FIN_TILE) {
+            const int32_t cnt = span_hi - tb < FIN_TILE ? span_hi - tb : FIN_TILE;
+            __syncthreads();                             // the previous tile (and `sums`) has been read
+            for (int32_t i = t; i < cnt; i += 256) tile[i] = partial[tb + i];
+            __syncthreads();
+            const int32_t lo = my_lo > tb ? my_lo : tb, hi = my_hi < tb + cnt ? my_hi : tb + cnt;
+            // sixteen LDS reads in flight, then their additions in chunk order: the chain of additions is what the order costs, the
+            // read latency is not
+            int32_t c = lo;
+            for (; c + 16 <= hi; c += 16) {
+                double d[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) d[k] = tile[c - tb + k];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) s += d[k];
+            }
+            for (; c < hi; ++c) s += tile[c - tb];
+        }
+        if (r < n_ranges) range_sumsq[r] = s;
+        // the partials are sums of squares: none is negative, so an inf or NaN among them stays in s (inf + x = inf, NaN + x = NaN)
+        if (!isfinite(s)) atomicOr(&bad, 1);             // an integer flag in LDS; no floating-point atomic anywhere
+        __syncthreads();
+        sums[t] = s;
+        __syncthreads();
+        if (t == 0)
+            for (int k = 0; k < r_end - r0; ++k) total += sums[k];
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int nonfinite = (bad || !isfinite(total)) ? 1 : 0;
+        float coef = 1.0f;
+        if (max_norm > 0.0f && isfinite(max_norm)) {
+            const double cc = (double)max_norm / (sqrt(total) + 1e-6);
+            if (cc < 1.0) coef = (float)cc;          // a NaN total compares false: 1
+        }
+        rec->total = total;
+        rec->clip_coef = coef;
+        rec->nonfinite = nonfinite;
+        if (nonfinite && skip) rec->skipped = rec->skipped + 1;
+        rec->n_ranges = n_ranges;
+        rec->reserved = 0;
+    }
+}
+
+// the argument checks of every range entry point; the number of chunks, or -1 with the error set.  No HIP call.
+int64_t optim_ranges_check(const char* who, const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows) {
+    if (!ranges || n_ranges <= 0 || n <= 0 || hyper_rows <= 0)
+        return mmfm_set_error(-1, "%s: bad arguments (ranges %p, n_ranges %d, n %lld, hyper_rows %d)", who, (const void*)ranges, n_ranges,
+                              (long long)n, hyper_rows);
+    int64_t chunks = 0, prev_end = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const mmfm_optim_range& x = ranges[r];
+        if (x.start < 0 || x.end <= x.start)
+            return mmfm_set_error(-1, "%s: range %d [%lld, %lld) is empty or negative", who, r, (long long)x.start, (long long)x.end);
+        if (x.start < prev_end)
+            return mmfm_set_error(-1, "%s: range %d [%lld, %lld) overlaps or precedes range %d (ranges are sorted and disjoint)", who, r,
+                                  (long long)x.start, (long long)x.end, r - 1);
+        if (x.end > n) return mmfm_set_error(-1, "%s: range %d [%lld, %lld) reaches past n = %lld", who, r, (long long)x.start, (long long)x.end, (long long)n);
+        if (x.hyper_row < 0 || x.hyper_row >= hyper_rows)
+            return mmfm_set_error(-1, "%s: range %d names hyper row %d of %d", who, r, x.hyper_row, hyper_rows);
+        chunks += (x.end - 1) / OPT_CHUNK - x.start / OPT_CHUNK + 1;
+        prev_end = x.end;
+    }
+    if (chunks > INT32_MAX) return mmfm_set_error(-1, "%s: %lld chunks do not fit the table's int32 index", who, (long long)chunks);
+    return chunks;
+}
+
+int opt_blocks(int64_t n_chunks) { return (int)std::min<int64_t>(4096, n_chunks); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
+
+extern "C" int64_t mmfm_optim_ranges_chunks(const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows) {
+    return optim_ranges_check("mmfm_optim_ranges_chunks", ranges, n_ranges, n, hyper_rows);
+}
+
+extern "C" int64_t mmfm_optim_ranges_table_bytes(int64_t n_chunks, int n_ranges) {
+    if (n_chunks <= 0 || n_ranges <= 0) return 0;
+    return n_chunks * (int64_t)sizeof(mmfm_optim_chunk) + ((int64_t)n_ranges + 1) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int64_t mmfm_optim_ranges_workspace(int64_t n_chunks, int n_ranges) {
+    if (n_chunks <= 0 || n_ranges <= 0) return 0;
+    return (int64_t)sizeof(mmfm_optim_record) + ((int64_t)n_ranges + n_chunks) * (int64_t)sizeof(double);
+}
+
+extern "C" int mmfm_optim_ranges_table(const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows, void* table_host,
+                                       int64_t table_bytes) {
+    const int64_t n_chunks = optim_ranges_check("mmfm_optim_ranges_table", ranges, n_ranges, n, hyper_rows);
+    if (n_chunks < 0) return -1;
+    MMFM_REQUIRE(table_host && table_bytes >= mmfm_optim_ranges_table_bytes(n_chunks, n_ranges),
+                 "mmfm_optim_ranges_table: table of %lld bytes, %lld needed", (long long)table_bytes,
+                 (long long)mmfm_optim_ranges_table_bytes(n_chunks, n_ranges));
+    mmfm_optim_chunk* ch = (mmfm_optim_chunk*)table_host;
+    int32_t* first = (int32_t*)(ch + n_chunks);
+    int64_t c = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        first[r] = (int32_t)c;
+        for (int64_t k = ranges[r].start / OPT_CHUNK; k <= (ranges[r].end - 1) / OPT_CHUNK; ++k, ++c) {
+            const int64_t lo = std::max<int64_t>(ranges[r].start, k * OPT_CHUNK), hi = std::min<int64_t>(ranges[r].end, (k + 1) * OPT_CHUNK);
+            ch[c] = mmfm_optim_chunk{lo, (int32_t)(hi - lo), r, ranges[r].hyper_row, 0};
+        }
+    }
+    first[n_ranges] = (int32_t)c;
+    return 0;
+}
+
+extern "C" int mmfm_grad_sumsq_ranges(const float* g, int64_t n, const mmfm_optim_range* ranges, int n_ranges, const void* table,
+                                      int64_t n_chunks, float coef_in, float max_norm, int skip_nonfinite, void* workspace,
+                                      int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(g && table && workspace, "mmfm_grad_sumsq_ranges: NULL pointer (g %p, table %p, workspace %p)", (const void*)g, table, workspace);
+    const int64_t want = optim_ranges_check("mmfm_grad_sumsq_ranges", ranges, n_ranges, n, 1 << 30);
+    if (want < 0) return -1;
+    MMFM_REQUIRE(n_chunks == want, "mmfm_grad_sumsq_ranges: the table has %lld chunks, these ranges cut into %lld", (long long)n_chunks, (long long)want);
+    MMFM_REQUIRE(workspace_bytes >= mmfm_optim_ranges_workspace(n_chunks, n_ranges) && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)table & 7) == 0,
+                 "mmfm_grad_sumsq_ranges: workspace of %lld bytes (%lld needed), workspace and table 8-byte aligned", (long long)workspace_bytes,
+                 (long long)mmfm_optim_ranges_workspace(n_chunks, n_ranges));
+    mmfm_optim_record* rec = (mmfm_optim_record*)workspace;
+    double* range_sumsq = (double*)(rec + 1);
+    double* partial = range_sumsq + n_ranges;
+    const mmfm_optim_chunk* chunks = (const mmfm_optim_chunk*)table;
+    const int32_t* first = (const int32_t*)(chunks + n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    if (aligned16(g))
+        hipLaunchKernelGGL(sumsq_ranges_kernel<true>, dim3(opt_blocks(n_chunks)), dim3(256), 0, st, g, n, chunks, n_chunks, coef_in, partial);
+    else
+        hipLaunchKernelGGL(sumsq_ranges_kernel<false>, dim3(opt_blocks(n_chunks)), dim3(256), 0, st, g, n, chunks, n_chunks, coef_in, partial);
+    MMFM_LAUNCH_CHECK("mmfm_grad_sumsq_ranges");
+    hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)partial, first, n_ranges, max_norm, skip_nonfinite, rec,
+                       range_sumsq);
+    MMFM_LAUNCH_CHECK("mmfm_grad_sumsq_ranges (closing phase)");
+    return 0;
+}
+
+extern "C" int mmfm_adamw_step_ranges(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, const mmfm_optim_range* ranges,
+                                      int n_ranges, const void* table, int64_t n_chunks, const float* hyper, int hyper_rows,
+                                      const mmfm_optim_record* record, int skip_nonfinite, mmfm_stream stream) {
+    MMFM_REQUIRE(p && g && m && v && table && hyper, "mmfm_adamw_step_ranges: NULL pointer (p %p, g %p, m %p, v %p, table %p, hyper %p)",
+                 (void*)p, (const void*)g, (void*)m, (void*)v, table, (const void*)hyper);
+    const int64_t want = optim_ranges_check("mmfm_adamw_step_ranges", ranges, n_ranges, n, hyper_rows);
+    if (want < 0) return -1;
+    MMFM_REQUIRE(n_chunks == want, "mmfm_adamw_step_ranges: the table has %lld chunks, these ranges cut into %lld", (long long)n_chunks, (long long)want);
+    MMFM_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)record & 7) == 0, "mmfm_adamw_step_ranges: table and record are 8-byte aligned");
+    const mmfm_optim_chunk* chunks = (const mmfm_optim_chunk*)table;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && ((uintptr_t)p_bf16 & 7) == 0;
+    if (vec)
+        hipLaunchKernelGGL(adamw_ranges_kernel<true>, dim3(opt_blocks(n_chunks)), dim3(256), 0, st, p, g, m, v, (uint16_t*)p_bf16, n, chunks, n_chunks,
+                           hyper, record, skip_nonfinite);
+    else
+        hipLaunchKernelGGL(adamw_ranges_kernel<false>, dim3(opt_blocks(n_chunks)), dim3(256), 0, st, p, g, m, v, (uint16_t*)p_bf16, n, chunks, n_chunks,
+                           hyper, record, skip_nonfinite);
+    MMFM_LAUNCH_CHECK("mmfm_adamw_step_ranges");
+    return 0;
+}
 
 extern "C" int mmfm_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, mmfm_stream stream) {
     MMFM_REQUIRE(p && g && m && v && hyper && n > 0, "mmfm_adamw_step: bad arguments");

@@ -358,6 +358,7 @@ class Engine:
         self.rng = torch.zeros(2, dtype=torch.int32, device=self.device)
         K.rng_seed(self.rng, seed)
         self.params: Dict[str, torch.nn.Parameter] = {}
+        self.adoptions = 0               # bumped by adopt(): whoever caches facts about `params` (the optimiser) re-derives them
         self.plans: Dict[Tuple, dict] = {}
         # Buffers are owned per batch shape (B, T): a plan (and its captured hipGraphs) holds raw device pointers, so a
         # buffer must never be re-allocated while a plan that names it is alive.  `self.b` is the pool of the shape in
@@ -399,6 +400,7 @@ class Engine:
                 p.data = v
                 p.grad = None
                 self.params[name] = p
+        self.adoptions += 1
         self.refresh_weights()
 
     def owns(self, named_params) -> bool:
@@ -692,7 +694,7 @@ class Engine:
         else:
             self.b["gout"].copy_(grad_out.reshape(1).to(torch.float32))
         accumulate_into = None
-        first = next(iter(self.params.values()), None)
+        first = next((p for p in self.params.values() if p.requires_grad), None)
         if first is not None and first.grad is not None:
             accumulate_into = self.G.clone()               # caller did not zero_grad(): keep torch's += semantics
         plan = self._last
@@ -716,8 +718,12 @@ class Engine:
                     hook(name)
         for hook in self.backward_done_hooks:
             hook()
+        # requires_grad is honoured where the gradients are handed out: the plan still computes every gradient into G (pruning a frozen
+        # parameter's weight-gradient launches is a change of the plan builder), a frozen parameter just never sees its slice
         for name, p in self.params.items():
-            if p.grad is None or p.grad.data_ptr() != self.Gv(name).data_ptr():
+            if not p.requires_grad:
+                p.grad = None
+            elif p.grad is None or p.grad.data_ptr() != self.Gv(name).data_ptr():
                 p.grad = self.Gv(name)
 
     def segment_range(self, name):

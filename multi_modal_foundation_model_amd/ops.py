@@ -266,6 +266,58 @@ def adamw_step(p, g, m, v, p_bf16, n, hyper, plan=None):
     _emit(plan, L.lib().mmfm_adamw_step, (P(p), P(g), P(m), P(v), P(p_bf16), n, P(hyper)))
 
 
+class OptimRanges:
+    """The range table of mmfm_grad_sumsq_ranges / mmfm_adamw_step_ranges (include/mmfm.h, MMFM_OPTIM_RANGES): `ranges` is a list of
+    (start, end, hyper_row), sorted and disjoint, over flat buffers of n elements.  The library checks them and cuts them into chunks on
+    the host; with a `device` the table is uploaded (once - it lives as long as this object) and the zeroed workspace of the
+    sum-of-squares launch allocated beside it.  device=None keeps the host table only (no GPU needed)."""
+
+    def __init__(self, ranges, n, hyper_rows, device=None):
+        lib = L.lib()
+        self.n, self.hyper_rows, self.n_ranges = int(n), int(hyper_rows), len(ranges)
+        self.ranges = (L.OptimRange * max(1, self.n_ranges))(*[L.OptimRange(int(s), int(e), int(row), 0) for s, e, row in ranges])
+        self.n_chunks = lib.mmfm_optim_ranges_chunks(self.ranges, self.n_ranges, self.n, self.hyper_rows)
+        if self.n_chunks < 0:
+            L.check(-1, "mmfm_optim_ranges_chunks")
+        nbytes = lib.mmfm_optim_ranges_table_bytes(self.n_chunks, self.n_ranges)
+        self.table_host = torch.zeros(nbytes, dtype=torch.uint8)
+        L.check(lib.mmfm_optim_ranges_table(self.ranges, self.n_ranges, self.n, self.hyper_rows, self.table_host.data_ptr(), nbytes),
+                "mmfm_optim_ranges_table")
+        self.table = self.workspace = None
+        if device is not None:
+            self.table = self.table_host.to(device)
+            self.workspace = torch.zeros(lib.mmfm_optim_ranges_workspace(self.n_chunks, self.n_ranges), dtype=torch.uint8, device=device)
+
+    def chunks(self):
+        """The host table as a list of (start, len, range, hyper_row), and first_chunk[n_ranges + 1]."""
+        raw = bytes(self.table_host.numpy().tobytes())
+        ch = (L.OptimChunk * self.n_chunks).from_buffer_copy(raw[:self.n_chunks * C.sizeof(L.OptimChunk)])
+        first = (C.c_int32 * (self.n_ranges + 1)).from_buffer_copy(raw[self.n_chunks * C.sizeof(L.OptimChunk):])
+        return [(c.start, c.len, c.range, c.hyper_row) for c in ch], list(first)
+
+    def record(self):
+        """The device record of the last sum-of-squares launch and the per-range sums (synchronises: a D2H copy)."""
+        nrec = C.sizeof(L.OptimRecord)
+        raw = bytes(self.workspace[:nrec + 8 * self.n_ranges].cpu().numpy().tobytes())
+        rec = L.OptimRecord.from_buffer_copy(raw[:nrec])
+        sums = list((C.c_double * self.n_ranges).from_buffer_copy(raw[nrec:]))
+        return dict(total=rec.total, clip_coef=rec.clip_coef, nonfinite=int(rec.nonfinite), skipped=int(rec.skipped), range_sumsq=sums)
+
+
+def grad_sumsq_ranges(g, tab, coef_in=1.0, max_norm=0.0, skip_nonfinite=False, plan=None):
+    _emit(plan, L.lib().mmfm_grad_sumsq_ranges, (P(g), tab.n, tab.ranges, tab.n_ranges, P(tab.table), tab.n_chunks, float(coef_in),
+                                                 float(max_norm), int(bool(skip_nonfinite)), P(tab.workspace), tab.workspace.numel()),
+          keep=(tab,))
+
+
+def adamw_step_ranges(p, g, m, v, p_bf16, tab, hyper, clipped=False, skip_nonfinite=False, plan=None):
+    """hyper: device fp32 [tab.hyper_rows][8].  clipped: read clip_coef (and, with skip_nonfinite, the non-finite flag) from the record
+    the last grad_sumsq_ranges(g, tab) left in tab.workspace."""
+    _emit(plan, L.lib().mmfm_adamw_step_ranges, (P(p), P(g), P(m), P(v), P(p_bf16), tab.n, tab.ranges, tab.n_ranges, P(tab.table), tab.n_chunks,
+                                                 P(hyper), tab.hyper_rows, P(tab.workspace) if clipped else None,
+                                                 int(bool(skip_nonfinite)), ), keep=(tab,))
+
+
 def rng_seed(state, seed, plan=None):
     _emit(plan, L.lib().mmfm_rng_seed, (P(state), int(seed) & (2 ** 64 - 1)))
 

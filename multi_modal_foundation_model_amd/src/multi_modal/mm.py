@@ -183,6 +183,14 @@ class MultiModal(nn.Module):
             self._engine.adopt(named)        # parameters were replaced (.to(), load_state_dict(assign=True), ...)
         return self._engine
 
+    def _grad_anchor(self):
+        """The parameter that ties the engine's loss into autograd: the first one that requires grad (any will do - the engine hands out
+        the gradients itself).  None where everything is frozen: the forward-only plan runs and the loss has no grad_fn, as torch's."""
+        w = self.decoder_norm.weight
+        if w.requires_grad:
+            return w
+        return next((p for p in self.parameters() if p.requires_grad), None)
+
     def __getstate__(self):                   # torch.save(model) (trainer/base.py:302-308): parameters own their data again
         state = self.__dict__.copy()
         state["_engine"] = None
@@ -232,7 +240,7 @@ class MultiModal(nn.Module):
                                "encoder's [B, Le, Le] mask (mm.py:152-158, 210), so the two sides need equally many modalities")
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
-                          training=self.training, anchor=self.decoder_norm.weight)
+                          training=self.training, anchor=self._grad_anchor())
         mod_loss, mod_n, preds, targets = {}, {}, {}, {}
         for i, mod in enumerate(dec_mods):      # the engine's outputs are the decoder's modalities, in this order
             mod_loss[mod], mod_n[mod] = out["mod_loss"][i], out["mod_n"][i]

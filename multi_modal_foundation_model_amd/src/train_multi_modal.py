@@ -107,7 +107,10 @@ def main(argv=None):
     print("(train) masking active: ", model.masker.force_active)
     model = accelerator.prepare(model)
 
-    optimizer = make_optimizer(model, lr=config.optimizer.lr, weight_decay=config.optimizer.wd, eps=config.optimizer.eps)
+    # optimizer.max_grad_norm is no key of the reference's YAML: absent or null builds the reference's optimiser (one launch per step),
+    # a number turns on the fused clip (optim.py)
+    optimizer = make_optimizer(model, lr=config.optimizer.lr, weight_decay=config.optimizer.wd, eps=config.optimizer.eps,
+                               max_grad_norm=config.optimizer.get("max_grad_norm", None))
     lr_scheduler = OneCycleLR(optimizer=optimizer,
                               total_steps=config.training.num_epochs * len(train_dataloader) // config.optimizer.gradient_accumulation_steps,
                               max_lr=config.optimizer.lr, pct_start=config.optimizer.warmup_pct, div_factor=config.optimizer.div_factor)
