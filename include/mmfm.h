@@ -32,6 +32,10 @@ extern "C" {
  * act codes 12 .. 25 (mmfm_gemm_desc), mmfm_stitch_fwd a NULL pos_emb and mmfm_stitch_bwd a NULL d_pos.  No struct changed its layout and
  * no export was added: MMFM_VERSION stays, as for MMFM_NULL_BIAS. */
 #define MMFM_EMBED_OPTS 1
+/* Feature macro: the du-only front half of the fused MLP backward.  With it defined mmfm_mlp_bwd takes t1 == NULL && g == NULL together
+ * with dx == NULL (mmfm_mlp_desc).  A library without it refuses the NULLs as an argument error; no struct changed its layout and no export
+ * was added: MMFM_VERSION stays, as for MMFM_NULL_BIAS. */
+#define MMFM_MLP_DX_ONLY 1
 /* activation kinds of mmfm_mlp_desc.act (the fused MLP's transformer.act) */
 #define MMFM_MLP_GELU 0        /* exact-erf GELU (bf16: the polynomial of act 1) */
 #define MMFM_MLP_RELU 1
@@ -610,7 +614,10 @@ int mmfm_rowgemm_groups(const mmfm_rowgemm_groups_desc* d, mmfm_stream stream);
  *   Weight / LayerNorm-parameter gradients then follow from mmfm_gemm (dW slabs) + mmfm_ln_linear_grad.
  *   Bias-free linears (mlp_bias: false): b_down may be NULL (nothing is added to Y).  b_up may be NULL only with scalenorm = 1; under a
  *   LayerNorm b_up is the prepared W_up . beta and is always present (a NULL one is an argument error).  The backward kernels (one-launch
- *   and front half) read the same b_up the forward read, so the recomputed u follows the same rule; they never read b_down. */
+ *   and front half) read the same b_up the forward read, so the recomputed u follows the same rule; they never read b_down.
+ *   du only (MMFM_MLP_DX_ONLY): the front half (dx == NULL) with t1 == NULL && g == NULL writes du and nothing else - for a caller that
+ *   wants neither dW_down nor G_up (both projections frozen), the only readers of t1 and g.  du is bit for bit what the full front half
+ *   writes.  t1 and g are both NULL or both set; one NULL, or NULLs with dx != NULL, is an argument error and nothing is launched. */
 typedef struct {
     int64_t R;
     const void* x; int ldx;           /* fwd: residual stream in (bf16 [R][256]) */

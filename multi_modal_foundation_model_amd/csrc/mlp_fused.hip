@@ -259,8 +259,11 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const mmfm_mlp_desc d) {
 // What the split buys: this half fits 256 registers, so EIGHT waves share a workgroup's weight ring (two per SIMD - the fused kernel
 // runs one wave per SIMD at 448 registers and pays every LDS / MFMA latency once) and a pass streams 2 x 256 KB of weights for 256
 // rows instead of 3 x 256 KB for 128; what it costs: du is read back once (210 MB at R = 204,800).
+// DXO (t1 == NULL && g == NULL, MMFM_MLP_DX_ONLY): du alone.  Only the weight-gradient products dW_down = t1^T g and G_up read t1 and g; a
+// caller that wants neither (both projections frozen) saves their stores - 1.5 KB of the 2.5 KB a row writes.  The t1 store, the g staging
+// and the g line flush are compiled out; the operands, the products and du are the same instructions, so du is the same bits.
 constexpr int NTD = 512, NWD = 8;
-template <int ACT>
+template <int ACT, bool DXO = false>
 __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc d) {
     constexpr int RING_B = RINGA_SLOTS * CHUNK;
     extern __shared__ __attribute__((aligned(16))) char smem[];        // RING_B + 2 * NWD * STG_BYTES + 512 * 4
@@ -323,9 +326,13 @@ __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc 
                 t1[s] = pack8o(f);
             }
         }
-        store_rows_lines<4, true>(stg, T1, wrow0, 512u, lane, m, h, t1);
-        // ODD tiles complete a pair of g / du tiles: their 16 line stores leave at the end of the iteration, and the next two ring steps
-        // may therefore leave eight more operations in flight (the EXTRA argument of RINGA_SYNC; same accounting as the fused kernel)
+        if constexpr (!DXO) store_rows_lines<4, true>(stg, T1, wrow0, 512u, lane, m, h, t1);
+        // ODD tiles complete a pair of g / du tiles: their line stores leave at the end of the iteration, behind the request of the chunk
+        // the second of the next two ring steps multiplies, and those two steps may therefore leave that many more operations in flight
+        // (the EXTRA argument of RINGA_SYNC; same accounting as the fused kernel).  The count is what this instantiation really issues
+        // there: one flush_lines (FLUSH_LINE_STORES stores per lane) for du and, unless DXO, one for g.  A larger value would let that
+        // second step's own weight chunk still be outstanding when it is multiplied
+        constexpr int DU_EXTRA = (DXO ? 1 : 2) * FLUSH_LINE_STORES;
 #define MLP_DU_TILE(TI, ODD, EXTRA_AB)                                                           \
         {                                                                                        \
             const int ti = (TI), tt = (ti + rot) & 15;                                           \
@@ -342,17 +349,17 @@ __global__ __launch_bounds__(NTD, 2) void mlp_bwd_du_kernel(const mmfm_mlp_desc 
             }                                                                                    \
             f32x16 Gt;                                                                           \
             act_fwd_bwd16<ACT>(U, Gt, DG, ab);                                                   \
-            stage_tile(stg_g, ODD, m, h, Gt);                                                    \
+            if constexpr (!DXO) stage_tile(stg_g, ODD, m, h, Gt);                                \
             stage_tile(stg_du, ODD, m, h, DG);                                                   \
             if (ODD) {                          /* the pair (tt-1, tt) is complete -> whole 128-B lines */ \
-                flush_lines<true>(stg_g, G, wrow0, 1024u, 64u * (tt - 1), lane);                 \
+                if constexpr (!DXO) flush_lines<true>(stg_g, G, wrow0, 1024u, 64u * (tt - 1), lane); \
                 flush_lines<true>(stg_du, DU, wrow0, 1024u, 64u * (tt - 1), lane);               \
             }                                                                                    \
         }
         MLP_DU_TILE(0, 0, 0)
         MLP_DU_TILE(1, 1, 0)
         for (int tp = 1; tp < 8; ++tp) {
-            MLP_DU_TILE(2 * tp, 0, 8)
+            MLP_DU_TILE(2 * tp, 0, DU_EXTRA)
             MLP_DU_TILE(2 * tp + 1, 1, 0)
         }
 #undef MLP_DU_TILE
@@ -635,8 +642,13 @@ int check(const mmfm_mlp_desc& d, bool bwd) {
     MMFM_REQUIRE(al16(d.x) && al16(d.w_up) && al16(d.w_down) && al16(d.y) && al16(d.xhat) && al16(d.dy) && al16(d.w_down_t) && al16(d.w_up_t) &&
                  al16(d.t1) && al16(d.g) && al16(d.du) && al16(d.dx) && al16(d.b_up) && al16(d.b_down), "mmfm_mlp: operands must be 16-byte aligned");
     if (!bwd) MMFM_REQUIRE(d.x && d.w_down && d.y && d.ldx % 8 == 0 && d.ldy % 8 == 0 && d.ldx >= 256 && d.ldy >= 256, "mmfm_mlp_fwd: bad arguments");
-    else MMFM_REQUIRE(d.xhat && d.dy && d.w_down_t && d.g && d.du && d.t1 && d.lddy % 8 == 0 && d.lddy >= 256 &&
-                      (d.dx == nullptr || (d.rstd && d.w_up_t && d.lddx % 8 == 0 && d.lddx >= 256)), "mmfm_mlp_bwd: bad arguments");
+    else {
+        MMFM_REQUIRE(d.xhat && d.dy && d.w_down_t && d.du && d.lddy % 8 == 0 && d.lddy >= 256 &&
+                     (d.dx == nullptr || (d.rstd && d.w_up_t && d.lddx % 8 == 0 && d.lddx >= 256)), "mmfm_mlp_bwd: bad arguments");
+        // MMFM_MLP_DX_ONLY: t1 and g both NULL = the front half writes du alone.  One of them NULL, or NULL with the one-launch kernel, is an error
+        MMFM_REQUIRE((d.t1 == nullptr) == (d.g == nullptr), "mmfm_mlp_bwd: t1 and g must both be set or both be NULL (du only)");
+        MMFM_REQUIRE(d.t1 != nullptr || d.dx == nullptr, "mmfm_mlp_bwd: t1 == g == NULL (du only) is a form of the front half: dx must be NULL");
+    }
     return 0;
 }
 
@@ -669,6 +681,12 @@ extern "C" int mmfm_mlp_bwd(const mmfm_mlp_desc* dp, mmfm_stream stream) {
         return with_act(d.act, [&](auto A) {
             constexpr int ACT = decltype(A)::value;
             constexpr int LDS_D = RINGA_SLOTS * CHUNK + 2 * NWD * STG_BYTES + 512 * 4;
+            if (d.t1 == nullptr) {        // du only (check: g is NULL too)
+                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_du_kernel<ACT, true>), LDS_D, "mmfm_mlp_bwd(front half, du only)")) return rc;
+                hipLaunchKernelGGL((mlp_bwd_du_kernel<ACT, true>), dim3(grid_for(d.R, per_cu, NWD)), dim3(NTD), LDS_D, (hipStream_t)stream, d);
+                MMFM_LAUNCH_CHECK("mmfm_mlp_bwd(front half, du only)");
+                return 0;
+            }
             if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(mlp_bwd_du_kernel<ACT>), LDS_D, "mmfm_mlp_bwd(front half)")) return rc;
             hipLaunchKernelGGL(mlp_bwd_du_kernel<ACT>, dim3(grid_for(d.R, per_cu, NWD)), dim3(NTD), LDS_D, (hipStream_t)stream, d);
             MMFM_LAUNCH_CHECK("mmfm_mlp_bwd(front half)");

@@ -662,11 +662,14 @@ __device__ __forceinline__ void stage_opnd(char* stg, int s, int m, int h, opnd 
 }
 // staging -> global: rows wrow0 .. wrow0+31 of a tensor with `ldb` bytes per row, 128 bytes starting at byte column `colb`;
 // `nchunk` (1..8) = 16-B chunks of the 128 that exist (ragged last tile pair)
+// FLUSH_LINE_STORES: the vector-memory stores one call issues per lane (what a kernel that flushes between ring steps counts into the
+// EXTRA argument of RINGA_SYNC)
+constexpr int FLUSH_LINE_STORES = 4;
 template <bool NTS>
 __device__ __forceinline__ void flush_lines(const char* stg, const GBuf& b, uint32_t wrow0, uint32_t ldb, uint32_t colb, int lane, int nchunk = 8) {
     const int c = lane & 7;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < FLUSH_LINE_STORES; ++i) {
         const int row = 8 * i + (lane >> 3);
         const uint4 v = *reinterpret_cast<const uint4*>(stg + stg_off(row, c));
         st16<NTS>(b, c < nchunk ? (wrow0 + row) * ldb + colb + 16 * c : 0xfffffff0u, v);

@@ -15,6 +15,7 @@ the collective on its own stream; `work.wait()` only makes the compute stream wa
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Optional
 
@@ -48,14 +49,36 @@ class GradBuckets:
         self.trigger = {name: (lo, hi) for name, lo, hi in self.buckets}
 
 
+def trainable_spans(layout, buckets, trainable):
+    """What each bucket all-reduces when only the parameters named in `trainable` take a gradient: {the bucket's trigger segment:
+    (start, end) from its first to its last trainable parameter, or None where it has none (no collective)}.  A bucket all of whose
+    parameters are trainable keeps its whole range, padding included: with everything trainable the ranges are the buckets'.
+    buckets: GradBuckets.buckets.  A pure function of the layout and the names: no engine, no device."""
+    trainable, out = set(trainable), {}
+    for name, lo, hi in buckets:
+        inside = [(off, off + int(math.prod(shape)), k in trainable) for k, (off, shape) in layout.entries.items() if lo <= off < hi]
+        live = [(a, b) for a, b, on in inside if on]
+        if len(live) == len(inside):
+            out[name] = (lo, hi)
+        else:
+            out[name] = (min(a for a, _ in live), max(b for _, b in live)) if live else None
+    return out
+
+
 class EngineDDP:
-    """Attach to an Engine: all-reduce each gradient bucket as soon as backward has produced it."""
+    """Attach to an Engine: all-reduce each gradient bucket as soon as backward has produced it.
+
+    With frozen parameters (requires_grad = False) a bucket all-reduces only the span from its first to its last trainable parameter,
+    and a bucket without one issues no collective (`trainable_spans`; the engine's backward computes nothing there).  The spans follow
+    the freeze pattern of the last forward.  EVERY RANK MUST FREEZE THE SAME PARAMETERS: ranks whose patterns differ would issue
+    collectives of different sizes, or different numbers of them, and hang."""
 
     def __init__(self, engine, process_group=None, bucket_bytes: int = 8 << 20, broadcast: bool = True):
         self.engine, self.pg = engine, process_group
         self.world = dist.get_world_size(process_group)
         self.buckets = GradBuckets(engine.layout, engine.cfg, bucket_bytes)
         self.works = []
+        self._spans = {None: dict(self.buckets.trigger)}      # freeze pattern -> trainable_spans
         backend = dist.get_backend(process_group)
         self.avg_op = dist.ReduceOp.AVG if backend == "nccl" else None
         if broadcast:                       # replicas start identical (rank 0's parameters), like torch DDP
@@ -65,7 +88,15 @@ class EngineDDP:
         engine.backward_done_hooks.append(self.finish)
 
     def on_segment(self, name: str):
-        rng = self.buckets.trigger.get(name)
+        if name not in self.buckets.trigger:
+            return
+        pattern = getattr(self.engine, "_pattern", None)      # the freeze pattern of the last forward (None: all trainable)
+        if pattern not in self._spans:                        # a new freeze pattern: recomputed once, kept with the few others
+            if len(self._spans) > 8:
+                self._spans = {None: self._spans[None]}
+            names = [k for k, on in zip(self.engine.layout.entries, pattern) if on]
+            self._spans[pattern] = trainable_spans(self.engine.layout, self.buckets.buckets, names)
+        rng = self._spans[pattern][name]
         if rng is None:
             return
         lo, hi = rng

@@ -33,6 +33,7 @@ from .plan import PlanBuilder, _align, read_switches
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
 HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention kernels are instantiated for (csrc/attention.hip check_common)
+MAX_PATTERNS = 4                           # freeze patterns per batch shape whose training plans (and graphs) are kept, most recently used
 BLOCK_NORMS = ("ln1", "ln2", "query_norm", "context_norm")     # the sites `use_scalenorm` switches (encoder_norm / decoder_norm stay LayerNorm)
 
 
@@ -365,6 +366,10 @@ class Engine:
         # use; pools (with their plans) are evicted least-recently-used beyond MMFM_MAX_SHAPES.
         self._pools: Dict[Tuple[int, int], Dict[str, torch.Tensor]] = {}
         self._pool_lru: List[Tuple[int, int]] = []
+        # Training plans are also owned per freeze pattern (`freeze_pattern`): the backward of a pattern launches only what its trainable
+        # parameters need.  Per batch shape the MAX_PATTERNS most recently used patterns keep their plans and graphs
+        self._pattern_lru: Dict[Tuple[int, int], list] = {}
+        self._pattern = None
         self.max_shapes = max(1, int(os.environ.get("MMFM_MAX_SHAPES", "4")))
         self._shared: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, torch.Tensor] = self._shared
@@ -449,6 +454,7 @@ class Engine:
                 for pk in [k for k in self.plans if (k[0], k[1]) == old]:
                     del self.plans[pk]
                 del self._pools[old]
+                self._pattern_lru.pop(old, None)
             pool = dict(self._shared)
             self._pools[key] = pool
         if key in self._pool_lru:
@@ -590,14 +596,59 @@ class Engine:
         kchunk = _align(-(-R // S), 64)          # multiple of both kernels' BK (32 fp32, 64 bf16)
         return -(-R // kchunk), kchunk
 
-    def _plan(self, B, T, training, grad=True):
-        """The cached step plan of (batch shape, mode); built by plan.PlanBuilder the first time.
-        grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward."""
-        key = (B, T, bool(training), bool(grad))
+    def freeze_pattern(self):
+        """The requires_grad flags of the adopted parameters in layout order, or None while every one is True (or nothing is adopted):
+        what a plan with a backward is keyed by besides its batch shape and mode."""
+        if not self.params:
+            return None
+        pattern = tuple(self.params[name].requires_grad for name in self.layout.entries)
+        return None if all(pattern) else pattern
+
+    def _plan(self, B, T, training, grad=True, pattern=None):
+        """The cached step plan of (batch shape, mode, freeze pattern); built by plan.PlanBuilder the first time.
+        grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward.
+        pattern (`freeze_pattern`; None: all trainable, the key and the plan are what they always were): the plan's backward is pruned
+        to what the trainable parameters need.  A forward-only plan has no pattern."""
+        pattern = pattern if grad else None
+        key = (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))
         self._select_pool(B, T)
+        if grad:
+            lru = self._pattern_lru.setdefault((B, T), [])
+            if pattern in lru:
+                lru.remove(pattern)
+            lru.append(pattern)
+            while len(lru) > MAX_PATTERNS:
+                old = lru.pop(0)
+                torch.cuda.synchronize(self.device)          # nothing may still be replaying the dropped graphs
+                for pk in [k for k in self.plans if k[:2] == (B, T) and k[3] and (k[4] if len(k) > 4 else None) == old]:
+                    del self.plans[pk]
         if key not in self.plans:
-            self.plans[key] = PlanBuilder(self, B, T, training, grad).build()
+            frozen = None if pattern is None else [name for name, on in zip(self.layout.entries, pattern) if not on]
+            self.plans[key] = PlanBuilder(self, B, T, training, grad, frozen=frozen).build()
         return self.plans[key]
+
+    def backward_report(self, B, T):
+        """What the backward of the training plan of batch shape (B, T) launches under the current freeze pattern:
+          segments  [(segment name, launches of this plan, launches of the all-trainable plan)] in backward order,
+          pruned    the gradient groups none of whose launches is emitted (a linear with its bias - and, on the fused path, the norm
+                    that feeds it; a stand-alone norm; a tokeniser's mod_emb + pos_embed),
+          pruned_params      the parameters no emitted launch writes the gradient of (G is unspecified in their spans),
+          launches / full    the two totals.
+        Read-only, builds nothing and launches nothing: the plan must exist (one training forward ran at this shape and pattern)."""
+        pattern = self.freeze_pattern()
+        key = (B, T, True, True) + (() if pattern is None else (pattern,))
+        if key not in self.plans:
+            raise KeyError(f"backward_report({B}, {T}): no training plan of this shape under the current freeze pattern has been built yet")
+        rep = self.plans[key]["report"]
+        return dict(segments=list(rep["segments"]), pruned=list(rep["pruned"]), pruned_params=list(rep["pruned_params"]), launches=sum(s[1] for s in rep["segments"]),
+                    full=sum(s[2] for s in rep["segments"]))
+
+    def backward_summary(self, B, T):
+        """`backward_report` as one line."""
+        r = self.backward_report(B, T)
+        live = [f"{name} {n}/{full}" for name, n, full in r["segments"] if n]
+        return (f"backward: {r['launches']} of {r['full']} launches, {len(r['pruned'])} gradient groups pruned; "
+                f"segments with launches: {', '.join(live) if live else 'none'}")
 
     def dropout_sites(self, B, T):
         """Read-only description of the dropout sites of the built training plan of batch shape (B, T), for tests that read the masks
@@ -661,7 +712,8 @@ class Engine:
     # ------------------------------------------------------------------ run
     def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None):
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
-        plan = self._plan(B, T, training, want_grad)
+        self._pattern = self.freeze_pattern() if want_grad else None          # read once per forward
+        plan = self._plan(B, T, training, want_grad, self._pattern)
         self.load_inputs(B, T, inputs, targets, masks, ts, attn)
         advance = training and any(sc.dropout > 0 or sc.embed_dropout > 0 for sc in map(self.cfg.side, ("encoder", "decoder")))
 
@@ -705,11 +757,12 @@ class Engine:
         self.b = plan["b"]
         if self.grad_ready_hooks and accumulate_into is None:
             for name, seg in plan["bwd"]:          # DDP: one graph per segment, collectives issued in between
-                self._run(plan, "bwd", lambda seg=seg: K.run_plan(seg), tag="bwd/" + name)
+                if seg:                            # (a segment a pruned plan left without launches is neither run nor captured; its hook still fires)
+                    self._run(plan, "bwd", lambda seg=seg: K.run_plan(seg), tag="bwd/" + name)
                 for hook in self.grad_ready_hooks:
                     hook(name)
         else:
-            self._run(plan, "bwd", lambda: [K.run_plan(seg) for _, seg in plan["bwd"]])
+            self._run(plan, "bwd", lambda: [K.run_plan(seg) for _, seg in plan["bwd"] if seg])
         plan["runs"]["bwd"] += 1
         if accumulate_into is not None:
             self.G.add_(accumulate_into)
@@ -718,8 +771,8 @@ class Engine:
                     hook(name)
         for hook in self.backward_done_hooks:
             hook()
-        # requires_grad is honoured where the gradients are handed out: the plan still computes every gradient into G (pruning a frozen
-        # parameter's weight-gradient launches is a change of the plan builder), a frozen parameter just never sees its slice
+        # requires_grad is honoured twice: the plan of this freeze pattern launched only what the trainable parameters need (plan.py,
+        # DESIGN.md §10), so G in the span of a frozen parameter is unspecified - and a frozen parameter never sees its slice
         for name, p in self.params.items():
             if not p.requires_grad:
                 p.grad = None

@@ -239,6 +239,25 @@ class FusedAdamW(torch.optim.Optimizer):
                 p.grad = None
 
 
+def freeze_parameters(model, patterns):
+    """requires_grad_(False) on every parameter of `model` whose name matches one of the fnmatch `patterns` (None or empty: nothing is
+    frozen).  Names are the module's own (`encoder.0.attn.query.weight`), with or without a data-parallel wrapper around it.  Returns the
+    frozen names; a pattern that matches no parameter is an error.  Call it before the optimiser is made: the engine launches only the
+    backward the trainable parameters need (Engine.backward_report), the optimiser skips the frozen ones."""
+    import fnmatch
+    patterns = [patterns] if isinstance(patterns, str) else list(patterns or [])
+    named = dict(getattr(model, "module", model).named_parameters())
+    frozen = []
+    for pat in patterns:
+        hit = [k for k in named if fnmatch.fnmatchcase(k, pat)]
+        if not hit:
+            raise ValueError(f"freeze pattern {pat!r} matches no parameter (names look like {next(iter(named))!r})")
+        frozen += [k for k in hit if k not in frozen]
+    for k in frozen:
+        named[k].requires_grad_(False)
+    return [k for k in named if k in frozen]
+
+
 def make_optimizer(model, lr, weight_decay, eps, param_groups=None, max_grad_norm=None, skip_nonfinite=False):
     """What train_multi_modal.py:197-202 builds, fused.  The engine is bound lazily at the first step.  param_groups: torch's list of
     dicts ({"params": [...], "lr": ..., "weight_decay": ...}); None: one group over model.parameters(), as the reference builds."""

@@ -50,6 +50,11 @@ CTX_GROUP_MIN = 16384
 CTX_GROUP_BIAS = 2560       # floats of bias the grouped forward keeps in LDS: groups * N of one launch (csrc/rowgemm.hip, GBIAS_MAX)
 
 
+# The du-only front half of the fused MLP backward (mmfm_mlp_bwd with t1 = g = NULL): what a pruned plan launches for
+# an MLP block neither projection of which takes a gradient.  False: such a block passes real t1 / g buffers, as the full plan does
+MLP_DX_ONLY = True
+
+
 def ctx_group_on(R):
     v = os.environ.get("MMFM_CTX_GROUP")
     return v == "1" if v in ("0", "1") else R >= CTX_GROUP_MIN
@@ -72,9 +77,14 @@ class Side:
 
 
 class PlanBuilder:
-    def __init__(self, engine, B, T, training, grad=True):
+    def __init__(self, engine, B, T, training, grad=True, frozen=None):
+        """frozen: the names (layout entries) of the parameters with requires_grad = False, or None / empty: everything is trainable and
+        the plan is the one it always was.  With frozen parameters the backward is pruned to what the others need."""
         e, c = self.e, self.c = engine, engine.cfg
         self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
+        self.frozen = frozenset(frozen) if frozen else None
+        self.groups = {}             # gradient group -> (its launches are emitted, the parameters whose gradients they write) (`keep`)
+        self.parts = {l.name: l.parts for l in e.linears if l.parts}
         self.sw = read_switches()
         # each side's modalities (EngineConfig.side_mods: index in cfg.mods, name, channels).  A modality's place in its side's list is
         # its slot in that side's stitched sequence; its index in cfg.mods names its buffers and is its mod_emb row.  M counts a side's
@@ -103,6 +113,7 @@ class PlanBuilder:
         self.fwd, self.bwd, self.cur = [], [], []      # the forward, the closed backward segments, the open one
         self.pend: list = []         # batched reduction: the open segment's slab regions, summed by ONE launch in close_segment
         self.late_lng: list = []     # ... and the norm-fed linears whose mmfm_ln_linear_grad runs behind that launch
+        self.lng_sites = 0           # ... counted with the pruned ones: a site keeps the reduced buffer it has in the full plan
         self.slabm_off = 0           # ... and the floats of ws/slabm the open segment has handed out
         self.deferred: list = []     # a parked weight gradient, waiting for a partner (mmfm_gemm_pair)
         self.used_wt: list = []      # weights whose bf16 transpose a dX product reads
@@ -151,9 +162,54 @@ class PlanBuilder:
         plan = dict(fwd=self.fwd, bwd=None, B=self.B, T=self.T, training=self.training, M=self.M, R=self.R, BT=self.BT,
                     runs=dict(fwd=0, bwd=0), graphs={}, b=self.b, count=self.mk("decoder", "count"))
         if self.grad:
+            full = None
+            if self.frozen is not None:
+                # the all-trainable backward first, for its launch counts (Engine.backward_report) and for what it leaves behind outside
+                # the backward: every buffer of the pool and every transposed weight the forward refreshes, so that the forward of a
+                # pruned plan is launch for launch the all-trainable one.  Its launches are dropped
+                frozen, self.frozen = self.frozen, None
+                self.backward(refresh=False)
+                full = [(name, len(seg)) for name, seg in self.bwd]
+                self.frozen, self.bwd, self.groups = frozen, [], {}
             self.backward()
-            plan.update(bwd=self.bwd, fused=self.fm, use_keep=any(sd.use_keep for sd in self.sides.values()))
+            plan.update(bwd=self.bwd, fused=self.fm, use_keep=any(sd.use_keep for sd in self.sides.values()),
+                        report=dict(segments=[(name, len(seg), n) for (name, seg), (_, n) in zip(self.bwd, full or [(n_, len(s_)) for n_, s_ in self.bwd])],
+                                    pruned=[g for g, (kept, _) in self.groups.items() if not kept],
+                                    pruned_params=sorted({k for kept, names in self.groups.values() if not kept for k in names}
+                                                         - {k for kept, names in self.groups.values() if kept for k in names})))
         return plan
+
+    # ------------------------------------------------------------------ which gradients are needed
+    def trainable(self, names):
+        """True where one of the parameters `names` (layout entries) takes a gradient."""
+        return self.frozen is None or any(n not in self.frozen for n in names)
+
+    def lin_names(self, wname):
+        """The layout entries linear `wname` writes the gradients of: weight and bias, or those of the nn.Linear's a fused projection aliases."""
+        has, parts = self.e.layout.has, self.parts.get(wname)
+        if parts:
+            pre = wname.rsplit(".", 1)[0]
+            return [f"{pre}.{nm}{kind}" for nm in parts for kind in (".weight", ".bias") if has(f"{pre}.{nm}{kind}")]
+        return [wname + kind for kind in (".weight", ".bias") if has(wname + kind)]
+
+    def norm_names(self, lnname):
+        return [lnname + ".scale"] if self.e.is_sn(lnname) else [lnname + ".weight", lnname + ".bias"]
+
+    def tl(self, wname, lnname=None):
+        """True where linear `wname`, or the norm that feeds it, takes a gradient."""
+        return self.trainable(self.lin_names(wname) + (self.norm_names(lnname) if lnname else []))
+
+    def keep(self, group, kept, names):
+        """Records whether the launches of gradient group `group` - they write the gradients of the parameters `names` - are emitted
+        (Engine.backward_report names the others) and returns it."""
+        self.groups[group] = (bool(kept), tuple(names))
+        return bool(kept)
+
+    def skip_slabs(self, S, N, Kd, nb):
+        """A pruned weight gradient of the batched-reduction regime still takes its slab region, so that every surviving product keeps
+        the region it has in the all-trainable plan."""
+        if self.batch_red and S > 1:
+            self.slab_region(S, _align(N * Kd + nb) if nb else N * Kd)
 
     # ------------------------------------------------------------------ static inputs, workspaces, the regime of this shape
     def workspaces(self):
@@ -276,11 +332,13 @@ class PlanBuilder:
             a = self.deferred.pop()
             self.dlin(plan, a["dY"], a["X"], a["wname"], a["Mr"], a["N"], a["Kd"])
 
-    def dlin(self, plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, live=None, **kw):
+    def dlin(self, plan, dY, X, wname, Mr, N, Kd, dX=None, ldx=None, defer=False, live=None, need_dx=True, **kw):
         """Backward of Y[Mr,N] = X[Mr,Kd] @ W[N,Kd]^T + b:  dW, db into G;  dX = dY @ W (optional, fused epilogue).
         ldx = row stride of X when its rows are padded.  live: the mmfm_live_rows of the row space Mr when dY, X and dX hold the live rows
-        only (the split count and the kernels are those of all Mr rows; the kernels read the live count off the record)."""
+        only (the split count and the kernels are those of all Mr rows; the kernels read the live count off the record).
+        Pruned plan: the dW / db launches leave only where the linear takes a gradient, the dX product only where `need_dx`."""
         e, code = self.e, self.code
+        want_w = self.keep(wname, self.tl(wname), self.lin_names(wname))
         S, kchunk = e._dw_split(N, Kd, Mr, ldn=ldx, sw=self.sw)
         gw, gb = e.Gv(wname + ".weight"), e.Gb(wname)
         # bf16: the bias gradient (column sums of dY) rides on the dW GEMM (mmfm_gemm_desc.colsum); when the bias
@@ -288,18 +346,23 @@ class PlanBuilder:
         # A bias-free linear (gb None) has no column sum anywhere: the GEMM runs without colsum, its slabs hold the weight gradient only
         fused = code == L.BF16 and gb is not None
         adjacent = fused and gb.data_ptr() == gw.data_ptr() + 4 * N * Kd
-        if defer and self.pair_ok and S > 1 and (adjacent or gb is None) and dX is None and ldx in (None, Kd):
+        if not want_w:
+            self.skip_slabs(S, N, Kd, N if adjacent and S > 1 else 0)
+        elif defer and self.pair_ok and S > 1 and (adjacent or gb is None) and dX is None and ldx in (None, Kd):
             self.flush_deferred(plan)
             self.deferred.append(dict(dY=dY, X=X, wname=wname, Mr=Mr, N=N, Kd=Kd, nb=N if gb is not None else 0))
             return
-        self.wgrad(plan, dY, X, gw, N, Kd, Mr, N if adjacent and S > 1 else 0, S, kchunk, wname, ldx=ldx, colsum=gb if fused else None, slab=self.slab,
-                   live=live)
-        if gb is not None and (not fused or (S > 1 and not adjacent)):
-            assert live is None, wname          # live_bias_ok
-            K.colsum(dY, Mr, N, N, gb, self.b["ws/col"], plan=plan)
+        if want_w:
+            self.wgrad(plan, dY, X, gw, N, Kd, Mr, N if adjacent and S > 1 else 0, S, kchunk, wname, ldx=ldx, colsum=gb if fused else None, slab=self.slab,
+                       live=live)
+            if gb is not None and (not fused or (S > 1 and not adjacent)):
+                assert live is None, wname          # live_bias_ok
+                K.colsum(dY, Mr, N, N, gb, self.b["ws/col"], plan=plan)
         if dX is not None:
             gemm = K.gemm if live is None else functools.partial(K.gemm_live, live=live)
             wT = e._w_transposed(wname, N, Kd, Mr, sw=self.sw) if code == L.BF16 else None
+            if not need_dx:
+                return
             if wT is not None:      # reduction >= 512: the 256-tile kernel (csrc/gemm_big.hip) against the K-contiguous transpose W^T [Kd, N]
                 self.used_wt.append(wname)
                 gemm(dY, wT, dX, Mr, Kd, N, lda=N, ldb=N, ldc=Kd, b_kcontig=1, dtype=code, plan=plan, **kw)
@@ -325,6 +388,12 @@ class PlanBuilder:
         # the colsum block behind G: N, or 0 for a bias-free linear behind a ScaleNorm (nobody reads db).  Behind a LayerNorm db = colsum dY
         # stays even without a bias: dW and dbeta need it (beta is folded into the linear)
         nb = N if (self.e.Gb(wname) is not None or not self.e.is_sn(lnname)) else 0
+        if not self.keep(wname, self.tl(wname, lnname), self.lin_names(wname) + self.norm_names(lnname)):
+            # nothing of the group (the linear, the norm that feeds it) takes a gradient: no product, no reduction, no
+            # mmfm_ln_linear_grad.  A parked partner stays parked: the caller's flush_deferred issues it alone
+            self.skip_slabs(S, N, H, nb)
+            self.lng_sites += self.batch_red and S > 1
+            return
         if deferred and S > 1 and deferred[-1]["Mr"] == R:
             a = deferred.pop()
             Sa, kca, Sb, kcb = self.pair_splits(a["N"], a["Kd"], N, H, R)
@@ -337,9 +406,10 @@ class PlanBuilder:
         elif self.batch_red and S > 1:
             # launch-bound regime: the slabs join the segment's ONE reduction launch (own region, own reduced buffer per site) and
             # mmfm_ln_linear_grad runs behind it at the end of the segment (close_segment) - one reduction launch per site less
-            g_site = self.buf(f"ws/gdb/{len(self.late_lng)}", (self.gdb.numel(),), torch.float32)
+            g_site = self.buf(f"ws/gdb/{self.lng_sites}", (self.gdb.numel(),), torch.float32)
             self.wgrad(plan, dYt, xh, g_site, N, H, R, nb, S, kchunk, wname)
             self.late_lng.append((g_site, wname, lnname, N))
+            self.lng_sites += 1
             return
         else:
             self.wgrad(plan, dYt, xh, self.gdb, N, H, R, nb, S, kchunk, wname, slab=self.slab)
@@ -580,24 +650,32 @@ class PlanBuilder:
         for g_site, wname, lnname, N in self.late_lng:
             self.lin_norm_grad(self.cur, g_site, wname, lnname, N)
         self.late_lng.clear()
+        self.lng_sites = 0
         self.slabm_off = 0                     # the reduction has consumed the regions (stream order): the next segment reuses them
         self.bwd.append((name, self.cur))
         self.cur = []
 
-    def mlp_back(self, plan, dS, p, tag, X_in):
-        """dS: running gradient of the residual stream (in place).  X_in = the stream value that fed ln2."""
+    def mlp_back(self, plan, dS, p, tag, X_in, below=True):
+        """dS: running gradient of the residual stream (in place).  X_in = the stream value that fed ln2.
+        below: a launch behind this block reads dS (pruned plan: False where the stream ends above)."""
         e, b, buf, R, H, sd = self.e, self.b, self.buf, self.R, self.H, self.side(p)
         I, dp = sd.I, sd.dp
+        up, down = self.tl(p + ".mlp.up_proj", p + ".ln2"), self.tl(p + ".mlp.down_proj")
+        need_du = up or below                        # du feeds the up-projection's group and the dX of ln2
         if sd.F_MLP:
             pu, pdn = self.prep["v"][p + ".mlp.up_proj"], self.prep["v"][p + ".mlp.down_proj"]
             t1b, gb, dub = buf("d/t1m", (R, H)), buf("d/g", (R, I)), buf("d/du", (R, I))
             # same-box A/B at B = 1024: 30.80 -> 30.37 ms/step.  A ScaleNorm ln2 always splits (the one-launch kernel has no ScaleNorm epilogue)
             split = self.sw.mlp_bwd_split or e.is_sn(p + ".ln2")
+            # neither projection takes a gradient: only the weight-gradient products read t1 and g, the front half writes du alone
+            dx_only = split and not up and not down and MLP_DX_ONLY
             d_ = K.mlp_desc(R, w_up=pu["Wp"], b_up=pu["bp"], drop=e._drop(tag + "/mlpdrop", dp), xhat=b[tag + "/ln2/xh"],
-                            rstd=b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=t1b, g=gb, du=dub,
+                            rstd=b[tag + "/ln2/rs"], dy=dS, w_down_t=pdn["WpT"], w_up_t=pu["WpTP"], t1=None if dx_only else t1b,
+                            g=None if dx_only else gb, du=dub,
                             dx=None if split else dS, scalenorm=e.is_sn(p + ".ln2"), act=sd.act[0], act_beta=sd.act[1])
-            K.mlp_bwd(d_, plan=plan)
-            if split:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
+            if need_du or down:
+                K.mlp_bwd(d_, plan=plan)
+            if split and below:     # front half only above (t1, g, du); dX + LayerNorm backward + residual by the row-owner K = I kernel
                 self.dx_ln(plan, dub, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", dS, dS)
             self.dlin(plan, t1b, gb, p + ".mlp.down_proj", R, H, I, defer=True)     # dW_down = t1^T g, db_down = colsum t1
             self.dlin_ln(plan, dub, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", I)
@@ -605,71 +683,124 @@ class PlanBuilder:
             return
         dSd = dS
         if dp > 0:                                                       # mm_utils.py:52 dropout(down_proj(.))
-            K.dropout_apply(dS, b["d/t1"], R, H, e._drop(tag + "/mlpdrop", dp), plan=plan)
+            if need_du or down:
+                K.dropout_apply(dS, b["d/t1"], R, H, e._drop(tag + "/mlpdrop", dp), plan=plan)
             dSd = b["d/t1"]
         du = self.rows(b["d/u"], R, I)
-        self.dlin(plan, dSd, b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, act=sd.act_grad, act_scale=sd.act[1], gradmul_pre=b[tag + "/u"])
-        self.norm_lin_back(plan, False, du, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", tag + "/h2", X_in, dS, dS)
+        self.dlin(plan, dSd, b[tag + "/g"], p + ".mlp.down_proj", R, H, I, dX=du, need_dx=need_du, act=sd.act_grad, act_scale=sd.act[1],
+                  gradmul_pre=b[tag + "/u"])
+        self.norm_lin_back(plan, False, du, I, tag + "/ln2", p + ".mlp.up_proj", p + ".ln2", tag + "/h2", X_in, dS, dS, need_dx=below)
 
-    def norm_lin_back(self, plan, fused, dYt, N, tag, wname, lnname, hkey, X_in, dres, dXout):
+    def norm_lin_back(self, plan, fused, dYt, N, tag, wname, lnname, hkey, X_in, dres, dXout, need_dx=True):
         """Backward of a norm-fed linear [N, H] and its norm (input X_in; un-fused: normalised rows saved under `hkey`): the residual
-        stream gradient dXout = dres + norm'(dYt W).  A parked weight gradient leaves with this one's (fused) or alone in front of it."""
+        stream gradient dXout = dres + norm'(dYt W).  A parked weight gradient leaves with this one's (fused) or alone in front of it.
+        need_dx: a later launch reads dXout.  The un-fused norm backward also runs for its own parameters' sake."""
         if fused:
             self.dlin_ln(plan, dYt, tag, wname, lnname, N)
             self.flush_deferred(plan)
-            self.dx_ln(plan, dYt, N, tag, wname, lnname, dres, dXout)
+            if need_dx:
+                self.dx_ln(plan, dYt, N, tag, wname, lnname, dres, dXout)
         else:
             self.flush_deferred(plan)
-            self.dlin(plan, dYt, self.b[hkey], wname, self.R, N, self.H, dX=self.b["d/h"])
-            self.ln_b(plan, self.b["d/h"], X_in, lnname, tag, dres, dXout)
+            norm = self.keep(lnname, need_dx or self.trainable(self.norm_names(lnname)), self.norm_names(lnname))
+            self.dlin(plan, dYt, self.b[hkey], wname, self.R, N, self.H, dX=self.b["d/h"], need_dx=norm)
+            if norm:
+                self.ln_b(plan, self.b["d/h"], X_in, lnname, tag, dres, dXout)
 
-    def out_proj_back(self, plan, dS, a, wname):
-        """dW, db of an attention out_proj and d(attention output) -> d/t2."""
+    def out_proj_back(self, plan, dS, a, wname, need_dx=True):
+        """dW, db of an attention out_proj and d(attention output) -> d/t2 (need_dx: the attention backward behind it runs)."""
         R, H, t2 = self.R, self.H, self.b["d/t2"]
         if self.F_OUT:
             self.dlin(plan, dS, a, wname, R, H, H, defer=True)        # leaves with the next LayerNorm-fed linear's weight gradient
-            K.rowgemm(dS, self.prep["v"][wname]["WpT"], t2, R, H, H, plan=plan)
+            if need_dx:
+                K.rowgemm(dS, self.prep["v"][wname]["WpT"], t2, R, H, H, plan=plan)
         else:
-            self.dlin(plan, dS, a, wname, R, H, H, dX=t2)
+            self.dlin(plan, dS, a, wname, R, H, H, dX=t2, need_dx=need_dx)
 
-    def self_back(self, plan, dS, p, tag, flags):
+    def self_back(self, plan, dS, p, tag, flags, below=True):
+        """below: a launch behind this block reads dS."""
         b, H = self.b, self.H
-        self.out_proj_back(plan, dS, b[tag + "/a"], p + ".attn.out_proj")
+        attn = below or self.tl(p + ".attn.qkv", p + ".ln1")          # d/qkv feeds the projection's group and the dX of ln1
+        self.out_proj_back(plan, dS, b[tag + "/a"], p + ".attn.out_proj", need_dx=attn)
         qkv, dqkv = b[tag + "/qkv"], b["d/qkv"]
-        K.attn_bwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, b[tag + "/a"], flags, d_o=b["d/t2"], dq=dqkv, dkv=dqkv,
-                                  lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), plan=plan)
-        self.norm_lin_back(plan, self.F_QKV, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", tag + "/h1", self.stream_in[tag], dS, dS)
+        if attn:
+            K.attn_bwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, b[tag + "/a"], flags, d_o=b["d/t2"], dq=dqkv, dkv=dqkv,
+                                      lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), plan=plan)
+        self.norm_lin_back(plan, self.F_QKV, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", tag + "/h1", self.stream_in[tag], dS, dS,
+                           need_dx=below)
 
-    def cross_back(self, plan, dY, p, tag, dctx_in):
-        """Cross attention (decoder_embeddings.py:143): query side -> the stream dY, context side -> d/ctx (added to `dctx_in`)."""
+    def cross_back(self, plan, dY, p, tag, dctx_in, below=True, ctx=True):
+        """Cross attention (decoder_embeddings.py:143): query side -> the stream dY, context side -> d/ctx (added to `dctx_in`).
+        below: a launch behind this block reads dY; ctx: something upstream of the context takes a gradient (d/ctx is needed)."""
         b, H, dqc = self.b, self.H, self.b["d/qc"]
         # grouped context side: every layer keeps its own d/kvc until the bridge segment sums their dX products (context_back)
         dkvc = b["d/kvc/" + tag[3:]] if self.ctx_group else b["d/kvc"]
-        self.out_proj_back(plan, dY, b[tag + "/a2"], p + ".cross_attn.out_proj")
-        K.attn_bwd(self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
-                                  d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=plan)
-        self.norm_lin_back(plan, self.F_LNL, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", tag + "/hq", b[tag + "/xa"], dY, dY)
+        # the attention backward runs if dq (the query group, the stream) or dk / dv (the kv group, the context) is needed
+        attn = below or ctx or self.tl(p + ".cross_attn.query", p + ".query_norm") or self.tl(p + ".cross_attn.kv", p + ".context_norm")
+        self.out_proj_back(plan, dY, b[tag + "/a2"], p + ".cross_attn.out_proj", need_dx=attn)
+        if attn:
+            K.attn_bwd(self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
+                                      d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=plan)
+        self.norm_lin_back(plan, self.F_LNL, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", tag + "/hq", b[tag + "/xa"], dY, dY,
+                           need_dx=below)
         if self.ctx_group:       # the weight gradient where it was; no context-side dX here
             self.dlin_ln(plan, dkvc, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", 2 * H)
             self.flush_deferred(plan)
             return
         self.norm_lin_back(plan, self.F_LNL, dkvc, 2 * H, tag + "/cn", p + ".cross_attn.kv", p + ".context_norm", tag + "/hc", b["context"],
-                           dctx_in, b["d/ctx"])
+                           dctx_in, b["d/ctx"], need_dx=ctx)
 
     # ------------------------------------------------------------------ backward (segments fire DDP hooks)
-    def backward(self):
+    def needs(self):
+        """Where the two gradient streams are still needed: a namespace of
+          tok[side, slot]  (token_embed, projection, mod_emb / pos_embed) of a tokeniser take a gradient,
+          ctx              d/ctx is needed: something upstream of the context is trainable,
+          enc_below[i] / dec_below[i]    a launch behind encoder / decoder layer i reads the stream,
+          dec_cross[i] / dec_mlp[i]      ... behind the cross-attention / the MLP block of decoder layer i,
+          enc_mlp[i], enc_top, dec_top   ... behind the MLP block of encoder layer i, behind the bridge, behind decoder_norm."""
+        c, t, tl = self.c, self.trainable, self.tl
+        n = type("Needs", (), {})()
+        n.tok = {}
+        for side, mods in self.mods_of.items():
+            for slot, (m, mod, _) in enumerate(mods):
+                p = f"{side}_embeddings.{mod}.embedder"
+                emb = [f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight"] + ([p + ".pos_embed.weight"] if self.sides[side].pos else [])
+                n.tok[side, slot] = (tl(p + ".token_embed"), tl(p + ".projection"), t(emb))
+        bottom = {side: any(any(v) for (s, _), v in n.tok.items() if s == side) for side in ("encoder", "decoder")}
+        layer = lambda side, i: t([k for k in self.e.layout.entries if k.startswith(f"{side}.{i}.")])
+        enc = [layer("encoder", i) for i in range(c.n_enc)]
+        n.enc_below = [bottom["encoder"] or any(enc[:i]) for i in range(c.n_enc)]
+        n.enc_mlp = [tl(f"encoder.{i}.attn.qkv", f"encoder.{i}.ln1") or tl(f"encoder.{i}.attn.out_proj") or n.enc_below[i] for i in range(c.n_enc)]
+        n.enc_top = bottom["encoder"] or any(enc)
+        n.ctx = n.enc_top or tl("decoder_proj_context", "encoder_norm")
+        # d/ctx needs every layer's d/kvc, and with it the stream down to layer 0's cross-attention
+        dec = [layer("decoder", i) or n.ctx for i in range(c.n_dec)]
+        n.dec_below = [bottom["decoder"] or any(dec[:i]) for i in range(c.n_dec)]
+        n.dec_cross = [tl(f"decoder.{i}.attn.qkv", f"decoder.{i}.ln1") or tl(f"decoder.{i}.attn.out_proj") or n.dec_below[i] for i in range(c.n_dec)]
+        n.dec_mlp = [n.ctx or n.dec_cross[i] or tl(f"decoder.{i}.cross_attn.out_proj") or tl(f"decoder.{i}.cross_attn.query", f"decoder.{i}.query_norm")
+                     or tl(f"decoder.{i}.cross_attn.kv", f"decoder.{i}.context_norm") for i in range(c.n_dec)]
+        n.dec_top = bottom["decoder"] or any(dec)
+        return n
+
+    def backward(self, refresh=True):
         e, c, b, buf = self.e, self.c, self.b, self.buf
         B, T, H, I, R, BT, Lq = self.B, self.T, self.H, self.Imax, self.R, self.BT, self.Lq
+        nd = self.needs()
         dY, dydec = buf("d/stream", (R, H)), buf("d/ydec", (R, H))
         buf("d/t1", (R, H)); buf("d/t2", (R, H)); buf("d/h", (R, H)); buf("d/u", (R, I)); buf("d/qkv", (R, 3 * H)); dctx = buf("d/ctx", (R, H))
         ydec = b["ydec"]
         tokmask = b[self.mk("decoder", "tokmask")]
+        # decoder_norm's backward reads d/ydec of every modality: it runs for the stream's sake or for its own parameters'
+        norm = self.keep("decoder_norm", nd.dec_top or self.trainable(self.norm_names("decoder_norm")), self.norm_names("decoder_norm"))
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             dpred = buf(f"d/pred/{m}", (BT, n))
-            self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, j * T:],
-                      Lq, T, BT, n, b["gout"], b["inv_n"], dpred)
-            self.dlin(self.cur, dpred, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[j * BT:(j + 1) * BT])
-        self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
+            if norm or self.tl(f"decoder_embeddings.{mod}.out"):
+                self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, j * T:],
+                          Lq, T, BT, n, b["gout"], b["inv_n"], dpred)
+            self.dlin(self.cur, dpred, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[j * BT:(j + 1) * BT],
+                      need_dx=norm)
+        if norm:
+            self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
         self.close_segment("head")
         buf("d/qc", (R, H))
         if self.ctx_group:
@@ -679,26 +810,30 @@ class PlanBuilder:
             buf("d/kvc", (R, 2 * H))
         for i in reversed(range(c.n_dec)):
             p, tag = f"decoder.{i}", f"dec{i}"
-            self.mlp_back(self.cur, dY, p, tag, b[tag + "/yb"])
-            self.cross_back(self.cur, dY, p, tag, None if i == c.n_dec - 1 else dctx)     # the last layer writes d/ctx, the others add
-            self.self_back(self.cur, dY, p, tag, self.dec_flags)
+            self.mlp_back(self.cur, dY, p, tag, b[tag + "/yb"], below=nd.dec_mlp[i])
+            # the last layer writes d/ctx, the others add (pruned plan: d/ctx is needed from every layer or from none, nd.ctx)
+            self.cross_back(self.cur, dY, p, tag, None if i == c.n_dec - 1 else dctx, below=nd.dec_cross[i], ctx=nd.ctx)
+            self.self_back(self.cur, dY, p, tag, self.dec_flags, below=nd.dec_below[i])
             self.close_segment(p)
         if c.n_dec == 0:
             raise NotImplementedError("n_dec == 0")
         # now dY = d(dec_tokens + dec_emb) and dctx = d(context); context = ctx_proj(enc_out) + encoder_emb (mm.py:292)
         dX = buf("d/xstream", (R, H))
-        if self.ctx_group:
+        if self.ctx_group and nd.ctx:
             self.context_back(self.cur, dctx)
-        self.norm_lin_back(self.cur, self.F_LNL, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", "enc_out", self.enc_last, None, dX)
+        self.norm_lin_back(self.cur, self.F_LNL, dctx, H, "encnorm", "decoder_proj_context", "encoder_norm", "enc_out", self.enc_last, None, dX,
+                           need_dx=nd.enc_top)
         self.close_segment("bridge")
         for i in reversed(range(c.n_enc)):
             p, tag = f"encoder.{i}", f"enc{i}"
-            self.mlp_back(self.cur, dX, p, tag, b[tag + "/xa"])
-            self.self_back(self.cur, dX, p, tag, self.enc_flags)
+            self.mlp_back(self.cur, dX, p, tag, b[tag + "/xa"], below=nd.enc_mlp[i])
+            self.self_back(self.cur, dX, p, tag, self.enc_flags, below=nd.enc_below[i])
             self.close_segment(p)
         # tokenisers: decoder side first (it overwrites the shared mod_emb gradient row, the encoder side adds).  The encoder side adds
         # only where a decoder tokeniser really wrote that row: a table no decoder tokeniser shares gets its gradient by overwriting,
-        # and a table the decoder owns gets its own
+        # and a table the decoder owns gets its own.  Pruned plan: a tokeniser's stitch backward runs if its d/tok or one of its tables
+        # is needed.  The decoder-side writer of a shared row and the encoder-side adder read the same table's flag, so they run or go
+        # together wherever that table takes a gradient; an adder left alone adds into a row nobody reads
         shared = {mod for _, mod, _ in self.mods_of["decoder"] if c.mod_emb_owner("decoder", mod) == "encoder"}
         for side, dS, dextra in (("decoder", dY, None), ("encoder", dX, dctx)):
             sd = self.sides[side]
@@ -706,6 +841,9 @@ class PlanBuilder:
                 pS = f"{side}_embeddings.{mod}.embedder"
                 lv = self.lv.get((side, slot))
                 stitch = K.stitch_bwd if lv is None else functools.partial(K.stitch_bwd_live, rec=lv._keep)
+                emb = [f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight"] + ([pS + ".pos_embed.weight"] if sd.pos else [])
+                if not self.keep(pS + ".mod_emb+pos_embed", any(nd.tok[side, slot]), emb):
+                    continue
                 stitch(dS, dextra, b["ts"], b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), d_tok=buf(f"d/tok/{side}/{m}", (BT, H)),
                        d_mod_row=e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
                        d_pos=e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
@@ -720,13 +858,13 @@ class PlanBuilder:
                 n2 = n * sd.mult
                 lv = self.lv.get((side, slot))
                 dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)
-                self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz,
+                self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz, need_dx=nd.tok[side, slot][0],
                           act=L.ACT_SOFTSIGN_GRAD_OUT if saved == "a" else sd.emb_grad, act_scale=sd.scale,
                           gradmul_pre=b[f"{side}/{saved}/{m}"] if saved else None, live=lv)
                 self.dlin(self.cur, dz, b[f"in/{m}"] if lv is None else b[self.mk(side, f"in_live/{m}")], p + ".token_embed", BT, n2, n,
                           ldx=_align(n, 8), live=lv)
         self.close_segment("embed")
-        if self.used_wt:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
+        if self.used_wt and refresh:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
             tw = e._wt_table()
             K.prep_weights(tw["table"], tw["n"], tw["tiles"], plan=self.fwd)
             self.fwd.insert(0, self.fwd.pop())

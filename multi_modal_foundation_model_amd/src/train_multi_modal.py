@@ -24,7 +24,7 @@ from multi_modal.decoder_embeddings import DecoderEmbedding
 from multi_modal.encoder_embeddings import EncoderEmbedding
 from multi_modal.mm import MultiModal
 from multi_modal_foundation_model_amd.ddp import Accelerator
-from multi_modal_foundation_model_amd.optim import make_optimizer
+from multi_modal_foundation_model_amd.optim import freeze_parameters, make_optimizer
 from multi_modal_foundation_model_amd.synthetic import SyntheticLoader
 from trainer.make import make_multimodal_trainer
 from utils.config_utils import config_from_kwargs, update_config
@@ -52,6 +52,10 @@ def build_parser():
                     help="modalities the encoder gets tokenisers for")
     ap.add_argument("--modal_filter_output", type=str, nargs="+", default=list(AVAIL_MOD), choices=AVAIL_MOD,
                     help="modalities the decoder gets tokenisers and heads for")
+    # fine-tuning on a frozen trunk: fnmatch patterns over parameter names (`encoder.*`, `*_embeddings.*.embedder.*`, ...).  The named
+    # parameters get requires_grad = False before the optimiser is made; the engine then launches only the backward the others need
+    ap.add_argument("--freeze", type=str, nargs="*", default=None,
+                    help="fnmatch patterns of parameter names to freeze (overrides training.freeze of the trainer config)")
     return ap
 
 
@@ -106,6 +110,11 @@ def main(argv=None):
     print("(train) masking ratio: ", model.masker.ratio)
     print("(train) masking active: ", model.masker.force_active)
     model = accelerator.prepare(model)
+
+    # training.freeze is no key of the reference's YAML either: absent or empty freezes nothing
+    frozen = freeze_parameters(model, args.freeze if args.freeze is not None else config.training.get("freeze", None))
+    if frozen:
+        print(f"(train) frozen: {len(frozen)} parameter tensors ({frozen[0]} .. {frozen[-1]})")
 
     # optimizer.max_grad_norm is no key of the reference's YAML: absent or null builds the reference's optimiser (one launch per step),
     # a number turns on the fused clip (optim.py)

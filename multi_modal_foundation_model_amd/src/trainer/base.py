@@ -124,6 +124,7 @@ class MultiModalTrainer():
         # modality-index scalars (a pageable H2D copy each = a stream drain per call) and the [B, N] region array
         self._mod_index_cache = {}
         self._const_mask_cache = {}
+        self._backward_reported = False
 
     # ------------------------------------------------------------------ batch -> mod_dict (trainer/base.py:51-103)
     def _forward_model_outputs(self, batch, masking_mode, training_mode):
@@ -238,9 +239,19 @@ class MultiModalTrainer():
             self.lr_scheduler.step()
             self.optimizer.zero_grad()
             losses.append(loss.detach())
+            if not self._backward_reported:
+                self._report_backward()
         # one host sync per epoch instead of one per step; float64 sum in step order == sum of .item()s
         train_loss = float(sum(x.item() for x in torch.stack(losses).double().cpu())) if losses else 0.
         return {"train_loss": train_loss}
+
+    def _report_backward(self):
+        """One line after the first training step: what the backward launches under the model's freeze pattern (training.freeze / --freeze)."""
+        self._backward_reported = True
+        eng = getattr(self.model, "_engine", None)
+        plan = getattr(eng, "_last", None)
+        if plan is not None and plan.get("bwd") is not None and self._rank_world()[0] == 0:
+            print("(train) " + eng.backward_summary(plan["B"], plan["T"]))
 
     def eval_epoch(self):
         self.model.eval()
