@@ -346,6 +346,50 @@ int mmfm_stitch_bwd_live(int dtype, const void* dx, const void* dextra, const in
                          int B, int T, int L, int m, int H, int max_F,
                          void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- modality segments
+ * MMFM_MOD_SEGMENTS: the edges of the model over modalities of different length.  Upstream concatenates along the token axis
+ * (mm.py:97-138), every tokeniser looks up its own time stamps (encoder_embeddings.py:56-59), the key mask is the concatenation of the
+ * per-modality masks (mm.py:152-158) and the heads pick their rows with y[decoder_mod_mask == mod_idx] (decoder_embeddings.py:105-107).
+ * Slot j of a side's stitched sequence has its own length T_j, time stamps ts_j [B][T_j] and attention mask attn_j [B][T_j]; it starts
+ * at off_j = sum_{i<j} T_i and L = sum_j T_j.  The entry points above are the case T_j = T, ts_j = ts, attn_j = attn, off_j = j * T,
+ * and at that case these give the same bits.  At most MMFM_MAX_SEGMENTS slots; seg_T is a HOST array read during the call (the table
+ * travels to the kernels as launch arguments: no allocation, hipGraph-capturable).  Everything between the edges - attention, the
+ * row-owner linears, the MLP, the weight gradients, the masked loss (base pointer, mask_ld = L, T = T_j) - takes R = B * L rows as it is.
+ * The live-bin entry points (mmfm_live_bins, the _live stitches, mmfm_gather_live_rows) have no segment forms. */
+#define MMFM_MOD_SEGMENTS 1
+#define MMFM_MAX_SEGMENTS 8
+/* mmfm_mask_prep over segments: mask_src[j] has element (b,t) at mask_src[j][(b*seg_T[j]+t)*mask_stride[j]], attn[j] is int64
+ * [B][seg_T[j]] (mask_src and attn are host arrays of M device pointers).  Outputs as mmfm_mask_prep with M*T replaced by L:
+ * tokmask, keypad u8 [B][L], keep0, mod_id u8 [L] (mod_id = the slot j), count int64 [M] = channels[j] * sum(tokmask of slot j).
+ * Bit-exact. */
+int mmfm_mask_prep_seg(int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
+                       const int64_t* const* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad,
+                       uint8_t* keep0, uint8_t* mod_id, int64_t* count, mmfm_stream stream);
+/* mmfm_stitch_fwd / _bwd for the slot of T bins at offset off (off + T <= L):
+ *   emb[b, off+t] = mod_emb[mod_row] + pos_emb[ts[b][t]],   x[b, off+t] = keep0[off+t] * tok[b*T+t] + emb[...]
+ *   d_tok[b*T+t] = keep0[off+t] * dropout'(dx[b, off+t]);  d_mod_row (+)= sum_{b,t} (dx + dextra);  d_pos[ts[b][t]] (+)= dx + dextra
+ * tok / d_tok are [B*T][H], ts is the slot's own [B][T].  The NULL pos_emb / d_pos contract (MMFM_EMBED_OPTS), acc_mod / acc_pos, the
+ * dropout counter (the row b*T+t inside the modality, times H, plus the column) and the determinism (no atomics, fixed-order
+ * reductions; bf16 with H % 8 == 0: the one-hot product, or its column sum without a table) are those of mmfm_stitch_fwd / _bwd. */
+int mmfm_stitch_fwd_seg(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb,
+                        const int64_t* ts, const uint8_t* keep0, void* x, void* emb,
+                        int B, int T, int L, int off, int H, int max_F, mmfm_stream stream);
+int64_t mmfm_stitch_bwd_seg_workspace(int dtype, int B, int T, int L, int off, int H, int max_F);
+int mmfm_stitch_bwd_seg(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
+                        mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
+                        int B, int T, int L, int off, int H, int max_F,
+                        void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+/* mmfm_layernorm_fwd / _bwd de-stitching over segments: with B = R / L, the output row for input row r = (b, off_j + t) is
+ * B*off_j + b*seg_T[j] + t, so the final decoder_norm writes one contiguous [B*T_j][H] block per decoder modality, slot j's at row
+ * B*off_j; the backward reads dy the same way.  Workspace: mmfm_layernorm_bwd_workspace(R, H). */
+int mmfm_layernorm_fwd_seg(int dtype, const void* x, const float* gamma, const float* beta, void* y,
+                           float* mean, float* rstd, int64_t R, int H, float eps,
+                           int n_seg, const int32_t* seg_T, mmfm_stream stream);
+int mmfm_layernorm_bwd_seg(int dtype, const void* dy, const void* x, const float* mean, const float* rstd,
+                           const float* gamma, const void* dres, void* dx, float* dgamma, float* dbeta,
+                           int accumulate, int64_t R, int H, int n_seg, const int32_t* seg_T,
+                           void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- loader collate
  * BaseDataset._preprocess_ibl_data + get_binned_spikes_from_sparse (loader/base.py:304-450,
  * utils/dataset_utils.py:38-43), pad_to_right path: B trials given as concatenated CSR pieces

@@ -116,6 +116,7 @@ class RowGemmDesc(C.Structure):
 
 
 ROWGEMM_MAX_GROUPS = 8
+MAX_SEGMENTS = 8                 # MMFM_MAX_SEGMENTS
 
 
 class RowGemmGroupsDesc(C.Structure):
@@ -173,6 +174,14 @@ _PROTOS = {
     "mmfm_stitch_bwd_live": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mmfm_stitch_bwd_workspace": (C.c_int64, [_i, _i, _i, _i, _i, _i]),
     "mmfm_stitch_bwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    # modality segments (MMFM_MOD_SEGMENTS)
+    "mmfm_mask_prep_seg": (C.c_int, [_i, _i, C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "mmfm_stitch_fwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmfm_stitch_bwd_seg_workspace": (C.c_int64, [_i, _i, _i, _i, _i, _i, _i]),
+    "mmfm_stitch_bwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "mmfm_layernorm_fwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _i, C.POINTER(C.c_int32), _vp]),
+    "mmfm_layernorm_bwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, C.POINTER(C.c_int32), _vp, _i64, _vp]),
     "mmfm_masked_loss_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_masked_loss_fwd": (C.c_int, [_i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _i64, _vp]),
     "mmfm_masked_loss_kind_fwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _i64, _vp]),

@@ -19,16 +19,34 @@ __device__ __forceinline__ int64_t destitch_row(int64_t r, int L, int T, int64_t
     return (int64_t)(l / T) * (Btot * T) + b * T + (l % T);
 }
 
+// The de-stitch over modality segments (MMFM_MOD_SEGMENTS): slot j holds the T_j = off[j + 1] - off[j] bins from off[j]; the row of input
+// row r = (b, l) is B * off[j] + b * T_j + (l - off[j]).  The table travels as a kernel argument (at most MMFM_MAX_SEGMENTS slots):
+// nothing to allocate, capturable as it is.  The kernels below take it as a trailing argument pack, empty for every launch that has no
+// segments: those instantiations keep their argument list and their code.
+struct DsSeg {
+    int n;
+    int off[MMFM_MAX_SEGMENTS + 1];
+};
+__device__ __forceinline__ int64_t destitch_row(int64_t r, int L, int, int64_t Btot, const DsSeg& s) {
+    const int64_t b = r / L;
+    const int l = (int)(r % L);
+    int o = 0, T = s.off[1];
+#pragma unroll
+    for (int j = 1; j < MMFM_MAX_SEGMENTS; ++j)
+        if (j < s.n && l >= s.off[j]) { o = s.off[j]; T = s.off[j + 1] - s.off[j]; }
+    return Btot * o + b * T + (l - o);
+}
+
 // NV = 256-column chunks per lane (H <= 256*NV); UNR = rows a wave keeps in flight per iteration.  Measured at [204800, 256]
 // bf16 (scripts/ln_bench.py): forward 41 us (5.1 TB/s) at UNR = 1 or 2, 56 us at 4, 63 us at 8 (registers cost more
 // waves than the extra rows in flight buy); backward 135 / 113 / 103 us at UNR = 1 / 2 / 4.  The kernels are
 // latency-bound at one row per wave (16 waves/CU x 1.5 KB in flight = 3 TB/s by Little's law, measured 137 us for
 // the [204800, 256] bf16 backward = 3.07 TB/s): all loads of UNR consecutive rows are issued before the first use.
-template <typename T, int NV, int UNR, bool SN = false>
+template <typename T, int NV, int UNR, bool SN = false, typename... SEG>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, T* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int64_t R, int H,
-                                                     float eps, int dsL, int dsT) {
+                                                     float eps, int dsL, int dsT, SEG... seg) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t Btot = dsT > 0 ? R / dsL : 0;
     float4 g[NV], bt[NV];
@@ -78,7 +96,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                 rs = rsqrtf(wave_sum(q) * invH + eps);
                 if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
             }
-            const int64_t orow = destitch_row(row, dsL, dsT, Btot);
+            const int64_t orow = destitch_row(row, dsL, dsT, Btot, seg...);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = i * 256 + lane * 4;
@@ -97,11 +115,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 
 // dx = dres + rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat));  per-block partial dgamma/dbeta
 // SN: dx = dres + rinv * (g*dy - xhat * sum(g*dy*xhat)), the sum dropped for clamped rows;  per-block partial dg = sum xhat . dy
-template <typename T, int NV, int UNR, bool SN = false>
+template <typename T, int NV, int UNR, bool SN = false, typename... SEG>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, const T* dres, T* dx,
-                                                     float* __restrict__ part, int64_t R, int H, int dsL, int dsT) {
+                                                     float* __restrict__ part, int64_t R, int H, int dsL, int dsT, SEG... seg) {
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4][2][H]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t Btot = dsT > 0 ? R / dsL : 0;
@@ -123,7 +141,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
             const bool ok = row < R;
             mu[u] = (ok && !SN) ? mean[row] : 0.f;
             rs[u] = ok ? rstd[row] : 0.f;
-            const int64_t yrow = ok ? destitch_row(row, dsL, dsT, Btot) : 0;
+            const int64_t yrow = ok ? destitch_row(row, dsL, dsT, Btot, seg...) : 0;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = i * 256 + lane * 4;
@@ -237,51 +255,97 @@ int ln_bwd_blocks(int64_t R) {
 
 extern "C" int mmfm_reduce_slabs(float*, const float*, int64_t, int, int64_t, int, mmfm_stream);
 
-extern "C" int mmfm_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y,
-                                  float* mean, float* rstd, int64_t R, int H, float eps, int dsL, int dsT,
-                                  mmfm_stream stream) {
-    MMFM_REQUIRE(x && gamma && beta && y && mean && rstd, "mmfm_layernorm_fwd: null pointer");
-    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "mmfm_layernorm_fwd: H=%d must be a multiple of 4, <= 1024", H);
-    MMFM_REQUIRE(dsT == 0 || (dsL > 0 && dsL % dsT == 0 && R % dsL == 0), "mmfm_layernorm_fwd: bad destitch L=%d T=%d", dsL, dsT);
+// the two LayerNorm launches; seg: nothing (mmfm_layernorm_*) or the DsSeg of mmfm_layernorm_*_seg (then dsL = L, dsT = 1).  The callers checked those
+template <typename... SEG>
+static int ln_fwd_impl(const char* what, int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                       int64_t R, int H, float eps, int dsL, int dsT, mmfm_stream stream, SEG... seg) {
+    MMFM_REQUIRE(x && gamma && beta && y && mean && rstd, "%s: null pointer", what);
+    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "%s: H=%d must be a multiple of 4, <= 1024", what, H);
     dim3 grid(ln_blocks(R)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "mmfm_layernorm_fwd: bad dtype %d", dtype);
-#define LN_FWD(TT, NVV, UU) hipLaunchKernelGGL((ln_fwd_kernel<TT, NVV, UU>), grid, block, 0, st, (const TT*)x, gamma, beta, (TT*)y, mean, rstd, R, H, eps, dsL, dsT)
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "%s: bad dtype %d", what, dtype);
+#define LN_FWD(TT, NVV, UU) hipLaunchKernelGGL((ln_fwd_kernel<TT, NVV, UU, false, SEG...>), grid, block, 0, st, (const TT*)x, gamma, beta, (TT*)y, mean, rstd, R, H, eps, dsL, dsT, seg...)
     static const int fwd_unr = [] { const char* e = getenv("MMFM_LN_FWD_UNR"); return e ? atoi(e) : 2; }();
 #define LN_FWD_T(TT) if (H <= 256) { if (fwd_unr == 8) LN_FWD(TT, 1, 8); else if (fwd_unr == 2) LN_FWD(TT, 1, 2); else if (fwd_unr == 1) LN_FWD(TT, 1, 1); else LN_FWD(TT, 1, 4); } else if (H <= 512) LN_FWD(TT, 2, 2); else LN_FWD(TT, 4, 1)
     if (dtype == MMFM_F32) { LN_FWD_T(float); } else { LN_FWD_T(uint16_t); }
 #undef LN_FWD_T
 #undef LN_FWD
-    MMFM_LAUNCH_CHECK("mmfm_layernorm_fwd");
+    MMFM_LAUNCH_CHECK(what);
     return 0;
+}
+
+extern "C" int mmfm_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y,
+                                  float* mean, float* rstd, int64_t R, int H, float eps, int dsL, int dsT,
+                                  mmfm_stream stream) {
+    MMFM_REQUIRE(dsT == 0 || (dsL > 0 && dsL % dsT == 0 && R % dsL == 0), "mmfm_layernorm_fwd: bad destitch L=%d T=%d", dsL, dsT);
+    return ln_fwd_impl("mmfm_layernorm_fwd", dtype, x, gamma, beta, y, mean, rstd, R, H, eps, dsL, dsT, stream);
 }
 
 extern "C" int64_t mmfm_layernorm_bwd_workspace(int64_t R, int H) { return (int64_t)ln_bwd_blocks(R) * 2 * H * sizeof(float); }
 
-extern "C" int mmfm_layernorm_bwd(int dtype, const void* dy, const void* x, const float* mean, const float* rstd,
-                                  const float* gamma, const void* dres, void* dx, float* dgamma, float* dbeta,
-                                  int accumulate, int64_t R, int H, int dsL, int dsT, void* workspace,
-                                  int64_t workspace_bytes, mmfm_stream stream) {
-    MMFM_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta, "mmfm_layernorm_bwd: null pointer");
-    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "mmfm_layernorm_bwd: H=%d must be a multiple of 4, <= 1024", H);
-    MMFM_REQUIRE(dsT == 0 || (dsL > 0 && dsL % dsT == 0 && R % dsL == 0), "mmfm_layernorm_bwd: bad destitch");
-    MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_layernorm_bwd_workspace(R, H), "mmfm_layernorm_bwd: workspace too small");
+template <typename... SEG>
+static int ln_bwd_impl(const char* what, int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                       const void* dres, void* dx, float* dgamma, float* dbeta, int accumulate, int64_t R, int H, int dsL, int dsT, void* workspace,
+                       int64_t workspace_bytes, mmfm_stream stream, SEG... seg) {
+    MMFM_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta, "%s: null pointer", what);
+    MMFM_REQUIRE(R > 0 && H > 0 && H % 4 == 0 && H <= 1024, "%s: H=%d must be a multiple of 4, <= 1024", what, H);
+    MMFM_REQUIRE(workspace && workspace_bytes >= mmfm_layernorm_bwd_workspace(R, H), "%s: workspace too small", what);
     const int nblk = ln_bwd_blocks(R);
     const size_t lds = (size_t)4 * 2 * H * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "mmfm_layernorm_bwd: bad dtype %d", dtype);
-#define LN_BWD(TT, NVV, UU) hipLaunchKernelGGL((ln_bwd_kernel<TT, NVV, UU>), dim3(nblk), dim3(256), lds, st, (const TT*)dy, (const TT*)x, mean, rstd, gamma, (const TT*)dres, (TT*)dx, (float*)workspace, R, H, dsL, dsT)
+    if (dtype != MMFM_F32 && dtype != MMFM_BF16) return mmfm_set_error(-1, "%s: bad dtype %d", what, dtype);
+#define LN_BWD(TT, NVV, UU) hipLaunchKernelGGL((ln_bwd_kernel<TT, NVV, UU, false, SEG...>), dim3(nblk), dim3(256), lds, st, (const TT*)dy, (const TT*)x, mean, rstd, gamma, (const TT*)dres, (TT*)dx, (float*)workspace, R, H, dsL, dsT, seg...)
     static const int bwd_unr = [] { const char* e = getenv("MMFM_LN_BWD_UNR"); return e ? atoi(e) : 4; }();
 #define LN_BWD_T(TT) if (H <= 256) { if (bwd_unr == 2) LN_BWD(TT, 1, 2); else if (bwd_unr == 1) LN_BWD(TT, 1, 1); else LN_BWD(TT, 1, 4); } else if (H <= 512) LN_BWD(TT, 2, 2); else LN_BWD(TT, 4, 1)
     if (dtype == MMFM_F32) { LN_BWD_T(float); } else { LN_BWD_T(uint16_t); }
 #undef LN_BWD_T
 #undef LN_BWD
-    MMFM_LAUNCH_CHECK("mmfm_layernorm_bwd");
+    MMFM_LAUNCH_CHECK(what);
     // per-block partials [nblk][2][H] -> dgamma, dbeta (two tall-skinny slab reductions)
     if (dbeta == dgamma + H)     // adjacent in the flat gradient buffer (the engine's layout): one reduction over [2H]
         return mmfm_reduce_slabs(dgamma, (const float*)workspace, 2 * (int64_t)H, nblk, 2 * (int64_t)H, accumulate, stream);
     if (int rc = mmfm_reduce_slabs(dgamma, (const float*)workspace, H, nblk, 2 * (int64_t)H, accumulate, stream)) return rc;
     return mmfm_reduce_slabs(dbeta, (const float*)workspace + H, H, nblk, 2 * (int64_t)H, accumulate, stream);
+}
+
+extern "C" int mmfm_layernorm_bwd(int dtype, const void* dy, const void* x, const float* mean, const float* rstd,
+                                  const float* gamma, const void* dres, void* dx, float* dgamma, float* dbeta,
+                                  int accumulate, int64_t R, int H, int dsL, int dsT, void* workspace,
+                                  int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(dsT == 0 || (dsL > 0 && dsL % dsT == 0 && R % dsL == 0), "mmfm_layernorm_bwd: bad destitch");
+    return ln_bwd_impl("mmfm_layernorm_bwd", dtype, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, accumulate, R, H, dsL, dsT, workspace,
+                       workspace_bytes, stream);
+}
+
+// ---- de-stitch over modality segments (MMFM_MOD_SEGMENTS): slot j of the stitched sequence holds seg_T[j] bins
+static bool ds_seg(DsSeg& ds, int& L, int64_t R, int n_seg, const int32_t* seg_T) {
+    if (!seg_T || n_seg < 1 || n_seg > MMFM_MAX_SEGMENTS) return false;
+    ds.n = n_seg;
+    ds.off[0] = 0;
+    for (int j = 0; j < MMFM_MAX_SEGMENTS; ++j) {
+        if (j < n_seg && seg_T[j] < 1) return false;
+        ds.off[j + 1] = ds.off[j] + (j < n_seg ? seg_T[j] : 0);
+    }
+    L = ds.off[n_seg];
+    return R % L == 0;
+}
+
+extern "C" int mmfm_layernorm_fwd_seg(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                      int64_t R, int H, float eps, int n_seg, const int32_t* seg_T, mmfm_stream stream) {
+    DsSeg ds;
+    int L;
+    MMFM_REQUIRE(ds_seg(ds, L, R, n_seg, seg_T), "mmfm_layernorm_fwd_seg: bad segments (1..%d of them, lengths > 0, R a multiple of their sum)", MMFM_MAX_SEGMENTS);
+    return ln_fwd_impl("mmfm_layernorm_fwd_seg", dtype, x, gamma, beta, y, mean, rstd, R, H, eps, L, 1, stream, ds);
+}
+
+extern "C" int mmfm_layernorm_bwd_seg(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                      const void* dres, void* dx, float* dgamma, float* dbeta, int accumulate, int64_t R, int H, int n_seg,
+                                      const int32_t* seg_T, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    DsSeg ds;
+    int L;
+    MMFM_REQUIRE(ds_seg(ds, L, R, n_seg, seg_T), "mmfm_layernorm_bwd_seg: bad segments (1..%d of them, lengths > 0, R a multiple of their sum)", MMFM_MAX_SEGMENTS);
+    return ln_bwd_impl("mmfm_layernorm_bwd_seg", dtype, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, accumulate, R, H, L, 1, workspace,
+                       workspace_bytes, stream, ds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ScaleNorm

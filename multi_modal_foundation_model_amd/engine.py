@@ -661,13 +661,14 @@ class Engine:
         Builds nothing and launches nothing: the plan must exist (one training forward ran at this shape)."""
         plan = self.plans[(B, T, True, True)]
         c = self.cfg
-        H, Lq = c.hidden, len(c.side_mods("encoder")) * T
+        Tm = (lambda m: T[m]) if isinstance(T, tuple) else (lambda m: T)          # a segmented plan: per-modality lengths
+        H, Lq = c.hidden, sum(Tm(m) for m, _, _ in c.side_mods("encoder"))
         out = []
         for key, site in self._sites.items():
             side = "encoder" if key.startswith("enc") else "decoder"          # `encoder/embdrop/0`, `enc0/sa/p`, `dec1/mlpdrop`
             sc = c.side(side)
             if "/embdrop/" in key:
-                d = dict(p=sc.embed_dropout, kind="flat", shape=(B * T, H))
+                d = dict(p=sc.embed_dropout, kind="flat", shape=(B * Tm(int(key.rsplit("/", 1)[1])), H))
             elif key.endswith("/mlpdrop"):
                 d = dict(p=sc.dropout, kind="rowdrop" if self.fused_mlp(side, plan["fused"]) else "flat", shape=(B * Lq, H))
             elif key.endswith("/o"):
@@ -699,18 +700,43 @@ class Engine:
 
     # ------------------------------------------------------------------ data in
     def load_inputs(self, B, T, inputs, targets, masks, ts, attn):
-        """Copy one batch into the static input buffers (device tensors or host tensors)."""
+        """Copy one batch into the static input buffers (device tensors or host tensors).  T a tuple (a segmented plan): modality m
+        has T[m] bins and its own stamps ts[m] and attention mask attn[m]."""
+        seg = isinstance(T, tuple)
         dec = {m for m, _, _ in self.cfg.side_mods("decoder")}
         for m in sorted(dec | {m for m, _, _ in self.cfg.side_mods("encoder")}):      # (a modality no side has is not staged)
-            self.b[f"in/{m}"].view(B, T, -1)[..., :inputs[m].shape[-1]].copy_(inputs[m], non_blocking=True)
+            Tm = T[m] if seg else T
+            self.b[f"in/{m}"].view(B, Tm, -1)[..., :inputs[m].shape[-1]].copy_(inputs[m], non_blocking=True)
             if m in dec:
-                self.b[f"tgt/{m}"].view(B, T, -1).copy_(targets[m], non_blocking=True)
+                self.b[f"tgt/{m}"].view(B, Tm, -1).copy_(targets[m], non_blocking=True)
             self.b[f"mask/{m}"].copy_(masks[m], non_blocking=True)
-        self.b["ts"].copy_(ts, non_blocking=True)
-        self.b["attn"].copy_(attn, non_blocking=True)
+            if seg:
+                self.b[f"ts/{m}"].copy_(ts[m], non_blocking=True)
+                self.b[f"attn/{m}"].copy_(attn[m], non_blocking=True)
+        if not seg:
+            self.b["ts"].copy_(ts, non_blocking=True)
+            self.b["attn"].copy_(attn, non_blocking=True)
+
+    def batch_key(self, T, ts, attn):
+        """What a batch's plan is keyed by besides B, with its stamps and attention masks in the matching form: (T, ts, attn) with T an
+        int and one tensor each - every modality has T bins and they share stamps and mask: the plan it always was - or T the tuple of
+        per-modality lengths in cfg.mods order and one tensor per modality: a segmented plan.  Sharing is by identity:
+        a caller that holds equal copies (MultiModal.forward compares them) passes the same tensor."""
+        n = len(self.cfg.mods)
+        per_mod = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        Ts = tuple(int(t) for t in T) if isinstance(T, (list, tuple)) else (int(T),) * n
+        tss, attns = per_mod(ts), per_mod(attn)
+        if not (len(Ts) == len(tss) == len(attns) == n):
+            raise ValueError(f"engine: {n} modalities, {len(Ts)} lengths, {len(tss)} time-stamp and {len(attns)} attention-mask tensors")
+        if len(set(Ts)) == 1 and all(t is tss[0] for t in tss) and all(a is attns[0] for a in attns):
+            return Ts[0], tss[0], attns[0]
+        return Ts, tss, attns
 
     # ------------------------------------------------------------------ run
     def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None):
+        """T: the number of bins, or a tuple of per-modality numbers in cfg.mods order; ts / attn: one tensor [B, T], or one per modality."""
+        T, ts, attn = self.batch_key(T, ts, attn)
+        seg = isinstance(T, tuple)
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
         self._pattern = self.freeze_pattern() if want_grad else None          # read once per forward
         plan = self._plan(B, T, training, want_grad, self._pattern)
@@ -730,7 +756,7 @@ class Engine:
         dec, count = self.cfg.side_mods("decoder"), self.b[plan["count"]]
         out = dict(mod_loss=[self.b["loss_sum"][j].clone() for j in range(len(dec))],
                    mod_n=[count[j].clone() for j in range(len(dec))],
-                   preds=[self.b[f"pred/{m}"].view(B, T, -1) for m, _, _ in dec])
+                   preds=[self.b[f"pred/{m}"].view(B, T[m] if seg else T, -1) for m, _, _ in dec])
         if want_grad:
             out["loss"] = _StepFn.apply(anchor, self, self._token)
         else:

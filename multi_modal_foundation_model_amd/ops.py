@@ -230,6 +230,45 @@ def stitch_bwd(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, ac
                                           ws.numel() * ws.element_size()))
 
 
+# ---- modality segments (MMFM_MOD_SEGMENTS): slot j of the stitched sequence has Ts[j] bins, its own stamps and attention mask
+def _seg_T(Ts):
+    return (C.c_int32 * len(Ts))(*[int(t) for t in Ts])
+
+
+def mask_prep_seg(B, Ts, masks, strides, attns, channels, tokmask, keypad, keep0, mod_id, count, plan=None):
+    M = len(masks)
+    if not (len(Ts) == len(attns) == len(strides) == len(channels) == M):
+        raise ValueError("mask_prep_seg: one length, mask, stride, attention mask and channel count per slot")
+    seg = _seg_T(Ts)
+    src = (C.c_void_p * M)(*[m.data_ptr() for m in masks])
+    at = (C.c_void_p * M)(*[a.data_ptr() for a in attns])
+    st = (C.c_int64 * M)(*strides)
+    ch = (C.c_int64 * M)(*channels)
+    _emit(plan, L.lib().mmfm_mask_prep_seg, (B, M, seg, src, st, at, ch, P(tokmask), P(keypad), P(keep0), P(mod_id), P(count)),
+          keep=(seg, src, st, at, ch))
+
+
+def stitch_fwd_seg(tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, off, H, max_F, plan=None):
+    _emit(plan, L.lib().mmfm_stitch_fwd_seg, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(x), P(emb), B, T, Lseq, off, H, max_F))
+
+
+def stitch_bwd_seg(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, off, H, max_F, ws, plan=None):
+    _emit(plan, L.lib().mmfm_stitch_bwd_seg, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), drop if drop is not None else L.NO_DROP,
+                                              P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, off, H, max_F, P(ws),
+                                              ws.numel() * ws.element_size()))
+
+
+def layernorm_fwd_seg(x, gamma, beta, y, mean, rstd, R, H, Ts, eps=1e-5, plan=None):
+    seg = _seg_T(Ts)
+    _emit(plan, L.lib().mmfm_layernorm_fwd_seg, (dt(x), P(x), P(gamma), P(beta), P(y), P(mean), P(rstd), R, H, eps, len(Ts), seg), keep=(seg,))
+
+
+def layernorm_bwd_seg(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R, H, ws, Ts, accumulate=False, plan=None):
+    seg = _seg_T(Ts)
+    _emit(plan, L.lib().mmfm_layernorm_bwd_seg, (dt(x), P(dy), P(x), P(mean), P(rstd), P(gamma), P(dres), P(dx), P(dgamma), P(dbeta),
+                                                 int(accumulate), R, H, len(Ts), seg, P(ws), ws.numel() * ws.element_size()), keep=(seg,))
+
+
 def masked_loss_fwd(kind, pred, target, rowmask, mask_ld, T, R, N, loss_sum, ws, plan=None):
     _emit(plan, L.lib().mmfm_masked_loss_fwd, (dt(pred), kind, P(pred), P(target), P(rowmask), mask_ld, T, R, N, P(loss_sum), P(ws),
                                                ws.numel() * ws.element_size()))

@@ -91,10 +91,33 @@ class PlanBuilder:
         # modalities: both sides have as many (cross-attention pairs the two sequences position for position, mm.py:152-158, 210)
         self.mods_of = {side: c.side_mods(side) for side in ("encoder", "decoder")}
         self.H, self.M = c.hidden, len(self.mods_of["encoder"])
-        if len(self.mods_of["decoder"]) != self.M:
+        # T: one length for every modality, or a tuple of per-modality lengths in cfg.mods order - a segmented plan:
+        # slot j of a side's stitched sequence starts at off[side][j], each modality has its own stamps and attention mask
+        # (ts/{m}, attn/{m}) and the edges run the mmfm_*_seg entry points.  Tm[m] / BTm[m]: bins / tokeniser rows of modality m
+        self.seg = isinstance(T, tuple)
+        if self.seg and (len(T) != len(c.mods) or any(int(t) < 1 for t in T)):
+            raise ValueError(f"engine: per-modality lengths {T}: one positive length per modality of {[m for m, _ in c.mods]}")
+        self.Tm = {m: int(T[m]) if self.seg else T for m in range(len(c.mods))}
+        self.BTm = {m: B * t for m, t in self.Tm.items()}
+        self.off = {}
+        for side, mods in self.mods_of.items():
+            self.off[side] = [0]
+            for m, _, _ in mods:
+                self.off[side].append(self.off[side][-1] + self.Tm[m])
+        if self.seg:
+            if len(self.mods_of["decoder"]) > L.MAX_SEGMENTS or self.M > L.MAX_SEGMENTS:
+                raise NotImplementedError(f"engine: a segmented plan holds at most {L.MAX_SEGMENTS} modalities per side")
+            if self.off["encoder"][-1] != self.off["decoder"][-1]:
+                raise RuntimeError(f"engine: the encoder's sequence has {self.off['encoder'][-1]} tokens, the decoder's "
+                                   f"{self.off['decoder'][-1]}: cross-attention needs the two lengths equal")
+        elif len(self.mods_of["decoder"]) != self.M:
             raise RuntimeError(f"engine: the encoder's sequence has {self.M * T} tokens ({self.M} modalities x {T}), the decoder's "
                                f"{len(self.mods_of['decoder']) * T}: cross-attention needs the two lengths equal")
-        self.Lq, self.R, self.BT = self.M * T, B * self.M * T, B * T
+        self.Lq = self.off["encoder"][-1]
+        self.R = B * self.Lq
+        # BT: the rows of a tokeniser (uniform) / of the longest one (segmented: what sizes a workspace every modality uses)
+        self.BT = max(self.BTm[m] for mods in self.mods_of.values() for m, _, _ in mods) if self.seg else B * T
+        self.Md = len(self.mods_of["decoder"])         # the decoder's modalities: M, unless a segmented plan's sides split their bins differently
         # the mask products (tokmask / keypad / keep0 / mod_id / count) come from the side's own modalities' masks: one buffer set while
         # the two sides have the same modalities, else the decoder's own under "dec/"
         self.split_masks = [m for m, _, _ in self.mods_of["encoder"]] != [m for m, _, _ in self.mods_of["decoder"]]
@@ -104,7 +127,8 @@ class PlanBuilder:
         self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
         # the tokeniser chains on the live rows only (bf16; the fp32 parity path keeps the full row space).  lv: (side, slot) -> the
         # slot's mmfm_live_rows, filled by forward()
-        self.live = self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
+        # (a segmented plan runs without live-row compaction: the live-bin entry points have no segment forms)
+        self.live = not self.seg and self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
         self.lv = {}
         self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
         # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
@@ -221,20 +245,25 @@ class PlanBuilder:
         for m in self.staged:
             n = c.mods[m][1]
             # input rows padded to 16 B (zeros): the tokeniser's weight-gradient GEMM streams them by LDS-DMA (csrc/gemm_dw.hip)
-            buf(f"in/{m}", (BT, _align(n, 8)), zero=True); buf(f"mask/{m}", (B, T), i64)
+            buf(f"in/{m}", (self.BTm[m], _align(n, 8)), zero=True); buf(f"mask/{m}", (B, self.Tm[m]), i64)
             if m in dec:            # targets: decoder modalities only
-                buf(f"tgt/{m}", (BT, n), f32)
-        buf("ts", (B, T), i64); buf("attn", (B, T), i64); buf("loss_sum", (M,), f32)
+                buf(f"tgt/{m}", (self.BTm[m], n), f32)
+            if self.seg:            # the modality's own time stamps and attention mask
+                buf(f"ts/{m}", (B, self.Tm[m]), i64); buf(f"attn/{m}", (B, self.Tm[m]), i64)
+        if not self.seg:
+            buf("ts", (B, T), i64); buf("attn", (B, T), i64)
+        Mmax = max(M, self.Md)
+        buf("loss_sum", (Mmax,), f32)
         for pre in ("", "dec/") if self.split_masks else ("",):
             buf(pre + "tokmask", (B, Lq), u8); buf(pre + "keypad", (B, Lq), u8)
-            buf(pre + "keep0", (Lq,), u8); buf(pre + "mod_id", (Lq,), u8); buf(pre + "count", (M,), i64)
+            buf(pre + "keep0", (Lq,), u8); buf(pre + "mod_id", (Lq,), u8); buf(pre + "count", (Mmax,), i64)
         max_slab = 1
-        for n in chans:
+        for m, n in zip(self.staged, chans):
             # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
             # streaming kernel and with it another split count)
             for mult in sorted({sd.mult for sd in self.sides.values()}):
                 for (mm, nn, ldn) in ((n * mult, n, _align(n, 8)), (H, n * mult, None), (n, H, None)):
-                    max_slab = max(max_slab, e._dw_split(mm, nn, BT, ldn=ldn, sw=sw)[0] * _align(mm * nn + mm))
+                    max_slab = max(max_slab, e._dw_split(mm, nn, self.BTm[m], ldn=ldn, sw=sw)[0] * _align(mm * nn + mm))
         for l in e.linears:
             max_slab = max(max_slab, e._dw_split(l.N, l.K, R, sw=sw)[0] * _align(l.N * l.K + l.N))
         self.slab = buf("ws/slab", (max_slab,), f32)
@@ -250,7 +279,12 @@ class PlanBuilder:
         maxN = max([3 * H, self.Imax] + [n * self.mult_max for n in chans])
         buf("ws/col", (max(1, L.lib().mmfm_colsum_workspace(R, maxN) // 4),), f32)
         buf("ws/ln", (max(1, L.lib().mmfm_layernorm_bwd_workspace(R, H) // 4),), f32)
-        buf("ws/stitch", (max(1, max(L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, sd.max_F) for sd in self.sides.values()) // 4),), f32)
+        if self.seg:
+            need = max(L.lib().mmfm_stitch_bwd_seg_workspace(self.code, B, self.Tm[m], Lq, self.off[side][slot], H, self.sides[side].max_F)
+                       for side, mods in self.mods_of.items() for slot, (m, _, _) in enumerate(mods))
+        else:
+            need = max(L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, sd.max_F) for sd in self.sides.values())
+        buf("ws/stitch", (max(1, need // 4),), f32)
         buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
         # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
         # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
@@ -421,6 +455,11 @@ class PlanBuilder:
         if e.is_sn(name):
             K.scalenorm_fwd(X, e.Pf(name + ".scale"), Y, self.buf(tag + "/rstd", (R,), f32), R, H, plan=plan)
             return
+        seg_T = kw.pop("seg_T", None)
+        if seg_T is not None:
+            K.layernorm_fwd_seg(X, e.Pf(name + ".weight"), e.Pf(name + ".bias"), Y, self.buf(tag + "/mean", (R,), f32),
+                                self.buf(tag + "/rstd", (R,), f32), R, H, seg_T, plan=plan)
+            return
         K.layernorm_fwd(X, e.Pf(name + ".weight"), e.Pf(name + ".bias"), Y, self.buf(tag + "/mean", (R,), f32),
                         self.buf(tag + "/rstd", (R,), f32), R, H, plan=plan, **kw)
 
@@ -428,6 +467,11 @@ class PlanBuilder:
         e, b, R, H = self.e, self.b, self.R, self.H
         if e.is_sn(name):       # (ws/ln, sized for the LayerNorm backward, covers the ScaleNorm's per-block partials)
             K.scalenorm_bwd(dY, X, b[tag + "/rstd"], e.Pf(name + ".scale"), dres, dX, e.Gv(name + ".scale"), R, H, b["ws/ln"], plan=plan)
+            return
+        seg_T = kw.pop("seg_T", None)
+        if seg_T is not None:
+            K.layernorm_bwd_seg(dY, X, b[tag + "/mean"], b[tag + "/rstd"], e.Pf(name + ".weight"), dres, dX,
+                                e.Gv(name + ".weight"), e.Gv(name + ".bias"), R, H, b["ws/ln"], seg_T, plan=plan)
             return
         K.layernorm_bwd(dY, X, b[tag + "/mean"], b[tag + "/rstd"], e.Pf(name + ".weight"), dres, dX,
                         e.Gv(name + ".weight"), e.Gv(name + ".bias"), R, H, b["ws/ln"], plan=plan, **kw)
@@ -525,8 +569,13 @@ class PlanBuilder:
         B, T, H, R, BT, Lq, M = self.B, self.T, self.H, self.R, self.BT, self.Lq, self.M
         mk = self.mk
         for side in ("encoder", "decoder") if self.split_masks else ("encoder",):       # mm.py:147-149 / 169-171: each side's own masks
-            K.mask_prep(B, T, [b[f"mask/{m}"] for m, _, _ in self.mods_of[side]], [1] * M, b["attn"], [n for _, _, n in self.mods_of[side]],
-                        b[mk(side, "tokmask")], b[mk(side, "keypad")], b[mk(side, "keep0")], b[mk(side, "mod_id")], b[mk(side, "count")], plan=fwd)
+            mods = self.mods_of[side]
+            outs = [b[mk(side, k)] for k in ("tokmask", "keypad", "keep0", "mod_id", "count")]
+            if self.seg:
+                K.mask_prep_seg(B, [self.Tm[m] for m, _, _ in mods], [b[f"mask/{m}"] for m, _, _ in mods], [1] * len(mods),
+                                [b[f"attn/{m}"] for m, _, _ in mods], [n for _, _, n in mods], *outs, plan=fwd)
+            else:
+                K.mask_prep(B, T, [b[f"mask/{m}"] for m, _, _ in mods], [1] * M, b["attn"], [n for _, _, n in mods], *outs, plan=fwd)
             if self.live:
                 # the live-bin records of the side's modality slots, from its keep0 (device side: nothing is read back)
                 rec = buf(mk(side, "live"), (M, L.live_rec_ints(T)), torch.int32)
@@ -539,6 +588,7 @@ class PlanBuilder:
             for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
+                BT, off = self.BTm[m], self.off[side][slot]
                 a = buf(f"{side}/a/{m}", (BT, n2))
                 # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
                 # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
@@ -555,11 +605,14 @@ class PlanBuilder:
                         gathered.add(mk(side, f"in_live/{m}"))
                         K.gather_live_rows(b[f"in/{m}"], xin, B, T, _align(n, 8) * self.es, rec, plan=fwd)
                 self.lin(fwd, xin, p + ".token_embed", a, BT, n2, n, ldx=_align(n, 8), pre_out=z, act=sd.emb_fwd, act_scale=sd.scale, live=lv)
-                self.lin(fwd, a, p + ".projection", tok_tmp, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), live=lv)
+                tok = self.rows(tok_tmp, BT, H)
+                self.lin(fwd, a, p + ".projection", tok, BT, H, n2, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), live=lv)
                 # row mod_to_indx[mod] of the table this tokeniser reads: its own, or the encoder's where the two share it
                 mod_row = e.Pf(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m]
                 pos = e.Pf(p + ".pos_embed.weight") if sd.pos else None            # embedder.pos: false -> emb = the modality row
-                if lv is not None:
+                if self.seg:
+                    K.stitch_fwd_seg(tok, mod_row, pos, b[f"ts/{m}"], b[mk(side, "keep0")], xs, es_, B, self.Tm[m], Lq, off, H, sd.max_F, plan=fwd)
+                elif lv is not None:
                     K.stitch_fwd_live(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], lv._keep, xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
                 else:
                     K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
@@ -599,14 +652,26 @@ class PlanBuilder:
             Y = self.mlp_block(fwd, Yb, p, tag)
         self.dec_last = Y
         ydec = buf("ydec", (R, H))                         # de-stitched: [M][B*T][H]
-        self.ln_f(fwd, Y, "decoder_norm", ydec, "decnorm", ds_L=Lq, ds_T=T)
+        self.ln_f(fwd, Y, "decoder_norm", ydec, "decnorm", **self.destitch())
         tokmask = b[mk("decoder", "tokmask")]
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
+            BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             pred = buf(f"pred/{m}", (BT, n))
-            self.lin(fwd, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
-            self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], tokmask[:, j * T:], Lq, T, BT, n,
+            self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n,
                       b["loss_sum"][j:j + 1], b["ws/loss"])
-        K.loss_finalize(b["loss_sum"], b[mk("decoder", "count")], M, b["loss"], b["inv_n"], plan=fwd)
+        K.loss_finalize(b["loss_sum"], b[mk("decoder", "count")], self.Md, b["loss"], b["inv_n"], plan=fwd)
+
+    def destitch(self):
+        """What tells decoder_norm's launches to write / read the per-modality blocks of ydec: ds_L / ds_T, or the decoder's segments."""
+        if self.seg:
+            return dict(seg_T=[self.Tm[m] for m, _, _ in self.mods_of["decoder"]])
+        return dict(ds_L=self.Lq, ds_T=self.T)
+
+    def ydec_rows(self, j):
+        """The rows of the de-stitched ydec / d/ydec that hold decoder slot j: [B * off_j, B * off_{j+1})."""
+        off = self.off["decoder"]
+        return self.B * off[j], self.B * off[j + 1]
 
     def ctx_norm_kind(self):
         """1 / 2: every decoder layer's context_norm is a LayerNorm / a ScaleNorm (the grouped launches norm once for all of them)."""
@@ -793,14 +858,14 @@ class PlanBuilder:
         # decoder_norm's backward reads d/ydec of every modality: it runs for the stream's sake or for its own parameters'
         norm = self.keep("decoder_norm", nd.dec_top or self.trainable(self.norm_names("decoder_norm")), self.norm_names("decoder_norm"))
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
+            BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             dpred = buf(f"d/pred/{m}", (BT, n))
             if norm or self.tl(f"decoder_embeddings.{mod}.out"):
-                self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, j * T:],
-                          Lq, T, BT, n, b["gout"], b["inv_n"], dpred)
-            self.dlin(self.cur, dpred, ydec[j * BT:(j + 1) * BT], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[j * BT:(j + 1) * BT],
-                      need_dx=norm)
+                self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:],
+                          Lq, self.Tm[m], BT, n, b["gout"], b["inv_n"], dpred)
+            self.dlin(self.cur, dpred, ydec[r0:r1], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[r0:r1], need_dx=norm)
         if norm:
-            self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, ds_L=Lq, ds_T=T)
+            self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, **self.destitch())
         self.close_segment("head")
         buf("d/qc", (R, H))
         if self.ctx_group:
@@ -841,8 +906,15 @@ class PlanBuilder:
                 pS = f"{side}_embeddings.{mod}.embedder"
                 lv = self.lv.get((side, slot))
                 stitch = K.stitch_bwd if lv is None else functools.partial(K.stitch_bwd_live, rec=lv._keep)
+                BT = self.BTm[m]
                 emb = [f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight"] + ([pS + ".pos_embed.weight"] if sd.pos else [])
                 if not self.keep(pS + ".mod_emb+pos_embed", any(nd.tok[side, slot]), emb):
+                    continue
+                if self.seg:
+                    K.stitch_bwd_seg(dS, dextra, b[f"ts/{m}"], b[self.mk(side, "keep0")], e._drop(f"{side}/embdrop/{m}", sd.dpe),
+                                     buf(f"d/tok/{side}/{m}", (BT, H)), e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
+                                     e.Gv(pS + ".pos_embed.weight") if sd.pos else None, side == "encoder" and mod in shared, False, B, self.Tm[m], Lq,
+                                     self.off[side][slot], H, sd.max_F, b["ws/stitch"], plan=self.cur)
                     continue
                 stitch(dS, dextra, b["ts"], b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), d_tok=buf(f"d/tok/{side}/{m}", (BT, H)),
                        d_mod_row=e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
@@ -857,6 +929,7 @@ class PlanBuilder:
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
                 lv = self.lv.get((side, slot))
+                BT = self.BTm[m]
                 dz = self.rows(buf(f"d/z/{m}", (BT, n * self.mult_max)), BT, n2)
                 self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz, need_dx=nd.tok[side, slot][0],
                           act=L.ACT_SOFTSIGN_GRAD_OUT if saved == "a" else sd.emb_grad, act_scale=sd.scale,

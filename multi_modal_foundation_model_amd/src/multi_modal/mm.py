@@ -8,8 +8,10 @@ Behavioural notes kept from the reference on purpose:
   * the loss is sum(mod_loss)/sum(n_examples) and is NaN when nothing is masked (mm.py:237);
   * `encoder_embeddings` / `decoder_embeddings` may hold subsets of `avail_mod` (the entry script's `modal_filter`): `mod_dict` still
     carries every modality, the masker is still called once per modality in that order, and each side keeps the modalities it has
-    tokenisers for (mm.py:277-287); the outputs hold the decoder's modalities.  Two sets of different size fail in cross-attention
+    tokenisers for (mm.py:277-287); the outputs hold the decoder's modalities.  Sides of different total length fail in cross-attention
     upstream (the [B, Le, Le] encoder mask cannot be expanded to [B, h, Ld, Le]); here `forward` raises before any launch;
+  * every modality has its own number of bins, its own `inputs_timestamp` and its own `inputs_attn_mask` (mm.py:97-158;
+    encoder_embeddings.py:56-59); `mod_preds[mod]` is [B, T_mod, N_mod];
   * `masking_mode` (mask_type: input) fails exactly like upstream (`mask` is never bound, mm.py:256-272).
 """
 import os
@@ -208,6 +210,11 @@ class MultiModal(nn.Module):
             if mod == 'behavior' and d['inputs'].dim() == 2:
                 d['inputs'] = d['inputs'].unsqueeze(-1)
                 d['targets'] = d['targets'].unsqueeze(-1)
+            # a modality's own number of bins: its inputs, targets, mask, stamps and attention mask must agree on it
+            shapes = {k: tuple(d[k].shape[:2]) for k in ('inputs', 'targets', 'inputs_timestamp', 'inputs_attn_mask', 'eval_mask')
+                      if d.get(k) is not None}
+            if d['inputs'].dim() != 3 or len(set(shapes.values())) != 1:
+                raise ValueError(f"modality {mod!r}: inputs / targets / mask / time stamps disagree in [batch, bins]: {shapes}")
             regions = d['inputs_regions'] if mod == 'ap' else None
             if d['masking_mode']:
                 self.masker.mode = d['masking_mode']
@@ -226,18 +233,26 @@ class MultiModal(nn.Module):
             d['encoder_attn_mask'] = d['decoder_attn_mask'] = d['inputs_attn_mask']
             masks.append(mask)
         first = mod_dict[mods[0]]
-        ts, attn = first['inputs_timestamp'], first['inputs_attn_mask']
-        for mod in mods[1:]:
-            d = mod_dict[mod]
-            for key, ref in (('inputs_timestamp', ts), ('inputs_attn_mask', attn)):
-                if d[key] is not ref and not torch.equal(d[key], ref):
-                    raise NotImplementedError(f"per-modality {key} differ: the stitched sequence assumes shared bins")
-        B, T, _ = first['inputs'].shape
+        B = first['inputs'].shape[0]
+        Ts = {mod: mod_dict[mod]['inputs'].shape[1] for mod in mods}
         enc_mods, dec_mods = ([m for m in mods if m in emb] for emb in (self.encoder_embeddings, self.decoder_embeddings))
-        if len(enc_mods) != len(dec_mods):
-            raise RuntimeError(f"encoder sequence length {len(enc_mods) * T} ({len(enc_mods)} modalities x {T} bins) != decoder sequence "
-                               f"length {len(dec_mods) * T} ({len(dec_mods)} x {T}): cross-attention masks the decoder's queries with the "
-                               "encoder's [B, Le, Le] mask (mm.py:152-158, 210), so the two sides need equally many modalities")
+        Le, Ld = (sum(Ts[m] for m in side) for side in (enc_mods, dec_mods))
+        if Le != Ld:
+            raise RuntimeError(f"encoder sequence length {Le} ({' + '.join(f'{m} {Ts[m]}' for m in enc_mods)} bins) != decoder sequence "
+                               f"length {Ld} ({' + '.join(f'{m} {Ts[m]}' for m in dec_mods)}): cross-attention masks the decoder's queries "
+                               "with the encoder's [B, Le, Le] mask (mm.py:152-158, 210), so the two sides need equally long sequences")
+        # Shared bins - every modality as long as the first, with its time stamps and its attention mask (the same tensors, or equal
+        # ones) - run the plan of one T, one `ts` and one `attn`.  Anything else is a batch of modality segments: each modality's own
+        # length, stamps and mask, as upstream concatenates them (mm.py:97-158; encoder_embeddings.py:56-59)
+        ts, attn = first['inputs_timestamp'], first['inputs_attn_mask']
+        shared = len(set(Ts.values())) == 1 and all(
+            mod_dict[mod][key] is ref or torch.equal(mod_dict[mod][key], ref)
+            for mod in mods[1:] for key, ref in (('inputs_timestamp', ts), ('inputs_attn_mask', attn)))
+        if shared:
+            T = Ts[mods[0]]
+        else:
+            T = tuple(Ts[m] for m in mods)
+            ts, attn = ([mod_dict[m][key] for m in mods] for key in ('inputs_timestamp', 'inputs_attn_mask'))
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
                           training=self.training, anchor=self._grad_anchor())
