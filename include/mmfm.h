@@ -527,6 +527,24 @@ int mmfm_adamw_step_ranges(float* p, const float* g, float* m, float* v, void* p
                            int n_ranges, const void* table, int64_t n_chunks, const float* hyper, int hyper_rows,
                            const mmfm_optim_record* record, int skip_nonfinite, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- gradient accumulation
+ * torch's `p.grad += new` for a backward that OVERWRITES its gradient buffer: stash the range before the backward, add it back after.
+ * MMFM_GRAD_ACCUM is the feature macro for this export (MMFM_VERSION stays, as for MMFM_NULL_BIAS: no existing struct changed).
+ *
+ * Both modes work over elements [start, end) of two flat fp32 buffers of n elements:
+ *   MMFM_GRAD_STASH   stash[i] = g[i]
+ *   MMFM_GRAD_ADD     g[i] = g[i] + stash[i]
+ * 16-byte accesses over the interior that is 16-byte aligned in both buffers, element accesses over its head and tail (over the whole
+ * range where the buffers disagree modulo 16 bytes).  Exactly one lane handles each element; no atomics, no reduction: neither grid
+ * size nor occupancy changes any bit.  Elements outside the range are neither read nor written.  One launch, no allocation, no
+ * synchronisation (capturable); start == end returns 0 without a launch.
+ * Argument checks (NULL pointers, start < 0, end > n, start > end, an unknown mode) return -1 before any HIP call: a machine without a
+ * GPU answers them. */
+#define MMFM_GRAD_ACCUM 1
+#define MMFM_GRAD_STASH 0
+#define MMFM_GRAD_ADD 1
+int mmfm_grad_accumulate(float* g, float* stash, int64_t n, int64_t start, int64_t end, int mode, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- evaluation metrics
  * utils/utils.py:107-115 (metrics_list "r2" = torcheval R2Score per series; trainer/base.py:252-262 calls it for 50
  * neurons x every trial on the host):  out[g*C + c] = 1 - sum_s (y-p)^2 / sum_s (y - mean_s y)^2 over the S elements

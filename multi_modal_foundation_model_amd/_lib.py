@@ -65,6 +65,7 @@ class LiveRows(C.Structure):
 
 
 OPTIM_CHUNK = 4096               # MMFM_OPTIM_CHUNK
+GRAD_STASH, GRAD_ADD = 0, 1      # MMFM_GRAD_STASH, MMFM_GRAD_ADD
 
 
 class OptimRange(C.Structure):
@@ -197,6 +198,7 @@ _PROTOS = {
     "mmfm_optim_ranges_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_grad_sumsq_ranges": (C.c_int, [_vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _f, _f, _i, _vp, _i64, _vp]),
     "mmfm_adamw_step_ranges": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _vp, _i, _vp, _i, _vp]),
+    "mmfm_grad_accumulate": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i, _vp]),
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
     "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),

@@ -269,6 +269,38 @@ int64_t optim_ranges_check(const char* who, const mmfm_optim_range* ranges, int 
 int opt_blocks(int64_t n_chunks) { return (int)std::min<int64_t>(4096, n_chunks); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// ------------------------------------------------------------------ gradient accumulation (include/mmfm.h, MMFM_GRAD_ACCUM)
+// Elements [lo, hi) of two flat fp32 buffers; ADD: g += stash, otherwise stash = g.  [a0, a1) is the interior whose quads are 16-byte
+// aligned in BOTH buffers (empty where the two disagree modulo 16 bytes: everything is head then).  Quad q of the interior belongs to
+// one lane of the grid-stride walk; the at most three elements of the head [lo, a0) and of the tail [a1, hi) belong to the first
+// lanes of workgroup 0, and where there is no interior the "head" [lo, hi) is walked element by element.  One lane per element, one
+// rounding per element: the grid changes nothing.
+template <bool ADD>
+__device__ __forceinline__ void accum_one(float* __restrict__ g, float* __restrict__ stash, int64_t i) {
+    if (ADD) g[i] = g[i] + stash[i];
+    else stash[i] = g[i];
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ g, float* __restrict__ stash, int64_t lo, int64_t a0,
+                                                              int64_t a1, int64_t hi) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    const int64_t nq = (a1 - a0) >> 2;
+    for (int64_t q = tid; q < nq; q += step) {
+        const int64_t i = a0 + 4 * q;
+        if (ADD) {
+            float4 x = *reinterpret_cast<const float4*>(g + i);
+            const float4 s = *reinterpret_cast<const float4*>(stash + i);
+            x.x = x.x + s.x; x.y = x.y + s.y; x.z = x.z + s.z; x.w = x.w + s.w;
+            *reinterpret_cast<float4*>(g + i) = x;
+        } else {
+            *reinterpret_cast<float4*>(stash + i) = *reinterpret_cast<const float4*>(g + i);
+        }
+    }
+    for (int64_t i = lo + tid; i < a0; i += step) accum_one<ADD>(g, stash, i);
+    for (int64_t i = a1 + tid; i < hi; i += step) accum_one<ADD>(g, stash, i);
+}
+
 }  // namespace
 
 extern "C" int64_t mmfm_optim_ranges_chunks(const mmfm_optim_range* ranges, int n_ranges, int64_t n, int hyper_rows) {
@@ -352,6 +384,28 @@ extern "C" int mmfm_adamw_step_ranges(float* p, const float* g, float* m, float*
         hipLaunchKernelGGL(adamw_ranges_kernel<false>, dim3(opt_blocks(n_chunks)), dim3(256), 0, st, p, g, m, v, (uint16_t*)p_bf16, n, chunks, n_chunks,
                            hyper, record, skip_nonfinite);
     MMFM_LAUNCH_CHECK("mmfm_adamw_step_ranges");
+    return 0;
+}
+
+extern "C" int mmfm_grad_accumulate(float* g, float* stash, int64_t n, int64_t start, int64_t end, int mode, mmfm_stream stream) {
+    MMFM_REQUIRE(g && stash, "mmfm_grad_accumulate: NULL pointer (g %p, stash %p)", (void*)g, (void*)stash);
+    MMFM_REQUIRE(start >= 0 && start <= end && end <= n, "mmfm_grad_accumulate: range [%lld, %lld) of n = %lld", (long long)start,
+                 (long long)end, (long long)n);
+    MMFM_REQUIRE(mode == MMFM_GRAD_STASH || mode == MMFM_GRAD_ADD, "mmfm_grad_accumulate: unknown mode %d", mode);
+    if (start == end) return 0;
+    int64_t a0 = end, a1 = end;                      // no 16-byte interior unless the two buffers agree modulo 16 bytes
+    if ((((uintptr_t)g ^ (uintptr_t)stash) & 15) == 0 && ((uintptr_t)g & 3) == 0) {
+        const int64_t mis = (int64_t)(((uintptr_t)(g + start) & 15) >> 2);
+        a0 = std::min<int64_t>(end, start + ((4 - mis) & 3));
+        a1 = a0 + ((end - a0) & ~(int64_t)3);
+    }
+    const int64_t work = std::max<int64_t>((a1 - a0) >> 2, std::max<int64_t>(a0 - start, end - a1));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (work + 255) / 256));
+    if (mode == MMFM_GRAD_ADD)
+        hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, stash, start, a0, a1, end);
+    else
+        hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, stash, start, a0, a1, end);
+    MMFM_LAUNCH_CHECK("mmfm_grad_accumulate");
     return 0;
 }
 

@@ -15,6 +15,7 @@ the collective on its own stream; `work.wait()` only makes the compute stream wa
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import List, Optional
@@ -71,13 +72,21 @@ class EngineDDP:
     With frozen parameters (requires_grad = False) a bucket all-reduces only the span from its first to its last trainable parameter,
     and a bucket without one issues no collective (`trainable_spans`; the engine's backward computes nothing there).  The spans follow
     the freeze pattern of the last forward.  EVERY RANK MUST FREEZE THE SAME PARAMETERS: ranks whose patterns differ would issue
-    collectives of different sizes, or different numbers of them, and hang."""
+    collectives of different sizes, or different numbers of them, and hang.
+
+    Gradient accumulation: a backward under `no_sync()` issues no collective and leaves its gradient in G; the first backward outside
+    the context (the caller skipped zero_grad(), so the engine adds into G) all-reduces the accumulated G bucket by bucket, as each
+    segment's add completes.  Without `no_sync` an accumulating backward all-reduces every time, as torch DDP does.  EVERY RANK MUST
+    CLOSE ITS GROUPS AT THE SAME BATCHES, for the same reason as above: a rank still inside `no_sync` issues no collective and the
+    others would wait for it."""
 
     def __init__(self, engine, process_group=None, bucket_bytes: int = 8 << 20, broadcast: bool = True):
         self.engine, self.pg = engine, process_group
         self.world = dist.get_world_size(process_group)
         self.buckets = GradBuckets(engine.layout, engine.cfg, bucket_bytes)
         self.works = []
+        self.sync = True                    # False inside no_sync()
+        self.collectives = 0                # all-reduces issued so far
         self._spans = {None: dict(self.buckets.trigger)}      # freeze pattern -> trainable_spans
         backend = dist.get_backend(process_group)
         self.avg_op = dist.ReduceOp.AVG if backend == "nccl" else None
@@ -87,8 +96,18 @@ class EngineDDP:
         engine.grad_ready_hooks.append(self.on_segment)
         engine.backward_done_hooks.append(self.finish)
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """Backwards inside the context issue no collective (torch DDP's no_sync): the gradient stays local until the first backward
+        outside it."""
+        old, self.sync = self.sync, False
+        try:
+            yield
+        finally:
+            self.sync = old
+
     def on_segment(self, name: str):
-        if name not in self.buckets.trigger:
+        if not self.sync or name not in self.buckets.trigger:
             return
         pattern = getattr(self.engine, "_pattern", None)      # the freeze pattern of the last forward (None: all trainable)
         if pattern not in self._spans:                        # a new freeze pattern: recomputed once, kept with the few others
@@ -101,6 +120,7 @@ class EngineDDP:
             return
         lo, hi = rng
         g = self.engine.G[lo:hi]
+        self.collectives += 1
         if self.avg_op is not None:
             self.works.append((dist.all_reduce(g, op=self.avg_op, group=self.pg, async_op=True), None))
         else:
@@ -121,6 +141,7 @@ class DataParallelModel(torch.nn.Module):
         super().__init__()
         self.module = module
         self._pg, self._bucket_bytes, self._ddp = process_group, bucket_bytes, None
+        self._no_sync = 0                    # depth of no_sync() contexts
 
     def forward(self, *a, **kw):
         eng = self.module.engine()           # builds / re-adopts the engine from the module's current parameters
@@ -128,7 +149,22 @@ class DataParallelModel(torch.nn.Module):
             # like torch DDP's constructor: rank 0's parameters are broadcast BEFORE the first forward, so every replica's
             # first loss and gradient are taken at the same parameters even if the replicas were initialised differently
             self._ddp = EngineDDP(eng, self._pg, self._bucket_bytes, broadcast=True)
+            self._ddp.sync = self._no_sync == 0          # built inside no_sync(): the group's first forward
         return self.module(*a, **kw)
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """torch DDP's no_sync: backwards inside the context keep their gradient local (EngineDDP.no_sync).  Before the first
+        forward there is no engine to tell yet, and nothing to hold back."""
+        self._no_sync += 1
+        if self._ddp is not None:
+            self._ddp.sync = False
+        try:
+            yield
+        finally:
+            self._no_sync -= 1
+            if self._ddp is not None:
+                self._ddp.sync = self._no_sync == 0
 
     def __getattr__(self, name):
         try:

@@ -382,6 +382,8 @@ class Engine:
         self._wt = dict(views={}, entries=[], table=None)             # bf16 transposes for the big-GEMM dX products (_w_transposed)
         self.grad_ready_hooks = []       # DDP: callables(segment_name) fired as backward completes a segment of G
         self.backward_done_hooks = []    # DDP: wait for the collectives (stream-side) before anyone reads G
+        self._stash = None               # G's size, allocated by the first backward that accumulates (caller skipped zero_grad()), never before
+        self._param_spans, self._spans_of = [], -1
         # hipGraph replay of the step plan: the plan neither allocates nor synchronises, so after one eager
         # (warm-up) run per batch shape it is captured once and replayed.  MMFM_GRAPH=0 disables.
         self.use_graphs = os.environ.get("MMFM_GRAPH", "1") != "0"
@@ -771,30 +773,36 @@ class Engine:
             self.b["gout"].fill_(1.0)
         else:
             self.b["gout"].copy_(grad_out.reshape(1).to(torch.float32))
-        accumulate_into = None
-        first = next((p for p in self.params.values() if p.requires_grad), None)
-        if first is not None and first.grad is not None:
-            accumulate_into = self.G.clone()               # caller did not zero_grad(): keep torch's += semantics
         plan = self._last
         if plan["bwd"] is None:
             raise RuntimeError("backward(): the last forward ran without gradient tracking (forward-only plan)")
         if (plan["B"], plan["T"]) not in self._pools or self._pools[(plan["B"], plan["T"])] is not plan["b"]:
             raise RuntimeError("backward(): the batch shape of this loss was evicted (MMFM_MAX_SHAPES) before its backward ran")
         self.b = plan["b"]
-        if self.grad_ready_hooks and accumulate_into is None:
+        # caller did not zero_grad(): keep torch's += semantics.  The backward kernels overwrite G, so the accumulating runs are stashed
+        # before the first launch and added back behind the launches that wrote them; the launches are not part of the plan
+        runs = self.accumulating_runs()
+        if runs:
+            if self._stash is None:                # one persistent buffer, from the first accumulating backward on
+                self._stash = torch.empty_like(self.G)
+            for s, e in runs:
+                K.grad_accumulate(self.G, self._stash, s, e, L.GRAD_STASH)
+        if self.grad_ready_hooks:
             for name, seg in plan["bwd"]:          # DDP: one graph per segment, collectives issued in between
                 if seg:                            # (a segment a pruned plan left without launches is neither run nor captured; its hook still fires)
                     self._run(plan, "bwd", lambda seg=seg: K.run_plan(seg), tag="bwd/" + name)
+                if runs:
+                    lo, hi = self.segment_range(name)
+                    for s, e in runs:
+                        if max(s, lo) < min(e, hi):
+                            K.grad_accumulate(self.G, self._stash, max(s, lo), min(e, hi), L.GRAD_ADD)
                 for hook in self.grad_ready_hooks:
                     hook(name)
         else:
             self._run(plan, "bwd", lambda: [K.run_plan(seg) for _, seg in plan["bwd"] if seg])
+            for s, e in runs:
+                K.grad_accumulate(self.G, self._stash, s, e, L.GRAD_ADD)
         plan["runs"]["bwd"] += 1
-        if accumulate_into is not None:
-            self.G.add_(accumulate_into)
-            for hook in self.grad_ready_hooks:
-                for name, _ in self._last["bwd"]:
-                    hook(name)
         for hook in self.backward_done_hooks:
             hook()
         # requires_grad is honoured twice: the plan of this freeze pattern launched only what the trainable parameters need (plan.py,
@@ -804,6 +812,27 @@ class Engine:
                 p.grad = None
             elif p.grad is None or p.grad.data_ptr() != self.Gv(name).data_ptr():
                 p.grad = self.Gv(name)
+
+    def accumulating_runs(self):
+        """The [start, end) ranges of G the next backward adds into instead of overwriting.  Torch's rule, per parameter: a trainable
+        parameter whose .grad is not None when backward() starts accumulates; one whose .grad is None ends with this backward's gradient
+        alone.  The accumulating parameters form maximal contiguous runs in layout order; alignment padding between two members joins
+        their run.  Empty after zero_grad() - the ordinary step."""
+        if self._spans_of != self.adoptions:          # (parameter, start, end) in layout order, rebuilt when adopt() re-points them
+            self._param_spans = [(self.params[name], off, off + int(math.prod(shape))) for name, (off, shape) in self.layout.entries.items()
+                                 if name in self.params]
+            self._spans_of = self.adoptions
+        runs, open_run = [], False
+        for p, s, e in self._param_spans:
+            if p.grad is not None and p.requires_grad:
+                if open_run:
+                    runs[-1][1] = e
+                else:
+                    runs.append([s, e])
+                    open_run = True
+            else:
+                open_run = False
+        return [(s, e) for s, e in runs]
 
     def segment_range(self, name):
         for n, s, e in self.layout.segments:

@@ -357,6 +357,12 @@ def adamw_step_ranges(p, g, m, v, p_bf16, tab, hyper, clipped=False, skip_nonfin
                                                  int(bool(skip_nonfinite)), ), keep=(tab,))
 
 
+def grad_accumulate(g, stash, start, end, mode, plan=None):
+    """mmfm_grad_accumulate over elements [start, end) of the flat fp32 buffers g and stash: mode L.GRAD_STASH copies g into stash,
+    L.GRAD_ADD adds stash into g.  An empty range launches nothing."""
+    _emit(plan, L.lib().mmfm_grad_accumulate, (P(g), P(stash), g.numel(), int(start), int(end), int(mode)))
+
+
 def rng_seed(state, seed, plan=None):
     _emit(plan, L.lib().mmfm_rng_seed, (P(state), int(seed) & (2 ** 64 - 1)))
 

@@ -26,6 +26,7 @@ from multi_modal.mm import MultiModal
 from multi_modal_foundation_model_amd.ddp import Accelerator
 from multi_modal_foundation_model_amd.optim import freeze_parameters, make_optimizer
 from multi_modal_foundation_model_amd.synthetic import SyntheticLoader
+from trainer.base import accumulation_groups, validate_accumulation_steps
 from trainer.make import make_multimodal_trainer
 from utils.config_utils import config_from_kwargs, update_config
 from utils.utils import set_seed
@@ -43,6 +44,8 @@ def build_parser():
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--base_path", type=str, default="/tmp/mmfm_results")
     ap.add_argument("--epochs", type=int, default=None, help="override training.num_epochs (2000 upstream)")
+    ap.add_argument("--grad_accum_steps", type=int, default=None,
+                    help="override optimizer.gradient_accumulation_steps: batches per optimiser step (the mean gradient of the group is applied)")
     ap.add_argument("--batches_per_epoch", type=int, default=8)
     ap.add_argument("--n_neurons", type=int, default=668)
     ap.add_argument("--dtype", type=str, default=os.environ.get("MMFM_DTYPE", "fp32"), choices=["fp32", "bf16"])
@@ -75,6 +78,8 @@ def main(argv=None):
     config["model"]["masker"]["ratio"] = args.mask_ratio
     if args.epochs is not None:
         config["training"]["num_epochs"] = args.epochs
+    if args.grad_accum_steps is not None:
+        config["optimizer"]["gradient_accumulation_steps"] = args.grad_accum_steps
     set_seed(config.seed)
 
     avail_mod = list(AVAIL_MOD)
@@ -120,8 +125,12 @@ def main(argv=None):
     # a number turns on the fused clip (optim.py)
     optimizer = make_optimizer(model, lr=config.optimizer.lr, weight_decay=config.optimizer.wd, eps=config.optimizer.eps,
                                max_grad_norm=config.optimizer.get("max_grad_norm", None))
+    # one scheduler step per optimiser step, one optimiser step per group of gradient_accumulation_steps batches; the last group of an
+    # epoch closes short (trainer/base.py, accumulation_groups).  Upstream's floor(epochs * batches / k) is this number for k = 1 and
+    # whenever k divides the epoch length - the only cases in which OneCycleLR ends on the last optimiser step with it
+    k = validate_accumulation_steps(config.optimizer.gradient_accumulation_steps)
     lr_scheduler = OneCycleLR(optimizer=optimizer,
-                              total_steps=config.training.num_epochs * len(train_dataloader) // config.optimizer.gradient_accumulation_steps,
+                              total_steps=config.training.num_epochs * len(accumulation_groups(len(train_dataloader), k)),
                               max_lr=config.optimizer.lr, pct_start=config.optimizer.warmup_pct, div_factor=config.optimizer.div_factor)
 
     trainer_ = make_multimodal_trainer(model=model, train_dataloader=train_dataloader, eval_dataloader=val_dataloader,

@@ -4,8 +4,12 @@ Same constructor kwargs (log_dir, accelerator, lr_scheduler, config, num_neurons
 modal_filter, mixed_training), same methods and return values.  Differences, all on the host side:
   * the per-step `loss.item()` sync (trainer/base.py:199) is deferred to the end of the epoch: losses
     stay on the device and are summed in float64 in step order, which gives the same `train_loss`;
+  * `optimizer.gradient_accumulation_steps` is honoured (upstream reads it for OneCycleLR's length only and steps on every batch):
+    one optimiser / scheduler step per group of k batches, `accumulation_groups`; k = 1 is the reference's loop;
   * wandb / matplotlib are optional (absent in this image): logging falls back to print / PNG files.
 """
+import contextlib
+import itertools
 import os
 import random
 
@@ -69,6 +73,22 @@ class LazyRegions:
         return self.materialize().T
 
 
+def validate_accumulation_steps(k):
+    """optimizer.gradient_accumulation_steps as an int >= 1, or ValueError (a bool, a float - 1.5, 2.0 - and anything below 1)."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"optimizer.gradient_accumulation_steps must be an int >= 1, got {k!r}")
+    return k
+
+
+def accumulation_groups(n_batches, k):
+    """The sizes of the groups an epoch of n_batches batches is cut into: k consecutive batches each, and the last batch of the epoch
+    closes its group even when fewer than k came (no checkpoint or evaluation at an epoch boundary holds a half-applied gradient).
+    One optimiser step and one scheduler step per group: len() of this is the number of steps per epoch."""
+    k = validate_accumulation_steps(k)
+    n_batches = int(n_batches)
+    return [k] * (n_batches // k) + ([n_batches % k] if n_batches % k else [])
+
+
 class MultiModalTrainer():
     def __init__(self, model, train_dataloader, eval_dataloader, optimizer, **kwargs):
         self.model = model
@@ -81,6 +101,10 @@ class MultiModalTrainer():
         self.lr_scheduler = kwargs.get("lr_scheduler", None)
         self.config = kwargs.get("config", None)
         self.num_neurons = kwargs.get("num_neurons", None)
+
+        # batches per optimiser step (train_epoch); a config without the key takes a step per batch
+        opt_cfg = self.config.get("optimizer", None) or {}
+        self.accum_steps = validate_accumulation_steps(opt_cfg.get("gradient_accumulation_steps", 1))
 
         self.model_class = self.config.model.model_class
         self.metric = 'r2'
@@ -230,16 +254,30 @@ class MultiModalTrainer():
     def train_epoch(self, epoch):
         self.model.train()
         losses = []
+        # optimizer.gradient_accumulation_steps = k: one optimiser (and scheduler) step per group of k consecutive batches, on the MEAN
+        # of the group's gradients - with max_grad_norm it is that mean's norm that is measured.  The epoch's last group closes short
+        # (accumulation_groups).  All but a group's last backward run under the model's no_sync() where it has one (data parallelism:
+        # one all-reduce per group; EVERY RANK MUST SEE THE SAME NUMBER OF BATCHES PER EPOCH, or the groups close at different batches).
+        # k = 1 makes the calls it always made
+        k = self.accum_steps
+        sizes = iter(accumulation_groups(len(self.train_dataloader), k)) if k > 1 else itertools.repeat(1)
+        no_sync = getattr(self.model, "no_sync", None)
+        r = left = 0
         for batch in self.train_dataloader:
+            if left == 0:
+                r = left = next(sizes, k)
+            left -= 1
             self._sample_modes()
-            outputs = self._forward_model_outputs(batch, masking_mode=self.masking_mode, training_mode=self.training_mode)
-            loss = outputs.loss
-            loss.backward()
-            self.optimizer.step()
-            self.lr_scheduler.step()
-            self.optimizer.zero_grad()
+            with (no_sync() if left and no_sync is not None else contextlib.nullcontext()):
+                outputs = self._forward_model_outputs(batch, masking_mode=self.masking_mode, training_mode=self.training_mode)
+                loss = outputs.loss
+                (loss if r == 1 else loss / r).backward()
+            if left == 0:
+                self.optimizer.step()
+                self.lr_scheduler.step()
+                self.optimizer.zero_grad()
             losses.append(loss.detach())
-            if not self._backward_reported:
+            if left == 0 and not self._backward_reported:
                 self._report_backward()
         # one host sync per epoch instead of one per step; float64 sum in step order == sum of .item()s
         train_loss = float(sum(x.item() for x in torch.stack(losses).double().cpu())) if losses else 0.
