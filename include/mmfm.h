@@ -446,6 +446,42 @@ int mmfm_masked_loss_kind_bwd(int dtype, int kind, float param, int flags, const
                               const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const float* grad_out,
                               const float* inv_n, void* dpred, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- softmax cross-entropy (categorical modalities)
+ * Kind 7, the one loss whose row elements are coupled (a log-sum-exp over the N classes of a row), with entry points of its own:
+ * mmfm_masked_loss_kind_fwd / _bwd answer "bad kind" for it.  For logits p[c], targets t[c] (one-hot or any non-negative weights, not
+ * necessarily summing to 1), class weights w[c] (class_weight == NULL: 1) and label smoothing eps in [0, 1]:
+ *   t'[c]   = (1 - eps) t[c] + eps / N
+ *   e[c]    = - w[c] t'[c] log_softmax(p)[c]                 the [R][N] tensor upstream multiplies by the token mask (mm.py:217-239)
+ *   row     = sum_c e[c] = sum_c w[c] t'[c] (lse(p) - p[c])  = F.cross_entropy(p, t, weight=w, label_smoothing=eps, reduction='none')
+ *   d/dp[j] = softmax(p)[j] sum_c w[c] t'[c] - w[j] t'[j]
+ * and n_examples stays N * (masked rows), upstream's targets_mask.sum() over [B,T,N]: what mmfm_mask_prep counts with channels = N.
+ * pred [R][N] (dtype), target [R][N] fp32, rowmask as above; un-masked rows are never read by the forward.  fp32 arithmetic, the row
+ * maximum subtracted before the exponential; fwd writes the masked SUM to loss_sum[0] (fixed-order two-stage sum, the same bits on
+ * every call; no allocation, no sync, no floating-point atomic).  A row is owned by G lanes, G the smallest power of two
+ * >= min(N, 64), 64 / G rows to a wavefront; for N > 64 a wavefront owns the row and its lanes stride over the columns.
+ * rowstat (or NULL) [R][2] fp32: fwd leaves (lse, sum_c w t') of every MASKED row there (other rows are not written); bwd reads them
+ * when given - one pass over the row - and recomputes them otherwise, to the same bits.  bwd writes dpred as mmfm_masked_loss_bwd
+ * does: grad_out[0] * inv_n[0] * d/dp on masked rows, that factor times 0 on the others (exactly 0, or NaN when inv_n is inf).
+ * Non-finite logits are outside the contract.
+ *
+ * mmfm_argmax_confusion: conf[N][N] int64 is OVERWRITTEN with the counts of (arg-max of target, arg-max of pred) over the masked
+ * rows (rowmask == NULL: every row), row = target class; the lowest index wins a tie in both.  Exact (integer atomics).
+ *
+ * Argument checks (null pointers, dtype, label_smoothing outside [0, 1], R % T != 0, mask_ld < T, workspace size) return -1 before
+ * any HIP call.  MMFM_SOFTMAX_CE is the feature macro (MMFM_VERSION stays, as for MMFM_LOSS_KINDS). */
+#define MMFM_SOFTMAX_CE 1
+#define MMFM_LOSS_SOFTMAX_CE 7
+int64_t mmfm_softmax_ce_workspace(int64_t R, int N);
+int mmfm_softmax_ce_fwd(int dtype, const void* pred, const float* target, const float* class_weight /* [N] or NULL */,
+                        float label_smoothing, const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N,
+                        float* loss_sum, float* rowstat /* [R][2] = (lse, sum w t') of masked rows, or NULL */,
+                        void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_softmax_ce_bwd(int dtype, const void* pred, const float* target, const float* class_weight, float label_smoothing,
+                        const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const float* rowstat /* NULL: recompute */,
+                        const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream);
+int mmfm_argmax_confusion(int dtype, const void* pred, const float* target, const uint8_t* rowmask /* or NULL */, int mask_ld,
+                          int T, int64_t R, int N, int64_t* conf /* [N][N], row = target class */, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- elementwise
  * dst = dropout(src) with counter row*N + col (the backward of a dropout whose forward was fused
  * into a GEMM epilogue). */

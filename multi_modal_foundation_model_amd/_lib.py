@@ -37,6 +37,8 @@ MLP_GELU, MLP_RELU, MLP_SIGMOID, MLP_GELU_TANH = 0, 1, 2, 3
 # masked-loss kinds (MMFM_LOSS_*) and the PoissonNLLLoss(full=True) flag
 LOSS_POISSON_LOG, LOSS_MSE, LOSS_POISSON_RATE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_BCE_LOGITS = range(7)
 LOSS_FULL = 1
+# softmax cross-entropy (MMFM_LOSS_SOFTMAX_CE): served by mmfm_softmax_ce_fwd / _bwd only, the kind entry points refuse it
+LOSS_SOFTMAX_CE = 7
 
 
 class MmfmError(RuntimeError):
@@ -189,6 +191,11 @@ _PROTOS = {
     "mmfm_loss_finalize": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mmfm_masked_loss_bwd": (C.c_int, [_i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "mmfm_masked_loss_kind_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
+    # softmax cross-entropy and the arg-max confusion matrix (MMFM_SOFTMAX_CE)
+    "mmfm_softmax_ce_workspace": (C.c_int64, [_i64, _i]),
+    "mmfm_softmax_ce_fwd": (C.c_int, [_i, _vp, _vp, _vp, _f, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _i64, _vp]),
+    "mmfm_softmax_ce_bwd": (C.c_int, [_i, _vp, _vp, _vp, _f, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mmfm_argmax_confusion": (C.c_int, [_i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp]),
     "mmfm_dropout_apply": (C.c_int, [_i, _vp, _vp, _i64, _i, Dropout, _vp]),
     "mmfm_cast_f32_to_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mmfm_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

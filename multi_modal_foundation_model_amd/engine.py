@@ -50,6 +50,9 @@ PER_SIDE_EMBED = ("embed_act", "embed_pos", "embed_bias")
 # The modality sets of the two sides (modal_filter) and whether their tokenisers share mod_emb tables: constructor keywords and attributes
 # like the embedder options, and like them no dataclass fields
 MODAL = ("enc_mods", "dec_mods", "share_mod_emb")
+# The class weights of the softmax cross-entropy modalities (loss_kind 7): a constructor keyword and attribute like the two groups above
+# and like them no dataclass field - the field list, asdict() and the default config stay what they were
+LOSS_EXTRA = ("loss_weight",)
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -96,12 +99,17 @@ class EngineConfig:
     enc_mods: InitVar[Optional[List[str]]] = None
     dec_mods: InitVar[Optional[List[str]]] = None
     share_mod_emb: InitVar[bool] = True
+    # loss_kind[mod] = L.LOSS_SOFTMAX_CE: loss_param[mod] is the label smoothing and loss_weight[mod] the class weights, one per channel
+    # of the head (absent: 1).  Tuples, so that __eq__ and the plan pool compare them by value; uploaded once per engine
+    loss_weight: InitVar[Optional[Dict[str, Tuple[float, ...]]]] = None
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
     # `n_modality` (a shared mod_emb is one tensor, mm.py:84-87, and the row is the modality's index in `mods` on either side).  Read a
     # side's values through `side()`
 
-    def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True):
+    def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True,
+                      loss_weight=None):
         self.embed_act, self.embed_pos, self.embed_bias = embed_act, embed_pos, embed_bias
+        self.loss_weight = {m: tuple(float(x) for x in w) for m, w in (loss_weight or {}).items()}
         names = [m for m, _ in self.mods]
         for k, v in (("enc_mods", enc_mods), ("dec_mods", dec_mods)):
             if v is not None:
@@ -122,7 +130,7 @@ class EngineConfig:
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL)
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA)
 
     __hash__ = None
 
@@ -390,6 +398,21 @@ class Engine:
         self._shared["loss"] = torch.zeros(1, device=self.device)
         self._shared["inv_n"] = torch.zeros(1, device=self.device)
         self._shared["gout"] = torch.ones(1, device=self.device)
+        # softmax cross-entropy modalities: the label smoothing is checked and the class weights are uploaded here, once per engine
+        # (a modality without weights, or of another kind, has no entry: the launches pass NULL)
+        self.loss_w: Dict[str, torch.Tensor] = {}
+        chans = dict(cfg.mods)
+        for mod, kind in cfg.loss_kind.items():
+            w = getattr(cfg, "loss_weight", {}).get(mod)
+            if kind != L.LOSS_SOFTMAX_CE:
+                continue
+            if not 0.0 <= float(cfg.loss_param.get(mod, 0.0)) <= 1.0:
+                raise ValueError(f"EngineConfig.loss_param[{mod!r}] = {cfg.loss_param[mod]}: the label smoothing must be in [0, 1]")
+            if w is not None:
+                if len(w) != chans.get(mod) or any(not x >= 0 for x in w):
+                    raise ValueError(f"EngineConfig.loss_weight[{mod!r}]: {len(w)} class weights for a head of {chans.get(mod)} channels "
+                                     "(one non-negative weight per channel)")
+                self.loss_w[mod] = torch.tensor(w, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ parameters
     def adopt(self, named_params: Dict[str, torch.nn.Parameter]):

@@ -8,6 +8,10 @@
 * `bits_per_spike_per_neuron(rates, spikes)` - the per-neuron loop of `spiking_activity_recon_eval`
                                (`utils/eval_utils.py:846-851`, N host calls upstream) in one pass; inf -> nan like upstream.
 
+* `confusion(pred, target, mask=None)` - the [C, C] count matrix of a categorical modality (row = target class): arg-max of the
+                               logits against arg-max of the targets over the masked tokens, one launch (mmfm_argmax_confusion).
+* `accuracy(...)`, `balanced_accuracy(...)` - its trace over its sum, and the mean recall of the classes that occur.
+
 There is no CPU path here: tensors must live on the GPU (the CPU restatement is oracle/metrics_oracle.py, test-only).
 """
 from __future__ import annotations
@@ -80,3 +84,42 @@ def bits_per_spike_per_neuron(rates, spikes) -> torch.Tensor:
     out = torch.empty(N, device=r.device, dtype=torch.float32)
     L.check(L.lib().mmfm_bits_per_spike_neurons(P(r), P(s), R, N, P(out), P(ws), ws.numel(), stream()), "mmfm_bits_per_spike_neurons")
     return torch.where(torch.isinf(out), torch.full_like(out, float("nan")), out)
+
+
+def confusion(pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor = None) -> torch.Tensor:
+    """pred [..., C] logits (fp32 or bf16), target [..., C] (one-hot labels or class probabilities), mask [...] or None (every
+    token): int64 [C, C] on the device, conf[i, j] = masked tokens whose target arg-max is i and whose predicted arg-max is j.  The
+    lowest index wins a tie on either side."""
+    _need_cuda(pred, target)
+    if pred.shape != target.shape or pred.dim() < 1:
+        raise ValueError(f"confusion: pred {tuple(pred.shape)} and target {tuple(target.shape)} must have one shape [..., C]")
+    Cn = pred.shape[-1]
+    p = pred if pred.dtype in (torch.float32, torch.bfloat16) else pred.float()
+    p, t = p.reshape(-1, Cn).contiguous(), target.reshape(-1, Cn).float().contiguous()
+    R = p.shape[0]
+    conf = torch.empty(Cn, Cn, dtype=torch.int64, device=p.device)
+    if R == 0:
+        return conf.zero_()
+    m = None
+    if mask is not None:
+        _need_cuda(mask)
+        if tuple(mask.shape) != tuple(pred.shape[:-1]):
+            raise ValueError(f"confusion: mask {tuple(mask.shape)} must be pred's shape without the class axis {tuple(pred.shape[:-1])}")
+        m = (mask.reshape(-1) != 0).to(torch.uint8).contiguous()
+    dtype = L.F32 if p.dtype == torch.float32 else L.BF16
+    L.check(L.lib().mmfm_argmax_confusion(dtype, P(p), P(t), P(m), 1, 1, R, Cn, P(conf), stream()), "mmfm_argmax_confusion")
+    return conf
+
+
+def accuracy(pred, target, mask=None) -> float:
+    """Correct over counted tokens (NaN when nothing is counted)."""
+    conf = confusion(pred, target, mask).double()
+    return float((conf.diagonal().sum() / conf.sum()).item())
+
+
+def balanced_accuracy(pred, target, mask=None) -> float:
+    """The mean over the classes that occur among the targets of their recall (sklearn's balanced_accuracy_score); NaN when none does."""
+    conf = confusion(pred, target, mask).double()
+    support = conf.sum(1)
+    seen = support > 0
+    return float((conf.diagonal()[seen] / support[seen]).mean().item())

@@ -293,6 +293,24 @@ def masked_loss_kind_bwd(kind, param, flags, pred, target, rowmask, mask_ld, T, 
                                                     P(grad_out), P(inv_n), P(dpred)))
 
 
+def softmax_ce_fwd(pred, target, weight, eps, rowmask, mask_ld, T, R, N, loss_sum, rowstat, ws, plan=None):
+    """Softmax cross-entropy (L.LOSS_SOFTMAX_CE) of [R, N] logits against fp32 targets: the masked sum to loss_sum[0].  weight: fp32 [N]
+    class weights or None; eps: label smoothing; rowstat: fp32 [R, 2] for the backward's (lse, sum w t'), or None."""
+    _emit(plan, L.lib().mmfm_softmax_ce_fwd, (dt(pred), P(pred), P(target), P(weight), float(eps), P(rowmask), mask_ld, T, R, N, P(loss_sum),
+                                              P(rowstat), P(ws), ws.numel() * ws.element_size()))
+
+
+def softmax_ce_bwd(pred, target, weight, eps, rowmask, mask_ld, T, R, N, rowstat, grad_out, inv_n, dpred, plan=None):
+    """rowstat: what softmax_ce_fwd left (one pass over the row), or None (recomputed, the same bits)."""
+    _emit(plan, L.lib().mmfm_softmax_ce_bwd, (dt(pred), P(pred), P(target), P(weight), float(eps), P(rowmask), mask_ld, T, R, N, P(rowstat),
+                                              P(grad_out), P(inv_n), P(dpred)))
+
+
+def argmax_confusion(pred, target, rowmask, mask_ld, T, R, N, conf, plan=None):
+    """conf int64 [N, N] <- counts of (arg-max of target, arg-max of pred) over the masked rows (rowmask None: all), lowest index on a tie."""
+    _emit(plan, L.lib().mmfm_argmax_confusion, (dt(pred), P(pred), P(target), P(rowmask), mask_ld, T, R, N, P(conf)))
+
+
 def dropout_apply(src, dst, R, N, drop, plan=None):
     _emit(plan, L.lib().mmfm_dropout_apply, (dt(src), P(src), P(dst), R, N, drop))
 

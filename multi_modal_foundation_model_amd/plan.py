@@ -285,7 +285,11 @@ class PlanBuilder:
         else:
             need = max(L.lib().mmfm_stitch_bwd_workspace(self.code, B, T, Lq, H, sd.max_F) for sd in self.sides.values())
         buf("ws/stitch", (max(1, need // 4),), f32)
-        buf("ws/loss", (max(1, L.lib().mmfm_masked_loss_workspace(BT, 1) // 4),), f32)
+        need = L.lib().mmfm_masked_loss_workspace(BT, 1)
+        for m, mod, n in self.mods_of["decoder"]:          # (a model without a softmax cross-entropy modality sizes it as it always did)
+            if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+                need = max(need, L.lib().mmfm_softmax_ce_workspace(self.BTm[m], n))
+        buf("ws/loss", (max(1, need // 4),), f32)
         # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
         # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
         # parked one alone.  Each product then makes half as many K-slabs (csrc/gemm_dw.hip).
@@ -514,13 +518,24 @@ class PlanBuilder:
 
     def loss(self, plan, mod, two_kind, kind_fn, *args):
         """A modality's masked loss, forward or backward.  PoissonNLL(log_input) / MSE without a flag go through the two-kind entry
-        points (`two_kind`), call for call the plan it always was; every other kind through `kind_fn` with its float and flags."""
+        points (`two_kind`), call for call the plan it always was; every other elementwise kind through `kind_fn` with its float and
+        flags.  Softmax cross-entropy has calls of its own: `softmax_ce`."""
         c = self.c
         kind, param, flags = c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
         if kind in (L.LOSS_POISSON_LOG, L.LOSS_MSE) and flags == 0:
             two_kind(kind, *args, plan=plan)
         else:
             kind_fn(kind, param, flags, *args, plan=plan)
+
+    def softmax_ce(self, plan, m, mod, pred, target, rowmask, mask_ld, T, R, N, loss_sum=None, ws=None, dpred=None):
+        """The softmax cross-entropy of modality `m` (loss_kind 7): the forward (`loss_sum`, `ws`) or, with `dpred`, the backward.  The
+        training plan saves (lse, sum w t') per row in `rowstat/{m}` for a one-pass backward; the forward-only plan passes NULL."""
+        w, eps, b = self.e.loss_w.get(mod), float(self.c.loss_param.get(mod, 0.0)), self.b
+        if dpred is None:
+            stat = self.buf(f"rowstat/{m}", (R, 2), torch.float32) if self.grad else None
+            K.softmax_ce_fwd(pred, target, w, eps, rowmask, mask_ld, T, R, N, loss_sum, stat, ws, plan=plan)
+        else:
+            K.softmax_ce_bwd(pred, target, w, eps, rowmask, mask_ld, T, R, N, b[f"rowstat/{m}"], b["gout"], b["inv_n"], dpred, plan=plan)
 
     # ------------------------------------------------------------------ forward blocks
     def out_proj(self, plan, a, wname, Xres, Xout):
@@ -658,6 +673,9 @@ class PlanBuilder:
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             pred = buf(f"pred/{m}", (BT, n))
             self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+                self.softmax_ce(fwd, m, mod, pred, b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n, loss_sum=b["loss_sum"][j:j + 1], ws=b["ws/loss"])
+                continue
             self.loss(fwd, mod, K.masked_loss_fwd, K.masked_loss_kind_fwd, pred, b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n,
                       b["loss_sum"][j:j + 1], b["ws/loss"])
         K.loss_finalize(b["loss_sum"], b[mk("decoder", "count")], self.Md, b["loss"], b["inv_n"], plan=fwd)
@@ -860,7 +878,9 @@ class PlanBuilder:
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             dpred = buf(f"d/pred/{m}", (BT, n))
-            if norm or self.tl(f"decoder_embeddings.{mod}.out"):
+            if (norm or self.tl(f"decoder_embeddings.{mod}.out")) and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+                self.softmax_ce(self.cur, m, mod, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n, dpred=dpred)
+            elif norm or self.tl(f"decoder_embeddings.{mod}.out"):
                 self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:],
                           Lq, self.Tm[m], BT, n, b["gout"], b["inv_n"], dpred)
             self.dlin(self.cur, dpred, ydec[r0:r1], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[r0:r1], need_dx=norm)

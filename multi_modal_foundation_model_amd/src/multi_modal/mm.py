@@ -25,6 +25,7 @@ from models.masker import Masker
 from models.model_output import ModelOutput
 from multi_modal.decoder_embeddings import DecoderLayer
 from multi_modal.encoder_embeddings import EncoderLayer
+from multi_modal.losses import SoftmaxCrossEntropy
 from multi_modal.mm_utils import create_context_mask  # noqa: F401  (re-exported like the reference)
 from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd.engine import Engine, EngineConfig
@@ -44,7 +45,8 @@ class MultiModalOutput(ModelOutput):
 
 # loss_mod strings of the kinds beyond the reference's two, with torch's default parameters: (MMFM_LOSS_* kind, param, flags)
 _LOSS_STRINGS = {"poisson_nll_rate": (L.LOSS_POISSON_RATE, 1e-8, 0), "l1": (L.LOSS_L1, 0.0, 0), "smooth_l1": (L.LOSS_SMOOTH_L1, 1.0, 0),
-                 "huber": (L.LOSS_HUBER, 1.0, 0), "bce_with_logits": (L.LOSS_BCE_LOGITS, 0.0, 0)}
+                 "huber": (L.LOSS_HUBER, 1.0, 0), "bce_with_logits": (L.LOSS_BCE_LOGITS, 0.0, 0),
+                 "softmax_cross_entropy": (L.LOSS_SOFTMAX_CE, 0.0, 0)}
 
 
 def _loss_spec(spec):
@@ -53,10 +55,20 @@ def _loss_spec(spec):
     nn.PoissonNLLLoss(reduction="none", log_input=True) / nn.MSELoss(reduction="none") (mm.py:79-82), accepted too, so
     `model.loss_mod['lfp'] = nn.MSELoss(reduction='none')` adds a modality exactly as it would upstream.  So do, by exact class,
     nn.PoissonNLLLoss (either log_input, full), nn.L1Loss, nn.SmoothL1Loss, nn.HuberLoss and nn.BCEWithLogitsLoss, and the strings of
-    _LOSS_STRINGS.  What was accepted before those maps as it did: any other string or class name containing 'poisson' -> 0, 'mse' -> 1."""
+    _LOSS_STRINGS.  What was accepted before those maps as it did: any other string or class name containing 'poisson' -> 0, 'mse' -> 1.
+    multi_modal.losses.SoftmaxCrossEntropy (the exact class) and "softmax_cross_entropy" -> L.LOSS_SOFTMAX_CE, param = the label
+    smoothing; the class weights are read by `_loss_weight`.  nn.CrossEntropyLoss itself stays refused: it reads dim 1 as the class axis
+    and returns [B, T], not the [B, T, N] tensor the reference multiplies by the token mask."""
     if isinstance(spec, str):
         if spec.lower() in _LOSS_STRINGS:
             return _LOSS_STRINGS[spec.lower()]
+    elif isinstance(spec, SoftmaxCrossEntropy):
+        if type(spec) is not SoftmaxCrossEntropy:
+            raise NotImplementedError(f"loss {spec!r}: no HIP kernel for this class - a subclass of SoftmaxCrossEntropy may compute "
+                                      "anything; the engine reads weight and label_smoothing off the exact class")
+        if not 0.0 <= float(spec.label_smoothing) <= 1.0:
+            raise ValueError(f"loss {spec!r}: label_smoothing must be in [0, 1]")
+        return L.LOSS_SOFTMAX_CE, float(spec.label_smoothing), 0
     else:
         cls = type(spec)
         legacy = cls is nn.PoissonNLLLoss and spec.log_input and not spec.full       # the reference's own spike loss: as before, unchecked
@@ -87,6 +99,20 @@ def _loss_spec(spec):
         return L.LOSS_MSE, 0.0, 0
     raise NotImplementedError(f"loss {spec!r}: no HIP kernel for this class / name - built are PoissonNLLLoss, MSELoss, L1Loss, SmoothL1Loss, "
                               f"HuberLoss, BCEWithLogitsLoss (reduction='none') and the strings {sorted(_LOSS_STRINGS)}")
+
+
+def _loss_weight(spec, channels=None):
+    """The class weights of a SoftmaxCrossEntropy entry as a tuple of floats, None for every other entry and for weight=None.
+    channels: the head's output channels, which the number of weights must equal."""
+    w = spec.weight if type(spec) is SoftmaxCrossEntropy else None
+    if w is None:
+        return None
+    w = tuple(float(x) for x in w.detach().cpu().reshape(-1).tolist())
+    if channels is not None and len(w) != channels:
+        raise ValueError(f"loss {spec!r}: {len(w)} class weights for a head of {channels} channels")
+    if any(not x >= 0 for x in w):
+        raise ValueError(f"loss {spec!r}: class weights must be >= 0")
+    return w
 
 
 def _loss_kind(spec) -> int:
@@ -130,7 +156,7 @@ class MultiModal(nn.Module):
         self.decoder = nn.ModuleList([DecoderLayer(i, config.decoder.transformer) for i in range(self.n_dec_layers)])
         self.decoder_norm = nn.LayerNorm(self.hidden_size)
         # loss per modality (mm.py:79-82): 'ap' PoissonNLL(log_input), 'behavior' MSE — computed by mmfm_masked_loss_*; _loss_spec lists
-        # what an added or replaced entry may be
+        # what an added or replaced entry may be (a categorical modality: multi_modal.losses.SoftmaxCrossEntropy, mmfm_softmax_ce_*)
         self.loss_mod = {"ap": "poisson_nll_log_input", "behavior": "mse"}
 
         self._model_config = config
@@ -179,6 +205,9 @@ class MultiModal(nn.Module):
             cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
             cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
             cfg.loss_flags = {m: sp[2] for m, sp in specs.items()}
+            chans = dict(mods)
+            weights = {m: _loss_weight(self.loss_mod[m], chans[m]) for m in specs}
+            cfg.loss_weight = {m: w for m, w in weights.items() if w is not None}
             self._engine = Engine(cfg, dev, dtype=self.compute_dtype, seed=self.engine_seed)
             self._engine.adopt(named)
         elif not self._engine.owns(named):
