@@ -446,6 +446,35 @@ int mmfm_masked_loss_kind_bwd(int dtype, int kind, float param, int flags, const
                               const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const float* grad_out,
                               const float* inv_n, void* dpred, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- masked loss under a per-element mask
+ * Input masking (mask_type: input): the loss mask is per element, logically u8 [B][T][N], and is passed in whatever compact form the
+ * caller holds - a base pointer and three element strides, any of which may be 0: element (b,t,n) sits at
+ * mask[b*sb + t*st + n*sn].  A [B,1,N] tensor is (N, 0, 1), a [1,T,1] tensor (0, 1, 0), a full contiguous one (T*N, N, 1); nothing
+ * is expanded in memory.  pred [B*T][N] (dtype), target [B*T][N] fp32, every kind and flag of mmfm_masked_loss_kind_*.
+ *   fwd  loss_sum[0] = sum of the elements whose mask is set (fixed-order two-stage sum), count[0] = their exact number (int64; per-block
+ *        integer partials, summed by the second stage).  No memset, no floating-point atomic, the same bits on every call.  An element
+ *        whose mask is 0 is never loaded: a NaN or Inf there does not reach the sum.
+ *   bwd  dpred = grad_out[0] * inv_n[0] * d/dp on set elements, that factor times 0 on the others (exactly 0, or NaN when inv_n is inf).
+ * Rows, lanes and columns are walked as mmfm_masked_loss_kind_* walk them: an all-ones mask gives their bits with every row masked, a
+ * [B,T,1] mask their bits with that row mask.  workspace: mmfm_masked_loss_elem_workspace bytes, 8-byte aligned.
+ *
+ * mmfm_stage_masked: dst[b,t,n] = cm(b,t,n) ? 0 : src[b,t,n] for n < N - the staging copy of a batch's inputs with the masker's
+ * zeroing folded in.  src fp32 [B*T][N] contiguous, cm a strided mask as above, dst [B*T][ld_dst] of `dtype` (ld_dst >= N; columns
+ * N.. are not written).  16-byte accesses where N, ld_dst and the two base pointers allow.
+ *
+ * Argument checks (null pointers, dtype, kind / param / flags, sizes, negative strides, workspace) return -1 before any HIP call; no
+ * call allocates or synchronises.  MMFM_LOSS_ELEM is the feature macro for the four exports (MMFM_VERSION stays, as for MMFM_LOSS_KINDS). */
+#define MMFM_LOSS_ELEM 1
+int64_t mmfm_masked_loss_elem_workspace(int64_t R, int N);
+int mmfm_masked_loss_elem_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* mask, int64_t sb, int64_t st, int64_t sn, int B, int T, int N, float* loss_sum,
+                              int64_t* count, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_masked_loss_elem_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* mask, int64_t sb, int64_t st, int64_t sn, int B, int T, int N,
+                              const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream);
+int mmfm_stage_masked(int dtype, const float* src, const uint8_t* cm, int64_t sb, int64_t st, int64_t sn, int B, int T, int N,
+                      void* dst, int ld_dst, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- softmax cross-entropy (categorical modalities)
  * Kind 7, the one loss whose row elements are coupled (a log-sum-exp over the N classes of a row), with entry points of its own:
  * mmfm_masked_loss_kind_fwd / _bwd answer "bad kind" for it.  For logits p[c], targets t[c] (one-hot or any non-negative weights, not

@@ -191,6 +191,11 @@ _PROTOS = {
     "mmfm_loss_finalize": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mmfm_masked_loss_bwd": (C.c_int, [_i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "mmfm_masked_loss_kind_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
+    # per-element masks: base pointer + (sb, st, sn) element strides (MMFM_LOSS_ELEM)
+    "mmfm_masked_loss_elem_workspace": (C.c_int64, [_i64, _i]),
+    "mmfm_masked_loss_elem_fwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "mmfm_masked_loss_elem_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mmfm_stage_masked": (C.c_int, [_i, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _vp]),
     # softmax cross-entropy and the arg-max confusion matrix (MMFM_SOFTMAX_CE)
     "mmfm_softmax_ce_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_softmax_ce_fwd": (C.c_int, [_i, _vp, _vp, _vp, _f, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _i64, _vp]),

@@ -4,6 +4,7 @@
 // algorithmic bytes are (rows masked) * N * (sizeof(T) + 4).  fp32 accumulation, fixed-order
 // two-stage reduction (bitwise reproducible); n_examples is an exact int64 from mmfm_mask_prep.
 // The kind (and the Stirling flag) is a template parameter: the inner loop carries no per-element switch.
+// mmfm_masked_loss_elem_*: the same walk under a per-element mask given as a base pointer and three element strides (input masking).
 #include "common.h"
 #include <algorithm>
 #include <type_traits>
@@ -92,6 +93,68 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(float a, const T* __restr
             // unmasked rows: mask * g with mask = 0 - i.e. 0 normally, NaN when nothing at all is masked (g = grad / 0 = inf), which is
             // what upstream's (loss * mask).sum() / mask.sum() hands to autograd (mm.py:217-239): every gradient of that step is NaN there
             io<T>::st(dpred + o, on ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
+        }
+    }
+}
+
+// ---- per-element masks (MMFM_LOSS_ELEM): element (b, t, n) of the mask sits at base[b * sb + t * st + n * sn], any stride may be 0.
+// Rows, lanes and columns are walked exactly as in loss_fwd_kernel / loss_bwd_kernel, so an all-ones mask and a [B,T,1] mask give those
+// kernels' bits.  An element whose mask is 0 is never loaded.
+struct ElemMask {
+    const uint8_t* base;
+    int64_t sb, st, sn;
+};
+
+template <typename T, int KIND, bool FULL>
+__global__ __launch_bounds__(256) void loss_elem_fwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target, ElemMask mk,
+                                                            int Tn, int64_t R, int N, float* __restrict__ part, int64_t* __restrict__ cpart) {
+    __shared__ float red[4];
+    __shared__ long long cred[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float s = 0.f;
+    long long cnt = 0;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < R; row += (int64_t)gridDim.x * 4) {
+        const uint8_t* mrow = mk.base + (row / Tn) * mk.sb + (row % Tn) * mk.st;
+        for (int c = lane; c < N; c += 64) {
+            if (!mrow[c * mk.sn]) continue;
+            s += loss_elem<KIND, FULL>(io<T>::ld(pred + (size_t)row * N + c), target[(size_t)row * N + c], a);
+            ++cnt;
+        }
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) { red[wave] = s; cred[wave] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        cpart[blockIdx.x] = cred[0] + cred[1] + cred[2] + cred[3];
+    }
+}
+
+// second stage: the float partials in loss_sum_kernel's order, the integer partials exactly
+__global__ void loss_elem_sum_kernel(const float* __restrict__ part, const int64_t* __restrict__ cpart, int n, float* out, int64_t* count) {
+    float s = 0.f;
+    long long cnt = 0;
+    for (int i = threadIdx.x; i < n; i += 64) { s += part[i]; cnt += cpart[i]; }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (threadIdx.x == 0) { out[0] = s; count[0] = cnt; }
+}
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void loss_elem_bwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target, ElemMask mk,
+                                                            int Tn, int64_t R, int N, const float* __restrict__ grad_out,
+                                                            const float* __restrict__ inv_n, T* __restrict__ dpred) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float g = grad_out[0] * inv_n[0];
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < R; row += (int64_t)gridDim.x * 4) {
+        const uint8_t* mrow = mk.base + (row / Tn) * mk.sb + (row % Tn) * mk.st;
+        for (int c = lane; c < N; c += 64) {
+            const size_t o = (size_t)row * N + c;
+            // unset elements: g * 0 - 0 normally, NaN when nothing at all is set (g = grad / 0 = inf), as loss_bwd_kernel
+            io<T>::st(dpred + o, mrow[c * mk.sn] ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
         }
     }
 }
@@ -202,4 +265,67 @@ extern "C" int mmfm_masked_loss_kind_bwd(int dtype, int kind, float param, int f
     MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_kind_bwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
     MMFM_REQUIRE(R > 0 && N > 0 && T > 0 && R % T == 0 && mask_ld >= T, "mmfm_masked_loss_kind_bwd: bad arguments");
     return launch_bwd("mmfm_masked_loss_kind_bwd", dtype, kind, param, pred, target, rowmask, mask_ld, T, R, N, grad_out, inv_n, dpred, stream);
+}
+
+// ---- per-element masks.  workspace: loss_blocks(R) float partials, then (8-byte aligned) as many int64 count partials
+namespace {
+int64_t elem_cpart_offset(int64_t R) { return ((int64_t)loss_blocks(R) * (int64_t)sizeof(float) + 7) / 8 * 8; }
+bool elem_shape_ok(int B, int T, int N, int64_t sb, int64_t st, int64_t sn) { return B > 0 && T > 0 && N > 0 && sb >= 0 && st >= 0 && sn >= 0; }
+}  // namespace
+
+extern "C" int64_t mmfm_masked_loss_elem_workspace(int64_t R, int N) {
+    (void)N;
+    return elem_cpart_offset(R) + (int64_t)loss_blocks(R) * (int64_t)sizeof(int64_t);
+}
+
+extern "C" int mmfm_masked_loss_elem_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* mask, int64_t sb, int64_t st, int64_t sn, int B, int T, int N, float* loss_sum,
+                                         int64_t* count, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && mask && loss_sum && count, "mmfm_masked_loss_elem_fwd: null pointer");
+    MMFM_REQUIRE(dtype == MMFM_F32 || dtype == MMFM_BF16, "mmfm_masked_loss_elem_fwd: bad dtype %d", dtype);
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_elem_fwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(elem_shape_ok(B, T, N, sb, st, sn), "mmfm_masked_loss_elem_fwd: bad arguments");
+    const int64_t R = (int64_t)B * T;
+    MMFM_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= mmfm_masked_loss_elem_workspace(R, N),
+                 "mmfm_masked_loss_elem_fwd: workspace too small or not 8-byte aligned");
+    const int nb = loss_blocks(R);
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    int64_t* cpart = (int64_t*)((char*)workspace + elem_cpart_offset(R));
+    const ElemMask mk = {mask, sb, st, sn};
+    const int rc = with_loss(kind, (flags & MMFM_LOSS_FULL) != 0, [&](auto K) {
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_elem_fwd_kernel<float, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, s, param, (const float*)pred, target, mk, T, R, N, part, cpart);
+        else
+            hipLaunchKernelGGL((loss_elem_fwd_kernel<uint16_t, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, s, param, (const uint16_t*)pred, target, mk, T, R, N, part, cpart);
+        MMFM_LAUNCH_CHECK("mmfm_masked_loss_elem_fwd");
+        return 0;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_elem_sum_kernel, dim3(1), dim3(64), 0, s, (const float*)part, (const int64_t*)cpart, nb, loss_sum, count);
+    MMFM_LAUNCH_CHECK("mmfm_masked_loss_elem_fwd");
+    return 0;
+}
+
+extern "C" int mmfm_masked_loss_elem_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* mask, int64_t sb, int64_t st, int64_t sn, int B, int T, int N,
+                                         const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && mask && grad_out && inv_n && dpred, "mmfm_masked_loss_elem_bwd: null pointer");
+    MMFM_REQUIRE(dtype == MMFM_F32 || dtype == MMFM_BF16, "mmfm_masked_loss_elem_bwd: bad dtype %d", dtype);
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_elem_bwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(elem_shape_ok(B, T, N, sb, st, sn), "mmfm_masked_loss_elem_bwd: bad arguments");
+    const int64_t R = (int64_t)B * T;
+    const int nb = loss_blocks(R);
+    hipStream_t s = (hipStream_t)stream;
+    const ElemMask mk = {mask, sb, st, sn};
+    return with_loss(kind, false, [&](auto K) {            // the Stirling term has no gradient: one backward per kind
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_elem_bwd_kernel<float, Kd::kind>), dim3(nb), dim3(256), 0, s, param, (const float*)pred, target, mk, T, R, N, grad_out, inv_n, (float*)dpred);
+        else
+            hipLaunchKernelGGL((loss_elem_bwd_kernel<uint16_t, Kd::kind>), dim3(nb), dim3(256), 0, s, param, (const uint16_t*)pred, target, mk, T, R, N, grad_out, inv_n, (uint16_t*)dpred);
+        MMFM_LAUNCH_CHECK("mmfm_masked_loss_elem_bwd");
+        return 0;
+    });
 }

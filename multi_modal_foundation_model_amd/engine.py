@@ -29,7 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops as K
-from .plan import PlanBuilder, _align, read_switches
+from .plan import PlanBuilder, _align, elem_buf, read_switches
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
 HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention kernels are instantiated for (csrc/attention.hip check_common)
@@ -378,6 +378,9 @@ class Engine:
         # parameters need.  Per batch shape the MAX_PATTERNS most recently used patterns keep their plans and graphs
         self._pattern_lru: Dict[Tuple[int, int], list] = {}
         self._pattern = None
+        # ... and per element-mask pattern (`elem_key`: the compact shapes of each modality's corruption and target mask, whose strides
+        # are launch arguments of the plan): again the MAX_PATTERNS most recently used per batch shape
+        self._elem_lru: Dict[Tuple[int, int], list] = {}
         self.max_shapes = max(1, int(os.environ.get("MMFM_MAX_SHAPES", "4")))
         self._shared: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, torch.Tensor] = self._shared
@@ -480,6 +483,7 @@ class Engine:
                     del self.plans[pk]
                 del self._pools[old]
                 self._pattern_lru.pop(old, None)
+                self._elem_lru.pop(old, None)
             pool = dict(self._shared)
             self._pools[key] = pool
         if key in self._pool_lru:
@@ -629,13 +633,26 @@ class Engine:
         pattern = tuple(self.params[name].requires_grad for name in self.layout.entries)
         return None if all(pattern) else pattern
 
-    def _plan(self, B, T, training, grad=True, pattern=None):
+    def elem_key(self, elem):
+        """What an element-masked plan is keyed by besides the rest: per modality (cfg.mods order) None or the compact shapes of its
+        (corruption mask, target mask) - the broadcast pattern, since B, T and N are fixed.  None: no modality carries element masks."""
+        if elem is None or all(e is None for e in elem):
+            return None
+        if len(elem) != len(self.cfg.mods):
+            raise ValueError(f"engine: {len(self.cfg.mods)} modalities, {len(elem)} element-mask entries")
+        return tuple(None if e is None else (tuple(e[0].shape), tuple(e[1].shape)) for e in elem)
+
+    def _plan(self, B, T, training, grad=True, pattern=None, elem=None):
         """The cached step plan of (batch shape, mode, freeze pattern); built by plan.PlanBuilder the first time.
         grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward.
         pattern (`freeze_pattern`; None: all trainable, the key and the plan are what they always were): the plan's backward is pruned
-        to what the trainable parameters need.  A forward-only plan has no pattern."""
+        to what the trainable parameters need.  A forward-only plan has no pattern.
+        elem (`elem_key`; None: the key and the plan are what they always were): the modalities whose loss runs under a per-element
+        mask, with the masks' compact shapes."""
         pattern = pattern if grad else None
         key = (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))
+        if elem is not None:
+            key = (B, T, bool(training), bool(grad), pattern, elem)
         self._select_pool(B, T)
         if grad:
             lru = self._pattern_lru.setdefault((B, T), [])
@@ -649,7 +666,17 @@ class Engine:
                     del self.plans[pk]
         if key not in self.plans:
             frozen = None if pattern is None else [name for name, on in zip(self.layout.entries, pattern) if not on]
-            self.plans[key] = PlanBuilder(self, B, T, training, grad, frozen=frozen).build()
+            self.plans[key] = PlanBuilder(self, B, T, training, grad, frozen=frozen, elem=elem).build()
+        if elem is not None:                # (behind the build: a refused mask shape leaves no trace)
+            lru = self._elem_lru.setdefault((B, T), [])
+            if elem in lru:
+                lru.remove(elem)
+            lru.append(elem)
+            while len(lru) > MAX_PATTERNS:
+                old = lru.pop(0)
+                torch.cuda.synchronize(self.device)          # nothing may still be replaying the dropped graphs
+                for pk in [k for k in self.plans if k[:2] == (B, T) and len(k) > 5 and k[5] == old]:
+                    del self.plans[pk]
         return self.plans[key]
 
     def backward_report(self, B, T):
@@ -662,6 +689,13 @@ class Engine:
         Read-only, builds nothing and launches nothing: the plan must exist (one training forward ran at this shape and pattern)."""
         pattern = self.freeze_pattern()
         key = (B, T, True, True) + (() if pattern is None else (pattern,))
+        if key not in self.plans:
+            # element-masked plans (input masking) have keys of their own: the most recently used one of this shape and pattern.  Their
+            # backward differs from the plain plan's in the loss launches' entry points alone
+            for elem in reversed(self._elem_lru.get((B, T), [])):
+                if (B, T, True, True, pattern, elem) in self.plans:
+                    key = (B, T, True, True, pattern, elem)
+                    break
         if key not in self.plans:
             raise KeyError(f"backward_report({B}, {T}): no training plan of this shape under the current freeze pattern has been built yet")
         rep = self.plans[key]["report"]
@@ -724,14 +758,28 @@ class Engine:
         graph.replay()
 
     # ------------------------------------------------------------------ data in
-    def load_inputs(self, B, T, inputs, targets, masks, ts, attn):
+    def load_inputs(self, B, T, inputs, targets, masks, ts, attn, elem=None):
         """Copy one batch into the static input buffers (device tensors or host tensors).  T a tuple (a segmented plan): modality m
-        has T[m] bins and its own stamps ts[m] and attention mask attn[m]."""
+        has T[m] bins and its own stamps ts[m] and attention mask attn[m].  elem[m] = (cm, tm, corrupted or None): the modality's
+        element masks go into their static buffers, and its inputs are staged by mmfm_stage_masked - zeroed under cm on the way - or,
+        where the masker corrupted them itself, copied from `corrupted`."""
         seg = isinstance(T, tuple)
         dec = {m for m, _, _ in self.cfg.side_mods("decoder")}
         for m in sorted(dec | {m for m, _, _ in self.cfg.side_mods("encoder")}):      # (a modality no side has is not staged)
             Tm = T[m] if seg else T
-            self.b[f"in/{m}"].view(B, Tm, -1)[..., :inputs[m].shape[-1]].copy_(inputs[m], non_blocking=True)
+            e = elem[m] if elem is not None else None
+            if e is not None:
+                cm, tm, corrupted = e
+                cmb = self.b[elem_buf("cm", m, cm.shape)]
+                cmb.copy_(cm, non_blocking=True)
+                self.b[elem_buf("tm", m, tm.shape)].copy_(tm, non_blocking=True)
+            if e is not None and corrupted is None:
+                dst = self.b[f"in/{m}"]
+                src = inputs[m].to(self.device, torch.float32, non_blocking=True).contiguous()
+                K.stage_masked(src, cmb, B, Tm, src.shape[-1], dst, dst.shape[-1])
+            else:
+                x = inputs[m] if e is None else corrupted
+                self.b[f"in/{m}"].view(B, Tm, -1)[..., :x.shape[-1]].copy_(x, non_blocking=True)
             if m in dec:
                 self.b[f"tgt/{m}"].view(B, Tm, -1).copy_(targets[m], non_blocking=True)
             self.b[f"mask/{m}"].copy_(masks[m], non_blocking=True)
@@ -758,14 +806,19 @@ class Engine:
         return Ts, tss, attns
 
     # ------------------------------------------------------------------ run
-    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None):
-        """T: the number of bins, or a tuple of per-modality numbers in cfg.mods order; ts / attn: one tensor [B, T], or one per modality."""
+    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None, elem=None):
+        """T: the number of bins, or a tuple of per-modality numbers in cfg.mods order; ts / attn: one tensor [B, T], or one per modality.
+        elem (None: the call it always was): per modality, in cfg.mods order, None or (cm, tm, corrupted or None) - the corruption mask
+        and the target mask as uint8 tensors [B or 1, T or 1, N or 1] (Masker.element_masks) and, where the masker corrupted the inputs
+        itself, the corrupted inputs.  Such a modality's loss is summed over the set elements of tm and its count is their number;
+        its token mask (`masks`) is expected all zero.  DESIGN.md §3w."""
         T, ts, attn = self.batch_key(T, ts, attn)
         seg = isinstance(T, tuple)
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
         self._pattern = self.freeze_pattern() if want_grad else None          # read once per forward
-        plan = self._plan(B, T, training, want_grad, self._pattern)
-        self.load_inputs(B, T, inputs, targets, masks, ts, attn)
+        ekey = self.elem_key(elem)
+        plan = self._plan(B, T, training, want_grad, self._pattern, elem=ekey)
+        self.load_inputs(B, T, inputs, targets, masks, ts, attn, elem=None if ekey is None else elem)
         advance = training and any(sc.dropout > 0 or sc.embed_dropout > 0 for sc in map(self.cfg.side, ("encoder", "decoder")))
 
         def fwd_entries():

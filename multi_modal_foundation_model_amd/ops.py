@@ -293,6 +293,41 @@ def masked_loss_kind_bwd(kind, param, flags, pred, target, rowmask, mask_ld, T, 
                                                     P(grad_out), P(inv_n), P(dpred)))
 
 
+def elem_strides(mask, B, T, N):
+    """The (sb, st, sn) element strides of a per-element mask: a u8 tensor of three dimensions, each the full size (B, T, N) or 1 (a
+    broadcast dimension: stride 0).  The tensor itself is passed as it is - nothing is expanded in memory."""
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or any(s not in (1, full) for s, full in zip(mask.shape, (B, T, N))):
+        raise ValueError(f"element mask: a uint8 tensor of shape [{B} or 1, {T} or 1, {N} or 1], got {mask.dtype} {tuple(mask.shape)}")
+    return tuple(0 if s == 1 else int(st) for s, st in zip(mask.shape, mask.stride()))
+
+
+def masked_loss_elem_workspace(B, T, N):
+    return L.lib().mmfm_masked_loss_elem_workspace(B * T, N)
+
+
+def masked_loss_elem_fwd(kind, param, flags, pred, target, mask, B, T, N, loss_sum, count, ws, plan=None):
+    """Every elementwise MMFM_LOSS_* kind under a per-element mask (`elem_strides`): the masked sum to loss_sum[0], the exact number
+    of set elements to count[0] (int64).  ws: masked_loss_elem_workspace bytes."""
+    sb, st, sn = elem_strides(mask, B, T, N)
+    _emit(plan, L.lib().mmfm_masked_loss_elem_fwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(mask), sb, st, sn, B, T, N,
+                                                    P(loss_sum), P(count), P(ws), ws.numel() * ws.element_size()), keep=(mask,))
+
+
+def masked_loss_elem_bwd(kind, param, flags, pred, target, mask, B, T, N, grad_out, inv_n, dpred, plan=None):
+    sb, st, sn = elem_strides(mask, B, T, N)
+    _emit(plan, L.lib().mmfm_masked_loss_elem_bwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(mask), sb, st, sn, B, T, N,
+                                                    P(grad_out), P(inv_n), P(dpred)), keep=(mask,))
+
+
+def stage_masked(src, cm, B, T, N, dst, ld, plan=None):
+    """dst[b,t,n] = cm(b,t,n) ? 0 : src[b,t,n]: src fp32 [B, T, N] contiguous, cm a per-element mask (`elem_strides`), dst fp32 / bf16 rows
+    of pitch ld >= N (the padding columns are not written)."""
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("stage_masked: src must be a contiguous fp32 tensor")
+    sb, st, sn = elem_strides(cm, B, T, N)
+    _emit(plan, L.lib().mmfm_stage_masked, (dt(dst), P(src), P(cm), sb, st, sn, B, T, N, P(dst), ld), keep=(src, cm))
+
+
 def softmax_ce_fwd(pred, target, weight, eps, rowmask, mask_ld, T, R, N, loss_sum, rowstat, ws, plan=None):
     """Softmax cross-entropy (L.LOSS_SOFTMAX_CE) of [R, N] logits against fp32 targets: the masked sum to loss_sum[0].  weight: fp32 [N]
     class weights or None; eps: label smoothing; rowstat: fp32 [R, 2] for the backward's (lse, sum w t'), or None."""

@@ -76,11 +76,20 @@ class Side:
         self.use_keep = self.F_MLP = False
 
 
+def elem_buf(which, m, shape):
+    """The pool key of modality m's static element-mask buffer ("cm" / "tm") of compact shape `shape`: one buffer per broadcast pattern."""
+    return f"{which}/{m}/{'x'.join(str(int(s)) for s in shape)}"
+
+
 class PlanBuilder:
-    def __init__(self, engine, B, T, training, grad=True, frozen=None):
+    def __init__(self, engine, B, T, training, grad=True, frozen=None, elem=None):
         """frozen: the names (layout entries) of the parameters with requires_grad = False, or None / empty: everything is trainable and
-        the plan is the one it always was.  With frozen parameters the backward is pruned to what the others need."""
+        the plan is the one it always was.  With frozen parameters the backward is pruned to what the others need.
+        elem (Engine.elem_key; None: the plan it always was): per modality None or the compact shapes of its (corruption, target)
+        element masks.  Such a decoder modality's loss launches are mmfm_masked_loss_elem_* on its static target-mask buffer; they write
+        the modality's count behind mmfm_mask_prep.  Everything upstream of the heads is unchanged."""
         e, c = self.e, self.c = engine, engine.cfg
+        self.elem = elem
         self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
         self.frozen = frozenset(frozen) if frozen else None
         self.groups = {}             # gradient group -> (its launches are emitted, the parameters whose gradients they write) (`keep`)
@@ -290,6 +299,20 @@ class PlanBuilder:
             if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 need = max(need, L.lib().mmfm_softmax_ce_workspace(self.BTm[m], n))
         buf("ws/loss", (max(1, need // 4),), f32)
+        if self.elem is not None:
+            for m, shapes in enumerate(self.elem):
+                if shapes is None or m not in self.staged:
+                    continue
+                if c.loss_kind.get(c.mods[m][0]) == L.LOSS_SOFTMAX_CE and tuple(shapes[1]) != (B, self.Tm[m], 1):
+                    raise NotImplementedError(f"modality {c.mods[m][0]!r}: softmax cross-entropy couples its classes - it takes a target "
+                                              f"mask of shape [{B}, {self.Tm[m]}, 1] (one value per row), not {tuple(shapes[1])}")
+                for which, shape in zip(("cm", "tm"), shapes):
+                    if len(shape) != 3 or any(s not in (1, full) for s, full in zip(shape, (B, self.Tm[m], c.mods[m][1]))):
+                        raise ValueError(f"modality {c.mods[m][0]!r}: element mask of shape {tuple(shape)} for [{B}, {self.Tm[m]}, {c.mods[m][1]}]")
+                    buf(elem_buf(which, m, shape), tuple(shape), u8, zero=True)
+            # sized for the decoder's longest modality, whichever of them carry element masks: one size per pool
+            need = max(K.masked_loss_elem_workspace(B, self.Tm[m], n) for m, _, n in self.mods_of["decoder"])
+            buf("ws/loss_elem", (need // 4 + 2,), f32)
         # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
         # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
         # parked one alone.  Each product then makes half as many K-slabs (csrc/gemm_dw.hip).
@@ -516,6 +539,15 @@ class PlanBuilder:
                            d_o=K.P(d_o), lddo=H, dq=K.P(dq), dk=None if dkv is None else dkv.data_ptr() + dkoff * es,
                            dv=None if dkv is None else dkv.data_ptr() + dvoff * es, lddq=lddq, lddk=lddkv, lddv=lddkv, keepbits=keep)
 
+    def elem_tm(self, m):
+        """Modality m's static target-mask buffer where its loss runs under a per-element mask, else None."""
+        shapes = self.elem[m] if self.elem is not None else None
+        return None if shapes is None else self.b[elem_buf("tm", m, shapes[1])]
+
+    def loss_spec(self, mod):
+        c = self.c
+        return c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
+
     def loss(self, plan, mod, two_kind, kind_fn, *args):
         """A modality's masked loss, forward or backward.  PoissonNLL(log_input) / MSE without a flag go through the two-kind entry
         points (`two_kind`), call for call the plan it always was; every other elementwise kind through `kind_fn` with its float and
@@ -673,6 +705,17 @@ class PlanBuilder:
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             pred = buf(f"pred/{m}", (BT, n))
             self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            if self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+                # coupled classes: the [B,T,1] target mask IS a row mask of pitch T for the softmax cross-entropy kernels; the count -
+                # N per set row, as mmfm_mask_prep counts a token mask - comes from one element-mask launch whose sum is discarded
+                K.masked_loss_elem_fwd(L.LOSS_MSE, 0.0, 0, pred, b[f"tgt/{m}"], self.elem_tm(m), B, self.Tm[m], n, buf("loss_sum/unused", (1,), torch.float32),
+                                       b[mk("decoder", "count")][j:j + 1], b["ws/loss_elem"], plan=fwd)
+                self.softmax_ce(fwd, m, mod, pred, b[f"tgt/{m}"], self.elem_tm(m), self.Tm[m], self.Tm[m], BT, n, loss_sum=b["loss_sum"][j:j + 1], ws=b["ws/loss"])
+                continue
+            if self.elem_tm(m) is not None:       # per-element target mask: the sum and (behind mmfm_mask_prep) the modality's count
+                K.masked_loss_elem_fwd(*self.loss_spec(mod), pred, b[f"tgt/{m}"], self.elem_tm(m), B, self.Tm[m], n, b["loss_sum"][j:j + 1],
+                                       b[mk("decoder", "count")][j:j + 1], b["ws/loss_elem"], plan=fwd)
+                continue
             if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 self.softmax_ce(fwd, m, mod, pred, b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n, loss_sum=b["loss_sum"][j:j + 1], ws=b["ws/loss"])
                 continue
@@ -878,7 +921,12 @@ class PlanBuilder:
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             dpred = buf(f"d/pred/{m}", (BT, n))
-            if (norm or self.tl(f"decoder_embeddings.{mod}.out")) and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+            if (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+                self.softmax_ce(self.cur, m, mod, b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), self.Tm[m], self.Tm[m], BT, n, dpred=dpred)
+            elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None:
+                K.masked_loss_elem_bwd(*self.loss_spec(mod), b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), B, self.Tm[m], n,
+                                       b["gout"], b["inv_n"], dpred, plan=self.cur)
+            elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 self.softmax_ce(self.cur, m, mod, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:], Lq, self.Tm[m], BT, n, dpred=dpred)
             elif norm or self.tl(f"decoder_embeddings.{mod}.out"):
                 self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:],

@@ -12,7 +12,8 @@ Behavioural notes kept from the reference on purpose:
     upstream (the [B, Le, Le] encoder mask cannot be expanded to [B, h, Ld, Le]); here `forward` raises before any launch;
   * every modality has its own number of bins, its own `inputs_timestamp` and its own `inputs_attn_mask` (mm.py:97-158;
     encoder_embeddings.py:56-59); `mod_preds[mod]` is [B, T_mod, N_mod];
-  * `masking_mode` (mask_type: input) fails exactly like upstream (`mask` is never bound, mm.py:256-272).
+  * `masking_mode` (mask_type: input) fails exactly like upstream (`mask` is never bound, mm.py:256-272) - unless `input_masking`
+    is set: then the branch runs as upstream evidently meant it to (`_input_mask`).
 """
 import os
 from dataclasses import dataclass
@@ -21,7 +22,7 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from models.masker import Masker
+from models.masker import TOKEN_MODES, Masker
 from models.model_output import ModelOutput
 from multi_modal.decoder_embeddings import DecoderLayer
 from multi_modal.encoder_embeddings import EncoderLayer
@@ -32,6 +33,7 @@ from multi_modal_foundation_model_amd.engine import Engine, EngineConfig
 from utils.config_utils import DictConfig
 
 DEFAULT_CONFIG = "src/configs/multi_modal/mm.yaml"
+ROW_MODES = TOKEN_MODES + ("forward-pred",)      # the masking modes whose target mask is constant over the channels
 
 
 @dataclass
@@ -121,6 +123,7 @@ def _loss_kind(spec) -> int:
 
 
 class MultiModal(nn.Module):
+    input_masking = False        # the switch of mask_type: input (a class default, so that a module pickled before it existed has it too)
 
     def __init__(self, encoder_embeddings: Dict[str, nn.Module], decoder_embeddings: Dict[str, nn.Module],
                  avail_mod: List, config: DictConfig, share_modality_embeddings: bool = True, **kwargs):
@@ -165,6 +168,10 @@ class MultiModal(nn.Module):
         # "fp32": parity mode (fp32 MFMA); "bf16": throughput mode (bf16 storage/MFMA, fp32 accumulate + master weights)
         self.compute_dtype = os.environ.get("MMFM_DTYPE", "fp32")
         self.engine_seed = 0
+        # mask_type: input (a truthy `masking_mode` in mod_dict).  False: fails as upstream does.  True: upstream's evident intent - the
+        # masker's element masks corrupt the inputs and weigh the loss per element, no token is masked (`_input_mask`)
+        if "input_masking" in kwargs:
+            self.input_masking = bool(kwargs["input_masking"])
 
     def share_modality_embeddings(self):
         for mod in self.encoder_modalities & self.decoder_modalities:
@@ -228,12 +235,46 @@ class MultiModal(nn.Module):
         state["_sentinels"] = None
         return state
 
+    # ------------------------------------------------------------------ input masking (mask_type: input, `input_masking` on)
+    def _is_softmax_ce(self, mod):
+        return mod in self.decoder_embeddings and _loss_kind(self.loss_mod[mod]) == L.LOSS_SOFTMAX_CE
+
+    def _input_mask(self, mod, d, regions):
+        """One modality of the branch upstream leaves one line short (mm.py:256-272): sets `masker.mode`, draws the masker's corruption
+        mask cm and target mask tm in compact form (Masker.element_masks), leaves tm in d['spike_mask'] (int64 [B, T, N], an expanded
+        view) and returns what the engine stages and weighs the loss with: (cm, tm, corrupted inputs or None).  With zero_ratio == 1
+        the engine zeroes the cm elements on the device while it stages the batch and d['inputs'] stays the caller's tensor; for any
+        other zero_ratio d['inputs'] becomes the masker's corrupted copy, as upstream.  eval_mask is ignored, as upstream.
+        A modality without region information under inter-region / intra-region (upstream's masker asserts there) is left alone: no
+        draw, inputs untouched, an all-zero spike_mask, nothing added to either sum of the loss - returns None."""
+        mode = d['masking_mode']
+        self.masker.mode = mode
+        B, T, N = d['inputs'].shape
+        if mode in ("inter-region", "intra-region") and regions is None:
+            d['spike_mask'] = torch.zeros(1, 1, 1, dtype=torch.int64, device=d['inputs'].device).expand(B, T, N)
+            return None
+        cm, tm, corrupted = self.masker.element_masks(d['inputs'], regions)
+        d['spike_mask'] = tm.to(torch.int64).expand(B, T, N)
+        if self._is_softmax_ce(mod):          # the row mask of mmfm_softmax_ce_*: one byte per (b, t), pitch T
+            tm = tm.expand(B, T, 1).contiguous()
+        if corrupted is not None:
+            d['inputs'] = corrupted
+        return cm, tm, corrupted
+
     # ------------------------------------------------------------------ forward
     def forward(self, mod_dict: Dict[str, Dict[str, Any]]) -> MultiModalOutput:
         mods = list(mod_dict.keys())
         if mods != list(self.avail_mod):
             raise Exception(f"mod_dict modalities {mods} != avail_mod {list(self.avail_mod)}")
-        masks = []
+        masks, elem = [], {}
+        if self.input_masking:
+            # a softmax cross-entropy modality couples its classes: it takes a target mask only where the mask is constant over the
+            # channels (the token modes and forward-pred: a row mask).  Every other mode is refused before any draw or launch
+            for mod in mods:
+                mode = mod_dict[mod]['masking_mode']
+                if mode and self._is_softmax_ce(mod) and mode not in ROW_MODES:
+                    raise NotImplementedError(f"modality {mod!r}: masking mode {mode!r} under input_masking - a softmax cross-entropy "
+                                              f"modality couples its classes and takes a target mask per row only ({', '.join(ROW_MODES)})")
         for mod in mods:
             d = mod_dict[mod]
             if mod == 'behavior' and d['inputs'].dim() == 2:
@@ -245,6 +286,13 @@ class MultiModal(nn.Module):
             if d['inputs'].dim() != 3 or len(set(shapes.values())) != 1:
                 raise ValueError(f"modality {mod!r}: inputs / targets / mask / time stamps disagree in [batch, bins]: {shapes}")
             regions = d['inputs_regions'] if mod == 'ap' else None
+            if d['masking_mode'] and self.input_masking:
+                elem[mod] = self._input_mask(mod, d, regions)
+                mask = torch.zeros_like(d['inputs_attn_mask']) & d['inputs_attn_mask']       # the line upstream lacks: no token is masked
+                d['inputs_mask'] = d['targets_mask'] = mask
+                d['encoder_attn_mask'] = d['decoder_attn_mask'] = d['inputs_attn_mask']
+                masks.append(mask)
+                continue
             if d['masking_mode']:
                 self.masker.mode = d['masking_mode']
                 d['inputs'], d['spike_mask'] = self.masker(d['inputs'].clone(), regions)
@@ -284,7 +332,7 @@ class MultiModal(nn.Module):
             ts, attn = ([mod_dict[m][key] for m in mods] for key in ('inputs_timestamp', 'inputs_attn_mask'))
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
-                          training=self.training, anchor=self._grad_anchor())
+                          training=self.training, anchor=self._grad_anchor(), **({"elem": [elem.get(m) for m in mods]} if elem else {}))
         mod_loss, mod_n, preds, targets = {}, {}, {}, {}
         for i, mod in enumerate(dec_mods):      # the engine's outputs are the decoder's modalities, in this order
             mod_loss[mod], mod_n[mod] = out["mod_loss"][i], out["mod_n"][i]

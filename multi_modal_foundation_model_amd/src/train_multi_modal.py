@@ -59,6 +59,9 @@ def build_parser():
     # parameters get requires_grad = False before the optimiser is made; the engine then launches only the backward the others need
     ap.add_argument("--freeze", type=str, nargs="*", default=None,
                     help="fnmatch patterns of parameter names to freeze (overrides training.freeze of the trainer config)")
+    ap.add_argument("--input_masking", action="store_true",
+                    help="train with mask_type: input (training.mask_mode sampled per step; per-element corruption and loss masks) "
+                         "instead of failing on it as upstream does: sets training.mask_type = input and training.input_masking")
     return ap
 
 
@@ -80,6 +83,9 @@ def main(argv=None):
         config["training"]["num_epochs"] = args.epochs
     if args.grad_accum_steps is not None:
         config["optimizer"]["gradient_accumulation_steps"] = args.grad_accum_steps
+    if args.input_masking:
+        config["training"]["mask_type"] = "input"
+        config["training"]["input_masking"] = True
     set_seed(config.seed)
 
     avail_mod = list(AVAIL_MOD)

@@ -117,6 +117,13 @@ class MultiModalTrainer():
             self.masking_schemes = self.config.training.mask_mode
         else:
             self.masking_mode = None
+        # training.input_masking (no key of the reference's YAML: absent = false): run mask_type 'input' as upstream evidently meant it
+        # - per-element corruption and loss masks from the masker, MultiModal.input_masking - instead of failing as upstream does
+        input_masking = bool(self.config.training.get("input_masking", False)) if hasattr(self.config.training, "get") else False
+        if input_masking and self.config.training.mask_type != "input":
+            raise ValueError(f"training.input_masking: true needs training.mask_type: input (got {self.config.training.mask_type!r})")
+        if input_masking:
+            getattr(self.model, "module", self.model).input_masking = True       # (a DDP wrapper holds the model as .module)
         self.mixed_training = kwargs.get("mixed_training", False)
         if self.mixed_training:
             self.training_schemes = list(OBJECTIVES)
