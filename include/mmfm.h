@@ -365,7 +365,8 @@ int mmfm_stitch_bwd_live(int dtype, const void* dx, const void* dextra, const in
 int mmfm_mask_prep_seg(int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
                        const int64_t* const* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad,
                        uint8_t* keep0, uint8_t* mod_id, int64_t* count, mmfm_stream stream);
-/* mmfm_stitch_fwd / _bwd for the slot of T bins at offset off (off + T <= L):
+/* mmfm_stitch_fwd / _bwd for the slot of T bins at offset off (off + T <= L) - the same kernels at another offset: the uniform entry
+ * points are these at off = m * T:
  *   emb[b, off+t] = mod_emb[mod_row] + pos_emb[ts[b][t]],   x[b, off+t] = keep0[off+t] * tok[b*T+t] + emb[...]
  *   d_tok[b*T+t] = keep0[off+t] * dropout'(dx[b, off+t]);  d_mod_row (+)= sum_{b,t} (dx + dextra);  d_pos[ts[b][t]] (+)= dx + dextra
  * tok / d_tok are [B*T][H], ts is the slot's own [B][T].  The NULL pos_emb / d_pos contract (MMFM_EMBED_OPTS), acc_mod / acc_pos, the

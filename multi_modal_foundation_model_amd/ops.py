@@ -210,24 +210,35 @@ def mask_prep(B, T, masks, strides, attn, channels, tokmask, keypad, keep0, mod_
           keep=(src, st, ch))
 
 
+def _stitch_fwd(plan, fn, rec, tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, slot, H, max_F):
+    """The three stitch forwards: `rec` - (the live-bin record,) for mmfm_stitch_fwd_live, else () - sits behind keep0; `slot` is the
+    modality's index m (the uniform and live forms) or its first token (the segment form)."""
+    _emit(plan, fn, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), *map(P, rec), P(x), P(emb), B, T, Lseq, slot, H, max_F))
+
+
+def _stitch_bwd(plan, fn, rec, dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, slot, H, max_F, ws):
+    """The three stitch backwards; `rec` and `slot` as in _stitch_fwd."""
+    _emit(plan, fn, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), *map(P, rec), drop if drop is not None else L.NO_DROP,
+                     P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, slot, H, max_F, P(ws),
+                     ws.numel() * ws.element_size()))
+
+
 def stitch_fwd(tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, m, H, max_F, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_fwd, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(x), P(emb), B, T, Lseq, m, H, max_F))
+    _stitch_fwd(plan, L.lib().mmfm_stitch_fwd, (), tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, m, H, max_F)
 
 
 def stitch_fwd_live(tok, mod_row, pos, ts, keep0, rec, x, emb, B, T, Lseq, m, H, max_F, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_fwd_live, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(rec), P(x), P(emb), B, T, Lseq, m, H, max_F))
+    _stitch_fwd(plan, L.lib().mmfm_stitch_fwd_live, (rec,), tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, m, H, max_F)
 
 
 def stitch_bwd_live(dx, dextra, ts, keep0, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, m, H, max_F, ws, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_bwd_live, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), P(rec), drop if drop is not None else L.NO_DROP,
-                                               P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, m, H, max_F, P(ws),
-                                               ws.numel() * ws.element_size()))
+    _stitch_bwd(plan, L.lib().mmfm_stitch_bwd_live, (rec,), dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq,
+                m, H, max_F, ws)
 
 
 def stitch_bwd(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, m, H, max_F, ws, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_bwd, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), drop if drop is not None else L.NO_DROP,
-                                          P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, m, H, max_F, P(ws),
-                                          ws.numel() * ws.element_size()))
+    _stitch_bwd(plan, L.lib().mmfm_stitch_bwd, (), dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq,
+                m, H, max_F, ws)
 
 
 # ---- modality segments (MMFM_MOD_SEGMENTS): slot j of the stitched sequence has Ts[j] bins, its own stamps and attention mask
@@ -249,13 +260,12 @@ def mask_prep_seg(B, Ts, masks, strides, attns, channels, tokmask, keypad, keep0
 
 
 def stitch_fwd_seg(tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, off, H, max_F, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_fwd_seg, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep0), P(x), P(emb), B, T, Lseq, off, H, max_F))
+    _stitch_fwd(plan, L.lib().mmfm_stitch_fwd_seg, (), tok, mod_row, pos, ts, keep0, x, emb, B, T, Lseq, off, H, max_F)
 
 
 def stitch_bwd_seg(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, off, H, max_F, ws, plan=None):
-    _emit(plan, L.lib().mmfm_stitch_bwd_seg, (dt(dx), P(dx), P(dextra), P(ts), P(keep0), drop if drop is not None else L.NO_DROP,
-                                              P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod), int(acc_pos), B, T, Lseq, off, H, max_F, P(ws),
-                                              ws.numel() * ws.element_size()))
+    _stitch_bwd(plan, L.lib().mmfm_stitch_bwd_seg, (), dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq,
+                off, H, max_F, ws)
 
 
 def layernorm_fwd_seg(x, gamma, beta, y, mean, rstd, R, H, Ts, eps=1e-5, plan=None):

@@ -503,6 +503,32 @@ class PlanBuilder:
         K.layernorm_bwd(dY, X, b[tag + "/mean"], b[tag + "/rstd"], e.Pf(name + ".weight"), dres, dX,
                         e.Gv(name + ".weight"), e.Gv(name + ".bias"), R, H, b["ws/ln"], plan=plan, **kw)
 
+    def stitch_mode(self, side, slot):
+        """The stitch entry points of slot `slot` of `side` - segment, live-row or uniform - as the suffix of their names, and the
+        operands the three differ in: the slot's own stamps and offset, or the shared stamps and the slot index (and the live-bin record)."""
+        if self.seg:
+            return "_seg", dict(ts=self.b[f"ts/{self.mods_of[side][slot][0]}"], off=self.off[side][slot])
+        lv = self.lv.get((side, slot))
+        return ("", dict(ts=self.b["ts"], m=slot)) if lv is None else ("_live", dict(ts=self.b["ts"], m=slot, rec=lv._keep))
+
+    def stitch_f(self, plan, side, slot, tok, mod_row, pos, x, emb):
+        sfx, kw = self.stitch_mode(side, slot)
+        getattr(K, "stitch_fwd" + sfx)(tok=tok, mod_row=mod_row, pos=pos, keep0=self.b[self.mk(side, "keep0")], x=x, emb=emb, B=self.B,
+                                       T=self.Tm[self.mods_of[side][slot][0]], Lseq=self.Lq, H=self.H, max_F=self.sides[side].max_F,
+                                       plan=plan, **kw)
+
+    def stitch_b(self, plan, side, slot, dS, dextra, acc_mod):
+        """acc_mod: the modality's mod_emb gradient row is added to (the encoder side of a shared table), else overwritten."""
+        e, sd = self.e, self.sides[side]
+        m, mod, _ = self.mods_of[side][slot]
+        pS = f"{side}_embeddings.{mod}.embedder"
+        sfx, kw = self.stitch_mode(side, slot)
+        getattr(K, "stitch_bwd" + sfx)(dx=dS, dextra=dextra, keep0=self.b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe),
+                                       d_tok=self.buf(f"d/tok/{side}/{m}", (self.BTm[m], self.H)),
+                                       d_mod_row=e.Gv(f"{self.c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
+                                       d_pos=e.Gv(pS + ".pos_embed.weight") if sd.pos else None, acc_mod=acc_mod, acc_pos=False, B=self.B,
+                                       T=self.Tm[m], Lseq=self.Lq, H=self.H, max_F=sd.max_F, ws=self.b["ws/stitch"], plan=plan, **kw)
+
     def ln_lin(self, plan, Xin, lnname, wname, Yout, N, tag, residual=None, alias=None):
         """LayerNorm (or ScaleNorm) + the linear it feeds in one launch; x_hat / rstd saved for the backward when training.
         alias = tag of an earlier call on the SAME input: x_hat / rstd do not depend on the norm's affine / gain (it is folded
@@ -635,7 +661,7 @@ class PlanBuilder:
             for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 p = f"{side}_embeddings.{mod}.embedder"
                 n2 = n * sd.mult
-                BT, off = self.BTm[m], self.off[side][slot]
+                BT = self.BTm[m]
                 a = buf(f"{side}/a/{m}", (BT, n2))
                 # bf16 mode: the backward takes softsign' from the activation itself (act 5), no saved pre-activation (274 MB per
                 # tokeniser at B = 1024, written here and read back there); the fp32 parity path keeps the exact form
@@ -657,12 +683,7 @@ class PlanBuilder:
                 # row mod_to_indx[mod] of the table this tokeniser reads: its own, or the encoder's where the two share it
                 mod_row = e.Pf(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m]
                 pos = e.Pf(p + ".pos_embed.weight") if sd.pos else None            # embedder.pos: false -> emb = the modality row
-                if self.seg:
-                    K.stitch_fwd_seg(tok, mod_row, pos, b[f"ts/{m}"], b[mk(side, "keep0")], xs, es_, B, self.Tm[m], Lq, off, H, sd.max_F, plan=fwd)
-                elif lv is not None:
-                    K.stitch_fwd_live(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], lv._keep, xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
-                else:
-                    K.stitch_fwd(tok_tmp, mod_row, pos, b["ts"], b[mk(side, "keep0")], xs, es_, B, T, Lq, slot, H, sd.max_F, plan=fwd)
+                self.stitch_f(fwd, side, slot, tok, mod_row, pos, xs, es_)
         X = x_enc
         for i in range(c.n_enc):
             p, tag = f"encoder.{i}", f"enc{i}"
@@ -972,23 +993,9 @@ class PlanBuilder:
             sd = self.sides[side]
             for slot, (m, mod, n) in enumerate(self.mods_of[side]):
                 pS = f"{side}_embeddings.{mod}.embedder"
-                lv = self.lv.get((side, slot))
-                stitch = K.stitch_bwd if lv is None else functools.partial(K.stitch_bwd_live, rec=lv._keep)
-                BT = self.BTm[m]
                 emb = [f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight"] + ([pS + ".pos_embed.weight"] if sd.pos else [])
-                if not self.keep(pS + ".mod_emb+pos_embed", any(nd.tok[side, slot]), emb):
-                    continue
-                if self.seg:
-                    K.stitch_bwd_seg(dS, dextra, b[f"ts/{m}"], b[self.mk(side, "keep0")], e._drop(f"{side}/embdrop/{m}", sd.dpe),
-                                     buf(f"d/tok/{side}/{m}", (BT, H)), e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
-                                     e.Gv(pS + ".pos_embed.weight") if sd.pos else None, side == "encoder" and mod in shared, False, B, self.Tm[m], Lq,
-                                     self.off[side][slot], H, sd.max_F, b["ws/stitch"], plan=self.cur)
-                    continue
-                stitch(dS, dextra, b["ts"], b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe), d_tok=buf(f"d/tok/{side}/{m}", (BT, H)),
-                       d_mod_row=e.Gv(f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
-                       d_pos=e.Gv(pS + ".pos_embed.weight") if sd.pos else None,
-                       acc_mod=side == "encoder" and mod in shared, acc_pos=False, B=B, T=T, Lseq=Lq, m=slot, H=H, max_F=sd.max_F, ws=b["ws/stitch"],
-                       plan=self.cur)
+                if self.keep(pS + ".mod_emb+pos_embed", any(nd.tok[side, slot]), emb):
+                    self.stitch_b(self.cur, side, slot, dS, dextra, acc_mod=side == "encoder" and mod in shared)
         # the softsign gradient from the activation itself (bf16), or from the saved pre-activation (fp32, and every other activation)
         for side in ("decoder", "encoder"):
             sd = self.sides[side]

@@ -1,9 +1,12 @@
 """The modality-segment kernels (MMFM_MOD_SEGMENTS in include/mmfm.h) on the MI355X.
 
-At equal lengths, shared stamps and a shared attention mask every segment entry point must give the bits of its uniform counterpart:
-the segment arithmetic is the only difference between the two, so this is the cheapest place to catch an indexing error.  On ragged
-slots - lengths (8, 5, 1) and (1, 7), stamps with repeats and distinct per slot, per-slot padding - they are compared with the fp64
-references of tests/mod_segments_refs.py at the bounds tests/test_edge_kernels_gpu.py holds the uniform kernels to."""
+At equal lengths, shared stamps and a shared attention mask every segment entry point must give the bits of its uniform counterpart.
+For mask preparation and the stitch the two entry points run the same kernels (csrc/stitch.hip: one kernel set, the slot given by its
+offset), so there these tests guard the entry points' offset arithmetic - m * T against the segment's own offset, the slot table of
+mmfm_mask_prep against the one built from seg_T - not two kernels; for the LayerNorm it is the optional segment pack.  The independent
+evidence is on ragged slots - lengths (8, 5, 1) and (1, 7), stamps with repeats and distinct per slot, per-slot padding - where the
+segment entry points are compared with the fp64 references of tests/mod_segments_refs.py at the bounds tests/test_edge_kernels_gpu.py
+holds the uniform ones to."""
 import pytest
 import torch
 
@@ -75,6 +78,7 @@ def run_mask_prep_seg(ops, Ts, evals, attns, chans):
 
 
 # ------------------------------------------------------------------------------------------------- bit-identity at equal lengths
+# (mask prep and stitch: both entry points launch the same kernels, these guard the offsets and tables they hand them)
 def test_mask_prep_equal_lengths_is_uniform(ops):
     T, M, chans = 8, 2, [12, 2]
     evals, attns = mask_inputs((T,) * M, chans)
@@ -222,25 +226,66 @@ def test_stitch_ragged(ops, Ts, H, dtype, with_pos):
                 runs.append((d_tok, d_mod, d_pos))
             same_bits(runs[0][1], runs[1][1], f"{what}: d_mod_row of two calls")
             same_bits(runs[0][2], runs[1][2], f"{what}: d_pos of two calls")
-            d_tok, d_mod, d_pos = runs[0]
             r = S.stitch_bwd(dx, extra, tss[j], keep0, keep if with_drop else None, p, off[j], MAX_F)
-            sums = [("d_mod", d_mod, prior_mod, acc_mod, r["d_mod"], r["n_mod"], r["abs_mod"])]
-            if with_pos:
-                sums.append(("d_pos", d_pos, prior_pos, acc_pos, r["d_pos"], r["n_pos"], r["abs_pos"]))
-            else:
-                E.check_exact(d_pos, prior_pos, f"{what}: d_pos untouched without a table")
-            for name, out, prior, acc, ref, cnt, sabs in sums:
-                terr = E.U32 * sabs if with_extra else 0.0
-                if acc:
-                    ref, cnt, sabs = ref + E.f64(prior), cnt + 1, sabs + E.f64(prior).abs()
-                E.check_sum(out, ref, cnt, sabs, f"{what} {name}", term_err=terr)
-            if with_drop:
-                if dtype == BF16:
-                    E.check_bf16(d_tok, r["d_tok"], E.DROP_SCALE_REL * r["d_tok"].abs(), f"{what} d_tok")
-                else:
-                    E.check_close(d_tok, r["d_tok"], E.TOL_STITCH, f"{what} d_tok")
-            else:
-                E.check_exact(d_tok, r["d_tok"].to(dtype), f"{what} d_tok")
+            check_stitch_bwd(what, runs[0], (prior_mod, prior_pos), r, with_pos, with_extra, with_drop, acc_mod, acc_pos)
+
+
+def check_stitch_bwd(what, outs, priors, r, with_pos, with_extra, with_drop, acc_mod, acc_pos):
+    """(d_tok, d_mod, d_pos) of one stitch backward over (prior_mod, prior_pos) against the reference dict r, at edge_refs' bounds."""
+    (d_tok, d_mod, d_pos), (prior_mod, prior_pos) = outs, priors
+    sums = [("d_mod", d_mod, prior_mod, acc_mod, r["d_mod"], r["n_mod"], r["abs_mod"])]
+    if with_pos:
+        sums.append(("d_pos", d_pos, prior_pos, acc_pos, r["d_pos"], r["n_pos"], r["abs_pos"]))
+    else:
+        E.check_exact(d_pos, prior_pos, f"{what}: d_pos untouched without a table")
+    for name, out, prior, acc, ref, cnt, sabs in sums:
+        terr = E.U32 * sabs if with_extra else 0.0
+        if acc:
+            ref, cnt, sabs = ref + E.f64(prior), cnt + 1, sabs + E.f64(prior).abs()
+        E.check_sum(out, ref, cnt, sabs, f"{what} {name}", term_err=terr)
+    if with_drop:
+        if d_tok.dtype == BF16:
+            E.check_bf16(d_tok, r["d_tok"], E.DROP_SCALE_REL * r["d_tok"].abs(), f"{what} d_tok")
+        else:
+            E.check_close(d_tok, r["d_tok"], E.TOL_STITCH, f"{what} d_tok")
+    else:
+        E.check_exact(d_tok, r["d_tok"].to(d_tok.dtype), f"{what} d_tok")
+
+
+@pytest.mark.parametrize("with_pos", [True, False], ids=["table", "notable"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_stitch_bwd_many_samples(ops, dtype, with_pos):
+    """300 samples of two 2-bin slots at H = 32: more samples than the 256 slabs the bf16 column sum (no table) takes, so a slab sums
+    two samples and the last slab index is not B - 1, and for the per-column kernel (fp32) a grid of 300 chunks, inside the 512 its
+    chunk count is clamped to.  Both entry points at the second slot's offset as well as the first, against their own references."""
+    Bn, T, M, H, p = 300, 2, 2, 32, 0.2
+    L = M * T
+    dx, dextra = rnd(Bn, L, H, seed=240, dtype=dtype), rnd(Bn, L, H, seed=241, dtype=dtype)
+    keep0 = torch.tensor([1, 0, 1, 1], dtype=torch.uint8, device="cuda")
+    tss = [((torch.arange(T, device="cuda")[None, :] * (j + 2) + torch.arange(Bn, device="cuda")[:, None] * 3 + j) % (MAX_F + 2) - 1).contiguous()
+           for j in range(M)]                           # -1 .. MAX_F: every table row and both clamps
+    drop, keep, _state = dropout_of(ops, Bn * T, H, dtype, p)
+    code = ops.dt(dx)
+    nbytes = lib().mmfm_stitch_bwd_workspace(code, Bn, T, L, H, MAX_F)
+    assert nbytes > 0 and lib().mmfm_stitch_bwd_seg_workspace(code, Bn, T, L, T, H, MAX_F) == nbytes
+    for m in range(M):
+        for with_extra, with_drop, acc_mod, acc_pos in ((True, True, True, False), (False, False, False, True)):
+            extra = dextra if with_extra else None
+            refs = dict(stitch_bwd=E.stitch_bwd(dx, extra, tss[m], keep0, keep if with_drop else None, p, m, MAX_F),
+                        stitch_bwd_seg=S.stitch_bwd(dx, extra, tss[m], keep0, keep if with_drop else None, p, m * T, MAX_F))
+            prior_mod, prior_pos = rnd(H, seed=250), rnd(MAX_F, H, seed=251)
+            outs = {}
+            for entry, where in (("stitch_bwd", m), ("stitch_bwd_seg", m * T)):
+                what = f"{entry} B={Bn} slot {m} dextra={with_extra} drop={with_drop} acc=({acc_mod},{acc_pos})"
+                d_tok, d_mod, d_pos = nan(Bn * T, H, dtype=dtype), prior_mod.clone(), prior_pos.clone()
+                buf, ws = guarded(nbytes)
+                getattr(ops, entry)(dx, extra, tss[m] if with_pos else None, keep0, drop if with_drop else None, d_tok, d_mod,
+                                    d_pos if with_pos else None, acc_mod, acc_pos, Bn, T, L, where, H, MAX_F, ws)
+                assert bool((buf[nbytes:] == SENT).all()), f"{what}: wrote behind its {nbytes}-byte workspace"
+                outs[entry] = (d_tok, d_mod, d_pos)
+                check_stitch_bwd(what, outs[entry], (prior_mod, prior_pos), refs[entry], with_pos, with_extra, with_drop, acc_mod, acc_pos)
+            for name, a, b in zip(("d_tok", "d_mod", "d_pos"), outs["stitch_bwd_seg"], outs["stitch_bwd"]):
+                same_bits(a, b, f"stitch_bwd_seg and stitch_bwd at B={Bn} slot {m}: {name}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
