@@ -476,6 +476,31 @@ int mmfm_masked_loss_elem_bwd(int dtype, int kind, float param, int flags, const
 int mmfm_stage_masked(int dtype, const float* src, const uint8_t* cm, int64_t sb, int64_t st, int64_t sn, int B, int T, int N,
                       void* dst, int ld_dst, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- masked loss under a row mask x channel mask
+ * Padded neurons (space_attn_mask): the loss mask is the product of the [B,T] token mask and a [B,N] channel mask, kept as the two
+ * factors.  Element (row, c) with b = row / T, t = row % T is set iff rowmask[b*mask_ld + t] && chanmask[b*chan_ld + c]; mask_ld == 0
+ * is one row mask u8 [T] for all samples, chan_ld == 0 one channel mask u8 [N] for all samples (otherwise mask_ld >= T, chan_ld >= N).
+ * pred [R][N] (dtype), target [R][N] fp32, every kind and flag of mmfm_masked_loss_kind_* (kind 7 is "bad kind" here too).
+ *   fwd  loss_sum[0] = sum over the set elements (fixed-order two-stage sum), count[0] = their exact number (int64, integer partials).
+ *        A row whose rowmask is 0 is skipped without loading any of its pred / target; in a masked row an element whose channel bit is
+ *        0 is never loaded; a sample's channel-mask bytes are read once per masked row.  No memset, no floating-point atomic, no
+ *        allocation, no synchronisation; the same bits on every call.
+ *   bwd  writes every element of dpred: grad_out[0] * inv_n[0] * d/dp on set elements, that factor times 0 on the others (exactly 0, or
+ *        NaN when inv_n is inf).
+ * Rows, lanes and columns are walked as mmfm_masked_loss_kind_* walk them: an all-ones channel mask gives their bits (and count =
+ * masked rows x N), any mask pair the bits of mmfm_masked_loss_elem_* on the expanded [B,T,N] product.  workspace:
+ * mmfm_masked_loss_chan_workspace bytes, 8-byte aligned.  Argument checks (null pointers, dtype, kind / param / flags, sizes, negative
+ * leading dimensions, R % T != 0, workspace) return -1 before any HIP call.  MMFM_LOSS_CHAN is the feature macro for the three exports
+ * (MMFM_VERSION stays, as for MMFM_LOSS_KINDS). */
+#define MMFM_LOSS_CHAN 1
+int64_t mmfm_masked_loss_chan_workspace(int64_t R, int N);
+int mmfm_masked_loss_chan_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const uint8_t* chanmask, int chan_ld,
+                              float* loss_sum, int64_t* count, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_masked_loss_chan_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                              const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const uint8_t* chanmask, int chan_ld,
+                              const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- softmax cross-entropy (categorical modalities)
  * Kind 7, the one loss whose row elements are coupled (a log-sum-exp over the N classes of a row), with entry points of its own:
  * mmfm_masked_loss_kind_fwd / _bwd answer "bad kind" for it.  For logits p[c], targets t[c] (one-hot or any non-negative weights, not

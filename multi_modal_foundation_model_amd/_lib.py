@@ -196,6 +196,10 @@ _PROTOS = {
     "mmfm_masked_loss_elem_fwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "mmfm_masked_loss_elem_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mmfm_stage_masked": (C.c_int, [_i, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _vp]),
+    # row mask x channel mask (MMFM_LOSS_CHAN)
+    "mmfm_masked_loss_chan_workspace": (C.c_int64, [_i64, _i]),
+    "mmfm_masked_loss_chan_fwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "mmfm_masked_loss_chan_bwd": (C.c_int, [_i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     # softmax cross-entropy and the arg-max confusion matrix (MMFM_SOFTMAX_CE)
     "mmfm_softmax_ce_workspace": (C.c_int64, [_i64, _i]),
     "mmfm_softmax_ce_fwd": (C.c_int, [_i, _vp, _vp, _vp, _f, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _i64, _vp]),

@@ -5,6 +5,7 @@
 // two-stage reduction (bitwise reproducible); n_examples is an exact int64 from mmfm_mask_prep.
 // The kind (and the Stirling flag) is a template parameter: the inner loop carries no per-element switch.
 // mmfm_masked_loss_elem_*: the same walk under a per-element mask given as a base pointer and three element strides (input masking).
+// mmfm_masked_loss_chan_*: the same walk under the product of a [B,T] row mask and a [B,N] channel mask (padded neurons).
 #include "common.h"
 #include <algorithm>
 #include <type_traits>
@@ -155,6 +156,88 @@ __global__ __launch_bounds__(256) void loss_elem_bwd_kernel(float a, const T* __
             const size_t o = (size_t)row * N + c;
             // unset elements: g * 0 - 0 normally, NaN when nothing at all is set (g = grad / 0 = inf), as loss_bwd_kernel
             io<T>::st(dpred + o, mrow[c * mk.sn] ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
+        }
+    }
+}
+
+// ---- row mask x channel mask (MMFM_LOSS_CHAN): element (row, c) is set iff rowmask[b * mask_ld + t] && chanmask[b * chan_ld + c], either
+// leading dimension may be 0 (one mask for all samples).  The walk is loss_fwd_kernel's, so an all-ones channel mask gives its bits, and
+// loss_elem_fwd_kernel's on the expanded product.  An unmasked row costs its one mask byte; in a masked row a cleared channel is never loaded.
+// Up to 32 columns per lane (N <= 2048) the lane's bits of the sample's channel-mask row are gathered into one register: bit k = column
+// lane + 64 k.  Each byte is still read once per row; wider rows read their byte inside the walk.
+constexpr int CHAN_BITS_MAX = 64 * 32;
+__device__ __forceinline__ uint32_t chan_bits(const uint8_t* __restrict__ crow, int lane, int N) {
+    uint32_t bits = 0;
+    for (int c = lane, k = 0; c < N; c += 64, ++k) bits |= (crow[c] ? 1u : 0u) << k;
+    return bits;
+}
+
+template <typename T, int KIND, bool FULL>
+__global__ __launch_bounds__(256) void loss_chan_fwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target,
+                                                            const uint8_t* __restrict__ rowmask, int mask_ld, int Tn, int64_t R, int N,
+                                                            const uint8_t* __restrict__ chanmask, int chan_ld, float* __restrict__ part,
+                                                            int64_t* __restrict__ cpart) {
+    __shared__ float red[4];
+    __shared__ long long cred[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float s = 0.f;
+    long long cnt = 0;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < R; row += (int64_t)gridDim.x * 4) {
+        const int64_t bi = row / Tn;
+        if (!rowmask[bi * mask_ld + (row % Tn)]) continue;
+        const uint8_t* crow = chanmask + bi * chan_ld;
+        if (N <= CHAN_BITS_MAX) {             // the lane's channel bits first, in one batch of independent byte loads: no load of the walk waits for a mask byte
+            const uint32_t bits = chan_bits(crow, lane, N);
+            for (int c = lane, k = 0; c < N; c += 64, ++k) {
+                if (!((bits >> k) & 1u)) continue;
+                s += loss_elem<KIND, FULL>(io<T>::ld(pred + (size_t)row * N + c), target[(size_t)row * N + c], a);
+                ++cnt;
+            }
+            continue;
+        }
+        for (int c = lane; c < N; c += 64) {
+            if (!crow[c]) continue;
+            s += loss_elem<KIND, FULL>(io<T>::ld(pred + (size_t)row * N + c), target[(size_t)row * N + c], a);
+            ++cnt;
+        }
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) { red[wave] = s; cred[wave] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        cpart[blockIdx.x] = cred[0] + cred[1] + cred[2] + cred[3];
+    }
+}
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void loss_chan_bwd_kernel(float a, const T* __restrict__ pred, const float* __restrict__ target,
+                                                            const uint8_t* __restrict__ rowmask, int mask_ld, int Tn, int64_t R, int N,
+                                                            const uint8_t* __restrict__ chanmask, int chan_ld,
+                                                            const float* __restrict__ grad_out, const float* __restrict__ inv_n,
+                                                            T* __restrict__ dpred) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float g = grad_out[0] * inv_n[0];
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < R; row += (int64_t)gridDim.x * 4) {
+        const int64_t bi = row / Tn;
+        const uint8_t* crow = chanmask + bi * chan_ld;
+        if (!rowmask[bi * mask_ld + (row % Tn)]) {          // g * 0: 0 normally, NaN when nothing at all is set, as loss_bwd_kernel
+            for (int c = lane; c < N; c += 64) io<T>::st(dpred + (size_t)row * N + c, g * 0.f);
+            continue;
+        }
+        if (N <= CHAN_BITS_MAX) {
+            const uint32_t bits = chan_bits(crow, lane, N);
+            for (int c = lane, k = 0; c < N; c += 64, ++k) {
+                const size_t o = (size_t)row * N + c;
+                io<T>::st(dpred + o, ((bits >> k) & 1u) ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
+            }
+            continue;
+        }
+        for (int c = lane; c < N; c += 64) {
+            const size_t o = (size_t)row * N + c;
+            io<T>::st(dpred + o, crow[c] ? g * loss_grad<KIND>(io<T>::ld(pred + o), target[o], a) : g * 0.f);
         }
     }
 }
@@ -326,6 +409,64 @@ extern "C" int mmfm_masked_loss_elem_bwd(int dtype, int kind, float param, int f
         else
             hipLaunchKernelGGL((loss_elem_bwd_kernel<uint16_t, Kd::kind>), dim3(nb), dim3(256), 0, s, param, (const uint16_t*)pred, target, mk, T, R, N, grad_out, inv_n, (uint16_t*)dpred);
         MMFM_LAUNCH_CHECK("mmfm_masked_loss_elem_bwd");
+        return 0;
+    });
+}
+
+// ---- row mask x channel mask.  The workspace is the per-element form's: float partials, then int64 count partials
+namespace {
+// shared by both entry points: everything but the pointers and the workspace
+bool chan_shape_ok(int mask_ld, int T, int64_t R, int N, int chan_ld) {
+    return R > 0 && N > 0 && T > 0 && R % T == 0 && (mask_ld == 0 || mask_ld >= T) && (chan_ld == 0 || chan_ld >= N);
+}
+}  // namespace
+
+extern "C" int64_t mmfm_masked_loss_chan_workspace(int64_t R, int N) { return mmfm_masked_loss_elem_workspace(R, N); }
+
+extern "C" int mmfm_masked_loss_chan_fwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const uint8_t* chanmask, int chan_ld,
+                                         float* loss_sum, int64_t* count, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && rowmask && chanmask && loss_sum && count, "mmfm_masked_loss_chan_fwd: null pointer");
+    MMFM_REQUIRE(dtype == MMFM_F32 || dtype == MMFM_BF16, "mmfm_masked_loss_chan_fwd: bad dtype %d", dtype);
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_chan_fwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(chan_shape_ok(mask_ld, T, R, N, chan_ld), "mmfm_masked_loss_chan_fwd: bad arguments");
+    MMFM_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= mmfm_masked_loss_chan_workspace(R, N),
+                 "mmfm_masked_loss_chan_fwd: workspace too small or not 8-byte aligned");
+    const int nb = loss_blocks(R);
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    int64_t* cpart = (int64_t*)((char*)workspace + elem_cpart_offset(R));
+    const int rc = with_loss(kind, (flags & MMFM_LOSS_FULL) != 0, [&](auto K) {
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_chan_fwd_kernel<float, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, s, param, (const float*)pred, target, rowmask, mask_ld, T, R, N, chanmask, chan_ld, part, cpart);
+        else
+            hipLaunchKernelGGL((loss_chan_fwd_kernel<uint16_t, Kd::kind, Kd::full>), dim3(nb), dim3(256), 0, s, param, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, chanmask, chan_ld, part, cpart);
+        MMFM_LAUNCH_CHECK("mmfm_masked_loss_chan_fwd");
+        return 0;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_elem_sum_kernel, dim3(1), dim3(64), 0, s, (const float*)part, (const int64_t*)cpart, nb, loss_sum, count);
+    MMFM_LAUNCH_CHECK("mmfm_masked_loss_chan_fwd");
+    return 0;
+}
+
+extern "C" int mmfm_masked_loss_chan_bwd(int dtype, int kind, float param, int flags, const void* pred, const float* target,
+                                         const uint8_t* rowmask, int mask_ld, int T, int64_t R, int N, const uint8_t* chanmask, int chan_ld,
+                                         const float* grad_out, const float* inv_n, void* dpred, mmfm_stream stream) {
+    MMFM_REQUIRE(pred && target && rowmask && chanmask && grad_out && inv_n && dpred, "mmfm_masked_loss_chan_bwd: null pointer");
+    MMFM_REQUIRE(dtype == MMFM_F32 || dtype == MMFM_BF16, "mmfm_masked_loss_chan_bwd: bad dtype %d", dtype);
+    MMFM_REQUIRE(loss_kind_ok(kind, param, flags), "mmfm_masked_loss_chan_bwd: bad kind %d / param %g / flags %d", kind, (double)param, flags);
+    MMFM_REQUIRE(chan_shape_ok(mask_ld, T, R, N, chan_ld), "mmfm_masked_loss_chan_bwd: bad arguments");
+    const int nb = loss_blocks(R);
+    hipStream_t s = (hipStream_t)stream;
+    return with_loss(kind, false, [&](auto K) {            // the Stirling term has no gradient: one backward per kind
+        using Kd = decltype(K);
+        if (dtype == MMFM_F32)
+            hipLaunchKernelGGL((loss_chan_bwd_kernel<float, Kd::kind>), dim3(nb), dim3(256), 0, s, param, (const float*)pred, target, rowmask, mask_ld, T, R, N, chanmask, chan_ld, grad_out, inv_n, (float*)dpred);
+        else
+            hipLaunchKernelGGL((loss_chan_bwd_kernel<uint16_t, Kd::kind>), dim3(nb), dim3(256), 0, s, param, (const uint16_t*)pred, target, rowmask, mask_ld, T, R, N, chanmask, chan_ld, grad_out, inv_n, (uint16_t*)dpred);
+        MMFM_LAUNCH_CHECK("mmfm_masked_loss_chan_bwd");
         return 0;
     });
 }

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops as K
-from .plan import PlanBuilder, _align, elem_buf, read_switches
+from .plan import PlanBuilder, _align, chan_buf, combine_chan, elem_buf, mask_key, read_switches
 
 LOSS_KIND = {"ap": 0, "behavior": 1}       # mm.py:79-82: PoissonNLL(log_input) / MSE
 HEAD_DIMS = (8, 16, 32, 64, 128)           # hidden_size / n_heads the attention kernels are instantiated for (csrc/attention.hip check_common)
@@ -640,16 +640,43 @@ class Engine:
             return None
         if len(elem) != len(self.cfg.mods):
             raise ValueError(f"engine: {len(self.cfg.mods)} modalities, {len(elem)} element-mask entries")
-        return tuple(None if e is None else (tuple(e[0].shape), tuple(e[1].shape)) for e in elem)
+        return tuple(None if e is None else (tuple(e[0].shape), None if e[1] is None else tuple(e[1].shape)) for e in elem)
 
-    def _plan(self, B, T, training, grad=True, pattern=None, elem=None):
+    def fold_chan(self, B, T, elem, chan):
+        """Folds the channel masks `chan` (per modality None or u8 [B or 1, N]; neuron padding) into the element masks:
+        returns (elem', chan', padded) with plan.combine_chan applied per modality - elem' carries every such modality's staging mask,
+        chan' the channel mask of those whose loss runs the chan form, padded the modalities that came with a channel mask.  chan None
+        or all None: (elem, None, ()), the call it always was."""
+        if chan is None or all(v is None for v in chan):
+            return elem, None, ()
+        mods = self.cfg.mods
+        if len(chan) != len(mods) or (elem is not None and len(elem) != len(mods)):
+            raise ValueError(f"engine: {len(mods)} modalities, {len(chan)} channel-mask entries")
+        elem = list(elem) if elem is not None else [None] * len(mods)
+        out = [None] * len(mods)
+        for m, v in enumerate(chan):
+            if v is not None:
+                if elem[m] is not None and torch.is_tensor(v) and v.device != elem[m][0].device:      # the masker's masks live where it drew them
+                    v = v.to(elem[m][0].device)
+                elem[m], out[m] = combine_chan(elem[m], v, B, T[m] if isinstance(T, tuple) else T, mods[m][1])
+        return elem, (None if all(v is None for v in out) else out), tuple(m for m, v in enumerate(chan) if v is not None)
+
+    @staticmethod
+    def chan_key(chan):
+        """What a channel-masked plan is keyed by besides the rest: per modality None or the shape of its channel mask."""
+        return None if chan is None else tuple(None if v is None else tuple(v.shape) for v in chan)
+
+    def _plan(self, B, T, training, grad=True, pattern=None, elem=None, chan=None):
         """The cached step plan of (batch shape, mode, freeze pattern); built by plan.PlanBuilder the first time.
         grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward.
         pattern (`freeze_pattern`; None: all trainable, the key and the plan are what they always were): the plan's backward is pruned
         to what the trainable parameters need.  A forward-only plan has no pattern.
         elem (`elem_key`; None: the key and the plan are what they always were): the modalities whose loss runs under a per-element
-        mask, with the masks' compact shapes."""
+        mask, with the masks' compact shapes.
+        chan (`chan_key`; None: the key and the plan are what they always were): the modalities whose loss runs under a channel mask.
+        Such plans are pooled with the element-masked ones, under `mask_key`."""
         pattern = pattern if grad else None
+        elem_arg, elem = elem, mask_key(elem, chan)
         key = (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))
         if elem is not None:
             key = (B, T, bool(training), bool(grad), pattern, elem)
@@ -666,7 +693,7 @@ class Engine:
                     del self.plans[pk]
         if key not in self.plans:
             frozen = None if pattern is None else [name for name, on in zip(self.layout.entries, pattern) if not on]
-            self.plans[key] = PlanBuilder(self, B, T, training, grad, frozen=frozen, elem=elem).build()
+            self.plans[key] = PlanBuilder(self, B, T, training, grad, frozen=frozen, elem=elem_arg, chan=chan).build()
         if elem is not None:                # (behind the build: a refused mask shape leaves no trace)
             lru = self._elem_lru.setdefault((B, T), [])
             if elem in lru:
@@ -758,11 +785,14 @@ class Engine:
         graph.replay()
 
     # ------------------------------------------------------------------ data in
-    def load_inputs(self, B, T, inputs, targets, masks, ts, attn, elem=None):
+    def load_inputs(self, B, T, inputs, targets, masks, ts, attn, elem=None, chan=None, padded=()):
         """Copy one batch into the static input buffers (device tensors or host tensors).  T a tuple (a segmented plan): modality m
         has T[m] bins and its own stamps ts[m] and attention mask attn[m].  elem[m] = (cm, tm, corrupted or None): the modality's
         element masks go into their static buffers, and its inputs are staged by mmfm_stage_masked - zeroed under cm on the way - or,
-        where the masker corrupted them itself, copied from `corrupted`."""
+        where the masker corrupted them itself, copied from `corrupted`.  chan[m] (with elem[m] from `combine_chan`: tm may be None):
+        the modality's channel mask goes into its static buffer.  padded: the modalities whose cm holds padded channels (`fold_chan`) -
+        their inputs are always staged by mmfm_stage_masked; for `corrupted` inputs cm is the padding alone (plan.combine_chan), so the
+        masker's noise and kept values stay and only the padded channels are zeroed."""
         seg = isinstance(T, tuple)
         dec = {m for m, _, _ in self.cfg.side_mods("decoder")}
         for m in sorted(dec | {m for m, _, _ in self.cfg.side_mods("encoder")}):      # (a modality no side has is not staged)
@@ -772,10 +802,13 @@ class Engine:
                 cm, tm, corrupted = e
                 cmb = self.b[elem_buf("cm", m, cm.shape)]
                 cmb.copy_(cm, non_blocking=True)
-                self.b[elem_buf("tm", m, tm.shape)].copy_(tm, non_blocking=True)
-            if e is not None and corrupted is None:
+                if tm is not None:
+                    self.b[elem_buf("tm", m, tm.shape)].copy_(tm, non_blocking=True)
+            if chan is not None and chan[m] is not None:
+                self.b[chan_buf(m, chan[m].shape)].copy_(chan[m], non_blocking=True)
+            if e is not None and (corrupted is None or m in padded):
                 dst = self.b[f"in/{m}"]
-                src = inputs[m].to(self.device, torch.float32, non_blocking=True).contiguous()
+                src = (inputs[m] if corrupted is None else corrupted).to(self.device, torch.float32, non_blocking=True).contiguous()
                 K.stage_masked(src, cmb, B, Tm, src.shape[-1], dst, dst.shape[-1])
             else:
                 x = inputs[m] if e is None else corrupted
@@ -806,19 +839,23 @@ class Engine:
         return Ts, tss, attns
 
     # ------------------------------------------------------------------ run
-    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None, elem=None):
+    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None, elem=None, chan=None):
         """T: the number of bins, or a tuple of per-modality numbers in cfg.mods order; ts / attn: one tensor [B, T], or one per modality.
         elem (None: the call it always was): per modality, in cfg.mods order, None or (cm, tm, corrupted or None) - the corruption mask
         and the target mask as uint8 tensors [B or 1, T or 1, N or 1] (Masker.element_masks) and, where the masker corrupted the inputs
         itself, the corrupted inputs.  Such a modality's loss is summed over the set elements of tm and its count is their number;
-        its token mask (`masks`) is expected all zero.  DESIGN.md §3w."""
+        its token mask (`masks`) is expected all zero.  DESIGN.md §3w.
+        chan (None, or all None: the call it always was): per modality, in cfg.mods order, None or its channel mask, uint8 [B, N] or
+        [1, N], 1 = a real channel.  Such a modality's inputs are zeroed in the other channels on both sides, its loss is summed over
+        row mask x channel mask and its count is the number of those elements.  DESIGN.md §3x."""
         T, ts, attn = self.batch_key(T, ts, attn)
         seg = isinstance(T, tuple)
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
         self._pattern = self.freeze_pattern() if want_grad else None          # read once per forward
+        elem, chan, padded = self.fold_chan(B, T, elem, chan)
         ekey = self.elem_key(elem)
-        plan = self._plan(B, T, training, want_grad, self._pattern, elem=ekey)
-        self.load_inputs(B, T, inputs, targets, masks, ts, attn, elem=None if ekey is None else elem)
+        plan = self._plan(B, T, training, want_grad, self._pattern, elem=ekey, chan=self.chan_key(chan))
+        self.load_inputs(B, T, inputs, targets, masks, ts, attn, elem=None if ekey is None else elem, chan=chan, padded=padded)
         advance = training and any(sc.dropout > 0 or sc.embed_dropout > 0 for sc in map(self.cfg.side, ("encoder", "decoder")))
 
         def fwd_entries():

@@ -338,6 +338,30 @@ def stage_masked(src, cm, B, T, N, dst, ld, plan=None):
     _emit(plan, L.lib().mmfm_stage_masked, (dt(dst), P(src), P(cm), sb, st, sn, B, T, N, P(dst), ld), keep=(src, cm))
 
 
+def chan_ld(chanmask, N):
+    """The leading dimension of a channel mask: a contiguous u8 [B, N] tensor (N) or one [1, N] mask for all samples (0)."""
+    if chanmask.dtype != torch.uint8 or chanmask.dim() != 2 or chanmask.shape[1] != N or not chanmask.is_contiguous():
+        raise ValueError(f"channel mask: a contiguous uint8 tensor of shape [B or 1, {N}], got {chanmask.dtype} {tuple(chanmask.shape)}")
+    return 0 if chanmask.shape[0] == 1 else N
+
+
+def masked_loss_chan_workspace(R, N):
+    return L.lib().mmfm_masked_loss_chan_workspace(R, N)
+
+
+def masked_loss_chan_fwd(kind, param, flags, pred, target, rowmask, mask_ld, T, R, N, chanmask, loss_sum, count, ws, plan=None):
+    """Every elementwise MMFM_LOSS_* kind under rowmask[b, t] & chanmask[b, c] (`chan_ld`; mask_ld 0: one row mask for all samples): the
+    sum to loss_sum[0], the exact number of set elements to count[0] (int64).  ws: masked_loss_chan_workspace bytes."""
+    _emit(plan, L.lib().mmfm_masked_loss_chan_fwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(rowmask), mask_ld, T, R, N,
+                                                    P(chanmask), chan_ld(chanmask, N), P(loss_sum), P(count), P(ws),
+                                                    ws.numel() * ws.element_size()), keep=(chanmask,))
+
+
+def masked_loss_chan_bwd(kind, param, flags, pred, target, rowmask, mask_ld, T, R, N, chanmask, grad_out, inv_n, dpred, plan=None):
+    _emit(plan, L.lib().mmfm_masked_loss_chan_bwd, (dt(pred), kind, float(param), flags, P(pred), P(target), P(rowmask), mask_ld, T, R, N,
+                                                    P(chanmask), chan_ld(chanmask, N), P(grad_out), P(inv_n), P(dpred)), keep=(chanmask,))
+
+
 def softmax_ce_fwd(pred, target, weight, eps, rowmask, mask_ld, T, R, N, loss_sum, rowstat, ws, plan=None):
     """Softmax cross-entropy (L.LOSS_SOFTMAX_CE) of [R, N] logits against fp32 targets: the masked sum to loss_sum[0].  weight: fp32 [N]
     class weights or None; eps: label smoothing; rowstat: fp32 [R, 2] for the backward's (lse, sum w t'), or None."""

@@ -81,15 +81,55 @@ def elem_buf(which, m, shape):
     return f"{which}/{m}/{'x'.join(str(int(s)) for s in shape)}"
 
 
+def chan_buf(m, shape):
+    """The pool key of modality m's static channel-mask buffer (u8 [B or 1, N]; 1 = a real channel): one buffer per shape, as `elem_buf`."""
+    return f"chan/{m}/{'x'.join(str(int(s)) for s in shape)}"
+
+
+def combine_chan(entry, v, B, T, N):
+    """A modality's element masks under its channel mask v (u8 [B or 1, N], 1 = a real channel; neuron padding), on
+    whatever device the tensors live: pure tensor arithmetic on compact shapes, nothing is expanded beyond what the result needs.
+    entry: None or (cm, tm, corrupted or None), the masks u8 [B or 1, T or 1, N or 1] (Masker.element_masks).  Returns (entry', chan):
+      cm'   - what mmfm_stage_masked zeroes.  Where the engine does the masker's zeroing (corrupted is None): cm | (1 - v)[:, None, :],
+              the masker's elements and every padded channel; its shape is the broadcast of the two, so a [B,T,1] / [1,T,1]
+              corruption mask becomes [B,T,N] (for staging only).  Where the masker corrupted the inputs itself (`corrupted`: noise
+              and kept values under cm, zero_ratio < 1): (1 - v)[:, None, :] alone - only the padded channels of `corrupted` go;
+      tm'   - no entry: None, the row mask is the plan's token mask and the loss runs the chan form (chan = v);
+            - tm [B,T,1] / [1,T,1]: tm itself, the row mask of the chan form (chan = v);
+            - any other tm (it carries the channel axis, or is one value per sample): tm & v[:, None, :] in compact form, the loss runs
+              the element form under the resulting shape (chan = None)."""
+    if v.dtype != torch.uint8 or v.dim() != 2 or v.shape[1] != N or v.shape[0] not in (1, B):
+        raise ValueError(f"channel mask: a uint8 tensor of shape [{B} or 1, {N}], got {v.dtype} {tuple(v.shape)}")
+    v = v.contiguous()
+    pad = (1 - v)[:, None, :]
+    if entry is None:
+        return (pad.contiguous(), None, None), v
+    cm, tm, corrupted = entry
+    cm2 = (cm | pad).contiguous() if corrupted is None else pad.contiguous()
+    if tm.shape[1] == T and tm.shape[2] == 1:
+        return (cm2, tm, corrupted), v
+    return (cm2, (tm & v[:, None, :]).contiguous(), corrupted), None
+
+
+def mask_key(elem, chan):
+    """What a plan is keyed by for its masks: `elem` (Engine.elem_key) alone - today's key, None included - while no modality carries a
+    channel mask, else both keys behind a tag that no elem key starts with."""
+    return elem if chan is None else ("chan", elem, chan)
+
+
 class PlanBuilder:
-    def __init__(self, engine, B, T, training, grad=True, frozen=None, elem=None):
+    def __init__(self, engine, B, T, training, grad=True, frozen=None, elem=None, chan=None):
         """frozen: the names (layout entries) of the parameters with requires_grad = False, or None / empty: everything is trainable and
         the plan is the one it always was.  With frozen parameters the backward is pruned to what the others need.
         elem (Engine.elem_key; None: the plan it always was): per modality None or the compact shapes of its (corruption, target)
         element masks.  Such a decoder modality's loss launches are mmfm_masked_loss_elem_* on its static target-mask buffer; they write
-        the modality's count behind mmfm_mask_prep.  Everything upstream of the heads is unchanged."""
+        the modality's count behind mmfm_mask_prep.  Everything upstream of the heads is unchanged.
+        chan (Engine.chan_key; None: the plan it always was): per modality None or the shape of its channel mask.  Such a decoder
+        modality's loss launches are mmfm_masked_loss_chan_* on its static channel-mask buffer and its row mask - the token mask, or
+        the [B,T,1] / [1,T,1] target mask where `elem` gives it one (its elem entry then has a corruption mask for staging and, in
+        the first case, no target mask: `combine_chan`).  DESIGN.md §3x."""
         e, c = self.e, self.c = engine, engine.cfg
-        self.elem = elem
+        self.elem, self.chan = elem, chan
         self.B, self.T, self.training, self.grad = B, T, bool(training), bool(grad)
         self.frozen = frozenset(frozen) if frozen else None
         self.groups = {}             # gradient group -> (its launches are emitted, the parameters whose gradients they write) (`keep`)
@@ -299,14 +339,28 @@ class PlanBuilder:
             if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 need = max(need, L.lib().mmfm_softmax_ce_workspace(self.BTm[m], n))
         buf("ws/loss", (max(1, need // 4),), f32)
+        if self.chan is not None:
+            for m, shape in enumerate(self.chan):
+                if shape is None or m not in self.staged:
+                    continue
+                mod, n = c.mods[m]
+                if c.loss_kind.get(mod) == L.LOSS_SOFTMAX_CE:
+                    raise ValueError(f"modality {mod!r}: softmax cross-entropy couples its classes - it takes no channel mask (space_attn_mask)")
+                if tuple(shape) not in ((B, n), (1, n)):
+                    raise ValueError(f"modality {mod!r}: channel mask of shape {tuple(shape)} for [{B} or 1, {n}]")
+                if self.elem is None or self.elem[m] is None:
+                    raise ValueError(f"modality {mod!r}: a channel mask comes with the staging mask of `combine_chan`")
+                buf(chan_buf(m, shape), tuple(shape), u8, zero=True)
         if self.elem is not None:
             for m, shapes in enumerate(self.elem):
                 if shapes is None or m not in self.staged:
                     continue
-                if c.loss_kind.get(c.mods[m][0]) == L.LOSS_SOFTMAX_CE and tuple(shapes[1]) != (B, self.Tm[m], 1):
+                if shapes[1] is not None and c.loss_kind.get(c.mods[m][0]) == L.LOSS_SOFTMAX_CE and tuple(shapes[1]) != (B, self.Tm[m], 1):
                     raise NotImplementedError(f"modality {c.mods[m][0]!r}: softmax cross-entropy couples its classes - it takes a target "
                                               f"mask of shape [{B}, {self.Tm[m]}, 1] (one value per row), not {tuple(shapes[1])}")
                 for which, shape in zip(("cm", "tm"), shapes):
+                    if shape is None:           # (a channel-masked modality whose row mask is the token mask has no target mask)
+                        continue
                     if len(shape) != 3 or any(s not in (1, full) for s, full in zip(shape, (B, self.Tm[m], c.mods[m][1]))):
                         raise ValueError(f"modality {c.mods[m][0]!r}: element mask of shape {tuple(shape)} for [{B}, {self.Tm[m]}, {c.mods[m][1]}]")
                     buf(elem_buf(which, m, shape), tuple(shape), u8, zero=True)
@@ -568,7 +622,17 @@ class PlanBuilder:
     def elem_tm(self, m):
         """Modality m's static target-mask buffer where its loss runs under a per-element mask, else None."""
         shapes = self.elem[m] if self.elem is not None else None
-        return None if shapes is None else self.b[elem_buf("tm", m, shapes[1])]
+        return None if shapes is None or shapes[1] is None else self.b[elem_buf("tm", m, shapes[1])]
+
+    def chan_rows(self, m, tokmask, off):
+        """Where modality m's loss runs under a channel mask: (row mask, its leading dimension, the static channel-mask buffer) - the
+        row mask is the [B,T,1] / [1,T,1] target mask where the modality has one (mask_ld T / 0), else the token mask - else None."""
+        if self.chan is None or self.chan[m] is None:
+            return None
+        tm = self.elem_tm(m)
+        if tm is None:
+            return tokmask[:, off:], self.Lq, self.b[chan_buf(m, self.chan[m])]
+        return tm, (0 if tm.shape[0] == 1 else self.Tm[m]), self.b[chan_buf(m, self.chan[m])]
 
     def loss_spec(self, mod):
         c = self.c
@@ -726,6 +790,11 @@ class PlanBuilder:
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             pred = buf(f"pred/{m}", (BT, n))
             self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            ch = self.chan_rows(m, tokmask, off)
+            if ch is not None:       # row mask x channel mask: the sum and (behind mmfm_mask_prep) the modality's count
+                K.masked_loss_chan_fwd(*self.loss_spec(mod), pred, b[f"tgt/{m}"], ch[0], ch[1], self.Tm[m], BT, n, ch[2], b["loss_sum"][j:j + 1],
+                                       b[mk("decoder", "count")][j:j + 1], b["ws/loss_elem"], plan=fwd)
+                continue
             if self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 # coupled classes: the [B,T,1] target mask IS a row mask of pitch T for the softmax cross-entropy kernels; the count -
                 # N per set row, as mmfm_mask_prep counts a token mask - comes from one element-mask launch whose sum is discarded
@@ -942,7 +1011,12 @@ class PlanBuilder:
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
             dpred = buf(f"d/pred/{m}", (BT, n))
-            if (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
+            ch = self.chan_rows(m, tokmask, off)
+            if ch is not None:
+                if norm or self.tl(f"decoder_embeddings.{mod}.out"):
+                    K.masked_loss_chan_bwd(*self.loss_spec(mod), b[f"pred/{m}"], b[f"tgt/{m}"], ch[0], ch[1], self.Tm[m], BT, n, ch[2],
+                                           b["gout"], b["inv_n"], dpred, plan=self.cur)
+            elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 self.softmax_ce(self.cur, m, mod, b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), self.Tm[m], self.Tm[m], BT, n, dpred=dpred)
             elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None:
                 K.masked_loss_elem_bwd(*self.loss_spec(mod), b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), B, self.Tm[m], n,

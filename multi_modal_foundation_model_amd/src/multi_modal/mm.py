@@ -124,6 +124,7 @@ def _loss_kind(spec) -> int:
 
 class MultiModal(nn.Module):
     input_masking = False        # the switch of mask_type: input (a class default, so that a module pickled before it existed has it too)
+    neuron_padding = False       # the switch of space_attn_mask: padded channels leave the inputs and the loss (a class default, as above)
 
     def __init__(self, encoder_embeddings: Dict[str, nn.Module], decoder_embeddings: Dict[str, nn.Module],
                  avail_mod: List, config: DictConfig, share_modality_embeddings: bool = True, **kwargs):
@@ -172,6 +173,11 @@ class MultiModal(nn.Module):
         # masker's element masks corrupt the inputs and weigh the loss per element, no token is masked (`_input_mask`)
         if "input_masking" in kwargs:
             self.input_masking = bool(kwargs["input_masking"])
+        # neuron padding: a modality whose mod_dict entry carries `space_attn_mask` [B, N] (1 = a real channel, collate.py) has its padded
+        # channels zeroed on both sides and left out of the loss and of n_examples (`_channel_masks`).  False: nobody
+        # reads the mask, as upstream
+        if "neuron_padding" in kwargs:
+            self.neuron_padding = bool(kwargs["neuron_padding"])
 
     def share_modality_embeddings(self):
         for mod in self.encoder_modalities & self.decoder_modalities:
@@ -261,12 +267,31 @@ class MultiModal(nn.Module):
             d['inputs'] = corrupted
         return cm, tm, corrupted
 
+    # ------------------------------------------------------------------ neuron padding (`neuron_padding` on)
+    def _channel_masks(self, mod_dict):
+        """Per modality None or its channel mask as the engine takes it: uint8 [B, N], 1 = a real channel, from the entry's
+        `space_attn_mask`.  Only the mask decides what is padding: the pad value is never read.  A mask of another shape is refused
+        here, before any draw or launch."""
+        chan = {}
+        for mod, d in mod_dict.items():
+            v = d.get('space_attn_mask')
+            if v is None:
+                continue
+            x = d['inputs']
+            want = (x.shape[0], x.shape[2] if x.dim() == 3 else 1)
+            if not torch.is_tensor(v) or tuple(v.shape) != want:
+                raise ValueError(f"modality {mod!r}: space_attn_mask of shape {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__} "
+                                 f"for inputs of [batch, channels] = {list(want)}")
+            chan[mod] = (v != 0).to(device=x.device, dtype=torch.uint8)
+        return chan
+
     # ------------------------------------------------------------------ forward
     def forward(self, mod_dict: Dict[str, Dict[str, Any]]) -> MultiModalOutput:
         mods = list(mod_dict.keys())
         if mods != list(self.avail_mod):
             raise Exception(f"mod_dict modalities {mods} != avail_mod {list(self.avail_mod)}")
         masks, elem = [], {}
+        chan = self._channel_masks(mod_dict) if self.neuron_padding else {}
         if self.input_masking:
             # a softmax cross-entropy modality couples its classes: it takes a target mask only where the mask is constant over the
             # channels (the token modes and forward-pred: a row mask).  Every other mode is refused before any draw or launch
@@ -332,7 +357,8 @@ class MultiModal(nn.Module):
             ts, attn = ([mod_dict[m][key] for m in mods] for key in ('inputs_timestamp', 'inputs_attn_mask'))
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
-                          training=self.training, anchor=self._grad_anchor(), **({"elem": [elem.get(m) for m in mods]} if elem else {}))
+                          training=self.training, anchor=self._grad_anchor(), **({"elem": [elem.get(m) for m in mods]} if elem else {}),
+                          **({"chan": [chan.get(m) for m in mods]} if chan else {}))
         mod_loss, mod_n, preds, targets = {}, {}, {}, {}
         for i, mod in enumerate(dec_mods):      # the engine's outputs are the decoder's modalities, in this order
             mod_loss[mod], mod_n[mod] = out["mod_loss"][i], out["mod_n"][i]

@@ -25,7 +25,7 @@ from multi_modal.encoder_embeddings import EncoderEmbedding
 from multi_modal.mm import MultiModal
 from multi_modal_foundation_model_amd.ddp import Accelerator
 from multi_modal_foundation_model_amd.optim import freeze_parameters, make_optimizer
-from multi_modal_foundation_model_amd.synthetic import SyntheticLoader
+from multi_modal_foundation_model_amd.synthetic import MultiSessionLoader, SyntheticLoader
 from trainer.base import accumulation_groups, validate_accumulation_steps
 from trainer.make import make_multimodal_trainer
 from utils.config_utils import config_from_kwargs, update_config
@@ -62,6 +62,12 @@ def build_parser():
     ap.add_argument("--input_masking", action="store_true",
                     help="train with mask_type: input (training.mask_mode sampled per step; per-element corruption and loss masks) "
                          "instead of failing on it as upstream does: sets training.mask_type = input and training.input_masking")
+    ap.add_argument("--neuron_padding", action="store_true",
+                    help="honour the loader's space_attn_mask: padded spike channels are zeroed on both sides and leave the loss and "
+                         "n_examples (sets training.neuron_padding)")
+    ap.add_argument("--n_sessions", type=int, default=1,
+                    help="K > 1: multi-session pretraining on synthetic sessions of 300..n_neurons neurons each, batch i from session "
+                         "i %% K, spikes right-padded with -1 up to n_neurons (1: one session, no padding)")
     return ap
 
 
@@ -86,6 +92,10 @@ def main(argv=None):
     if args.input_masking:
         config["training"]["mask_type"] = "input"
         config["training"]["input_masking"] = True
+    if args.neuron_padding:
+        config["training"]["neuron_padding"] = True
+    if args.n_sessions < 1:
+        raise ValueError(f"--n_sessions must be >= 1, got {args.n_sessions}")
     set_seed(config.seed)
 
     avail_mod = list(AVAIL_MOD)
@@ -101,9 +111,15 @@ def main(argv=None):
     n_behaviors, n_neurons = len(avail_beh), args.n_neurons
     meta_data = {"num_neurons": [n_neurons], "eids": [args.eid]}
     T = config.data.max_time_length
-    train_dataloader = SyntheticLoader(args.batches_per_epoch, config.training.train_batch_size, T, n_neurons, n_behaviors,
-                                       rank=accelerator.rank, seed0=0)
-    val_dataloader = SyntheticLoader(2, config.training.test_batch_size, T, n_neurons, n_behaviors, rank=accelerator.rank, seed0=10 ** 6)
+    if args.n_sessions > 1:
+        train_dataloader = MultiSessionLoader(args.batches_per_epoch, config.training.train_batch_size, T, n_neurons, n_behaviors,
+                                              n_sessions=args.n_sessions, rank=accelerator.rank, seed0=0)
+        val_dataloader = MultiSessionLoader(2, config.training.test_batch_size, T, n_neurons, n_behaviors, n_sessions=args.n_sessions,
+                                            rank=accelerator.rank, seed0=10 ** 6)
+    else:
+        train_dataloader = SyntheticLoader(args.batches_per_epoch, config.training.train_batch_size, T, n_neurons, n_behaviors,
+                                           rank=accelerator.rank, seed0=0)
+        val_dataloader = SyntheticLoader(2, config.training.test_batch_size, T, n_neurons, n_behaviors, rank=accelerator.rank, seed0=10 ** 6)
 
     encoder_embeddings, decoder_embeddings = {}, {}
     for mod in modal_filter["input"]:

@@ -124,6 +124,14 @@ class MultiModalTrainer():
             raise ValueError(f"training.input_masking: true needs training.mask_type: input (got {self.config.training.mask_type!r})")
         if input_masking:
             getattr(self.model, "module", self.model).input_masking = True       # (a DDP wrapper holds the model as .module)
+        # training.neuron_padding (no key of the reference's YAML either: absent = false): honour the loader's space_attn_mask - the
+        # channels it marks as padding leave the spike inputs and the loss (MultiModal.neuron_padding)
+        neuron_padding = self.config.training.get("neuron_padding", False) if hasattr(self.config.training, "get") else False
+        if not isinstance(neuron_padding, bool):
+            raise ValueError(f"training.neuron_padding must be true or false, got {neuron_padding!r}")
+        self.neuron_padding = neuron_padding
+        if neuron_padding:
+            getattr(self.model, "module", self.model).neuron_padding = True
         self.mixed_training = kwargs.get("mixed_training", False)
         if self.mixed_training:
             self.training_schemes = list(OBJECTIVES)
@@ -189,6 +197,10 @@ class MultiModalTrainer():
                 # clone and the engine copies inputs/targets into its static buffers - so the 2 x 274 MB copies are dropped)
                 d['inputs'], d['targets'] = spikes, spikes
                 d['inputs_regions'] = LazyRegions(batch['neuron_regions'])
+                if self.neuron_padding:
+                    if batch.get('space_attn_mask') is None:
+                        raise ValueError("training.neuron_padding: true needs the loader's space_attn_mask [B, N] in every batch")
+                    d['space_attn_mask'] = batch['space_attn_mask']
             elif mod == 'behavior':
                 d['inputs'], d['targets'] = behav, behav
             else:

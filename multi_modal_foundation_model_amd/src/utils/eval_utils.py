@@ -98,6 +98,8 @@ def eval_mod_dict(model, batch, mask_result, mask_mode, use_mtm=False, masked_mo
         if mod == 'ap':
             d['inputs'] = (mask_result['spikes'] if use_mtm and masked_mod == 'ap' else batch['spikes_data']).clone()
             d['inputs_regions'] = batch.get('neuron_regions')
+            if batch.get('space_attn_mask') is not None:       # read by the model only under MultiModal.neuron_padding
+                d['space_attn_mask'] = batch['space_attn_mask']
             d['targets'] = batch['spikes_data'].clone()
             d['eval_mask'] = mask_result['eval_mask'] if masked_mod == 'ap' else torch.zeros_like(batch['spikes_data']).to(torch.int64)
             d['mask_mode'] = mask_mode

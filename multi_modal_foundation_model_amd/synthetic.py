@@ -55,3 +55,33 @@ class SyntheticLoader:
                 if step not in self._cache:
                     self._cache[step] = self._make(step)
                 yield dict(self._cache[step])
+
+
+def session_sizes(n_sessions, n_ap, seed=2024):
+    """n_k, the neurons of session k: drawn once from numpy's default_rng(seed).integers(300, n_ap + 1), one draw per session in order."""
+    import numpy as np
+    if n_ap < 300:
+        raise ValueError(f"multi-session batches draw 300..n_ap neurons per session: n_ap = {n_ap} < 300")
+    rng = np.random.default_rng(seed)
+    return [int(rng.integers(300, n_ap + 1)) for _ in range(n_sessions)]
+
+
+class MultiSessionLoader(SyntheticLoader):
+    """Synthetic multi-session pretraining batches as the reference loader pads them (loader/base.py:399-425): batch i belongs to
+    session i % n_sessions, session k has n_k of the n_ap channels (`session_sizes`), the others are right-padded with pad_value = -1
+    and cleared in space_attn_mask; eid names the session.  The values of the real channels are synth_batch's own."""
+
+    def __init__(self, n_batches, batch_size, T=100, n_ap=668, n_beh=2, n_sessions=2, rank=0, seed0=0, device=None, cache=False):
+        super().__init__(n_batches, batch_size, T, n_ap, n_beh, rank=rank, seed0=seed0, device=device, cache=cache)
+        if n_sessions < 1:
+            raise ValueError(f"n_sessions must be >= 1, got {n_sessions}")
+        self.n_sessions, self.sizes = n_sessions, session_sizes(n_sessions, n_ap)
+
+    def _make(self, step):
+        k = step % self.n_sessions
+        b = synth_batch(self.B, self.T, self.n_ap, self.n_beh, seed=1000 * self.rank + self.seed0 + step, eid=f"session{k}")
+        b["spikes_data"][:, :, self.sizes[k]:] = -1.0
+        b["space_attn_mask"][:, self.sizes[k]:] = 0
+        if self.device is not None:
+            b = {key: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for key, v in b.items()}
+        return b
