@@ -300,6 +300,33 @@ float mmfm_attn_keep_prob(float p);
 #define MMFM_ATTN_FAMILY_BWD_SINGLE 0x10
 int mmfm_attn_family(const mmfm_attn_desc* d, int backward);
 
+/* MMFM_ATTN_WINDOW: attention inside a window over TIME STAMPS (mm.yaml context.forward / context.backward; upstream's
+ * create_context_mask, mm_utils.py:18-34, which its forward_mask_encoder leaves commented out at mm.py:152-158).  pos[b][i] is the
+ * time stamp of token i of sample b - not its index in the stitched sequence - and the rule of the window calls is
+ *   allowed(b,q,k) = (DIAG && q==k) | (keypad[b][k] && lo <= pos[b][k] - pos[b][q] <= hi).
+ * (lo, hi) for a config (F, Bk) = (context.forward, context.backward): hi = F >= 0 ? F : 2^30, lo = Bk > 0 ? -Bk : -2^30 (upstream's
+ * `if context_backward > 0`: backward 0 is unbounded, like -1).  lo / hi beyond +-2^30 are clamped to it; mmfm_attn_pos_prep clamps the
+ * stamps to +-2^29, so a difference always fits beside them.
+ * The descriptor is mmfm_attn_desc as it is (MMFM_VERSION stays).  win == NULL is mmfm_attn_fwd / _bwd, the same launch.  Refused with
+ * an error code and mmfm_last_error set, before any HIP call: Lq != Lk, CAUSAL or SEP in flags (not built under a window; no site of
+ * the model needs them), pos == NULL.  Kernels: the general families - csrc/attention.hip (F32, F32_TILED) and
+ * csrc/attention_bf16.hip (BF16, BF16_TILED), which stage the sample's pos row in LDS (4 bytes per position on top of their LDS
+ * formulas) and never take their mask-free shortcut under a window - and the keep-bit dh-32 kernels (csrc/attention_fast.hip), whose
+ * window forms classify (query tile, key tile) pairs from per-tile stamp minima / maxima: a launch they take (the shapes of keepbits
+ * above) stays on them, keep bits and all.  csrc/attention_long.hip (dh 64 / 128 keep-bit) has no window form: such a launch runs
+ * BF16 / BF16_TILED in both directions and draws drop_p from the counter hash even with a keepbits workspace; mmfm_attn_win_family
+ * says which.  A query row with no allowed key gives NaN, as in mmfm_attn_fwd. */
+#define MMFM_ATTN_WINDOW 1
+typedef struct { const int32_t* pos; /* [B][L], L = Lq = Lk */ int lo, hi; } mmfm_attn_window;
+int mmfm_attn_win_fwd(const mmfm_attn_desc* d, const mmfm_attn_window* win, mmfm_stream stream);
+int mmfm_attn_win_bwd(const mmfm_attn_desc* d, const mmfm_attn_window* win, mmfm_stream stream);
+/* no HIP call, as mmfm_attn_family */
+int mmfm_attn_win_family(const mmfm_attn_desc* d, const mmfm_attn_window* win, int backward);
+/* pos[b][off_j + t] = clamp(ts[j][b * seg_T[j] + t], -2^29, 2^29) for the M slots of a stitched sequence (off_j = sum_{i<j} seg_T[i],
+ * L = sum seg_T; the uniform form passes the one shared stamp tensor M times).  seg_T and ts are HOST arrays read during the call (they
+ * travel as launch arguments: no allocation, hipGraph-capturable); M <= MMFM_MAX_SEGMENTS.  Arguments are checked before any HIP call. */
+int mmfm_attn_pos_prep(int B, int M, const int32_t* seg_T, const int64_t* const* ts, int32_t* pos, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- masks / stitch
  * mm.py:245-275 (mask = eval_mask[:,:,0] & attn_mask), :102 (mod_mask), :145,167 (sample-0 ids),
  * :229-233 (n_examples).  For modality m: mask_src[m] is int64 with element (b,t) at

@@ -100,6 +100,15 @@ class AttnDesc(C.Structure):
                 ("dv", C.c_void_p), ("lddq", C.c_int), ("lddk", C.c_int), ("lddv", C.c_int), ("keepbits", C.c_void_p)]
 
 
+class AttnWindow(C.Structure):
+    """mmfm_attn_window (MMFM_ATTN_WINDOW): int32 time stamps [B][L] and the closed interval [lo, hi] of allowed pos[k] - pos[q]."""
+    _fields_ = [("pos", C.c_void_p), ("lo", C.c_int), ("hi", C.c_int)]
+
+
+ATTN_WINDOW_INF = 1 << 30        # lo / hi beyond it are clamped to it
+ATTN_POS_CLAMP = 1 << 29         # mmfm_attn_pos_prep clamps the stamps to it
+
+
 class PrepEntry(C.Structure):
     _fields_ = [("W", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("bias", C.c_void_p), ("Wp", C.c_void_p),
                 ("WpT", C.c_void_p), ("bp", C.c_void_p), ("N", C.c_int), ("K", C.c_int), ("tile0", C.c_int), ("scalar_gain", C.c_int),
@@ -170,6 +179,11 @@ _PROTOS = {
     "mmfm_attn_keepbits_bytes": (C.c_int64, [_i, _i, _i, _i]),
     "mmfm_attn_keep_prob": (C.c_float, [_f]),
     "mmfm_attn_family": (C.c_int, [C.POINTER(AttnDesc), _i]),
+    # attention inside a window over time stamps (MMFM_ATTN_WINDOW)
+    "mmfm_attn_win_fwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnWindow), _vp]),
+    "mmfm_attn_win_bwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnWindow), _vp]),
+    "mmfm_attn_win_family": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnWindow), _i]),
+    "mmfm_attn_pos_prep": (C.c_int, [_i, _i, C.POINTER(C.c_int32), C.POINTER(_vp), _vp, _vp]),
     "mmfm_mask_prep": (C.c_int, [_i, _i, _i, C.POINTER(_vp), C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_collate_csr": (C.c_int, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmfm_stitch_fwd": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -66,15 +66,18 @@ def _filtered(mods, modal_filter):
     return [(m, chan[m]) for m in modal_filter["input"]], [(m, chan[m]) for m in modal_filter["output"]]
 
 
-def build_model(mcfg, n_ap, n_beh, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False):
+def build_model(mcfg, n_ap, n_beh, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False,
+                context_mask=False):
     """train_multi_modal.py:160-189 (construction order = RNG contract).  modal_filter: dict(input=[...], output=[...]), the
     modalities the encoder / the decoder gets tokenisers for (None: both get both).  input_masking: MultiModal.input_masking.
-    neuron_padding: MultiModal.neuron_padding."""
+    neuron_padding: MultiModal.neuron_padding.  context_mask: MultiModal.context_mask."""
     return build_model_mods(mcfg, [("ap", n_ap), ("behavior", n_beh)], seed=seed, modal_filter=modal_filter,
-                            share_modality_embeddings=share_modality_embeddings, input_masking=input_masking, neuron_padding=neuron_padding)
+                            share_modality_embeddings=share_modality_embeddings, input_masking=input_masking, neuron_padding=neuron_padding,
+                            context_mask=context_mask)
 
 
-def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False):
+def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False,
+                     context_mask=False):
     """Same construction order for an arbitrary modality list [(name, channels)] (BASELINE configs[4]: 3 modalities)."""
     from multi_modal.mm import MultiModal
     from multi_modal.encoder_embeddings import EncoderEmbedding
@@ -86,7 +89,8 @@ def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_em
     dec = {m: DecoderEmbedding(hidden_size=mcfg.decoder.transformer.hidden_size, n_channel=n, output_channel=n, config=mcfg.decoder)
            for m, n in dec_mods}
     return MultiModal(enc, dec, avail_mod=[m for m, _ in mods], config=mcfg, share_modality_embeddings=share_modality_embeddings,
-                      **({"input_masking": True} if input_masking else {}), **({"neuron_padding": True} if neuron_padding else {}))
+                      **({"input_masking": True} if input_masking else {}), **({"neuron_padding": True} if neuron_padding else {}),
+                      **({"context_mask": True} if context_mask else {}))
 
 
 def make_optimizer(model, total_steps, lr=1e-4, wd=0.01, eps=1e-8):

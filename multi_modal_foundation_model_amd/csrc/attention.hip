@@ -2,7 +2,8 @@
 //
 // fp32 parity path on v_mfma_f32_32x32x2_f32.  One workgroup (4 wavefronts) per (batch, head);
 // the head's K and V (L <= a few hundred tokens at dh <= 64, L <= 64 at dh 128) stay in LDS for the whole workgroup.
-// The [B,h,L,L] mask of the reference is never materialised: keypad bytes + flags.
+// The [B,h,L,L] mask of the reference is never materialised: keypad bytes + flags, and under a window (mmfm_attn_win_fwd / _bwd,
+// MMFM_ATTN_WINDOW: the WIN instantiations) the sample's int32 time stamps in LDS and the interval [lo, hi].
 //
 // Forward (flash style, online softmax): each wave owns 32-query tiles and walks 32-key tiles.
 //   S^T = K Q^T is computed with the KEY on the MFMA row and the QUERY on the lane, so the
@@ -24,8 +25,10 @@ struct MaskCtx {
     const uint8_t* modq;   // LDS or null
     const uint8_t* modk;
     int flags;
+    AttnWin win;           // pos row in LDS, or null: no window
     __device__ __forceinline__ bool allowed(int q, int k) const {
         bool a = (flags & MMFM_ATTN_CAUSAL) ? (k <= q) : (kpad[k] != 0);
+        if (win.pos) a = a && win_allows(win, q, k);
         if ((flags & MMFM_ATTN_DIAG) && q == k) a = true;
         if ((flags & MMFM_ATTN_SEP) && modq[q] != modk[k]) a = true;
         return a;
@@ -52,8 +55,8 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 
 // ============================================================================ forward
-template <typename T, int DH>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const mmfm_attn_desc d) {
+template <typename T, int DH, bool WIN = false, typename... W>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int DT = (DH + 31) / 32;      // 32-row tiles of the head dim
     constexpr int LD = DH + 1;              // K / Q LDS row stride (odd: conflict-free column reads)
     constexpr int DVL = DT * 32;            // V LDS row stride (zero padded to the MFMA tile)
@@ -89,9 +92,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const mmfm_attn_desc d) {
     for (int i = t; i < LkP; i += 256) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += 256) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, 256, w...);
     __syncthreads();
 
-    MaskCtx mk{kpad, modl, modl, d.flags};
+    MaskCtx mk{kpad, modl, modl, d.flags, win};
     const Drop dp = drop_init(d.drop_p), dout = drop_init(d.drop_o);
     float* sc = Sc + wave * 32 * SLD;
     const int nqt = (Lq + 31) / 32, nkt = LkP / 32;
@@ -192,8 +196,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const mmfm_attn_desc d) {
 }
 
 // ============================================================================ backward
-template <typename T, int DH>
-__global__ __launch_bounds__(256) void attn_bwd_kernel(const mmfm_attn_desc d) {
+template <typename T, int DH, bool WIN = false, typename... W>
+__global__ __launch_bounds__(256) void attn_bwd_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int DT = (DH + 31) / 32;
     constexpr int LD = DH + 1;
     constexpr int SLD = 33;
@@ -247,9 +251,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const mmfm_attn_desc d) {
     for (int i = t; i < LkP; i += 256) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += 256) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, 256, w...);
     __syncthreads();
 
-    MaskCtx mk{kpad, modl, modl, d.flags};
+    MaskCtx mk{kpad, modl, modl, d.flags, win};
     float* sc = Sc + wave * 32 * SLD;
     const int nqt = LqP / 32, nkt = LkP / 32;
     const uint64_t pbase = (uint64_t)bh_ * Lq;
@@ -395,8 +400,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const mmfm_attn_desc d) {
 // pass the 160 KB.  A chunk always has as many rows as the workgroup owns: TCH = 32 * waves.
 constexpr int tiled_nw(int dh) { return dh > 64 ? 2 : 4; }
 
-template <typename T, int DH>
-__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_fwd_tiled_kernel(const mmfm_attn_desc d) {
+template <typename T, int DH, bool WIN = false, typename... W>
+__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_fwd_tiled_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int NW = tiled_nw(DH), NT = NW * 64, TCH = NW * 32;      // streamed rows per chunk
     constexpr int DT = (DH + 31) / 32;
     constexpr int LD = DH + 1;
@@ -423,8 +428,9 @@ __global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_fwd_tiled_kernel(const
     for (int i = t; i < LkP; i += NT) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
 
-    MaskCtx mk{kpad, modl, modl, d.flags};
+    MaskCtx mk{kpad, modl, modl, d.flags, win};
     const Drop dp = drop_init(d.drop_p), dout = drop_init(d.drop_o);
     float* sc = Sc + wave * 32 * SLD;
     const int nqt = (Lq + 31) / 32;
@@ -538,8 +544,8 @@ __global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_fwd_tiled_kernel(const
 }
 
 // PHASE 0: the workgroup owns 4 key tiles (dK, dV) and streams query chunks; PHASE 1: owns 4 query tiles (dQ), streams keys.
-template <typename T, int DH, int PHASE>
-__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_bwd_tiled_kernel(const mmfm_attn_desc d) {
+template <typename T, int DH, int PHASE, bool WIN = false, typename... W>
+__global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_bwd_tiled_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int NW = tiled_nw(DH), NT = NW * 64, TCH = NW * 32;
     constexpr int DT = (DH + 31) / 32;
     constexpr int LD = DH + 1;
@@ -597,7 +603,8 @@ __global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_bwd_tiled_kernel(const
     for (int i = t; i < LkP; i += NT) kpad[i] = (i < Lk && d.keypad) ? d.keypad[(size_t)b * Lk + i] : 0;
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
-    MaskCtx mk{kpad, modl, modl, d.flags};
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
+    MaskCtx mk{kpad, modl, modl, d.flags, win};
     float* sc = Sc + wave * 32 * SLD;
     const uint64_t pbase = (uint64_t)bh_ * Lq;
     const int own0 = blockIdx.y * TCH;                 // first owned row (key for phase 0, query for phase 1)
@@ -752,22 +759,22 @@ __global__ __launch_bounds__(tiled_nw(DH) * 64) void attn_bwd_tiled_kernel(const
     }
 }
 
-size_t fwd_tiled_lds_bytes(int Lq, int Lk, int dh) {
+size_t fwd_tiled_lds_bytes(int Lq, int Lk, int dh, bool win = false) {
     const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31, DVL = DT * 32, nw = tiled_nw(dh), tch = nw * 32;
-    return (size_t)(tch * (dh + 1) + tch * DVL + nw * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16;
+    return (size_t)(tch * (dh + 1) + tch * DVL + nw * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16 + attn_win_lds(win, Lk);
 }
-size_t bwd_tiled_lds_bytes(int Lq, int Lk, int dh) {
+size_t bwd_tiled_lds_bytes(int Lq, int Lk, int dh, bool win = false) {
     const int LkP = (Lk + 31) & ~31, nw = tiled_nw(dh), tch = nw * 32;
-    return (size_t)(4 * tch * (dh + 1) + 2 * tch + nw * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16;
+    return (size_t)(4 * tch * (dh + 1) + 2 * tch + nw * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16 + attn_win_lds(win, Lk);
 }
 
-size_t fwd_lds_bytes(int Lq, int Lk, int dh) {
+size_t fwd_lds_bytes(int Lq, int Lk, int dh, bool win = false) {
     const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31, DVL = DT * 32;
-    return (size_t)(LkP * (dh + 1) + LkP * DVL + 4 * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16;
+    return (size_t)(LkP * (dh + 1) + LkP * DVL + 4 * 32 * (DVL + 1)) * 4 + LkP + std::max(Lq, Lk) + 16 + attn_win_lds(win, Lk);
 }
-size_t bwd_lds_bytes(int Lq, int Lk, int dh) {
+size_t bwd_lds_bytes(int Lq, int Lk, int dh, bool win = false) {
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31;
-    return (size_t)(2 * LqP * (dh + 1) + 2 * LkP * (dh + 1) + 2 * LqP + 4 * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16;
+    return (size_t)(2 * LqP * (dh + 1) + 2 * LkP * (dh + 1) + 2 * LqP + 4 * 32 * 33) * 4 + LkP + std::max(Lq, Lk) + 16 + attn_win_lds(win, Lk);
 }
 
 int check_common(const mmfm_attn_desc& d, const char* who) {
@@ -789,8 +796,13 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
 
 }  // namespace
 
+// win (the route's window, or null) picks the WINDOW instantiation, which takes the window behind the descriptor
 #define ATTN_DISPATCH(KERN, TT, DHV)                                                             \
-    {                                                                                            \
+    if (win) {                                                                                   \
+        auto kern = KERN<TT, DHV, true, mmfm_attn_window>;                                       \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;  \
+        hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(256), lds, (hipStream_t)stream, d, *win); \
+    } else {                                                                                     \
         auto kern = KERN<TT, DHV>;                                                               \
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;  \
         hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(256), lds, (hipStream_t)stream, d);   \
@@ -816,7 +828,11 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
     }
 
 #define ATTN_TILED(KERN, GY, ...)                                                                                  \
-    {                                                                                                              \
+    if (win) {                                                                                                     \
+        auto kern = KERN<__VA_ARGS__, true, mmfm_attn_window>;                                                     \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;                    \
+        hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(tnw * 64), lds, (hipStream_t)stream, d, *win);      \
+    } else {                                                                                                       \
         auto kern = KERN<__VA_ARGS__>;                                                                             \
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, who)) return rc;                    \
         hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(tnw * 64), lds, (hipStream_t)stream, d);            \
@@ -847,10 +863,13 @@ int check_common(const mmfm_attn_desc& d, const char* who) {
 // The one thing only the backward sees is the gradient tensors' alignment, which the bf16 families need: where it is missing the
 // backward moves down the chain when no decision source changes with the move, and is an error otherwise.
 // MMFM_ATTN_FORCE_TILED: 1 = tiled kernels for every shape, 2 = as 1, and bf16 storage runs the fp32-compute kernels.
+// A window (r.win): the dh-32 keep-bit kernels have window forms and are asked like any launch; attention_long.hip (dh 64 / 128) has
+// none and is kept out in both directions; on the general kernels the pos row counts in every LDS formula the route consults.
 static int attn_route(const mmfm_attn_desc& d, bool backward, AttnRoute& r) {
+    const bool win = r.win != nullptr;
     static const int force_tiled = [] { const char* e = getenv("MMFM_ATTN_FORCE_TILED"); return e ? atoi(e) : 0; }();
     const bool bf16 = d.dtype == MMFM_BF16, misaligned = backward && bf16 && !attn_grads_aligned(d), drop = attn_drop_p_on(d);
-    bool fast = bf16 && mmfm_attn_fast_takes(d);
+    bool fast = bf16 && mmfm_attn_fast_takes(d, win);
     if (fast && misaligned) {
         // the forward of this shape took its decisions from the keep bits; the general backward would hash different ones
         if (drop) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 32): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 when "
@@ -858,7 +877,7 @@ static int attn_route(const mmfm_attn_desc& d, bool backward, AttnRoute& r) {
         fast = false;
     }
     if (fast) { r.family = MMFM_ATTN_FAMILY_KEEPBIT_DH32; return 0; }
-    if (bf16 && mmfm_attn_long_takes(d)) {
+    if (bf16 && !win && mmfm_attn_long_takes(d)) {
         if (misaligned) return mmfm_set_error(-1, "mmfm_attn_bwd(bf16, dh 64 / 128): gradient tensors must be 16-byte aligned with leading dims %% 8 == 0 on the "
                                                   "keep-bit path (mmfm_attn_desc.keepbits)");
         r.family = MMFM_ATTN_FAMILY_KEEPBIT_LONG;
@@ -874,8 +893,8 @@ static int attn_route(const mmfm_attn_desc& d, bool backward, AttnRoute& r) {
                                             "attention dropout is on (the fallback kernel family draws a different mask than the forward did)");
     }
     // fp32 compute, on fp32 or bf16 storage
-    if (force_tiled || fwd_lds_bytes(d.Lq, d.Lk, d.dh) > ATTN_LDS_MAX || bwd_lds_bytes(d.Lq, d.Lk, d.dh) > ATTN_LDS_MAX) {
-        const size_t lds = backward ? bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh) : fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+    if (force_tiled || fwd_lds_bytes(d.Lq, d.Lk, d.dh, win) > ATTN_LDS_MAX || bwd_lds_bytes(d.Lq, d.Lk, d.dh, win) > ATTN_LDS_MAX) {
+        const size_t lds = backward ? bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh, win) : fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh, win);
         MMFM_REQUIRE(lds <= ATTN_LDS_MAX, "mmfm_attn_%s: dh=%d Lq=%d Lk=%d needs %zu B of LDS (limit 163840: the mask bytes grow with L)",
                      backward ? "bwd" : "fwd", d.dh, d.Lq, d.Lk, lds);
         r.family = MMFM_ATTN_FAMILY_F32_TILED;
@@ -886,8 +905,18 @@ static int attn_route(const mmfm_attn_desc& d, bool backward, AttnRoute& r) {
 }
 
 // What every entry point does first: the descriptor as the kernels get it, the checks, the route.
-static int attn_prologue(const mmfm_attn_desc* dp, bool backward, const char* who, mmfm_attn_desc& d, AttnRoute& r) {
+// wp / w: the caller's window or null, and the copy the kernels get (lo / hi clamped to +-2^30)
+static int attn_prologue(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, bool backward, const char* who, mmfm_attn_desc& d,
+                         mmfm_attn_window& w, AttnRoute& r) {
     MMFM_REQUIRE(dp, "%s: null descriptor", who);
+    if (wp) {
+        MMFM_REQUIRE(wp->pos, "%s: window without pos", who);
+        MMFM_REQUIRE(dp->Lq == dp->Lk, "%s: a window needs Lq == Lk (Lq=%d, Lk=%d)", who, dp->Lq, dp->Lk);
+        MMFM_REQUIRE(!(dp->flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)), "%s: CAUSAL / SEP are not built under a window", who);
+        constexpr int WINF = 1 << 30;
+        w = mmfm_attn_window{wp->pos, std::max(wp->lo, -WINF), std::min(wp->hi, WINF)};
+        r.win = &w;
+    }
     static const int no_remap = [] { const char* e = getenv("MMFM_ATTN_NO_REMAP"); return e ? atoi(e) : 0; }();
     d = *dp;
     d.flags = (d.flags & 0xff) | (no_remap ? 0x100 : 0);          // bit 8: plain workgroup order (common.h attn_xcd_remap)
@@ -901,33 +930,39 @@ static int attn_prologue(const mmfm_attn_desc* dp, bool backward, const char* wh
     return attn_route(d, backward, r);
 }
 
-extern "C" int mmfm_attn_family(const mmfm_attn_desc* dp, int backward) {
+static int attn_family(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, int backward, const char* fwd, const char* bwd) {
     mmfm_attn_desc d;
+    mmfm_attn_window w;
     AttnRoute r;
-    if (int rc = attn_prologue(dp, backward != 0, backward ? "mmfm_attn_bwd" : "mmfm_attn_fwd", d, r)) return rc < 0 ? rc : -1;
+    if (int rc = attn_prologue(dp, wp, backward != 0, backward ? bwd : fwd, d, w, r)) return rc < 0 ? rc : -1;
     return r.family | (backward && r.family == MMFM_ATTN_FAMILY_BF16 && r.bwd_single ? MMFM_ATTN_FAMILY_BWD_SINGLE : 0);
 }
+extern "C" int mmfm_attn_family(const mmfm_attn_desc* dp, int backward) { return attn_family(dp, nullptr, backward, "mmfm_attn_fwd", "mmfm_attn_bwd"); }
+extern "C" int mmfm_attn_win_family(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, int backward) {
+    return attn_family(dp, wp, backward, "mmfm_attn_win_fwd", "mmfm_attn_win_bwd");
+}
 
-extern "C" int mmfm_attn_fwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
-    const char* who = "mmfm_attn_fwd";
+static int attn_fwd(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, mmfm_stream stream, const char* who) {
     mmfm_attn_desc d_;
+    mmfm_attn_window w_;
     AttnRoute r;
-    if (int rc = attn_prologue(dp, false, who, d_, r)) return rc;
+    if (int rc = attn_prologue(dp, wp, false, who, d_, w_, r)) return rc;
     const mmfm_attn_desc& d = d_;
+    const mmfm_attn_window* win = r.win;
     switch (r.family) {
-        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, false, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, false, (hipStream_t)stream, win);
         case MMFM_ATTN_FAMILY_KEEPBIT_LONG: return mmfm_attn_long_launch(d, false, (hipStream_t)stream);
         case MMFM_ATTN_FAMILY_BF16:
         case MMFM_ATTN_FAMILY_BF16_TILED: return mmfm_attn_bf16_launch(d, r, false, (hipStream_t)stream);
         case MMFM_ATTN_FAMILY_F32_TILED: {
-            const size_t lds = fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+            const size_t lds = fwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh, win != nullptr);
             const int tnw = tiled_nw(d.dh), gy = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
             ATTN_TILED_ALL(attn_fwd_tiled_kernel, gy)
             MMFM_LAUNCH_CHECK("mmfm_attn_fwd(tiled)");
             return 0;
         }
         default: {
-            const size_t lds = fwd_lds_bytes(d.Lq, d.Lk, d.dh);
+            const size_t lds = fwd_lds_bytes(d.Lq, d.Lk, d.dh, win != nullptr);
             ATTN_DISPATCH_ALL(attn_fwd_kernel)
             MMFM_LAUNCH_CHECK("mmfm_attn_fwd");
             return 0;
@@ -935,19 +970,25 @@ extern "C" int mmfm_attn_fwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
     }
 }
 
-extern "C" int mmfm_attn_bwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
-    const char* who = "mmfm_attn_bwd";
+extern "C" int mmfm_attn_fwd(const mmfm_attn_desc* dp, mmfm_stream stream) { return attn_fwd(dp, nullptr, stream, "mmfm_attn_fwd"); }
+extern "C" int mmfm_attn_win_fwd(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, mmfm_stream stream) {
+    return attn_fwd(dp, wp, stream, "mmfm_attn_win_fwd");
+}
+
+static int attn_bwd(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, mmfm_stream stream, const char* who) {
     mmfm_attn_desc d_;
+    mmfm_attn_window w_;
     AttnRoute r;
-    if (int rc = attn_prologue(dp, true, who, d_, r)) return rc;
+    if (int rc = attn_prologue(dp, wp, true, who, d_, w_, r)) return rc;
     const mmfm_attn_desc& d = d_;
+    const mmfm_attn_window* win = r.win;
     switch (r.family) {
-        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, true, (hipStream_t)stream);
+        case MMFM_ATTN_FAMILY_KEEPBIT_DH32: return mmfm_attn_fast_launch(d, true, (hipStream_t)stream, win);
         case MMFM_ATTN_FAMILY_KEEPBIT_LONG: return mmfm_attn_long_launch(d, true, (hipStream_t)stream);
         case MMFM_ATTN_FAMILY_BF16:
         case MMFM_ATTN_FAMILY_BF16_TILED: return mmfm_attn_bf16_launch(d, r, true, (hipStream_t)stream);
         case MMFM_ATTN_FAMILY_F32_TILED: {
-            const size_t lds = bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh);
+            const size_t lds = bwd_tiled_lds_bytes(d.Lq, d.Lk, d.dh, win != nullptr);
             const int tnw = tiled_nw(d.dh), gk = ((d.Lk + 31) / 32 + tnw - 1) / tnw, gq = ((d.Lq + 31) / 32 + tnw - 1) / tnw;
 #define COMMA_PHASE0 , 0
 #define COMMA_PHASE1 , 1
@@ -959,10 +1000,14 @@ extern "C" int mmfm_attn_bwd(const mmfm_attn_desc* dp, mmfm_stream stream) {
             return 0;
         }
         default: {
-            const size_t lds = bwd_lds_bytes(d.Lq, d.Lk, d.dh);
+            const size_t lds = bwd_lds_bytes(d.Lq, d.Lk, d.dh, win != nullptr);
             ATTN_DISPATCH_ALL(attn_bwd_kernel)
             MMFM_LAUNCH_CHECK("mmfm_attn_bwd");
             return 0;
         }
     }
+}
+extern "C" int mmfm_attn_bwd(const mmfm_attn_desc* dp, mmfm_stream stream) { return attn_bwd(dp, nullptr, stream, "mmfm_attn_bwd"); }
+extern "C" int mmfm_attn_win_bwd(const mmfm_attn_desc* dp, const mmfm_attn_window* wp, mmfm_stream stream) {
+    return attn_bwd(dp, wp, stream, "mmfm_attn_win_bwd");
 }

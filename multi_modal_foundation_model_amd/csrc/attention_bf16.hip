@@ -1,5 +1,6 @@
 // bf16 MFMA attention (throughput mode), forward and backward: v_mfma_f32_32x32x16_bf16, fp32
-// softmax statistics.  Same masks / dropout / LSE contract as attention.hip (the fp32 parity path).
+// softmax statistics.  Same masks / dropout / LSE contract as attention.hip (the fp32 parity path), the window over time stamps
+// (MMFM_ATTN_WINDOW: the WIN instantiations, which never take the mask-free shortcut) included.
 //
 // One workgroup per (batch, head); Q/K/V(/dO) of the head live in LDS as bf16 rows padded by 16 B
 // (80-B rows at dh = 32: a ds_read_b128 of 8 consecutive d per lane is conflict-free).
@@ -24,8 +25,10 @@ struct MaskCtx {
     const uint8_t* kpad;
     const uint8_t* modl;
     int flags;
+    AttnWin win;           // pos row in LDS, or null: no window
     __device__ __forceinline__ bool allowed(int q, int k) const {
         bool a = (flags & MMFM_ATTN_CAUSAL) ? (k <= q) : (kpad[k] != 0);
+        if (win.pos) a = a && win_allows(win, q, k);
         if ((flags & MMFM_ATTN_DIAG) && q == k) a = true;
         if ((flags & MMFM_ATTN_SEP) && modl[q] != modl[k]) a = true;
         return a;
@@ -102,8 +105,8 @@ __device__ __forceinline__ bool fwd_tile(const f32x16& st, float c2, float& m_ru
 
 // __launch_bounds__ second argument = waves per SIMD the register allocation must allow: 3 -> <= 168 VGPRs, so three
 // 4-wave workgroups (49 KB of LDS each at L = 200, dh = 32) co-reside on a CU
-template <int DH, int NW>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void attn_fwd_bf16_kernel(const mmfm_attn_desc d) {
+template <int DH, int NW, bool WIN = false, typename... W>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void attn_fwd_bf16_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int KRS = DH * 2 + 16;          // K rows (row reads)
     constexpr int VRS = DT * 64;              // V rows (transposed reads only), zero padded to 32 columns
@@ -135,6 +138,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void attn_fwd_bf16_kernel
     }
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
     // block-wide AND through the dynamic LDS (no static __shared__: it would shift the 16-B aligned carve-up
     // and shrink the >64 KB opt-in limit)
     const int wave_vote = __all(allk) ? 1 : 0;      // all 64 lanes vote BEFORE any divergence
@@ -143,9 +147,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void attn_fwd_bf16_kernel
     int vote = 1;
 #pragma unroll
     for (int w = 0; w < NW; ++w) vote &= wflag[w];
-    const bool nomask = vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
+    const bool nomask = !WIN && vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
 
-    const MaskCtx mk{kpad, modl, d.flags};
+    const MaskCtx mk{kpad, modl, d.flags, win};
     const Drop16 dp = drop16_init(d.drop_p);
     const Drop dout = drop_init(d.drop_o);
     float* sc = Sc + wave * 32 * SLD;
@@ -336,8 +340,8 @@ __device__ __forceinline__ void bwdB_tile(const f32x16& s, const f32x16& dpv, fl
 //   phase 1: K and V (row reads for S^T/dP^T, transposed K for dQ^T); the wave's own Q/dO rows go straight into
 //            registers, delta = rowsum(d_o * o) is a per-lane dot product.
 // ~48 KB of LDS per 4-wave workgroup -> three workgroups per CU, which is what hides each one's load prologue.
-template <int DH, int NW, int PHASE>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_bf16_kernel(const mmfm_attn_desc d) {
+template <int DH, int NW, int PHASE, bool WIN = false, typename... W>
+__global__ __launch_bounds__(NW * 64) void attn_bwd_bf16_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int RS = DH * 2 + 16;
     constexpr int NT = NW * 64;
@@ -415,15 +419,16 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_bf16_kernel(const mmfm_attn_
     }
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
     const int wave_vote = __all(allk) ? 1 : 0;      // all 64 lanes vote BEFORE any divergence
     if (lane == 0) wflag[wave] = wave_vote;
     __syncthreads();
     int vote = 1;
 #pragma unroll
     for (int w = 0; w < NW; ++w) vote &= wflag[w];
-    const bool nomask = vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
+    const bool nomask = !WIN && vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
 
-    const MaskCtx mk{kpad, modl, d.flags};
+    const MaskCtx mk{kpad, modl, d.flags, win};
     const int nqt = LqP / 32, nkt = LkP / 32;
     const uint32_t pbase = (uint32_t)bh_ * (uint32_t)Lq;
     const float c2 = d.scale * LOG2E;
@@ -577,8 +582,8 @@ constexpr int BW1_NW = 8, BW1_CW = 7, BW1_TS = 80, BW1_TILE = 32 * BW1_TS;
 
 // PIPE: issue S/dP of query tile qt+1 before the element-wise work of tile qt (costs 32 VGPRs; at dh <= 32 the kernel runs
 // four waves per SIMD under a 128-VGPR cap and lets the other waves cover the MFMA latency instead)
-template <int DH, bool PIPE>
-__global__ __launch_bounds__(BW1_NW * 64, DH <= 32 ? 4 : 2) void attn_bwd1_bf16_kernel(const mmfm_attn_desc d) {
+template <int DH, bool PIPE, bool WIN = false, typename... W>
+__global__ __launch_bounds__(BW1_NW * 64, DH <= 32 ? 4 : 2) void attn_bwd1_bf16_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int NW = BW1_NW, CW = BW1_CW, TS = BW1_TS, TILE = BW1_TILE;
     constexpr int KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int RS = DH * 2 + 16;
@@ -655,15 +660,16 @@ __global__ __launch_bounds__(BW1_NW * 64, DH <= 32 ? 4 : 2) void attn_bwd1_bf16_
     }
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
     const int wave_vote = __all(allk) ? 1 : 0;
     if (lane == 0) wflag[wave] = wave_vote;
     __syncthreads();
     int vote = 1;
 #pragma unroll
     for (int w = 0; w < NW; ++w) vote &= wflag[w];
-    const bool nomask = vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
+    const bool nomask = !WIN && vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
 
-    const MaskCtx mk{kpad, modl, d.flags};
+    const MaskCtx mk{kpad, modl, d.flags, win};
     const int nqt = LqP / 32, nkt = LkP / 32;        // nkt <= CW (launcher)
     const float c2 = d.scale * LOG2E;
 
@@ -781,16 +787,16 @@ __global__ __launch_bounds__(BW1_NW * 64, DH <= 32 ? 4 : 2) void attn_bwd1_bf16_
     }
 }
 
-size_t bwd1_lds(int Lq, int Lk, int dh) {
+size_t bwd1_lds(int Lq, int Lk, int dh, bool win = false) {
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31, RS = dh * 2 + 16;
-    return (size_t)2 * LqP * RS + (size_t)4 * LqP * 4 + (size_t)2 * BW1_CW * BW1_TILE + (size_t)32 * RS + BW1_NW * 4 + LkP + std::max(Lq, Lk) + 64;
+    return (size_t)2 * LqP * RS + (size_t)4 * LqP * 4 + (size_t)2 * BW1_CW * BW1_TILE + (size_t)32 * RS + BW1_NW * 4 + LkP + std::max(Lq, Lk) + 64 + attn_win_lds(win, Lk);
 }
 // shapes the single-pass backward takes: one key tile per compute wave, the K image fits the staging area, the dK/dV
 // store tiles fit the Q/dO images
-bool bwd1_ok(int Lq, int Lk, int dh) {
+bool bwd1_ok(int Lq, int Lk, int dh, bool win = false) {
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31, RS = dh * 2 + 16;
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_BWD_SINGLE"); return e && atoi(e) == 0; }();
-    return !off && LkP <= 32 * BW1_CW && LkP <= LqP && (size_t)LkP * RS <= (size_t)2 * BW1_CW * BW1_TILE && bwd1_lds(Lq, Lk, dh) <= 160 * 1024;
+    return !off && LkP <= 32 * BW1_CW && LkP <= LqP && (size_t)LkP * RS <= (size_t)2 * BW1_CW * BW1_TILE && bwd1_lds(Lq, Lk, dh, win) <= 160 * 1024;
 }
 
 // ============================================================================ tiled bf16 kernels (long sequences)
@@ -803,8 +809,8 @@ constexpr int TCH16 = 128;       // streamed rows per chunk
 
 // (dh 128: the O tile is 64 accumulator registers, dK^T + dV^T are 128 beside 64 of K / V operands: those instantiations are compiled for
 // one wave per SIMD, 512 registers per lane; the dh <= 64 ones keep their two)
-template <int DH>
-__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_fwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
+template <int DH, bool WIN = false, typename... W>
+__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_fwd_bf16_tiled_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int NW = 4, KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int KRS = DH * 2 + 16, VRS = DT * 64, SLD = DT * 32 + 1, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -832,15 +838,16 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_fwd_bf16_tiled_kern
     }
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
     const int wave_vote = __all(allk) ? 1 : 0;
     if (lane == 0) wflag[wave] = wave_vote;
     __syncthreads();
     int vote = 1;
 #pragma unroll
     for (int w = 0; w < NW; ++w) vote &= wflag[w];
-    const bool nomask = vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
+    const bool nomask = !WIN && vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
 
-    const MaskCtx mk{kpad, modl, d.flags};
+    const MaskCtx mk{kpad, modl, d.flags, win};
     const Drop16 dp = drop16_init(d.drop_p);
     const Drop dout = drop_init(d.drop_o);
     float* sc = Sc + wave * 32 * SLD;
@@ -943,8 +950,8 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_fwd_bf16_tiled_kern
 
 // PHASE 0: the workgroup owns 4 key tiles (dK, dV; K/V operands in registers) and streams Q / dO chunks;
 // PHASE 1: owns 4 query tiles (dQ; Q/dO operands and delta in registers) and streams K / V chunks.
-template <int DH, int PHASE>
-__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_bwd_bf16_tiled_kernel(const mmfm_attn_desc d) {
+template <int DH, int PHASE, bool WIN = false, typename... W>
+__global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_bwd_bf16_tiled_kernel(const mmfm_attn_desc d, W... w) {
     constexpr int NW = 4, KS = DH / 16, DT = (DH + 31) / 32;
     constexpr int RS = DH * 2 + 16, NT = NW * 64, C8 = DH / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -981,15 +988,16 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_bwd_bf16_tiled_kern
     }
     if (d.flags & MMFM_ATTN_SEP)
         for (int i = t; i < Lmx; i += NT) modl[i] = d.mod_id[i];
+    const AttnWin win = win_stage<WIN>(modl, Lmx, b, Lk, t, NT, w...);
     const int wave_vote = __all(allk) ? 1 : 0;
     if (lane == 0) wflag[wave] = wave_vote;
     __syncthreads();
     int vote = 1;
 #pragma unroll
     for (int w = 0; w < NW; ++w) vote &= wflag[w];
-    const bool nomask = vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
+    const bool nomask = !WIN && vote && !(d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP));
 
-    const MaskCtx mk{kpad, modl, d.flags};
+    const MaskCtx mk{kpad, modl, d.flags, win};
     const uint32_t pbase = (uint32_t)bh_ * (uint32_t)Lq;
     const float c2 = d.scale * LOG2E;
     char* sct = Sc + wave * 32 * RS;
@@ -1168,13 +1176,13 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attn_bwd_bf16_tiled_kern
     }
 }
 
-size_t fwd_tiled16_lds(int Lq, int Lk, int dh) {
+size_t fwd_tiled16_lds(int Lq, int Lk, int dh, bool win = false) {
     const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31;
-    return (size_t)TCH16 * (dh * 2 + 16) + (size_t)TCH16 * DT * 64 + (size_t)4 * 32 * (DT * 32 + 1) * 4 + 16 + LkP + std::max(Lq, Lk) + 64;
+    return (size_t)TCH16 * (dh * 2 + 16) + (size_t)TCH16 * DT * 64 + (size_t)4 * 32 * (DT * 32 + 1) * 4 + 16 + LkP + std::max(Lq, Lk) + 64 + attn_win_lds(win, Lk);
 }
-size_t bwd_tiled16_lds(int Lq, int Lk, int dh) {
+size_t bwd_tiled16_lds(int Lq, int Lk, int dh, bool win = false) {
     const int LkP = (Lk + 31) & ~31, RS = dh * 2 + 16;
-    return (size_t)2 * TCH16 * RS + (size_t)4 * TCH16 * 4 + (size_t)4 * 32 * RS + 16 + LkP + std::max(Lq, Lk) + 64;
+    return (size_t)2 * TCH16 * RS + (size_t)4 * TCH16 * 4 + (size_t)4 * 32 * RS + 16 + LkP + std::max(Lq, Lk) + 64 + attn_win_lds(win, Lk);
 }
 
 // waves per workgroup (MMFM_ATTN_FWD_WAVES / MMFM_ATTN_BWD_WAVES = 4 or 8).  Smaller workgroups let more of them
@@ -1194,14 +1202,14 @@ int fwd_waves_for(int Lq) {
 }
 int bwd_waves() { static int w = env_waves("MMFM_ATTN_BWD_WAVES", 4); return w; }
 
-size_t fwd_lds(int Lq, int Lk, int dh, int nw) {
+size_t fwd_lds(int Lq, int Lk, int dh, int nw, bool win = false) {
     const int DT = (dh + 31) / 32, LkP = (Lk + 31) & ~31;
-    return (size_t)LkP * (dh * 2 + 16) + (size_t)LkP * DT * 64 + (size_t)nw * 32 * (DT * 32 + 1) * 4 + LkP + std::max(Lq, Lk) + 64;
+    return (size_t)LkP * (dh * 2 + 16) + (size_t)LkP * DT * 64 + (size_t)nw * 32 * (DT * 32 + 1) * 4 + LkP + std::max(Lq, Lk) + 64 + attn_win_lds(win, Lk);
 }
-size_t bwd_lds(int Lq, int Lk, int dh, int nw, int phase) {
+size_t bwd_lds(int Lq, int Lk, int dh, int nw, int phase, bool win = false) {
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31, RS = dh * 2 + 16;
     const size_t images = (size_t)2 * (phase == 0 ? LqP : LkP) * RS;
-    return images + (phase == 0 ? (size_t)4 * LqP * 4 : 0) + (size_t)nw * 32 * RS + LkP + std::max(Lq, Lk) + 64;
+    return images + (phase == 0 ? (size_t)4 * LqP * 4 : 0) + (size_t)nw * 32 * RS + LkP + std::max(Lq, Lk) + 64 + attn_win_lds(win, Lk);
 }
 
 }  // namespace
@@ -1212,37 +1220,46 @@ size_t bwd_lds(int Lq, int Lk, int dh, int nw, int phase) {
 bool mmfm_attn_bf16_takes(const mmfm_attn_desc& d, bool force_tiled, AttnRoute& r) {
     if (!(d.dh == 16 || d.dh == 32 || d.dh == 64 || d.dh == 128) || !attn_io_aligned(d)) return false;
     const int nwb = bwd_waves();
-    const bool fits = fwd_lds(d.Lq, d.Lk, d.dh, fwd_waves()) <= ATTN_LDS_MAX && bwd_lds(d.Lq, d.Lk, d.dh, nwb, 0) <= ATTN_LDS_MAX &&
-                      bwd_lds(d.Lq, d.Lk, d.dh, nwb, 1) <= ATTN_LDS_MAX;
+    const bool win = r.win != nullptr;              // the pos row of a window launch counts in every formula
+    const bool fits = fwd_lds(d.Lq, d.Lk, d.dh, fwd_waves(), win) <= ATTN_LDS_MAX && bwd_lds(d.Lq, d.Lk, d.dh, nwb, 0, win) <= ATTN_LDS_MAX &&
+                      bwd_lds(d.Lq, d.Lk, d.dh, nwb, 1, win) <= ATTN_LDS_MAX;
     if (!fits || force_tiled || d.dh == 128) {
         r.family = MMFM_ATTN_FAMILY_BF16_TILED;
-        return fwd_tiled16_lds(d.Lq, d.Lk, d.dh) <= ATTN_LDS_MAX && bwd_tiled16_lds(d.Lq, d.Lk, d.dh) <= ATTN_LDS_MAX;
+        return fwd_tiled16_lds(d.Lq, d.Lk, d.dh, win) <= ATTN_LDS_MAX && bwd_tiled16_lds(d.Lq, d.Lk, d.dh, win) <= ATTN_LDS_MAX;
     }
     r.family = MMFM_ATTN_FAMILY_BF16;
     r.fwd_waves = fwd_waves_for(d.Lq);
-    if (r.fwd_waves == 8 && fwd_lds(d.Lq, d.Lk, d.dh, 8) > ATTN_LDS_MAX) r.fwd_waves = 4;
-    r.bwd_single = bwd1_ok(d.Lq, d.Lk, d.dh);
+    if (r.fwd_waves == 8 && fwd_lds(d.Lq, d.Lk, d.dh, 8, win) > ATTN_LDS_MAX) r.fwd_waves = 4;
+    r.bwd_single = bwd1_ok(d.Lq, d.Lk, d.dh, win);
     return true;
 }
 
+// ATTN_LAUNCH16: r.win picks the WINDOW instantiation, which takes the window behind the descriptor
+#define ATTN_LAUNCH16(GRID, BLOCK, LDSB, WHAT, KERN, ...)                                                            \
+    if (win) {                                                                                                        \
+        auto kern = KERN<__VA_ARGS__, true, mmfm_attn_window>;                                                        \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;                     \
+        hipLaunchKernelGGL(kern, GRID, BLOCK, LDSB, st, d, *win);                                                     \
+    } else {                                                                                                          \
+        auto kern = KERN<__VA_ARGS__>;                                                                                \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;                     \
+        hipLaunchKernelGGL(kern, GRID, BLOCK, LDSB, st, d);                                                           \
+    }
 int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, const AttnRoute& r, bool backward, hipStream_t st) {
+    const mmfm_attn_window* win = r.win;
+    const bool hw = win != nullptr;
     if (r.family == MMFM_ATTN_FAMILY_BF16_TILED) {
         const int gq = ((d.Lq + 31) / 32 + 3) / 4, gk = ((d.Lk + 31) / 32 + 3) / 4;
-#define TILED16(KERN, GY, LDSB, WHAT)                                                                             \
-        {                                                                                                         \
-            auto kern = KERN;                                                                                     \
-            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), LDSB, WHAT)) return rc;             \
-            hipLaunchKernelGGL(kern, dim3(d.B * d.heads, GY), dim3(256), LDSB, st, d);                            \
-        }
+#define TILED16(GY, LDSB, WHAT, KERN, ...) ATTN_LAUNCH16(dim3(d.B * d.heads, GY), dim3(256), LDSB, WHAT, KERN, __VA_ARGS__)
         if (backward) {
-            const size_t lds = bwd_tiled16_lds(d.Lq, d.Lk, d.dh);
-#define TILED16B(DHV) { TILED16((attn_bwd_bf16_tiled_kernel<DHV, 0>), gk, lds, "mmfm_attn_bwd(bf16, tiled)") TILED16((attn_bwd_bf16_tiled_kernel<DHV, 1>), gq, lds, "mmfm_attn_bwd(bf16, tiled)") }
+            const size_t lds = bwd_tiled16_lds(d.Lq, d.Lk, d.dh, hw);
+#define TILED16B(DHV) { TILED16(gk, lds, "mmfm_attn_bwd(bf16, tiled)", attn_bwd_bf16_tiled_kernel, DHV, 0) TILED16(gq, lds, "mmfm_attn_bwd(bf16, tiled)", attn_bwd_bf16_tiled_kernel, DHV, 1) }
             if (d.dh == 16) TILED16B(16) else if (d.dh == 32) TILED16B(32) else if (d.dh == 64) TILED16B(64) else TILED16B(128)
 #undef TILED16B
             MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, tiled)");
         } else {
-            const size_t lds = fwd_tiled16_lds(d.Lq, d.Lk, d.dh);
-#define TILED16F(DHV) TILED16((attn_fwd_bf16_tiled_kernel<DHV>), gq, lds, "mmfm_attn_fwd(bf16, tiled)")
+            const size_t lds = fwd_tiled16_lds(d.Lq, d.Lk, d.dh, hw);
+#define TILED16F(DHV) { TILED16(gq, lds, "mmfm_attn_fwd(bf16, tiled)", attn_fwd_bf16_tiled_kernel, DHV) }
             if (d.dh == 16) TILED16F(16) else if (d.dh == 32) TILED16F(32) else if (d.dh == 64) TILED16F(64) else TILED16F(128)
 #undef TILED16F
             MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, tiled)");
@@ -1252,26 +1269,20 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, const AttnRoute& r, bool back
     }
     if (backward) {
         if (r.bwd_single) {
-            const size_t lds = bwd1_lds(d.Lq, d.Lk, d.dh);
+            const size_t lds = bwd1_lds(d.Lq, d.Lk, d.dh, hw);
 #define BWD1S(DHV)                                                                                                \
-            {                                                                                                     \
-                auto kern = attn_bwd1_bf16_kernel<DHV, (DHV > 32)>;                                               \
-                if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16, single pass)")) return rc; \
-                hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(BW1_NW * 64), lds, st, d);                     \
-            }
+            { ATTN_LAUNCH16(dim3(d.B * d.heads), dim3(BW1_NW * 64), lds, "mmfm_attn_bwd(bf16, single pass)", attn_bwd1_bf16_kernel, DHV, (DHV > 32)) }
             if (d.dh == 16) BWD1S(16) else if (d.dh == 32) BWD1S(32) else BWD1S(64)
 #undef BWD1S
             MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, single pass)");
             return 0;
         }
         const int nw = bwd_waves();
-        const size_t lds0 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 0), lds1 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 1);
+        const size_t lds0 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 0, hw), lds1 = bwd_lds(d.Lq, d.Lk, d.dh, nw, 1, hw);
 #define BWD1(DHV, NWV, PH)                                                                                        \
         {                                                                                                         \
-            auto kern = attn_bwd_bf16_kernel<DHV, NWV, PH>;                                                       \
             const size_t lds = PH == 0 ? lds0 : lds1;                                                             \
-            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16)")) return rc; \
-            hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(NWV * 64), lds, st, d);                            \
+            ATTN_LAUNCH16(dim3(d.B * d.heads), dim3(NWV * 64), lds, "mmfm_attn_bwd(bf16)", attn_bwd_bf16_kernel, DHV, NWV, PH) \
         }
 #define BWD(DHV)                                                                                                  \
         if (nw == 8) { BWD1(DHV, 8, 0) BWD1(DHV, 8, 1) } else { BWD1(DHV, 4, 0) BWD1(DHV, 4, 1) }
@@ -1282,13 +1293,9 @@ int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, const AttnRoute& r, bool back
         return 0;
     }
     const int nw = r.fwd_waves;
-    const size_t lds = fwd_lds(d.Lq, d.Lk, d.dh, nw);
+    const size_t lds = fwd_lds(d.Lq, d.Lk, d.dh, nw, hw);
 #define FWD1(DHV, NWV)                                                                                            \
-    {                                                                                                             \
-        auto kern = attn_fwd_bf16_kernel<DHV, NWV>;                                                               \
-        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_fwd(bf16)")) return rc; \
-        hipLaunchKernelGGL(kern, dim3(d.B * d.heads), dim3(NWV * 64), lds, st, d);                                \
-    }
+    { ATTN_LAUNCH16(dim3(d.B * d.heads), dim3(NWV * 64), lds, "mmfm_attn_fwd(bf16)", attn_fwd_bf16_kernel, DHV, NWV) }
 #define FWD(DHV) if (nw == 8) FWD1(DHV, 8) else FWD1(DHV, 4)
     if (d.dh == 16) { FWD(16) } else if (d.dh == 32) { FWD(32) } else { FWD(64) }
 #undef FWD

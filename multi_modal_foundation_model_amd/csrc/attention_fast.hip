@@ -133,8 +133,13 @@ constexpr float F_OVERFLOW = 1.2676506e30f;                    // 2^100: a row s
 
 // NKT = key tiles of the head when known at compile time (7: the L = 200 / 224 step shapes), 0 = read from the descriptor.
 // MASKED = the launch carries CAUSAL and / or SEP (see "mask tiles" above); false compiles to the dense / DIAG kernel as it was.
-template <int NW, bool DROP, int NKT, bool MASKED>
-__global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale) {
+// WIN (with MASKED; CAUSAL / SEP are refused under a window) = the launch carries a window over time stamps as the trailing argument
+// (MMFM_ATTN_WINDOW): tiles are classified from per-tile stamp minima / maxima (attn_common.h win_tile_class), a mixed tile applies
+// the window per element, and the reference exponent comes from the DIAGONAL tile - under a window tile 0 can be skipped, or leave
+// rows without an allowed key, which would send every wave through the exact pass.
+template <int NW, bool DROP, int NKT, bool MASKED, bool WIN = false, typename... W>
+__global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale, W... w) {
+    static_assert(!WIN || MASKED, "the window forms ride on the MASKED machinery");
     constexpr int NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, kh = lane >> 5, l31 = lane & 31;
@@ -152,7 +157,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     int* tmod = wflag + 8;                                               // MASKED: per-tile modality votes (second half of the 64 bytes)
     float* kzero = reinterpret_cast<float*>(wflag + 16);                 // MASKED: 0 for every existing key, -inf beyond Lk
     uint8_t* modb = reinterpret_cast<uint8_t*>(kzero + LkP);             // MASKED: mod_id bytes
-    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
+    int* posb = reinterpret_cast<int*>(kzero);                           // WIN: time stamps [LkP] (no T_ZERO class: kzero is not needed),
+    int* tmin = tmod;                                                    //      per-tile minima (the modality votes' words)
+    int* tmax = reinterpret_cast<int*>(modb);                            //      and maxima (the mod_id bytes' first 32; LkP >= 32)
+    const bool causal = MASKED && !WIN && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && !WIN && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * 32;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * 32;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * 32;
@@ -184,6 +192,12 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     if constexpr (MASKED) {
         if (sep && t < LkP) mv = d.mod_id[min(t, Lk - 1)];
     }
+    int pv = 0, wlo = 0, whi = 0;
+    if constexpr (WIN) {
+        const mmfm_attn_window ww[1] = {w...};
+        wlo = ww[0].lo; whi = ww[0].hi;
+        if (t < LkP) pv = ww[0].pos[(size_t)b * Lk + min(t, Lk - 1)];
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = t + NT * j, row = c >> 2, col = c & 3;
@@ -194,7 +208,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
     }
     const bool kok = t < Lk && (kpv != 0 || causal);    // CAUSAL replaces the key padding: every existing key has bias 0
     if (t < LkP) kbias[t] = kok ? 0.f : -INFINITY;
-    if constexpr (MASKED) {
+    if constexpr (WIN) {
+        stage_pos(posb, tmin, tmax, t, LkP, pv);
+    } else if constexpr (MASKED) {
         if (t < LkP) kzero[t] = t < Lk ? 0.f : -INFINITY;
         stage_mod(modb, tmod, t, LkP, mv);
     }
@@ -221,7 +237,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
         const int tq = sep ? tmod[qt] : 0;
         nkt_run = 1;
         for (int kt = 0; kt < nkt; ++kt) {
-            const int c = tile_class(causal, sep, tq, sep ? tmod[kt] : 0, qt, kt);
+            int c;
+            if constexpr (WIN) c = win_tile_class((d.flags & MMFM_ATTN_DIAG) && kt == qt, tmin[qt], tmax[qt], tmin[kt], tmax[kt], wlo, whi);
+            else c = tile_class(causal, sep, tq, sep ? tmod[kt] : 0, qt, kt);
             m_skip |= (c == T_SKIP) << kt;
             m_zero |= (c == T_ZERO) << kt;
             m_mix |= (c == T_MIXED) << kt;
@@ -255,6 +273,17 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
             if ((m_mix >> kt) & 1) {                     // T_MIXED: the whole rule per element, on a branch like dfix
                 asm volatile("" ::: "memory");
                 const int fl = d.flags;
+                if constexpr (WIN) {
+                    const int pq = posb[q];                              // q < 32 nqt = LkP (Lq == Lk under a window)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int4 pk = *reinterpret_cast<const int4*>(posb + kt * 32 + 8 * g + 4 * kh);
+                        const int pks[4] = {pk.x, pk.y, pk.z, pk.w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            a[4 * g + i] = mixed_start_win(fl, q, kt * 32 + 8 * g + 4 * kh + i, Lk, a[4 * g + i], pq, pks[i], wlo, whi);
+                    }
+                } else {
                 const uint32_t mq = sep ? modb[q] : 0u;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -262,6 +291,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         a[4 * g + i] = mixed_start(fl, q, kt * 32 + 8 * g + 4 * kh + i, Lk, a[4 * g + i], mq, (mw >> (8 * i)) & 0xffu);
+                }
                 }
             }
         }
@@ -297,8 +327,15 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
         f32x16 sc[2];
         if (DROP) mk[0] = ld_masks(mkp);
         sc[0] = score(0);
+        if constexpr (WIN) {
+            // the diagonal tile: under DIAG every row has an allowed key there (padded rows of a ragged tile carry the -inf bias: no
+            // effect on the maximum).  Without DIAG a row may still find none: -1e30 then overflows its sum into the exact pass
+            const f32x16 sref = score(qt < nkt ? qt : 0);
+            m_ref = v_max(tile_max<4>(sref), -1e30f / c2) * c2;
+        } else {
         m_ref = v_max((nkt == 1 && gtail != 4) ? (gtail == 1 ? tile_max<1>(sc[0]) : gtail == 2 ? tile_max<2>(sc[0]) : tile_max<3>(sc[0]))
                                                 : tile_max<4>(sc[0]), -1e30f / c2) * c2;
+        }
 #pragma unroll
         for (int kt = 0; kt < F_MAXKT; ++kt) {
             if constexpr (!MASKED) {
@@ -309,7 +346,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
                 tile(kt, sc[kt & 1], mk[kt & 1]);
                 if (kt + 1 >= nkt) break;
             } else {
-                // tile 0 is never T_SKIP (k = 0 <= q); skipped tiles cost two scalar branches
+                // CAUSAL / SEP: tile 0 is never T_SKIP (k = 0 <= q); WIN: it may be - its scores are then computed and not used;
+                // skipped tiles cost two scalar branches
                 if (kt + 1 < nkt_run && !skipped(kt + 1)) {
                     sc[(kt + 1) & 1] = score(kt + 1);
                     if (DROP) mk[(kt + 1) & 1] = ld_masks(mkp + (kt + 1));
@@ -320,7 +358,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_fast_kernel(const mmfm_at
         }
     }
     float l_tot = xhalf_sum(l_run);
-    if (__any(!(l_tot < F_OVERFLOW))) {
+    // (WIN: lanes of queries beyond Lq - the padded rows of a ragged last tile, whose stamp repeats the last one and which have no key of
+    // their own - may find nothing in the diagonal tile and overflow; nothing of them is stored, so they do not send the wave anywhere)
+    if (__any(!(l_tot < F_OVERFLOW) && (!WIN || q < Lq))) {
         // EXACT PASS (rare; also taken by NaN inputs, once): running maximum per tile, output tile rescaled every tile.
         float m_run = -1e30f;
         l_run = 0.f;
@@ -461,8 +501,11 @@ __device__ __forceinline__ void bwd_tile(const f32x16& s, const f32x16& dpv, flo
 // NQT = query tiles of the head when known at compile time (7: the L = 200 / 224 step shapes - the query-tile loop is then straight-line
 // code and every LDS address in it a lane constant plus an immediate), 0 = read from the descriptor.
 // MASKED: as in the forward; a compute wave (one key tile) classifies its query tiles, a skipped tile stages zeros for the dQ wave.
-template <bool DROP, int NQT, bool MASKED>
-__global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale) {
+// WIN: as in the forward - a compute wave classifies its query tiles from the per-tile stamp minima / maxima, skipped tiles stage zeros,
+// mixed tiles apply the window per element (lane = key, register = query).
+template <bool DROP, int NQT, bool MASKED, bool WIN = false, typename... W>
+__global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_attn_desc d, const float keep_scale, W... w) {
+    static_assert(!WIN || MASKED, "the window forms ride on the MASKED machinery");
     constexpr int NW = B_NW, CW = B_CW, TS = B_TS, TILE = B_TILE, RS = B_RS, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, kh = lane >> 5, l31 = lane & 31;
@@ -481,7 +524,10 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     uint32_t* flags = reinterpret_cast<uint32_t*>(sc7 + 32 * B_QRS);      // [0..7]: per-wave pad votes
     int* tmod = reinterpret_cast<int*>(flags + 8);                        // MASKED: per-tile modality votes (rest of the 64 bytes)
     uint8_t* modb = reinterpret_cast<uint8_t*>(flags + 16);               // MASKED: mod_id bytes [LqP]
-    const bool causal = MASKED && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && (d.flags & MMFM_ATTN_SEP);
+    int* posb = reinterpret_cast<int*>(modb + LqP);                       // WIN: time stamps [LqP] (Lq == Lk), then the per-tile maxima [8];
+    int* tmin = tmod;                                                     //      the minima take the modality votes' words
+    int* tmax = posb + LqP;
+    const bool causal = MASKED && !WIN && (d.flags & MMFM_ATTN_CAUSAL), sep = MASKED && !WIN && (d.flags & MMFM_ATTN_SEP);
     const uint16_t* qg = reinterpret_cast<const uint16_t*>(d.q) + (size_t)b * Lq * d.ldq + h * 32;
     const uint16_t* kg = reinterpret_cast<const uint16_t*>(d.k) + (size_t)b * Lk * d.ldk + h * 32;
     const uint16_t* vg = reinterpret_cast<const uint16_t*>(d.v) + (size_t)b * Lk * d.ldv + h * 32;
@@ -530,6 +576,12 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     if constexpr (MASKED) {
         if (sep && t < LqP) mv = d.mod_id[min(t, Lq - 1)];
     }
+    int pv = 0, wlo = 0, whi = 0;
+    if constexpr (WIN) {
+        const mmfm_attn_window ww[1] = {w...};
+        wlo = ww[0].lo; whi = ww[0].hi;
+        if (t < LqP) pv = ww[0].pos[(size_t)b * Lq + min(t, Lq - 1)];
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = t + NT * j, row = c >> 2, col = c & 3;
@@ -558,7 +610,8 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     if (t < LqP) lse2[t] = lsev * LOG2E;
     const bool kok = t < Lk && (kpv != 0 || causal);    // CAUSAL replaces the key padding
     if (t < LkP) kbias[t] = kok ? 0.f : -INFINITY;
-    if constexpr (MASKED) stage_mod(modb, tmod, t, LqP, mv);
+    if constexpr (WIN) stage_pos(posb, tmin, tmax, t, LqP, pv);
+    else if constexpr (MASKED) stage_mod(modb, tmod, t, LqP, mv);
     const int pad = (t < Lk && !kok) ? 1 : 0;
     const int wv = __any(pad) ? 1 : 0;
     if (lane == 0) flags[wave] = (uint32_t)wv;
@@ -591,7 +644,9 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
             if (active) {
                 const int tk = sep ? tmod[kt] : 0;
                 for (int qt = 0; qt < nqt; ++qt) {
-                    const int c = tile_class(causal, sep, sep ? tmod[qt] : 0, tk, qt, kt);
+                    int c;
+                    if constexpr (WIN) c = win_tile_class((d.flags & MMFM_ATTN_DIAG) && kt == qt, tmin[qt], tmax[qt], tmin[kt], tmax[kt], wlo, whi);
+                    else c = tile_class(causal, sep, sep ? tmod[qt] : 0, tk, qt, kt);
                     m_skip |= (c == T_SKIP) << qt;
                     m_zero |= (c == T_ZERO) << qt;
                     m_mix |= (c == T_MIXED) << qt;
@@ -615,6 +670,17 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
             if (mixed) {
                 // T_MIXED: the whole rule per element (lane = key, register = query)
                 const int fl = d.flags;
+                if constexpr (WIN) {
+                    const int pk = posb[key];                            // an active wave's key < 32 nkt <= LqP
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int4 pq = *reinterpret_cast<const int4*>(posb + qt * 32 + 8 * g + 4 * kh);
+                        const int pqs[4] = {pq.x, pq.y, pq.z, pq.w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            s[4 * g + i] = mixed_start_win(fl, qt * 32 + 8 * g + 4 * kh + i, key, Lk, kbv, pqs[i], pk, wlo, whi);
+                    }
+                } else {
                 const uint32_t mk = sep ? modb[key] : 0u;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -622,6 +688,7 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         s[4 * g + i] = mixed_start(fl, qt * 32 + 8 * g + 4 * kh + i, key, Lk, kbv, (mw >> (8 * i)) & 0xffu, mk);
+                }
                 }
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Aq, roff0), kfr[0], s, 0, 0, 0);
                 dpv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(Bq, roff0), vfr[0], zero, 0, 0, 0);
@@ -724,10 +791,10 @@ __global__ __launch_bounds__(B_NW * 64, 4) void attn_bwd_fast_kernel(const mmfm_
     }
 }
 
-size_t bwd_fast_lds(int Lq, int Lk, bool masked) {
+size_t bwd_fast_lds(int Lq, int Lk, bool masked, bool win = false) {        // win (with masked): the stamps and the tile maxima behind the mod_id bytes
     const int LqP = (Lq + 31) & ~31, LkP = (Lk + 31) & ~31;
     return (size_t)2 * LqP * B_RS + (size_t)2 * LqP * 4 + (size_t)LkP * 4 + (size_t)2 * B_CW * B_TILE + (size_t)32 * B_QRS + 64 +
-           (masked ? (size_t)LqP : 0);
+           (masked ? (size_t)LqP : 0) + (win ? (size_t)LqP * 4 + 32 : 0);
 }
 
 }  // namespace
@@ -761,9 +828,10 @@ int mmfm_attn_keepbits_launch(const mmfm_attn_desc& d, hipStream_t st) {
 }
 
 // Shapes the fast kernels take (MMFM_ATTN_FAST=0: none).
-bool mmfm_attn_fast_takes(const mmfm_attn_desc& d) {
+bool mmfm_attn_fast_takes(const mmfm_attn_desc& d, bool win) {
     static const bool off = [] { const char* e = getenv("MMFM_ATTN_FAST"); return e && atoi(e) == 0; }();
     if (off || d.dh != 32) return false;
+    if (win && d.Lq != d.Lk) return false;               // (the entry points refuse it before the route asks)
     const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0;
     if (masked && (d.Lq != d.Lk || ((d.flags & MMFM_ATTN_SEP) && d.mod_id == nullptr))) return false;
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32;
@@ -776,8 +844,9 @@ bool mmfm_attn_fast_takes(const mmfm_attn_desc& d) {
     return attn_io_aligned(d) && (uintptr_t)d.keepbits % 128 == 0;
 }
 
-int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st) {
-    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0, drop = attn_drop_p_on(d);
+int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st, const mmfm_attn_window* win) {
+    // a window launch runs the WIN instantiations, which are MASKED ones: their LDS is the masked kernels' (plus the stamps, backward)
+    const bool masked = (d.flags & (MMFM_ATTN_CAUSAL | MMFM_ATTN_SEP)) != 0 || win != nullptr, drop = attn_drop_p_on(d);
     const int nqt = (d.Lq + 31) / 32, nkt = (d.Lk + 31) / 32;
     const int grid = d.B * d.heads;
     const float keep_scale = drop ? 1.f / mmfm_attn_keep_prob(d.drop_p.p) : 1.f;
@@ -791,7 +860,13 @@ int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
             if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_fwd(bf16, dh 32)")) return rc; \
             hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, st, d, keep_scale);                           \
         }
-#define FWDF3(NWV, DRP, NKT) { if (masked) FWDF4(NWV, DRP, NKT, true) else FWDF4(NWV, DRP, NKT, false) }
+#define FWDFW(NWV, DRP, NKT)                                                                                        \
+        {                                                                                                           \
+            auto kern = attn_fwd_fast_kernel<NWV, DRP, NKT, true, true, mmfm_attn_window>;                          \
+            if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_win_fwd(bf16, dh 32)")) return rc; \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, st, d, keep_scale, *win);                     \
+        }
+#define FWDF3(NWV, DRP, NKT) { if (win) FWDFW(NWV, DRP, NKT) else if (masked) FWDF4(NWV, DRP, NKT, true) else FWDF4(NWV, DRP, NKT, false) }
 #define FWDF(NWV)                                                                                                   \
         {                                                                                                           \
             if (drop) { if (nkt == 7 && NWV >= 7) FWDF3(NWV, true, 7) else FWDF3(NWV, true, 0) }                    \
@@ -800,21 +875,29 @@ int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st
         if (nw == 4) FWDF(4) else if (nw == 6) FWDF(6) else if (nw == 7) FWDF(7) else FWDF(8)
 #undef FWDF
 #undef FWDF3
+#undef FWDFW
 #undef FWDF4
         MMFM_LAUNCH_CHECK("mmfm_attn_fwd(bf16, dh 32)");
         return 0;
     }
-    const size_t lds = nqt == 7 ? bwd_fast_lds(224, 224, masked) : bwd_fast_lds(d.Lq, d.Lk, masked);
+    const size_t lds = nqt == 7 ? bwd_fast_lds(224, 224, masked, win != nullptr) : bwd_fast_lds(d.Lq, d.Lk, masked, win != nullptr);
 #define BWDF4(DRP, NQ, MSK)                                                                                         \
     {                                                                                                               \
         auto kern = attn_bwd_fast_kernel<DRP, NQ, MSK>;                                                             \
         if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_bwd(bf16, dh 32)")) return rc; \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(B_NW * 64), lds, st, d, keep_scale);                              \
     }
-#define BWDF3(DRP, NQ) { if (masked) BWDF4(DRP, NQ, true) else BWDF4(DRP, NQ, false) }
+#define BWDFW(DRP, NQ)                                                                                              \
+    {                                                                                                               \
+        auto kern = attn_bwd_fast_kernel<DRP, NQ, true, true, mmfm_attn_window>;                                    \
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(kern), lds, "mmfm_attn_win_bwd(bf16, dh 32)")) return rc; \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(B_NW * 64), lds, st, d, keep_scale, *win);                        \
+    }
+#define BWDF3(DRP, NQ) { if (win) BWDFW(DRP, NQ) else if (masked) BWDF4(DRP, NQ, true) else BWDF4(DRP, NQ, false) }
     if (drop) { if (nqt == 7) BWDF3(true, 7) else BWDF3(true, 0) }
     else { if (nqt == 7) BWDF3(false, 7) else BWDF3(false, 0) }
 #undef BWDF3
+#undef BWDFW
 #undef BWDF4
     MMFM_LAUNCH_CHECK("mmfm_attn_bwd(bf16, dh 32)");
     return 0;

@@ -176,4 +176,35 @@ __device__ __forceinline__ float mixed_start(int flags, int q, int key, int Lk, 
     return (al && key < Lk) ? 0.f : -INFINITY;
 }
 
+
+// ---- window over time stamps (MMFM_ATTN_WINDOW) on the keep-bit dh-32 kernels: the WIN instantiations ride on the MASKED machinery.
+// The prologue stages the lane's position t of the head - its int32 time stamp into LDS - and votes the minimum / maximum of every
+// 32-position tile (positions beyond L repeat the last stamp, so they move neither); all 64 lanes call it.
+__device__ __forceinline__ void stage_pos(int* posb, int* tmin, int* tmax, int t, int LP, int pv) {
+    if (t < LP) posb[t] = pv;
+    int lo = pv, hi = pv;
+#pragma unroll
+    for (int off = 1; off < 32; off <<= 1) {
+        lo = min(lo, __shfl_xor(lo, off));
+        hi = max(hi, __shfl_xor(hi, off));
+    }
+    if ((t & 31) == 0 && t < LP && (t >> 5) < 8) { tmin[t >> 5] = lo; tmax[t >> 5] = hi; }
+}
+// class of a (query tile, key tile) under the window [lo, hi] over pos[key] - pos[query]: no difference inside -> T_SKIP, unless the
+// tile holds the diagonal of a DIAG launch; every difference inside -> T_BIAS, the class the dense launch gives it; else T_MIXED with
+// the window per element.  Stamps need not be monotone: min / max only widen what is walked per element.  |pos| <= 2^29, |lo|, |hi| <=
+// 2^30: nothing overflows.
+__device__ __forceinline__ int win_tile_class(bool diag_tile, int qmin, int qmax, int kmin, int kmax, int lo, int hi) {
+    if ((kmax - qmin < lo || kmin - qmax > hi) && !diag_tile) return T_SKIP;
+    if (kmin - qmax >= lo && kmax - qmin <= hi) return T_BIAS;
+    return T_MIXED;
+}
+// accumulator start of one element of a T_MIXED tile under a window: bias = the key's padding bias (0 / -inf, or 0 on a fixed diagonal)
+__device__ __forceinline__ float mixed_start_win(int flags, int q, int key, int Lk, float bias, int pq, int pk, int lo, int hi) {
+    const int dlt = pk - pq;
+    bool al = bias == 0.f && dlt >= lo && dlt <= hi;
+    if (flags & MMFM_ATTN_DIAG) al = al || key == q;
+    return (al && key < Lk) ? 0.f : -INFINITY;
+}
+
 }  // namespace attn

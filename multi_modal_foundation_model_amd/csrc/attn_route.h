@@ -9,6 +9,7 @@ struct AttnRoute {
     int family = 0;              // MMFM_ATTN_FAMILY_*
     int fwd_waves = 4;           // MMFM_ATTN_FAMILY_BF16 forward: waves per workgroup
     bool bwd_single = false;     // MMFM_ATTN_FAMILY_BF16 backward: the single-pass kernel, not the two-phase pair
+    const mmfm_attn_window* win = nullptr;   // set by the entry point BEFORE the route runs: the launch's window (MMFM_ATTN_WINDOW), or none
 };
 
 // what the bf16 kernels' 16-byte accesses need of q / k / v / o ...
@@ -25,10 +26,12 @@ inline bool attn_drop_p_on(const mmfm_attn_desc& d) { return d.drop_p.p > 0.f &&
 
 // Per family file: a predicate over what the forward sees (shape, flags, operand alignment, workspace, dropout, the LDS formulas beside
 // the kernels) - never the direction - and a launch that assumes the route chose it and returns 0 or an error.
-bool mmfm_attn_fast_takes(const mmfm_attn_desc& d);                                      // attention_fast.hip: keep-bit kernels, dh 32
-int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);
+// attention_fast.hip: keep-bit kernels, dh 32; win: the launch carries a window (the WIN instantiations take it)
+bool mmfm_attn_fast_takes(const mmfm_attn_desc& d, bool win = false);
+int mmfm_attn_fast_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st, const mmfm_attn_window* win = nullptr);
 bool mmfm_attn_long_takes(const mmfm_attn_desc& d);                                      // attention_long.hip: keep-bit kernels, dh 64 / 128
 int mmfm_attn_long_launch(const mmfm_attn_desc& d, bool backward, hipStream_t st);
-// attention_bf16.hip: the bf16 MFMA kernels, LDS-resident or (force_tiled, dh 128, or a head that does not fit) tiled; fills r
+// attention_bf16.hip: the bf16 MFMA kernels, LDS-resident or (force_tiled, dh 128, or a head that does not fit) tiled; fills r.
+// r.win counts in the LDS formulas and picks the WINDOW instantiations at launch; attention_long.hip is never asked under a window.
 bool mmfm_attn_bf16_takes(const mmfm_attn_desc& d, bool force_tiled, AttnRoute& r);
 int mmfm_attn_bf16_launch(const mmfm_attn_desc& d, const AttnRoute& r, bool backward, hipStream_t st);

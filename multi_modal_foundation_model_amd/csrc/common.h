@@ -186,6 +186,29 @@ __device__ __forceinline__ int attn_xcd_remap(int bid, int nwg, int flags) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
+// ------------------------------------------------------------------ attention window (MMFM_ATTN_WINDOW)
+// The general attention kernels take the window as a template flag plus a trailing argument pack (empty without a window, one
+// mmfm_attn_window with it), the way the segment forms ride on the LayerNorm template: the instantiations without a window keep their
+// argument list and their code.  win_stage puts the sample's pos row into LDS behind the mod_id bytes (4-byte aligned; the LDS formulas
+// beside the kernels add attn_win_lds(L) for it) and hands back the row and the interval; the caller's barrier publishes it.
+struct AttnWin { const int32_t* pos; int lo, hi; };     // pos == nullptr: no window (a literal in those instantiations: the term folds away)
+inline size_t attn_win_lds(bool win, int L) { return win ? (size_t)4 * L + 4 : 0; }
+template <bool WIN, typename... W>
+__device__ __forceinline__ AttnWin win_stage(uint8_t* modl, int Lmx, int b, int L, int t, int nthreads, W... w) {
+    if constexpr (WIN) {
+        const mmfm_attn_window win[1] = {w...};
+        int32_t* p = reinterpret_cast<int32_t*>(modl + ((Lmx + 3) & ~3));
+        for (int i = t; i < L; i += nthreads) p[i] = win[0].pos[(size_t)b * L + i];
+        return AttnWin{p, win[0].lo, win[0].hi};
+    } else {
+        return AttnWin{nullptr, 0, 0};
+    }
+}
+__device__ __forceinline__ bool win_allows(const AttnWin& w, int q, int k) {
+    const int dlt = w.pos[k] - w.pos[q];
+    return dlt >= w.lo && dlt <= w.hi;
+}
+
 // ------------------------------------------------------------------ activations
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {

@@ -546,3 +546,44 @@ extern "C" int mmfm_gather_live_rows(const void* src, void* dst, int B, int T, i
     MMFM_LAUNCH_CHECK("mmfm_gather_live_rows");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- attention window: time stamps -> pos (MMFM_ATTN_WINDOW)
+// pos[b][off_j + t] = clamp(ts_j[b][t]) for the slots of a stitched sequence; the slot table travels as a launch argument.
+namespace {
+struct PosSeg {
+    const int64_t* ts[MAXM];
+    int T[MAXM], off[MAXM];
+    int M, L;
+};
+__global__ __launch_bounds__(256) void attn_pos_prep_kernel(const PosSeg s, int B, int32_t* __restrict__ pos) {
+    constexpr int64_t LIM = (int64_t)1 << 29;
+    const int64_t total = (int64_t)B * s.L;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(idx / s.L), i = (int)(idx - (int64_t)b * s.L);
+        int j = 0;
+#pragma unroll
+        for (int m = 1; m < MAXM; ++m)
+            if (m < s.M && i >= s.off[m]) j = m;
+        const int64_t v = s.ts[j][(int64_t)b * s.T[j] + (i - s.off[j])];
+        pos[idx] = (int32_t)(v < -LIM ? -LIM : v > LIM ? LIM : v);
+    }
+}
+}  // namespace
+
+extern "C" int mmfm_attn_pos_prep(int B, int M, const int32_t* seg_T, const int64_t* const* ts, int32_t* pos, mmfm_stream stream) {
+    MMFM_REQUIRE(B > 0 && M > 0 && M <= MAXM, "mmfm_attn_pos_prep: bad shape B=%d M=%d (M <= %d)", B, M, MAXM);
+    MMFM_REQUIRE(seg_T && ts && pos, "mmfm_attn_pos_prep: null pointer");
+    PosSeg s{};
+    int64_t L = 0;
+    for (int j = 0; j < M; ++j) {
+        MMFM_REQUIRE(seg_T[j] > 0 && ts[j], "mmfm_attn_pos_prep: slot %d: T=%d, ts %s", j, seg_T[j], ts[j] ? "set" : "null");
+        s.ts[j] = ts[j]; s.T[j] = seg_T[j]; s.off[j] = (int)L;
+        L += seg_T[j];
+        MMFM_REQUIRE(L < ((int64_t)1 << 30), "mmfm_attn_pos_prep: sequence too long");
+    }
+    s.M = M; s.L = (int)L;
+    const int64_t n = (int64_t)B * L;
+    hipLaunchKernelGGL(attn_pos_prep_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B, pos);
+    MMFM_LAUNCH_CHECK("mmfm_attn_pos_prep");
+    return 0;
+}

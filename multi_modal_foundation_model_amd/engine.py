@@ -53,6 +53,9 @@ MODAL = ("enc_mods", "dec_mods", "share_mod_emb")
 # The class weights of the softmax cross-entropy modalities (loss_kind 7): a constructor keyword and attribute like the two groups above
 # and like them no dataclass field - the field list, asdict() and the default config stay what they were
 LOSS_EXTRA = ("loss_weight",)
+# The attention window over time stamps (mm.yaml context.forward / context.backward under MultiModal.context_mask): a constructor keyword
+# and attribute like the groups above, no dataclass field.  None - the default, and what (-1, -1) folds into - is today's model
+CONTEXT = ("context",)
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -102,12 +105,22 @@ class EngineConfig:
     # loss_kind[mod] = L.LOSS_SOFTMAX_CE: loss_param[mod] is the label smoothing and loss_weight[mod] the class weights, one per channel
     # of the head (absent: 1).  Tuples, so that __eq__ and the plan pool compare them by value; uploaded once per engine
     loss_weight: InitVar[Optional[Dict[str, Tuple[float, ...]]]] = None
+    # (context.forward, context.backward), both ints >= -1, or None: the encoder's self-attention and the cross-attention see a key only
+    # inside the window over the tokens' time stamps (ops.context_window translates).  (-1, -1) is None
+    context: InitVar[Optional[Tuple[int, int]]] = None
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
     # `n_modality` (a shared mod_emb is one tensor, mm.py:84-87, and the row is the modality's index in `mods` on either side).  Read a
     # side's values through `side()`
 
     def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True,
-                      loss_weight=None):
+                      loss_weight=None, context=None):
+        if context is not None:
+            context = tuple(context)
+            if len(context) != 2:
+                raise ValueError(f"EngineConfig.context = {context!r}: (forward, backward) or None")
+            K.context_window(*context)              # refuses what is not an int >= -1
+            context = None if context == (-1, -1) else context
+        self.context = context
         self.embed_act, self.embed_pos, self.embed_bias = embed_act, embed_pos, embed_bias
         self.loss_weight = {m: tuple(float(x) for x in w) for m, w in (loss_weight or {}).items()}
         names = [m for m, _ in self.mods]
@@ -130,7 +143,7 @@ class EngineConfig:
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA)
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA + CONTEXT)
 
     __hash__ = None
 
@@ -164,7 +177,7 @@ class EngineConfig:
 
     @staticmethod
     def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False, enc_mods=None, dec_mods=None,
-                          share_mod_emb: bool = True) -> "EngineConfig":
+                          share_mod_emb: bool = True, context_window: bool = False) -> "EngineConfig":
         """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
         two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
         sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
@@ -172,7 +185,13 @@ class EngineConfig:
         embedder_opts = True (what MultiModal passes): embedder.act, pos and bias are read per side too (embed_act / embed_pos /
         embed_bias; an act without a kernel raises NotImplementedError naming the accepted ones).  Without it the call keeps the
         contract it had: any act but softsign, pos: false and bias: false raise NotImplementedError.
-        enc_mods / dec_mods / share_mod_emb: the config's fields of those names (modal_filter, share_modality_embeddings)."""
+        enc_mods / dec_mods / share_mod_emb: the config's fields of those names (modal_filter, share_modality_embeddings).
+        context_window = True (what MultiModal passes under its context_mask switch): context.forward / context.backward are read into
+        `context` - a value that is not an int >= -1 raises ValueError here.  Without it the two keys are not looked at, as upstream."""
+        context = None
+        if context_window:
+            ctx = mc["context"]
+            context = (ctx["forward"], ctx["backward"])
         tf = {side: mc[side]["transformer"] for side in ("encoder", "decoder")}
         em = {side: mc[side]["embedder"] for side in ("encoder", "decoder")}
         et, dtf, ee = tf["encoder"], tf["decoder"], em["encoder"]
@@ -215,7 +234,7 @@ class EngineConfig:
                             mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE + (PER_SIDE_EMBED if embedder_opts else ())},
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]),
-                            enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb)
+                            enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb, context=context)
 
 
 # a block's linear: name, the norm that feeds it (None: plain), weight [N, K], has a bias, the adjacent nn.Linear's a fused projection aliases
@@ -666,6 +685,16 @@ class Engine:
         """What a channel-masked plan is keyed by besides the rest: per modality None or the shape of its channel mask."""
         return None if chan is None else tuple(None if v is None else tuple(v.shape) for v in chan)
 
+    def plan_key(self, B, T, training, grad=True, pattern=None, elem=None):
+        """The key of a step plan in `plans`.  Without a context window (EngineConfig.context None) the keys are what they always were:
+        (B, T, training, grad), with the freeze pattern behind it where there is one, and the six-entry form (..., pattern, elem) for an
+        element-masked plan.  Under a window the key is always the six-entry form with ("window", lo, hi) behind it."""
+        if self.cfg.context is not None:
+            return (B, T, bool(training), bool(grad), pattern, elem, ("window",) + K.context_window(*self.cfg.context))
+        if elem is not None:
+            return (B, T, bool(training), bool(grad), pattern, elem)
+        return (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))
+
     def _plan(self, B, T, training, grad=True, pattern=None, elem=None, chan=None):
         """The cached step plan of (batch shape, mode, freeze pattern); built by plan.PlanBuilder the first time.
         grad = False: a forward-only plan (evaluation under no_grad) that skips the tensors saved for the backward.
@@ -677,9 +706,7 @@ class Engine:
         Such plans are pooled with the element-masked ones, under `mask_key`."""
         pattern = pattern if grad else None
         elem_arg, elem = elem, mask_key(elem, chan)
-        key = (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))
-        if elem is not None:
-            key = (B, T, bool(training), bool(grad), pattern, elem)
+        key = self.plan_key(B, T, training, grad, pattern, elem)
         self._select_pool(B, T)
         if grad:
             lru = self._pattern_lru.setdefault((B, T), [])
@@ -715,13 +742,13 @@ class Engine:
           launches / full    the two totals.
         Read-only, builds nothing and launches nothing: the plan must exist (one training forward ran at this shape and pattern)."""
         pattern = self.freeze_pattern()
-        key = (B, T, True, True) + (() if pattern is None else (pattern,))
+        key = self.plan_key(B, T, True, True, pattern)
         if key not in self.plans:
             # element-masked plans (input masking) have keys of their own: the most recently used one of this shape and pattern.  Their
             # backward differs from the plain plan's in the loss launches' entry points alone
             for elem in reversed(self._elem_lru.get((B, T), [])):
-                if (B, T, True, True, pattern, elem) in self.plans:
-                    key = (B, T, True, True, pattern, elem)
+                if self.plan_key(B, T, True, True, pattern, elem) in self.plans:
+                    key = self.plan_key(B, T, True, True, pattern, elem)
                     break
         if key not in self.plans:
             raise KeyError(f"backward_report({B}, {T}): no training plan of this shape under the current freeze pattern has been built yet")
@@ -745,7 +772,7 @@ class Engine:
                  "rowdrop" (the fused MLP's row-keyed hash over (R, 256)) or "attn" (drop_p over (B, heads, Lq, Lk)),
           shape  as above, and for "attn" also dh and keepbits: the site's keep-bit workspace, or None when both directions hash.
         Builds nothing and launches nothing: the plan must exist (one training forward ran at this shape)."""
-        plan = self.plans[(B, T, True, True)]
+        plan = self.plans[self.plan_key(B, T, True, True)]
         c = self.cfg
         Tm = (lambda m: T[m]) if isinstance(T, tuple) else (lambda m: T)          # a segmented plan: per-modality lengths
         H, Lq = c.hidden, sum(Tm(m) for m, _, _ in c.side_mods("encoder"))

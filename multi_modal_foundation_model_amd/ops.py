@@ -201,6 +201,57 @@ def attn_bwd(desc, plan=None):
     _emit(plan, L.lib().mmfm_attn_bwd, (C.byref(desc),), keep=(desc,))
 
 
+# ---- attention inside a window over time stamps (MMFM_ATTN_WINDOW)
+def context_window(forward, backward):
+    """(context.forward, context.backward) of mm.yaml -> the closed interval (lo, hi) of allowed pos[k] - pos[q], as upstream's
+    create_context_mask reads the two keys: -1 is unbounded, and so is backward 0 (`if context_backward > 0`)."""
+    for name, v in (("forward", forward), ("backward", backward)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < -1:
+            raise ValueError(f"context.{name} must be an int >= -1, got {v!r}")
+    hi = min(forward, L.ATTN_WINDOW_INF) if forward >= 0 else L.ATTN_WINDOW_INF
+    lo = -min(backward, L.ATTN_WINDOW_INF) if backward > 0 else -L.ATTN_WINDOW_INF
+    return lo, hi
+
+
+def attn_window(pos, lo, hi):
+    """mmfm_attn_window over `pos`, int32 [B][L] (attn_pos_prep writes it): allowed(q, k) needs lo <= pos[k] - pos[q] <= hi."""
+    if pos.dtype != torch.int32 or not pos.is_contiguous():
+        raise TypeError("attn_window: pos must be a contiguous int32 tensor [B][L]")
+    return L.AttnWindow(pos.data_ptr(), int(max(lo, -L.ATTN_WINDOW_INF)), int(min(hi, L.ATTN_WINDOW_INF)))
+
+
+def attn_win_family(desc, win, backward=False):
+    """attn_family for a window launch (mmfm_attn_win_family; win None = attn_family): the dh 64 / 128 keep-bit family never takes one."""
+    fam = L.lib().mmfm_attn_win_family(C.byref(desc), None if win is None else C.byref(win), int(backward))
+    if fam < 0:
+        L.check(fam, "mmfm_attn_win_family")
+    return fam
+
+
+def attn_win_fwd(desc, win, plan=None):
+    _emit(plan, L.lib().mmfm_attn_win_fwd, (C.byref(desc), None if win is None else C.byref(win)), keep=(desc, win))
+
+
+def attn_win_bwd(desc, win, plan=None):
+    _emit(plan, L.lib().mmfm_attn_win_bwd, (C.byref(desc), None if win is None else C.byref(win)), keep=(desc, win))
+
+
+def attn_pos_prep(B, Ts, stamps, pos, plan=None):
+    """pos[b][off_j + t] = clamp(stamps[j][b][t], +-2^29): one int64 [B][Ts[j]] stamp tensor per slot (the uniform form passes the shared
+    tensor once per slot), pos int32 [B][sum Ts]."""
+    M = len(Ts)
+    if len(stamps) != M:
+        raise ValueError("attn_pos_prep: one stamp tensor per slot")
+    for T, s in zip(Ts, stamps):
+        if s.dtype != torch.int64 or not s.is_contiguous() or s.numel() != B * int(T):
+            raise TypeError("attn_pos_prep: stamps must be contiguous int64 [B][T_j]")
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or pos.numel() != B * sum(int(t) for t in Ts):
+        raise TypeError("attn_pos_prep: pos must be a contiguous int32 tensor [B][sum T_j]")
+    seg = _seg_T(Ts)
+    src = (C.c_void_p * M)(*[s.data_ptr() for s in stamps])
+    _emit(plan, L.lib().mmfm_attn_pos_prep, (B, M, seg, src, P(pos)), keep=(seg, src))
+
+
 def mask_prep(B, T, masks, strides, attn, channels, tokmask, keypad, keep0, mod_id, count, plan=None):
     M = len(masks)
     src = (C.c_void_p * M)(*[m.data_ptr() for m in masks])

@@ -180,6 +180,12 @@ class PlanBuilder:
         self.live = not self.seg and self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
         self.lv = {}
         self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
+        # EngineConfig.context: the encoder's self-attention and the cross-attention (whose mask IS the encoder's, mm.py:210) see a key
+        # only inside [lo, hi] over the time stamps.  forward() writes the encoder side's `pos` once per step (mmfm_attn_pos_prep, from
+        # the stamp buffers the stitch launches read) and those sites launch mmfm_attn_win_*; the decoder's self-attention does not
+        # (adapt_decoder_attention_mask has no context term).  None: no window call anywhere in the plan
+        self.win_lohi = None if c.context is None else K.context_window(*c.context)
+        self.win = None              # the mmfm_attn_window of the windowed sites, set by forward()
         # mm.py:178-194.  The decoder self-attention sites pass these flags, mod_id and their keep-bit buffer like every other site: at
         # dh = 32 the fast kernels take CAUSAL / SEP (csrc/attention_fast.hip, "mask tiles"), at dh = 64 the general kernels do
         self.dec_flags = (L.ATTN_CAUSAL if c.causal_mask else 0) | (L.ATTN_SEP if c.sep_mask else 0)
@@ -612,12 +618,25 @@ class PlanBuilder:
         # the decoder's (its mod_id under CAUSAL / SEP) for the decoder's self-attention
         ms = "decoder" if tag.startswith("dec") and tag.endswith("/sa") else "encoder"
         dh = H // heads
-        keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if sd.use_keep else None
+        # (a windowed site at dh 64 / 128 runs the general kernels, which hash their drop_p decisions: no keep-bit workspace.  At dh 32 the
+        # keep-bit kernels have window forms and the site keeps the workspace it always had)
+        keep = buf(tag + "/keep", (K.attn_keepbits_bytes(B, heads, Lq, Lq),), torch.uint8) if sd.use_keep and (dh == 32 or not self.windowed(tag)) else None
         return K.attn_desc(self.code, B, heads, Lq, Lq, dh, q.data_ptr(), kv.data_ptr() + koff * es, kv.data_ptr() + voff * es, ldq, ldkv, ldkv,
                            o.data_ptr(), H, buf(tag + "/lse", (B, heads, Lq), torch.float32), b[self.mk(ms, "keypad")], b[self.mk(ms, "mod_id")], flags,
                            1.0 / math.sqrt(dh), drop_p=e._drop(tag + "/p", dp), drop_o=e._drop(tag + "/o", dp),
                            d_o=K.P(d_o), lddo=H, dq=K.P(dq), dk=None if dkv is None else dkv.data_ptr() + dkoff * es,
                            dv=None if dkv is None else dkv.data_ptr() + dvoff * es, lddq=lddq, lddk=lddkv, lddv=lddkv, keepbits=keep)
+
+    def windowed(self, tag):
+        """Whether attention site `tag` runs under the context window: every site but the decoder's self-attention, when there is one."""
+        return self.win_lohi is not None and not (tag.startswith("dec") and tag.endswith("/sa"))
+
+    def attn(self, plan, tag, desc, backward=False):
+        """Emits attention site `tag`: mmfm_attn_win_fwd / _bwd with the plan's window where `windowed`, else mmfm_attn_fwd / _bwd."""
+        if self.windowed(tag):
+            (K.attn_win_bwd if backward else K.attn_win_fwd)(desc, self.win, plan=plan)
+        else:
+            (K.attn_bwd if backward else K.attn_fwd)(desc, plan=plan)
 
     def elem_tm(self, m):
         """Modality m's static target-mask buffer where its loss runs under a per-element mask, else None."""
@@ -676,7 +695,7 @@ class PlanBuilder:
         else:
             self.ln_f(plan, X, p + ".ln1", buf(tag + "/h1", (R, H)), tag + "/ln1")
             self.lin(plan, self.b[tag + "/h1"], p + ".attn.qkv", qkv, R, 3 * H, H)
-        K.attn_fwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, a, flags), plan=plan)
+        self.attn(plan, tag + "/sa", self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, a, flags))
         self.out_proj(plan, a, p + ".attn.out_proj", X, Xa)
         return Xa
 
@@ -717,6 +736,12 @@ class PlanBuilder:
                 # the live-bin records of the side's modality slots, from its keep0 (device side: nothing is read back)
                 rec = buf(mk(side, "live"), (M, L.live_rec_ints(T)), torch.int32)
                 K.live_bins(b[mk(side, "keep0")], T, M, rec, plan=fwd)
+        if self.win_lohi is not None:
+            # the encoder side's time stamps as int32 [B, Lq], slot by slot: the shared stamp tensor once per slot, or each slot's own
+            enc = self.mods_of["encoder"]
+            pos = buf("attn/pos", (B, Lq), torch.int32)
+            K.attn_pos_prep(B, [self.Tm[m] for m, _, _ in enc], [b[f"ts/{m}"] if self.seg else b["ts"] for m, _, _ in enc], pos, plan=fwd)
+            self.win = K.attn_window(pos, *self.win_lohi)
         gathered = set()
         tok_tmp = buf("tok_tmp", (BT, H))
         x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
@@ -779,7 +804,7 @@ class PlanBuilder:
                 self.ln_f(fwd, context, p + ".context_norm", hc, tag + "/cn")
                 self.lin(fwd, hq, p + ".cross_attn.query", qc, R, H, H)
                 self.lin(fwd, hc, p + ".cross_attn.kv", kvc, R, 2 * H, H)
-            K.attn_fwd(self.attn_desc(tag + "/xa", qc, H, kvc, 2 * H, 0, H, a2, self.enc_flags), plan=fwd)   # xa_mask = encoder mask
+            self.attn(fwd, tag + "/xa", self.attn_desc(tag + "/xa", qc, H, kvc, 2 * H, 0, H, a2, self.enc_flags))   # xa_mask = encoder mask
             self.out_proj(fwd, a2, p + ".cross_attn.out_proj", Ya, Yb)
             Y = self.mlp_block(fwd, Yb, p, tag)
         self.dec_last = Y
@@ -940,8 +965,8 @@ class PlanBuilder:
         self.out_proj_back(plan, dS, b[tag + "/a"], p + ".attn.out_proj", need_dx=attn)
         qkv, dqkv = b[tag + "/qkv"], b["d/qkv"]
         if attn:
-            K.attn_bwd(self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, b[tag + "/a"], flags, d_o=b["d/t2"], dq=dqkv, dkv=dqkv,
-                                      lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), plan=plan)
+            self.attn(plan, tag + "/sa", self.attn_desc(tag + "/sa", qkv, 3 * H, qkv, 3 * H, H, 2 * H, b[tag + "/a"], flags, d_o=b["d/t2"], dq=dqkv,
+                                                        dkv=dqkv, lddq=3 * H, lddkv=3 * H, dkoff=H, dvoff=2 * H), backward=True)
         self.norm_lin_back(plan, self.F_QKV, dqkv, 3 * H, tag + "/ln1", p + ".attn.qkv", p + ".ln1", tag + "/h1", self.stream_in[tag], dS, dS,
                            need_dx=below)
 
@@ -955,8 +980,8 @@ class PlanBuilder:
         attn = below or ctx or self.tl(p + ".cross_attn.query", p + ".query_norm") or self.tl(p + ".cross_attn.kv", p + ".context_norm")
         self.out_proj_back(plan, dY, b[tag + "/a2"], p + ".cross_attn.out_proj", need_dx=attn)
         if attn:
-            K.attn_bwd(self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
-                                      d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), plan=plan)
+            self.attn(plan, tag + "/xa", self.attn_desc(tag + "/xa", b[tag + "/qc"], H, b[tag + "/kvc"], 2 * H, 0, H, b[tag + "/a2"], self.enc_flags,
+                                                        d_o=b["d/t2"], dq=dqc, dkv=dkvc, lddq=H, lddkv=2 * H, dkoff=0, dvoff=H), backward=True)
         self.norm_lin_back(plan, self.F_LNL, dqc, H, tag + "/qn", p + ".cross_attn.query", p + ".query_norm", tag + "/hq", b[tag + "/xa"], dY, dY,
                            need_dx=below)
         if self.ctx_group:       # the weight gradient where it was; no context-side dX here

@@ -29,6 +29,7 @@ from multi_modal.encoder_embeddings import EncoderLayer
 from multi_modal.losses import SoftmaxCrossEntropy
 from multi_modal.mm_utils import create_context_mask  # noqa: F401  (re-exported like the reference)
 from multi_modal_foundation_model_amd import _lib as L
+from multi_modal_foundation_model_amd import ops as K
 from multi_modal_foundation_model_amd.engine import Engine, EngineConfig
 from utils.config_utils import DictConfig
 
@@ -125,6 +126,7 @@ def _loss_kind(spec) -> int:
 class MultiModal(nn.Module):
     input_masking = False        # the switch of mask_type: input (a class default, so that a module pickled before it existed has it too)
     neuron_padding = False       # the switch of space_attn_mask: padded channels leave the inputs and the loss (a class default, as above)
+    context_mask = False         # the switch of context.forward / context.backward: windowed encoder attention (a class default, as above)
 
     def __init__(self, encoder_embeddings: Dict[str, nn.Module], decoder_embeddings: Dict[str, nn.Module],
                  avail_mod: List, config: DictConfig, share_modality_embeddings: bool = True, **kwargs):
@@ -178,6 +180,12 @@ class MultiModal(nn.Module):
         # reads the mask, as upstream
         if "neuron_padding" in kwargs:
             self.neuron_padding = bool(kwargs["neuron_padding"])
+        # context window: the encoder's self-attention and the cross-attention see a key only where its time stamp lies inside
+        # [-context.backward, +context.forward] of the query's (create_context_mask's reading of the two keys, over time stamps;
+        # DESIGN.md §3y).  False: the two keys are stored and nobody reads them, as upstream (its forward_mask_encoder builds
+        # context_mask = ones under a TO DO).  True: a value that is not an int >= -1 raises ValueError when the engine is built
+        if "context_mask" in kwargs:
+            self.context_mask = bool(kwargs["context_mask"])
 
     def share_modality_embeddings(self):
         for mod in self.encoder_modalities & self.decoder_modalities:
@@ -188,6 +196,8 @@ class MultiModal(nn.Module):
         # fast path (every forward): the cached engine is still valid if a few sentinel parameters are still
         # views of its flat buffer on the same device (.to()/load_state_dict(assign=True) replace them all)
         eng = self._engine
+        if eng is not None and eng.cfg.context != self._context():
+            eng = self._engine = None                   # the switch moved after the engine was built: another config, another engine
         if eng is not None and eng.dtype == self.compute_dtype and self._sentinels and \
                 all(eng.owns_one(p) for p in self._sentinels):
             return eng
@@ -213,7 +223,8 @@ class MultiModal(nn.Module):
             cfg = EngineConfig.from_model_config(self._model_config, mods, per_side=True, embedder_opts=True,
                                                  enc_mods=[m for m in self.avail_mod if m in self.encoder_embeddings],
                                                  dec_mods=[m for m in self.avail_mod if m in self.decoder_embeddings],
-                                                 share_mod_emb=getattr(self, "_share_mod_emb", True))      # (a module pickled before the flag existed shares)
+                                                 share_mod_emb=getattr(self, "_share_mod_emb", True),      # (a module pickled before the flag existed shares)
+                                                 **({"context_window": True} if self.context_mask else {}))
             specs = {m: _loss_spec(self.loss_mod[m]) for m in self.avail_mod if m in self.decoder_embeddings}
             cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
             cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
@@ -226,6 +237,17 @@ class MultiModal(nn.Module):
         elif not self._engine.owns(named):
             self._engine.adopt(named)        # parameters were replaced (.to(), load_state_dict(assign=True), ...)
         return self._engine
+
+    def _context(self):
+        """What EngineConfig.context is under the switch's current position: None with the switch off or at (-1, -1)."""
+        if not self.context_mask:
+            return None
+        ctx = (self.context_forward, self.context_backward)
+        seen = self.__dict__.get("_context_seen")          # validated once per value: engine() asks on every forward
+        if seen is None or seen[0] != ctx:
+            K.context_window(*ctx)
+            seen = self.__dict__["_context_seen"] = (ctx, None if ctx == (-1, -1) else ctx)
+        return seen[1]
 
     def _grad_anchor(self):
         """The parameter that ties the engine's loss into autograd: the first one that requires grad (any will do - the engine hands out

@@ -65,6 +65,9 @@ def build_parser():
     ap.add_argument("--neuron_padding", action="store_true",
                     help="honour the loader's space_attn_mask: padded spike channels are zeroed on both sides and leave the loss and "
                          "n_examples (sets training.neuron_padding)")
+    ap.add_argument("--context_mask", action="store_true",
+                    help="honour context.forward / context.backward of the model config: the encoder's self-attention and the "
+                         "cross-attention see a key only inside that window over the time stamps (sets training.context_mask)")
     ap.add_argument("--n_sessions", type=int, default=1,
                     help="K > 1: multi-session pretraining on synthetic sessions of 300..n_neurons neurons each, batch i from session "
                          "i %% K, spikes right-padded with -1 up to n_neurons (1: one session, no padding)")
@@ -94,6 +97,8 @@ def main(argv=None):
         config["training"]["input_masking"] = True
     if args.neuron_padding:
         config["training"]["neuron_padding"] = True
+    if args.context_mask:
+        config["training"]["context_mask"] = True
     if args.n_sessions < 1:
         raise ValueError(f"--n_sessions must be >= 1, got {args.n_sessions}")
     set_seed(config.seed)

@@ -132,6 +132,17 @@ class MultiModalTrainer():
         self.neuron_padding = neuron_padding
         if neuron_padding:
             getattr(self.model, "module", self.model).neuron_padding = True
+        # training.context_mask (no key of the reference's YAML either: absent = false): honour the model config's context.forward /
+        # context.backward - the encoder's self-attention and the cross-attention see a key only inside that window over the time
+        # stamps (MultiModal.context_mask).  A value of either key that is not an int >= -1 raises ValueError here, before the first step
+        context_mask = self.config.training.get("context_mask", False) if hasattr(self.config.training, "get") else False
+        if not isinstance(context_mask, bool):
+            raise ValueError(f"training.context_mask must be true or false, got {context_mask!r}")
+        self.context_mask = context_mask
+        if context_mask:
+            inner = getattr(self.model, "module", self.model)
+            inner.context_mask = True
+            inner._context()
         self.mixed_training = kwargs.get("mixed_training", False)
         if self.mixed_training:
             self.training_schemes = list(OBJECTIVES)
