@@ -861,6 +861,48 @@ int mmfm_mt19937_jump(uint32_t* state624, int32_t* consumed, uint64_t n);
 /* Drops the cached polynomials (the next long jump pays for phi and its power again): cold-cost measurements. */
 int mmfm_mt19937_jump_reset(void);
 
+/* ------------------------------------------------------------------ MT19937 on the device: the draws whose values ARE read
+ * The outputs of the same engine, generated on the GPU bit for bit as torch's CPU generator hands them out: output i of the
+ * position (state624, consumed) is the tempered word i, u_i = float(out_i & 0xFFFFFF) * 2^-24 is torch.rand's value and
+ * u_i < float(p) is torch.bernoulli's, element i of a row-major fp32 tensor taking output i.  The host generator is not touched: the
+ * caller moves it on with mmfm_mt19937_jump.
+ *   state624, consumed: HOST values with mmfm_mt19937_jump's meaning (624: regenerate first / freshly seeded), read during the call
+ *             and carried to the device as a launch argument: the caller may reuse the array when the call returns;
+ *   streams:  0 = the library's choice (a power of two, at least 64 blocks a run, at most 256 runs), 1 .. MMFM_MT_MAX_STREAMS forces it.  The n outputs are cut into `streams` runs of `blocks`
+ *             whole 624-output blocks, one workgroup each (mmfm_mt_plan names the cut: run s covers outputs [s * blocks * 624,
+ *             min(n, (s + 1) * blocks * 624)), trailing runs may be empty); run s > 0 starts from a state that is a jump of whole
+ *             blocks - applied on the device through t^(624 D) mod phi, in a doubling tree over ceil(log2 streams) polynomials whose
+ *             bit lists are uploaded once per block count D.  The result does not depend on `streams`.
+ *   workspace: mmfm_mt_workspace(n, streams) bytes of device memory, 16-byte aligned, contents arbitrary (n: outputs of one draw, for
+ *             mmfm_mt_corrupt B * T * N; the size serves all three entries).
+ * mmfm_mt_uniform    out[i] = u of output skip + i, i < n (fp32).
+ * mmfm_mt_bernoulli  out[i] = (u of output skip + i) < p (uint8 0 / 1); p in [0, 1].
+ * mmfm_mt_corrupt    one masker call (models/masker.py), draws u1, u2, u3 = outputs i, BTN + i, 2 BTN + i of element i:
+ *                      z = cm(b,t,n) & (u1 < zero_ratio);  dst = z ? 0 : src;  m = max(dst) over all elements, NaN if any NaN survives
+ *                      (torch.max);  dst = m * u3 (one fp32 multiply) where cm & !z & (u2 < random_ratio).
+ *                    src / dst fp32 [B][T][N] contiguous (dst may be src), cm a strided uint8 mask as for mmfm_stage_masked (any
+ *                    stride may be 0), B * T * N < 2^31.  m is found by a first pass that regenerates u1 alone (per-run maxima in the
+ *                    workspace, reduced in a fixed order by every workgroup of the second); the pass is skipped where no element can
+ *                    take noise (random_ratio == 0 or zero_ratio >= 1).
+ * Argument checks (null pointers, consumed outside 0..624, n == 0 or beyond 2^62, p / ratios outside [0, 1] or NaN, streams, negative
+ * strides, a short or misaligned workspace) return -1 before any HIP call.  The first call that needs a block count D computes its polynomial
+ * (host, tens of ms) and uploads it (one allocation, one synchronous copy; at most MMFM_MT_TABLES tables per device are kept); after
+ * that no call allocates or synchronises.  No atomics, no memset: the same bits on every call.
+ * MMFM_MT_DEVICE is the feature macro for the exports (MMFM_VERSION stays, as for MMFM_LOSS_ELEM). */
+#define MMFM_MT_DEVICE 1
+#define MMFM_MT_MAX_STREAMS 1024
+#define MMFM_MT_TABLES 64
+/* pure (no HIP call): the cut of n outputs; streams = 0 picks it.  Returns -1 for n == 0 or streams outside 0..MMFM_MT_MAX_STREAMS. */
+int mmfm_mt_plan(uint64_t n, int streams, int32_t* out_streams, int64_t* out_blocks);
+int64_t mmfm_mt_workspace(uint64_t n, int streams);
+int mmfm_mt_uniform(const uint32_t* state624, int32_t consumed, uint64_t skip, uint64_t n, float* out, int streams,
+                    void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_mt_bernoulli(const uint32_t* state624, int32_t consumed, uint64_t skip, uint64_t n, float p, uint8_t* out, int streams,
+                      void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+int mmfm_mt_corrupt(const uint32_t* state624, int32_t consumed, int B, int T, int N, const float* src, const uint8_t* cm,
+                    int64_t sb, int64_t st, int64_t sn, float zero_ratio, float random_ratio, float* dst, int streams,
+                    void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

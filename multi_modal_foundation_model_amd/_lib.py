@@ -129,6 +129,7 @@ class RowGemmDesc(C.Structure):
 
 ROWGEMM_MAX_GROUPS = 8
 MAX_SEGMENTS = 8                 # MMFM_MAX_SEGMENTS
+MT_MAX_STREAMS = 1024            # MMFM_MT_MAX_STREAMS
 
 
 class RowGemmGroupsDesc(C.Structure):
@@ -244,6 +245,12 @@ _PROTOS = {
     "mmfm_bits_per_spike_neurons": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "mmfm_mt19937_jump": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_uint64]),
     "mmfm_mt19937_jump_reset": (C.c_int, []),
+    # MT19937 on the device (MMFM_MT_DEVICE)
+    "mmfm_mt_plan": (C.c_int, [C.c_uint64, _i, C.POINTER(C.c_int32), C.POINTER(_i64)]),
+    "mmfm_mt_workspace": (C.c_int64, [C.c_uint64, _i]),
+    "mmfm_mt_uniform": (C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_uint64, _vp, _i, _vp, _i64, _vp]),
+    "mmfm_mt_bernoulli": (C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_uint64, _f, _vp, _i, _vp, _i64, _vp]),
+    "mmfm_mt_corrupt": (C.c_int, [_vp, C.c_int32, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _f, _f, _vp, _i, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -161,6 +161,15 @@ bool jump_poly(uint64_t D, std::vector<int>& out) {
 
 }  // namespace
 
+// Internal (C++ linkage, mt_device.hip): the set bits of t^(624 D) mod phi as 16-bit positions, ascending, from the cache above - the
+// table a device-side jump of D blocks uploads once.  false: phi could not be found.
+bool mmfm_mt_jump_bits(uint64_t D, std::vector<uint16_t>& out) {
+    std::vector<int> g;
+    if (!jump_poly(D, g)) return false;
+    out.assign(g.begin(), g.end());                       // every position is below 19937
+    return true;
+}
+
 extern "C" int mmfm_mt19937_jump(uint32_t* state624, int32_t* consumed, uint64_t n) {
     if (!state624 || !consumed) return mmfm_set_error(-1, "mmfm_mt19937_jump: null argument");
     if (*consumed < 0 || *consumed > MT_N) return mmfm_set_error(-1, "mmfm_mt19937_jump: consumed = %d is outside 0..624", (int)*consumed);

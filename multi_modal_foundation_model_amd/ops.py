@@ -677,3 +677,78 @@ def mt19937_jump(state, consumed, n):
 def mt19937_jump_reset():
     """Drops the cached jump polynomials (cold-cost measurements)."""
     L.check(L.lib().mmfm_mt19937_jump_reset(), "mmfm_mt19937_jump_reset")
+
+
+# ---------------------------------------------------------------------------------------------- MT19937 on the device (MMFM_MT_DEVICE)
+def mt_plan(n, streams=None):
+    """(streams, blocks_per_stream) of a device draw of `n` outputs (mmfm_mt_plan; no HIP call): run s covers outputs
+    [s * blocks * 624, min(n, (s + 1) * blocks * 624)).  `streams=None`: the library's choice; an int forces the count (never more runs
+    than blocks)."""
+    s, b = C.c_int32(0), C.c_int64(0)
+    L.check(L.lib().mmfm_mt_plan(int(n), 0 if streams is None else int(streams), C.byref(s), C.byref(b)), "mmfm_mt_plan")
+    return s.value, b.value
+
+
+def mt_workspace(n, streams=None, device=None):
+    """The workspace of the device draws of `n` outputs per draw (mmfm_mt_workspace), contents arbitrary."""
+    nbytes = L.lib().mmfm_mt_workspace(int(n), 0 if streams is None else int(streams))
+    if nbytes < 0:
+        L.check(-1, "mmfm_mt_workspace")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _mt_state(state, what):
+    if state.device.type != "cpu" or state.dtype != torch.int32 or state.numel() != 624 or not state.is_contiguous():
+        raise TypeError(f"{what}: state must be a contiguous CPU int32 tensor of 624 words")
+    return state.data_ptr()
+
+
+def _mt_out(out, n, dtype, device, what):
+    if out is None:
+        if device is None:
+            raise ValueError(f"{what}: give `out` or `device`")
+        return torch.empty(n, dtype=dtype, device=device)
+    if not out.is_cuda or out.dtype != dtype or out.numel() != n or not out.is_contiguous():
+        raise TypeError(f"{what}: out must be a contiguous device {dtype} tensor of {n} elements")
+    return out
+
+
+def mt_uniform(state, consumed, n, skip=0, streams=None, out=None, device=None, ws=None):
+    """out[i] = torch.rand's value for output skip + i of the MT19937 position (state, consumed) (rngjump.py; consumed as for
+    mt19937_jump), generated on the device (mmfm_mt_uniform).  fp32, `n` elements; the host generator is not moved."""
+    sp = _mt_state(state, "mt_uniform")
+    out = _mt_out(out, n, torch.float32, device, "mt_uniform")
+    ws = mt_workspace(n, streams, out.device) if ws is None else ws
+    L.check(L.lib().mmfm_mt_uniform(sp, int(consumed), int(skip), int(n), P(out), 0 if streams is None else int(streams), P(ws), ws.numel(),
+                                    _stream()), "mmfm_mt_uniform")
+    return out
+
+
+def mt_bernoulli(state, consumed, n, p, skip=0, streams=None, out=None, device=None, ws=None):
+    """out[i] = torch.bernoulli(full(p))'s value (uint8 0 / 1) for output skip + i (mmfm_mt_bernoulli)."""
+    sp = _mt_state(state, "mt_bernoulli")
+    out = _mt_out(out, n, torch.uint8, device, "mt_bernoulli")
+    ws = mt_workspace(n, streams, out.device) if ws is None else ws
+    L.check(L.lib().mmfm_mt_bernoulli(sp, int(consumed), int(skip), int(n), float(p), P(out), 0 if streams is None else int(streams), P(ws),
+                                      ws.numel(), _stream()), "mmfm_mt_bernoulli")
+    return out
+
+
+def mt_corrupt(state, consumed, src, cm, zero_ratio, random_ratio, streams=None, out=None, ws=None):
+    """The masker's corruption of `src` (fp32 [B, T, N], contiguous, on the device) under the compact mask `cm` (`elem_strides`), drawn
+    from outputs [0, 3 B T N) of the position (state, consumed): mmfm_mt_corrupt.  Returns the corrupted copy (`out=src` corrupts in place)."""
+    sp = _mt_state(state, "mt_corrupt")
+    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3 or not src.is_contiguous():
+        raise TypeError("mt_corrupt: src must be a contiguous fp32 device tensor [B, T, N]")
+    B, T, N = src.shape
+    if not cm.is_cuda:
+        raise TypeError("mt_corrupt: cm must be on the device")
+    sb, st, sn = elem_strides(cm, B, T, N)
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.data_ptr() != src.data_ptr() and (not out.is_cuda or out.dtype != torch.float32 or out.shape != src.shape or not out.is_contiguous()):
+        raise TypeError("mt_corrupt: out must be src or a contiguous fp32 device tensor of its shape")
+    ws = mt_workspace(B * T * N, streams, src.device) if ws is None else ws
+    L.check(L.lib().mmfm_mt_corrupt(sp, int(consumed), B, T, N, P(src), P(cm), sb, st, sn, float(zero_ratio), float(random_ratio), P(out),
+                                    0 if streams is None else int(streams), P(ws), ws.numel(), _stream()), "mmfm_mt_corrupt")
+    return out

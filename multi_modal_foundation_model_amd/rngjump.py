@@ -48,17 +48,30 @@ def build_state(seed, left, seeded, nxt, words, tail):
     return blob
 
 
-def _jump(gen, n):
-    from . import ops
+def _position(gen):
+    """(parsed blob, state int32[624], consumed) of a CPU generator, or None if its blob is not the layout this module knows."""
     blob = gen.get_state()
     parsed = parse_state(blob)
-    if parsed is None:
+    if parsed is None or not torch.equal(build_state(*parsed), blob):
+        return None
+    _, left, _, nxt, words, _ = parsed
+    return parsed, words.to(torch.int32), (N_WORDS if (left == 1 and nxt == 0) else nxt)     # wraps: the 32 bits of every word
+
+
+def cpu_generator_position(generator=None):
+    """(state, consumed) of `generator` (default: torch's global CPU generator) as ops.mt19937_jump and the device draws (ops.mt_uniform,
+    mt_bernoulli, mt_corrupt) take them, or None where `advance_cpu_generator` would fall back to drawing."""
+    pos = _position(torch.default_generator if generator is None else generator)
+    return None if pos is None else pos[1:]
+
+
+def _jump(gen, n):
+    from . import ops
+    pos = _position(gen)
+    if pos is None:
         return False
-    seed, left, seeded, nxt, words, tail = parsed
-    if not torch.equal(build_state(*parsed), blob):          # the layout is not the one this module knows
-        return False
-    state = words.to(torch.int32)                            # wraps: the 32 bits of every word
-    consumed = ops.mt19937_jump(state, N_WORDS if (left == 1 and nxt == 0) else nxt, n)
+    (seed, left, seeded, nxt, words, tail), state, consumed = pos
+    consumed = ops.mt19937_jump(state, consumed, n)
     words = state.to(torch.int64) & 0xFFFFFFFF
     gen.set_state(build_state(seed, N_WORDS + 1 - consumed, seeded, consumed, words, tail))
     return True

@@ -6,7 +6,9 @@ moving this to the GPU would change the random stream for no gain.  The order an
 generator calls below are what makes the masks bit-exact against the reference
 (tests/golden/masker_bits.npz): bernoulli(expand_prob) [, randint], bernoulli(mask_probs),
 bernoulli(zero_ratio x shape), bernoulli(random_ratio x shape), rand(shape) — all on the CPU
-generator, wherever `spikes` lives.
+generator, wherever `spikes` lives.  Where the values of the three [B, T, N] draws are read (zero_ratio < 1) and
+`spikes` is an fp32 CUDA tensor, the same generator outputs are produced on the device instead (`_device_corrupt`,
+csrc/mt_device.hip) and the CPU generator jumps past them: the stream and the bits stay the reference's.
 """
 import os
 import random
@@ -73,16 +75,72 @@ class Masker(nn.Module):
         # per call, mm.py) and it is never pickled: a checkpoint always starts on the reference's stream.
         self.token_mask_only = False
         self._ring = _PinnedRing()
+        self._mt_ws = {}                       # (device, ops.mt_plan of the call) -> workspace of the device-side draws
+        self.device_draws = 0                  # masker calls whose [B, T, N] draws were generated on the device
 
     def __getstate__(self):                    # checkpoints pickle the whole model: drop pinned buffers / events
         state = self.__dict__.copy()
         state["_ring"] = None
+        state["_mt_ws"] = {}
+        state["device_draws"] = 0
         state["token_mask_only"] = False       # a run's throughput switch must not leak into model_best.pt / model_last.pt
         return state
 
     @staticmethod
     def _no_mask(spikes):
         return spikes, torch.zeros_like(spikes).to(torch.int64)
+
+    # ---- the [B, T, N] draws whose values are read, generated on the device (csrc/mt_device.hip) bit for bit as the CPU generator hands
+    # them out; the generator itself moves on by jump-ahead.  MMFM_MASKER_DEVICE=0 (or MMFM_MASKER_JUMP=0) keeps the host draws; so does
+    # anything but a contiguous fp32 CUDA tensor below 2^31 elements, and a generator blob rngjump does not know.
+    @staticmethod
+    def _device_position(spikes):
+        if not (spikes.is_cuda and spikes.dtype == torch.float32 and spikes.is_contiguous() and 0 < spikes.numel() < 2 ** 31):
+            return None
+        if os.environ.get("MMFM_MASKER_JUMP", "1") == "0" or os.environ.get("MMFM_MASKER_DEVICE", "1") == "0":
+            return None
+        from multi_modal_foundation_model_amd.rngjump import cpu_generator_position
+        return cpu_generator_position()
+
+    def _device_ws(self, n, dev):
+        from multi_modal_foundation_model_amd import ops
+        ws = getattr(self, "_mt_ws", None)
+        if ws is None:
+            ws = self._mt_ws = {}
+        key = (dev, ops.mt_plan(n))
+        if key not in ws:
+            ws[key] = ops.mt_workspace(n, device=dev)
+        return ws[key]
+
+    def _device_bernoulli(self, spikes, p):
+        """torch.bernoulli(torch.full(spikes.shape, p)) as a uint8 tensor on spikes.device, or None (take it on the host)."""
+        p = float(p)
+        pos = self._device_position(spikes) if 0.0 <= p <= 1.0 else None
+        if pos is None:
+            return None
+        from multi_modal_foundation_model_amd import ops
+        from multi_modal_foundation_model_amd.rngjump import advance_cpu_generator
+        n = spikes.numel()
+        out = ops.mt_bernoulli(pos[0], pos[1], n, p, device=spikes.device, ws=self._device_ws(n, spikes.device))
+        advance_cpu_generator(n)
+        self.device_draws = getattr(self, "device_draws", 0) + 1
+        return out.view(spikes.shape)
+
+    def _device_corrupt(self, spikes, cm8, out):
+        """The zero / random corruption of `spikes` under the device mask cm8 (uint8, broadcast dimensions of size 1 or stride 0) into `out`
+        (`spikes` itself: in place), the three draws taken from the generator's position and the generator moved past them.  None: the host
+        lines run."""
+        zr, rr = float(self.zero_ratio), float(self.random_ratio)
+        pos = self._device_position(spikes) if (0.0 <= zr <= 1.0 and 0.0 <= rr <= 1.0) else None
+        if pos is None:
+            return None
+        from multi_modal_foundation_model_amd import ops
+        from multi_modal_foundation_model_amd.rngjump import advance_cpu_generator
+        n = spikes.numel()
+        out = ops.mt_corrupt(pos[0], pos[1], spikes, cm8, zr, rr, out=out, ws=self._device_ws(n, spikes.device))
+        advance_cpu_generator(3 * n)
+        self.device_draws = getattr(self, "device_draws", 0) + 1
+        return out
 
     def forward(self, spikes, neuron_regions=None, token_mask_only=False, spikes_discarded=False):
         """`token_mask_only=True` (callers that discard the returned spikes only): skip the zero / random corruption draws.
@@ -141,7 +199,9 @@ class Masker(nn.Module):
 
         if self._ring is None:
             self._ring = _PinnedRing()
-        drawn = self._ring.to(torch.bernoulli(probs), dev)
+        drawn = self._device_bernoulli(spikes, ratio) if self.mode == "random" else None
+        if drawn is None:
+            drawn = self._ring.to(torch.bernoulli(probs), dev)
         causal_target = None
         if self.mode in TOKEN_MODES:
             if timespan > 1:
@@ -173,6 +233,8 @@ class Masker(nn.Module):
                 torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio)))
                 torch.bernoulli(torch.full((B, T, N), float(self.random_ratio)))
                 torch.rand((B, T, N))
+        elif self._device_corrupt(spikes, mask.view(torch.uint8), spikes) is not None:
+            pass                                                     # corrupted in place, the generator moved on
         else:
             zero_idx = torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio))).to(dev).bool() & mask
             spikes[zero_idx] = 0
@@ -200,7 +262,9 @@ class Masker(nn.Module):
           corrupted  None when zero_ratio == 1: bernoulli(1.0) is always 1, so the zeroed elements are exactly cm and nothing takes
                      noise - the caller zeroes `spikes` under cm itself, and the three [B,T,N] draws are passed by jump-ahead
                      (MMFM_MASKER_JUMP=0: taken for real), as `forward(spikes_discarded=True)` passes them.  For any other zero_ratio the
-                     draws are taken as `forward` takes them and the corrupted copy of `spikes` is returned: host-bound at a large batch.
+                     corrupted copy of `spikes` is returned, with `forward`'s bits: for an fp32 CUDA tensor the three draws are generated
+                     on the device (ops.mt_corrupt) from the CPU generator's position and the generator jumps past them; otherwise
+                     (a CPU tensor, another dtype, MMFM_MASKER_DEVICE=0) they are taken on the host as `forward` takes them.
         The generator calls, their order and shapes, and the states of the CPU generator and of Python's `random` afterwards are
         `forward`'s.  `spikes` is not modified."""
         B, T, N = spikes.shape
@@ -267,10 +331,14 @@ class Masker(nn.Module):
             probs[list(self.timesteps)] = 1
             cm = torch.bernoulli(probs).bool()[None, :, None]
         elif mode == "random":
-            cm = torch.bernoulli(torch.full((B, T, N), ratio)).bool()
+            cm = self._device_bernoulli(spikes, ratio)                # uint8 on the device already, or None
+            if cm is None:
+                cm = torch.bernoulli(torch.full((B, T, N), ratio)).bool()
         else:
             raise Exception(f"Masking mode {self.mode} not implemented")
         tm = cm if tm is None else tm
+        cm8 = cm if cm.is_cuda else self._ring.to(cm.to(torch.uint8).contiguous(), dev)
+        tm8 = cm8 if tm is cm else self._ring.to(tm.to(torch.uint8).contiguous(), dev)
 
         corrupted = None
         if float(self.zero_ratio) == 1.0:
@@ -281,16 +349,16 @@ class Masker(nn.Module):
                 torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio)))
                 torch.bernoulli(torch.full((B, T, N), float(self.random_ratio)))
                 torch.rand((B, T, N))
+        elif (corrupted := self._device_corrupt(spikes, cm8, None)) is not None:
+            pass
         else:
-            mask = cm.to(dev).expand(B, T, N)
+            mask = cm.to(dev).bool().expand(B, T, N)
             corrupted = spikes.clone()
             zero_idx = torch.bernoulli(torch.full((B, T, N), float(self.zero_ratio))).to(dev).bool() & mask
             corrupted[zero_idx] = 0
             rand_idx = torch.bernoulli(torch.full((B, T, N), float(self.random_ratio))).to(dev).bool() & mask & ~zero_idx
             noise = (corrupted.max() * torch.rand((B, T, N)).to(dev)).to(corrupted.dtype)
             corrupted[rand_idx] = noise[rand_idx]
-        cm8 = self._ring.to(cm.to(torch.uint8).contiguous(), dev)
-        tm8 = cm8 if tm is cm else self._ring.to(tm.to(torch.uint8).contiguous(), dev)
         return cm8, tm8, corrupted
 
     @staticmethod
