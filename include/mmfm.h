@@ -663,6 +663,59 @@ int mmfm_adamw_step_ranges(float* p, const float* g, float* m, float* v, void* p
 #define MMFM_GRAD_ADD 1
 int mmfm_grad_accumulate(float* g, float* stash, int64_t n, int64_t start, int64_t end, int mode, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- per-session linear layers (use_session)
+ * A per-session read-in from the session's n_s neurons to a shared width P and a read-out from P back to n_s, over a batch whose
+ * samples may belong to different sessions.  MMFM_SESSION_LINEAR is the feature macro for these exports (MMFM_VERSION stays: no
+ * existing struct or kernel changed).
+ *
+ * Every session fact is DEVICE data, so that a captured launch serves every session and every mix of sessions of one batch shape:
+ *   sid[B]      the session of each sample
+ *   n[S]        the neurons of each session, 1 <= n[s] <= N_max
+ *   w_off[S]    element offset of the session's [n_s][P] row-major matrix from the base pointer `w` (of w_elems elements)
+ *   b_off[S]    the same for its bias from `bias` (of b_elems elements; fp32 always); unused where there is no bias
+ * A sample whose session index is outside [0, S), or whose session's span leaves [0, w_elems) / [0, b_elems), is treated as n_s = 0:
+ * nothing of that span is read or written.  The padded-side operand is [B*T][ld_pad] with the session's real channels in columns
+ * [0, n_s); columns >= n_s are NEVER read (they enter every product as zeros, whatever they hold, NaN included).
+ * dtype is the storage of the activations and the weights (MMFM_F32 / MMFM_BF16), accumulation is fp32; biases, dW and db are fp32.
+ * Any P, n_s, T >= 1.  No allocation, no synchronisation, no memset, no atomics: every call is capturable and gives the same bits
+ * for the same inputs.  Argument checks return -1 before any HIP call.
+ *
+ *   mmfm_session_reduce   y[b, t, p] = sum_{c < n_s} x_pad[b, t, c] W_s[c, p] (+ bias_s[p])              y: [B*T][ld_p], columns >= P not written
+ *                         the read-in forward; without a bias, also the read-out's input gradient df = dpred . Wout
+ *   mmfm_session_expand   y_pad[b, t, c] = sum_p f[b, t, p] W_s[c, p] (+ bias_s[c]) for c < n_s, exactly 0 for n_s <= c < N_max
+ *                         (columns [N_max, ld_pad) are not written); the read-out forward
+ *   mmfm_session_dw       dW_s[c, p] = sum_{b: sid[b] = s} sum_t a_pad[b, t, c] q[b, t, p]   at dw + w_off[s]   (d->w is not read)
+ *                         db (or NULL): bias_from_pad = 0: db_s[p] = sum q[.., p] (read-in);  1: db_s[c] = sum a_pad[.., c] (read-out),
+ *                         at db + b_off[s].  The spans of a session without a sample in the batch are not written.
+ * mmfm_session_dw reads the grouping of samples from `runs` (DEVICE int32 [mmfm_session_runs_ints(B, S, chunk)], built by the host
+ * from the session indices and staged with the inputs):
+ *   [0] live chunk entries  [1] chunk  [2] mmfm_session_dw_chunks(B, S, chunk)  [3] B
+ *   order[B]                the samples grouped by session
+ *   {session, start, count, k} per chunk entry: samples order[start .. start + count) ; k = 1: the only chunk of its session (written
+ *                           directly), k >= 2: the first of k consecutive chunks of its session, k = 0: a later one of them.
+ * A session of several chunks writes one fp32 slab per chunk into the workspace and a second launch sums them in chunk order.
+ * At most 64 distinct sessions per batch fit the table's capacity, min(B, ceil(B / chunk) + min(S, B, 64)) entries. */
+#define MMFM_SESSION_LINEAR 1
+typedef struct {
+    int dtype;
+    int B, T, P, N_max, S;
+    int ld_pad;                  /* row stride of the padded-side operand, >= N_max */
+    int ld_p;                    /* row stride of the P-side operand (y of _reduce, f of _expand, q of _dw), >= P */
+    const int32_t* sid;
+    const int32_t* n;
+    const int64_t* w_off;
+    const int64_t* b_off;
+    const void* w; int64_t w_elems;
+    const float* bias; int64_t b_elems;
+} mmfm_session_desc;
+int mmfm_session_reduce(const mmfm_session_desc* d, const void* x_pad, void* y, mmfm_stream stream);
+int mmfm_session_expand(const mmfm_session_desc* d, const void* f, void* y_pad, mmfm_stream stream);
+int mmfm_session_dw_chunks(int B, int S, int chunk);
+int64_t mmfm_session_runs_ints(int B, int S, int chunk);
+int64_t mmfm_session_dw_workspace(int B, int P, int N_max, int S, int chunk);
+int mmfm_session_dw(const mmfm_session_desc* d, const void* a_pad, const void* q, const int32_t* runs, int chunk, float* dw, float* db,
+                    int bias_from_pad, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- evaluation metrics
  * utils/utils.py:107-115 (metrics_list "r2" = torcheval R2Score per series; trainer/base.py:252-262 calls it for 50
  * neurons x every trial on the host):  out[g*C + c] = 1 - sum_s (y-p)^2 / sum_s (y - mean_s y)^2 over the S elements

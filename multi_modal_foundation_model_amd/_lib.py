@@ -120,6 +120,17 @@ class ReduceEntry(C.Structure):
                 ("accumulate", C.c_int32), ("chunk0", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SessionDesc(C.Structure):
+    """mmfm_session_desc (MMFM_SESSION_LINEAR): the batch shape, the device session tables and the flat weight / bias buffers."""
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("T", C.c_int), ("P", C.c_int), ("N_max", C.c_int), ("S", C.c_int), ("ld_pad", C.c_int), ("ld_p", C.c_int),
+                ("sid", C.c_void_p), ("n", C.c_void_p), ("w_off", C.c_void_p), ("b_off", C.c_void_p), ("w", C.c_void_p), ("w_elems", C.c_int64),
+                ("bias", C.c_void_p), ("b_elems", C.c_int64)]
+
+
+SESSION_MAX_PER_BATCH = 64       # distinct sessions in one batch (the capacity of mmfm_session_dw's chunk table)
+SESSION_RUN_HDR, SESSION_RUN_ENT = 4, 4
+
+
 class RowGemmDesc(C.Structure):
     _fields_ = [("R", C.c_int64), ("K", C.c_int), ("N", C.c_int), ("x", C.c_void_p), ("ldx", C.c_int), ("w", C.c_void_p),
                 ("ldw", C.c_int), ("bias", C.c_void_p), ("ln", C.c_int), ("eps", C.c_float), ("xhat", C.c_void_p),
@@ -230,6 +241,13 @@ _PROTOS = {
     "mmfm_grad_sumsq_ranges": (C.c_int, [_vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _f, _f, _i, _vp, _i64, _vp]),
     "mmfm_adamw_step_ranges": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(OptimRange), _i, _vp, _i64, _vp, _i, _vp, _i, _vp]),
     "mmfm_grad_accumulate": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i, _vp]),
+    # per-session linear layers (MMFM_SESSION_LINEAR)
+    "mmfm_session_reduce": (C.c_int, [C.POINTER(SessionDesc), _vp, _vp, _vp]),
+    "mmfm_session_expand": (C.c_int, [C.POINTER(SessionDesc), _vp, _vp, _vp]),
+    "mmfm_session_dw_chunks": (C.c_int, [_i, _i, _i]),
+    "mmfm_session_runs_ints": (C.c_int64, [_i, _i, _i]),
+    "mmfm_session_dw_workspace": (C.c_int64, [_i, _i, _i, _i, _i]),
+    "mmfm_session_dw": (C.c_int, [C.POINTER(SessionDesc), _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp]),
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
     "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),

@@ -81,6 +81,9 @@ class EngineDDP:
     others would wait for it."""
 
     def __init__(self, engine, process_group=None, bucket_bytes: int = 8 << 20, broadcast: bool = True):
+        if getattr(engine.cfg, "sessions", None):
+            raise NotImplementedError("EngineDDP over a model with per-session layers (use_session) is not built: ranks hold different "
+                                      "sessions, and whether a session is absent from a step is not a local fact")
         self.engine, self.pg = engine, process_group
         self.world = dist.get_world_size(process_group)
         self.buckets = GradBuckets(engine.layout, engine.cfg, bucket_bytes)

@@ -56,6 +56,11 @@ LOSS_EXTRA = ("loss_weight",)
 # The attention window over time stamps (mm.yaml context.forward / context.backward under MultiModal.context_mask): a constructor keyword
 # and attribute like the groups above, no dataclass field.  None - the default, and what (-1, -1) folds into - is today's model
 CONTEXT = ("context",)
+# The per-session read-in / read-out layers (use_session): `sessions` maps a stitched modality to the neuron counts of its
+# sessions, in session-index order; such a modality's entry in `mods` carries the shared width P (what its tokenisers and its head run
+# at).  stitch_bias: the session layers have biases.  Constructor keywords and attributes like the groups above, no dataclass fields;
+# None - the default - is today's model
+SESSION = ("sessions", "stitch_bias")
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -108,12 +113,22 @@ class EngineConfig:
     # (context.forward, context.backward), both ints >= -1, or None: the encoder's self-attention and the cross-attention see a key only
     # inside the window over the tokens' time stamps (ops.context_window translates).  (-1, -1) is None
     context: InitVar[Optional[Tuple[int, int]]] = None
+    sessions: InitVar[Optional[Dict[str, Tuple[int, ...]]]] = None
+    stitch_bias: InitVar[bool] = True
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
     # `n_modality` (a shared mod_emb is one tensor, mm.py:84-87, and the row is the modality's index in `mods` on either side).  Read a
     # side's values through `side()`
 
     def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True,
-                      loss_weight=None, context=None):
+                      loss_weight=None, context=None, sessions=None, stitch_bias=True):
+        if sessions is not None:
+            names = [m for m, _ in self.mods]
+            sessions = {m: tuple(int(n) for n in sizes) for m, sizes in sessions.items()}
+            for m, sizes in sessions.items():
+                if m not in names or not sizes or any(n < 1 for n in sizes):
+                    raise ValueError(f"EngineConfig.sessions[{m!r}] = {sizes}: a modality out of {names} and one neuron count >= 1 per session")
+            sessions = sessions or None
+        self.sessions, self.stitch_bias = sessions, bool(stitch_bias)
         if context is not None:
             context = tuple(context)
             if len(context) != 2:
@@ -143,7 +158,7 @@ class EngineConfig:
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA + CONTEXT)
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA + CONTEXT + SESSION)
 
     __hash__ = None
 
@@ -163,6 +178,15 @@ class EngineConfig:
         own = self.enc_mods if side == "encoder" else self.dec_mods
         return [(m, mod, n) for m, (mod, n) in enumerate(self.mods) if own is None or mod in own]
 
+    def stitched(self, m: int):
+        """The neuron counts of the sessions of modality index m where it is stitched (use_session), else None."""
+        return None if not self.sessions else self.sessions.get(self.mods[m][0])
+
+    def data_width(self, m: int) -> int:
+        """The channels of modality m's inputs, targets and predictions: its tokenisers' channels, or - stitched - the largest session."""
+        sizes = self.stitched(m)
+        return self.mods[m][1] if sizes is None else max(sizes)
+
     def mod_emb_owner(self, side: str, mod: str) -> str:
         """The side whose tokeniser of `mod` owns the mod_emb table the tokeniser of `side` reads: the encoder's for a decoder tokeniser
         that shares it (mm.py:84-87), else `side` itself."""
@@ -177,7 +201,7 @@ class EngineConfig:
 
     @staticmethod
     def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False, enc_mods=None, dec_mods=None,
-                          share_mod_emb: bool = True, context_window: bool = False) -> "EngineConfig":
+                          share_mod_emb: bool = True, context_window: bool = False, sessions=None, stitch_bias: bool = True) -> "EngineConfig":
         """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
         two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
         sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
@@ -234,7 +258,8 @@ class EngineConfig:
                             mods=list(mods), **{k: Sides(per["encoder"][k], per["decoder"][k]) for k in PER_SIDE + (PER_SIDE_EMBED if embedder_opts else ())},
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]),
-                            enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb, context=context)
+                            enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb, context=context,
+                            sessions=sessions, stitch_bias=stitch_bias)
 
 
 # a block's linear: name, the norm that feeds it (None: plain), weight [N, K], has a bias, the adjacent nn.Linear's a fused projection aliases
@@ -329,11 +354,22 @@ class ParamLayout:
                         pad(); add(p + ".mod_emb.weight", (cfg.n_modality, H))
                     if sc.embed_pos:            # embedder.pos: false builds no pos_embed module
                         pad(); add(p + ".pos_embed.weight", (sc.max_F, H))
+            session("session_in", lambda n, width: (width,))
+
+        def session(prefix, bias_shape):
+            """The session layers of the stitched modalities, behind everything else of their segment: per session a [n_k, P] weight and
+            (stitch_bias) its bias, each in its own aligned slot."""
+            for m, (mod, width) in enumerate(cfg.mods):
+                for k, n in enumerate(cfg.stitched(m) or ()):
+                    pad(); add(f"{prefix}.{mod}.{k}.weight", (n, width))
+                    if cfg.stitch_bias:
+                        pad(); add(f"{prefix}.{mod}.{k}.bias", bias_shape(n, width))
 
         def head():
             ln("decoder_norm")
             for _, mod, n in cfg.side_mods("decoder"):
                 lin(f"decoder_embeddings.{mod}.out", n, H)
+            session("session_out", lambda n, width: (n,))
 
         segment("embed", embed)
         for side, n in (("encoder", cfg.n_enc), ("bridge", 1), ("decoder", cfg.n_dec)):
@@ -412,6 +448,8 @@ class Engine:
         self._wt = dict(views={}, entries=[], table=None)             # bf16 transposes for the big-GEMM dX products (_w_transposed)
         self.grad_ready_hooks = []       # DDP: callables(segment_name) fired as backward completes a segment of G
         self.backward_done_hooks = []    # DDP: wait for the collectives (stream-side) before anyone reads G
+        self._shared_tables: Dict[str, dict] = {}
+        self._absent = frozenset()       # the parameters of the sessions without a sample in the last forward's batch (use_session)
         self._stash = None               # G's size, allocated by the first backward that accumulates (caller skipped zero_grad()), never before
         self._param_spans, self._spans_of = [], -1
         # hipGraph replay of the step plan: the plan neither allocates nor synchronises, so after one eager
@@ -483,6 +521,20 @@ class Engine:
 
     def Gb(self, wname):         # its gradient, None likewise
         return self.Gv(wname + ".bias") if self.layout.has(wname + ".bias") else None
+
+    def session_tables(self, m):
+        """The device tables of stitched modality m (EngineConfig.sessions), made once: n int32 [S] and the element offsets (int64 [S]) of
+        every session's read-in / read-out weight and bias in the flat buffers (P, Pw and G share the layout)."""
+        key = f"sess/tables/{m}"
+        if key not in self._shared_tables:
+            mod, sizes, ent = self.cfg.mods[m][0], self.cfg.stitched(m), self.layout.entries
+            off = lambda which, kind: torch.tensor([ent[f"session_{which}.{mod}.{k}.{kind}"][0] for k in range(len(sizes))], dtype=torch.int64,
+                                                   device=self.device)
+            t = dict(n=torch.tensor(sizes, dtype=torch.int32, device=self.device), w_in=off("in", "weight"), w_out=off("out", "weight"))
+            if self.cfg.stitch_bias:
+                t.update(b_in=off("in", "bias"), b_out=off("out", "bias"))
+            self._shared_tables[key] = t
+        return self._shared_tables[key]
 
     def is_sn(self, lnname):
         """True where the norm named `lnname` is a ScaleNorm (the block norms of a side with use_scalenorm: true)."""
@@ -673,11 +725,12 @@ class Engine:
             raise ValueError(f"engine: {len(mods)} modalities, {len(chan)} channel-mask entries")
         elem = list(elem) if elem is not None else [None] * len(mods)
         out = [None] * len(mods)
+        width = getattr(self.cfg, "data_width", lambda m: mods[m][1])       # (a stitched modality's mask spans its largest session)
         for m, v in enumerate(chan):
             if v is not None:
                 if elem[m] is not None and torch.is_tensor(v) and v.device != elem[m][0].device:      # the masker's masks live where it drew them
                     v = v.to(elem[m][0].device)
-                elem[m], out[m] = combine_chan(elem[m], v, B, T[m] if isinstance(T, tuple) else T, mods[m][1])
+                elem[m], out[m] = combine_chan(elem[m], v, B, T[m] if isinstance(T, tuple) else T, width(m))
         return elem, (None if all(v is None for v in out) else out), tuple(m for m, v in enumerate(chan) if v is not None)
 
     @staticmethod
@@ -812,7 +865,7 @@ class Engine:
         graph.replay()
 
     # ------------------------------------------------------------------ data in
-    def load_inputs(self, B, T, inputs, targets, masks, ts, attn, elem=None, chan=None, padded=()):
+    def load_inputs(self, B, T, inputs, targets, masks, ts, attn, elem=None, chan=None, padded=(), sess=None):
         """Copy one batch into the static input buffers (device tensors or host tensors).  T a tuple (a segmented plan): modality m
         has T[m] bins and its own stamps ts[m] and attention mask attn[m].  elem[m] = (cm, tm, corrupted or None): the modality's
         element masks go into their static buffers, and its inputs are staged by mmfm_stage_masked - zeroed under cm on the way - or,
@@ -833,15 +886,24 @@ class Engine:
                     self.b[elem_buf("tm", m, tm.shape)].copy_(tm, non_blocking=True)
             if chan is not None and chan[m] is not None:
                 self.b[chan_buf(m, chan[m].shape)].copy_(chan[m], non_blocking=True)
+            stitched = self.cfg.stitched(m) is not None
+            if stitched:                # the session of every sample and the run table of the weight gradients: data of the one captured plan
+                sid = sess[m]
+                self.b[f"sess/sid/{m}"].copy_(torch.tensor(sid, dtype=torch.int32), non_blocking=True)
+                runs = K.session_runs(sid, len(self.cfg.stitched(m)), K.session_dw_chunk(B))
+                self.b[f"sess/runs/{m}"].copy_(torch.from_numpy(runs), non_blocking=True)
+            in_key = f"sin/{m}" if stitched else f"in/{m}"          # a stitched modality's batch is staged as it came; the read-in writes in/{m}
             if e is not None and (corrupted is None or m in padded):
-                dst = self.b[f"in/{m}"]
+                dst = self.b[in_key]
                 src = (inputs[m] if corrupted is None else corrupted).to(self.device, torch.float32, non_blocking=True).contiguous()
                 K.stage_masked(src, cmb, B, Tm, src.shape[-1], dst, dst.shape[-1])
             else:
                 x = inputs[m] if e is None else corrupted
-                self.b[f"in/{m}"].view(B, Tm, -1)[..., :x.shape[-1]].copy_(x, non_blocking=True)
+                self.b[in_key].view(B, Tm, -1)[..., :x.shape[-1]].copy_(x, non_blocking=True)
             if m in dec:
-                self.b[f"tgt/{m}"].view(B, Tm, -1).copy_(targets[m], non_blocking=True)
+                tgt = self.b[f"tgt/{m}"].view(B, Tm, -1)         # (a stitched modality's batch may be narrower or wider than its largest session)
+                width = min(tgt.shape[-1], targets[m].shape[-1])
+                tgt[..., :width].copy_(targets[m][..., :width], non_blocking=True)
             self.b[f"mask/{m}"].copy_(masks[m], non_blocking=True)
             if seg:
                 self.b[f"ts/{m}"].copy_(ts[m], non_blocking=True)
@@ -866,7 +928,48 @@ class Engine:
         return Ts, tss, attns
 
     # ------------------------------------------------------------------ run
-    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None, elem=None, chan=None):
+    def stitch_batch(self, B, inputs, elem, chan, sess):
+        """A batch of a model with stitched modalities (EngineConfig.sessions): sess[m] = the session index of every sample of stitched
+        modality m.  Returns (inputs, elem, chan, absent): chan[m] becomes v[b, c] = c < n_s(b) over the modality's full width (a
+        space_attn_mask that came with it is not read); a batch narrower than that width has its inputs and element masks padded to
+        it (zeros; never read beyond n_s); absent = the parameters of the sessions without a sample in this batch."""
+        mods = self.cfg.mods
+        if sess is None or len(sess) != len(mods):
+            raise ValueError(f"engine: a model with per-session layers needs sess = one entry per modality of {[m for m, _ in mods]}")
+        pad_to = lambda t, N: t if t is None or t.shape[-1] in (1, N) else torch.nn.functional.pad(t, (0, N - t.shape[-1]))
+        inputs, chan, absent = list(inputs), list(chan) if chan is not None else [None] * len(mods), set()
+        elem = list(elem) if elem is not None else None
+        for m, (mod, _) in enumerate(mods):
+            sizes = self.cfg.stitched(m)
+            if sizes is None:
+                if sess[m] is not None:
+                    raise ValueError(f"engine: modality {mod!r} has no per-session layers, sess[{m}] must be None")
+                continue
+            N, sid = self.cfg.data_width(m), sess[m]
+            if sid is None or len(sid) != B or any(not 0 <= int(k) < len(sizes) for k in sid):
+                raise ValueError(f"engine: modality {mod!r}: sess[{m}] must hold {B} session indices in [0, {len(sizes)})")
+            if len(set(sid)) > L.SESSION_MAX_PER_BATCH:
+                raise ValueError(f"engine: modality {mod!r}: {len(set(sid))} distinct sessions in one batch, at most {L.SESSION_MAX_PER_BATCH} are built")
+            w = inputs[m].shape[-1]
+            if any(sizes[k] > w for k in sid):
+                raise ValueError(f"engine: modality {mod!r}: a batch {w} channels wide for sessions of up to {max(sizes[k] for k in sid)} neurons")
+            if w > N:                   # padded beyond the largest session: those columns belong to nobody and are dropped unread
+                cut = lambda t: t if t is None or t.shape[-1] != w else t[..., :N]
+                inputs[m] = cut(inputs[m])
+                if elem is not None and elem[m] is not None:
+                    elem[m] = tuple(cut(t) for t in elem[m])
+                w = N
+            n_b = torch.tensor([sizes[k] for k in sid], dtype=torch.int64)
+            chan[m] = (torch.arange(N)[None, :] < n_b[:, None]).to(torch.uint8)
+            if w < N:
+                inputs[m] = pad_to(inputs[m], N)
+                if elem is not None and elem[m] is not None:
+                    elem[m] = tuple(pad_to(t, N) for t in elem[m])
+            kinds = ("weight", "bias") if self.cfg.stitch_bias else ("weight",)
+            absent |= {f"session_{which}.{mod}.{k}.{kind}" for k in set(range(len(sizes))) - set(sid) for which in ("in", "out") for kind in kinds}
+        return inputs, elem, chan, frozenset(absent)
+
+    def forward(self, B, T, inputs, targets, masks, ts, attn, training=True, anchor=None, elem=None, chan=None, sess=None):
         """T: the number of bins, or a tuple of per-modality numbers in cfg.mods order; ts / attn: one tensor [B, T], or one per modality.
         elem (None: the call it always was): per modality, in cfg.mods order, None or (cm, tm, corrupted or None) - the corruption mask
         and the target mask as uint8 tensors [B or 1, T or 1, N or 1] (Masker.element_masks) and, where the masker corrupted the inputs
@@ -879,10 +982,15 @@ class Engine:
         seg = isinstance(T, tuple)
         want_grad = anchor is not None and torch.is_grad_enabled() and anchor.requires_grad
         self._pattern = self.freeze_pattern() if want_grad else None          # read once per forward
+        self._absent = frozenset()
+        if getattr(self.cfg, "sessions", None):               # (sess is read only by a model with per-session layers; None elsewhere is the call it always was)
+            inputs, elem, chan, self._absent = self.stitch_batch(B, inputs, elem, chan, sess)
+        elif sess is not None and any(s is not None for s in sess):
+            raise ValueError("engine: sess names sessions, the model has no per-session layers (EngineConfig.sessions)")
         elem, chan, padded = self.fold_chan(B, T, elem, chan)
         ekey = self.elem_key(elem)
         plan = self._plan(B, T, training, want_grad, self._pattern, elem=ekey, chan=self.chan_key(chan))
-        self.load_inputs(B, T, inputs, targets, masks, ts, attn, elem=None if ekey is None else elem, chan=chan, padded=padded)
+        self.load_inputs(B, T, inputs, targets, masks, ts, attn, elem=None if ekey is None else elem, chan=chan, padded=padded, sess=sess)
         advance = training and any(sc.dropout > 0 or sc.embed_dropout > 0 for sc in map(self.cfg.side, ("encoder", "decoder")))
 
         def fwd_entries():
@@ -948,6 +1056,8 @@ class Engine:
         # requires_grad is honoured twice: the plan of this freeze pattern launched only what the trainable parameters need (plan.py,
         # DESIGN.md §10), so G in the span of a frozen parameter is unspecified - and a frozen parameter never sees its slice
         for name, p in self.params.items():
+            if name in self._absent:             # a session without a sample in this batch: nothing wrote its span, .grad stays what it was
+                continue
             if not p.requires_grad:
                 p.grad = None
             elif p.grad is None or p.grad.data_ptr() != self.Gv(name).data_ptr():
@@ -963,8 +1073,9 @@ class Engine:
                                  if name in self.params]
             self._spans_of = self.adoptions
         runs, open_run = [], False
+        absent = {id(self.params[name]) for name in self._absent if name in self.params}
         for p, s, e in self._param_spans:
-            if p.grad is not None and p.requires_grad:
+            if p.grad is not None and p.requires_grad and id(p) not in absent:
                 if open_run:
                     runs[-1][1] = e
                 else:

@@ -752,3 +752,98 @@ def mt_corrupt(state, consumed, src, cm, zero_ratio, random_ratio, streams=None,
     L.check(L.lib().mmfm_mt_corrupt(sp, int(consumed), B, T, N, P(src), P(cm), sb, st, sn, float(zero_ratio), float(random_ratio), P(out),
                                     0 if streams is None else int(streams), P(ws), ws.numel(), _stream()), "mmfm_mt_corrupt")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- per-session linear layers (MMFM_SESSION_LINEAR)
+def session_desc(dtype, B, T, width, N_max, S, sid, n, w_off, *, ld_pad=None, ld_p=None, b_off=None, w=None, w_elems=None, bias=None, b_elems=None):
+    """mmfm_session_desc over the device tables sid int32 [B], n int32 [S], w_off / b_off int64 [S] and the flat buffers `w` (storage
+    `dtype`: L.F32 / L.BF16) and `bias` (fp32).  w_elems / b_elems default to the tensors' sizes (give them where w is None: mmfm_session_dw
+    bounds the gradient buffers with them)."""
+    d = L.SessionDesc()
+    d.dtype, d.B, d.T, d.P, d.N_max, d.S = dtype, B, T, width, N_max, S
+    d.ld_pad = N_max if ld_pad is None else ld_pad
+    d.ld_p = width if ld_p is None else ld_p
+    d.sid, d.n, d.w_off, d.b_off = P(sid), P(n), P(w_off), P(b_off)
+    d.w, d.w_elems = P(w), int(w.numel() if w_elems is None else w_elems)
+    d.bias, d.b_elems = P(bias), int((bias.numel() if bias is not None else 0) if b_elems is None else b_elems)
+    d._keep = (sid, n, w_off, b_off, w, bias)
+    return d
+
+
+def session_reduce(desc, x_pad, y, plan=None):
+    """y [B*T, P] = x_pad[.., :n_s] . W_s (+ bias_s), the session s of each sample from desc.sid (mmfm_session_reduce)."""
+    _emit(plan, L.lib().mmfm_session_reduce, (C.byref(desc), P(x_pad), P(y)), keep=(desc,))
+
+
+def session_expand(desc, f, y_pad, plan=None):
+    """y_pad [B*T, ld_pad] = f . W_s^T (+ bias_s) in columns [0, n_s), zeros in [n_s, N_max) (mmfm_session_expand)."""
+    _emit(plan, L.lib().mmfm_session_expand, (C.byref(desc), P(f), P(y_pad)), keep=(desc,))
+
+
+def session_dw_chunk(B):
+    """Samples per chunk of mmfm_session_dw's run table: about 64 chunks over the batch, so that one session owning the whole batch
+    still spreads over the chip and many small sessions keep one chunk (a direct write) each."""
+    return max(1, -(-int(B) // 64))
+
+
+def session_runs_ints(B, S, chunk):
+    """The int32 elements of the run table (mmfm_session_runs_ints)."""
+    return L.SESSION_RUN_HDR + int(B) + L.SESSION_RUN_ENT * session_dw_chunks(B, S, chunk)
+
+
+def session_dw_chunks(B, S, chunk):
+    """The capacity of the chunk table (mmfm_session_dw_chunks): min(B, ceil(B / chunk) + min(S, B, 64))."""
+    return min(int(B), -(-int(B) // int(chunk)) + min(int(S), int(B), L.SESSION_MAX_PER_BATCH))
+
+
+def session_runs(sid, S, chunk, names=None):
+    """The run table of mmfm_session_dw as a numpy int32 array (include/mmfm.h), from the per-sample session indices: a pure function
+    of its arguments, no device involved.  Samples keep their batch order inside a session and sessions come in index order, so the
+    table - and with it every sum - depends on the mix alone.  ValueError for an index outside [0, S) and for more than 64 distinct
+    sessions in the batch (`names`: index -> eid for the message)."""
+    import numpy as np
+    sid = np.asarray(sid, dtype=np.int64).reshape(-1)
+    B, S, chunk = int(sid.size), int(S), int(chunk)
+    if B < 1 or S < 1 or chunk < 1:
+        raise ValueError(f"session_runs: B {B}, S {S}, chunk {chunk} must all be >= 1")
+    bad = sid[(sid < 0) | (sid >= S)]
+    if bad.size:
+        raise ValueError(f"session_runs: session index {int(bad[0])} outside [0, {S})")
+    present = np.unique(sid)
+    if present.size > L.SESSION_MAX_PER_BATCH:
+        label = [str(names[int(k)]) if names is not None else str(int(k)) for k in present]
+        raise ValueError(f"session_runs: {present.size} distinct sessions in one batch, at most {L.SESSION_MAX_PER_BATCH} are built: "
+                         + ", ".join(label))
+    cap = session_dw_chunks(B, S, chunk)
+    order = np.argsort(sid, kind="stable")
+    entries, start = [], 0
+    for k in present:
+        m = int((sid == k).sum())
+        nch = -(-m // chunk)
+        for j in range(nch):
+            cnt = min(chunk, m - j * chunk)
+            entries.append((int(k), start, cnt, nch if j == 0 else 0))
+            start += cnt
+    assert len(entries) <= cap and start == B
+    out = np.zeros(L.SESSION_RUN_HDR + B + L.SESSION_RUN_ENT * cap, dtype=np.int32)
+    out[:4] = (len(entries), chunk, cap, B)
+    out[4:4 + B] = order
+    if entries:
+        out[4 + B:4 + B + 4 * len(entries)] = np.asarray(entries, dtype=np.int32).reshape(-1)
+    return out
+
+
+def session_dw_workspace(B, width, N_max, S, chunk, device):
+    """The slab workspace of mmfm_session_dw (contents arbitrary: nothing in it is read before it is written)."""
+    nbytes = L.lib().mmfm_session_dw_workspace(B, width, N_max, S, chunk)
+    if nbytes < 0:
+        L.check(-1, "mmfm_session_dw_workspace")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def session_dw(desc, a_pad, q, runs, chunk, dw, db, bias_from_pad, ws, plan=None):
+    """dW_s = sum over the samples of s of a_pad[.., :n_s]^T . q at dw + w_off[s]; db (or None) the column sum of q (bias_from_pad False:
+    the read-in) or of a_pad (True: the read-out) at db + b_off[s].  runs: the device copy of session_runs(...) for the same chunk;
+    absent sessions keep their spans (mmfm_session_dw)."""
+    _emit(plan, L.lib().mmfm_session_dw, (C.byref(desc), P(a_pad), P(q), P(runs), int(chunk), P(dw), P(db), int(bool(bias_from_pad)), P(ws),
+                                          ws.numel() * 4), keep=(desc, runs, ws))

@@ -172,12 +172,21 @@ class PlanBuilder:
         self.split_masks = [m for m, _, _ in self.mods_of["encoder"]] != [m for m, _, _ in self.mods_of["decoder"]]
         self.staged = sorted({m for side in self.mods_of.values() for m, _, _ in side})      # modalities some side uses
         self.sides = {side: Side(c.side(side), training) for side in ("encoder", "decoder")}
+        # stitched modalities (EngineConfig.sessions): st[m] = the neuron counts of m's sessions.  Such a modality's inputs,
+        # targets and predictions are nd[m] = max(st[m]) wide, its tokenisers and its head run at the shared width c.mods[m][1]
+        self.st = {m: c.stitched(m) for m in self.staged if c.stitched(m)}
+        self.nd = {m: c.data_width(m) for m in range(len(c.mods))}
+        for m in self.st:
+            if c.loss_kind.get(c.mods[m][0]) == L.LOSS_SOFTMAX_CE:
+                raise NotImplementedError(f"modality {c.mods[m][0]!r}: per-session layers (use_session) on a softmax cross-entropy modality are "
+                                          "not built - the read-out's zeros beyond n_k would enter every row's normaliser")
         self.Imax, self.mult_max = max(sd.I for sd in self.sides.values()), max(sd.mult for sd in self.sides.values())
         self.code, self.es, self.buf, self.b = e.code, 4 if e.dtype == "fp32" else 2, e._buf, e.b
         # the tokeniser chains on the live rows only (bf16; the fp32 parity path keeps the full row space).  lv: (side, slot) -> the
         # slot's mmfm_live_rows, filled by forward()
         # (a segmented plan runs without live-row compaction: the live-bin entry points have no segment forms)
-        self.live = not self.seg and self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
+        # (so does a plan with a stitched modality: the read-in runs on the full row space)
+        self.live = not self.seg and not self.st and self.code == L.BF16 and live_rows_on(self.BT) and self.live_bias_ok()
         self.lv = {}
         self.enc_flags = L.ATTN_DIAG                                                # mm.py:152-158
         # EngineConfig.context: the encoder's self-attention and the cross-attention (whose mask IS the encoder's, mm.py:210) see a key
@@ -301,8 +310,12 @@ class PlanBuilder:
             n = c.mods[m][1]
             # input rows padded to 16 B (zeros): the tokeniser's weight-gradient GEMM streams them by LDS-DMA (csrc/gemm_dw.hip)
             buf(f"in/{m}", (self.BTm[m], _align(n, 8)), zero=True); buf(f"mask/{m}", (B, self.Tm[m]), i64)
+            if m in self.st:        # the padded batch as it came (the read-in writes in/{m}), the session of every sample and the run table
+                buf(f"sin/{m}", (self.BTm[m], _align(self.nd[m], 8)), zero=True)
+                buf(f"sess/sid/{m}", (B,), torch.int32, zero=True)
+                buf(f"sess/runs/{m}", (K.session_runs_ints(B, len(self.st[m]), K.session_dw_chunk(B)),), torch.int32, zero=True)
             if m in dec:            # targets: decoder modalities only
-                buf(f"tgt/{m}", (self.BTm[m], n), f32)
+                buf(f"tgt/{m}", (self.BTm[m], self.nd[m]), f32, zero=m in self.st)
             if self.seg:            # the modality's own time stamps and attention mask
                 buf(f"ts/{m}", (B, self.Tm[m]), i64); buf(f"attn/{m}", (B, self.Tm[m]), i64)
         if not self.seg:
@@ -345,11 +358,18 @@ class PlanBuilder:
             if c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 need = max(need, L.lib().mmfm_softmax_ce_workspace(self.BTm[m], n))
         buf("ws/loss", (max(1, need // 4),), f32)
+        if self.st:
+            if self.grad:
+                buf("ws/sess", (max(L.lib().mmfm_session_dw_workspace(B, c.mods[m][1], self.nd[m], len(sz), K.session_dw_chunk(B)) for m, sz in self.st.items()) // 4,), f32)
+            for m in self.st:
+                # (an element target mask with a channel axis comes out of combine_chan with v folded in: the element form, no channel mask)
+                if (self.chan is None or self.chan[m] is None) and (self.elem is None or self.elem[m] is None or self.elem[m][1] is None):
+                    raise ValueError(f"modality {c.mods[m][0]!r}: a stitched modality's loss runs under the channel mask of its sessions (Engine.forward(sess=...))")
         if self.chan is not None:
             for m, shape in enumerate(self.chan):
                 if shape is None or m not in self.staged:
                     continue
-                mod, n = c.mods[m]
+                mod, n = c.mods[m][0], self.nd[m]
                 if c.loss_kind.get(mod) == L.LOSS_SOFTMAX_CE:
                     raise ValueError(f"modality {mod!r}: softmax cross-entropy couples its classes - it takes no channel mask (space_attn_mask)")
                 if tuple(shape) not in ((B, n), (1, n)):
@@ -367,11 +387,11 @@ class PlanBuilder:
                 for which, shape in zip(("cm", "tm"), shapes):
                     if shape is None:           # (a channel-masked modality whose row mask is the token mask has no target mask)
                         continue
-                    if len(shape) != 3 or any(s not in (1, full) for s, full in zip(shape, (B, self.Tm[m], c.mods[m][1]))):
-                        raise ValueError(f"modality {c.mods[m][0]!r}: element mask of shape {tuple(shape)} for [{B}, {self.Tm[m]}, {c.mods[m][1]}]")
+                    if len(shape) != 3 or any(s not in (1, full) for s, full in zip(shape, (B, self.Tm[m], self.nd[m]))):
+                        raise ValueError(f"modality {c.mods[m][0]!r}: element mask of shape {tuple(shape)} for [{B}, {self.Tm[m]}, {self.nd[m]}]")
                     buf(elem_buf(which, m, shape), tuple(shape), u8, zero=True)
             # sized for the decoder's longest modality, whichever of them carry element masks: one size per pool
-            need = max(K.masked_loss_elem_workspace(B, self.Tm[m], n) for m, _, n in self.mods_of["decoder"])
+            need = max(K.masked_loss_elem_workspace(B, self.Tm[m], self.nd[m]) for m, _, _ in self.mods_of["decoder"])
             buf("ws/loss_elem", (need // 4 + 2,), f32)
         # Two weight gradients whose operands are both at hand (MLP down / up, attention out_proj / qkv) leave in ONE launch
         # (mmfm_gemm_pair): `dlin(..., defer=True)` parks the first, the next `dlin_ln` takes it along; `flush_deferred` issues a
@@ -653,6 +673,28 @@ class PlanBuilder:
             return tokmask[:, off:], self.Lq, self.b[chan_buf(m, self.chan[m])]
         return tm, (0 if tm.shape[0] == 1 else self.Tm[m]), self.b[chan_buf(m, self.chan[m])]
 
+    def sess_desc(self, m, which, bias=True, grads=False, ld_p=None):
+        """The mmfm_session_desc of stitched modality m: which = "in" (read-in: the padded side is sin/{m}, the P side in/{m}'s rows) or
+        "out" (read-out: pred/{m} and the head's output).  grads: the gradient launch's form (no weights; dW / db are bounded by G)."""
+        e, c = self.e, self.c
+        t = e.session_tables(m)
+        width, N = c.mods[m][1], self.nd[m]
+        ld_pad, ld_p = (_align(N, 8), ld_p or _align(width, 8)) if which == "in" else (N, width)
+        return K.session_desc(self.code, self.B, self.Tm[m], width, N, len(self.st[m]), self.b[f"sess/sid/{m}"], t["n"], t["w_" + which],
+                              ld_pad=ld_pad, ld_p=ld_p, b_off=t["b_" + which] if c.stitch_bias else None, w=None if grads else e.Pw,
+                              w_elems=e.layout.n, bias=e.P if bias and c.stitch_bias and not grads else None, b_elems=e.layout.n)
+
+    def sess_names(self, m, which):
+        """The layout entries of modality m's read-in ("in") / read-out ("out") layers."""
+        mod = self.c.mods[m][0]
+        return [f"session_{which}.{mod}.{k}.{kind}" for k in range(len(self.st[m])) for kind in (("weight", "bias") if self.c.stitch_bias else ("weight",))]
+
+    def sess_dw(self, plan, m, which, a_pad, q):
+        """The weight (and bias) gradients of modality m's session layers in one call: absent sessions keep their spans of G."""
+        e = self.e
+        K.session_dw(self.sess_desc(m, which, grads=True, ld_p=self.c.mods[m][1]), a_pad, q, self.b[f"sess/runs/{m}"], K.session_dw_chunk(self.B), e.G,
+                     e.G if self.c.stitch_bias else None, which == "out", self.b["ws/sess"], plan=plan)
+
     def loss_spec(self, mod):
         c = self.c
         return c.loss_kind[mod], float(c.loss_param.get(mod, 0.0)), int(c.loss_flags.get(mod, 0))
@@ -743,6 +785,8 @@ class PlanBuilder:
             K.attn_pos_prep(B, [self.Tm[m] for m, _, _ in enc], [b[f"ts/{m}"] if self.seg else b["ts"] for m, _, _ in enc], pos, plan=fwd)
             self.win = K.attn_window(pos, *self.win_lohi)
         gathered = set()
+        for m in self.st:           # the read-in, once per stitched modality: both sides' tokenisers read in/{m}
+            K.session_reduce(self.sess_desc(m, "in"), b[f"sin/{m}"], b[f"in/{m}"], plan=fwd)
         tok_tmp = buf("tok_tmp", (BT, H))
         x_enc, emb_enc, x_dec = buf("x_enc", (R, H)), buf("emb_enc", (R, H)), buf("x_dec", (R, H))
         for side, xs, es_ in (("encoder", x_enc, emb_enc), ("decoder", x_dec, None)):
@@ -813,8 +857,14 @@ class PlanBuilder:
         tokmask = b[mk("decoder", "tokmask")]
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
-            pred = buf(f"pred/{m}", (BT, n))
-            self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
+            pred = buf(f"pred/{m}", (BT, self.nd[m]))
+            if m in self.st:        # the head writes f [BT, P]; the read-out expands it to the padded width, zeros beyond n_s
+                fP = buf(f"sess/f/{m}", (BT, n))
+                self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", fP, BT, n, H)
+                K.session_expand(self.sess_desc(m, "out"), fP, pred, plan=fwd)
+                n = self.nd[m]
+            else:
+                self.lin(fwd, ydec[r0:r1], f"decoder_embeddings.{mod}.out", pred, BT, n, H)
             ch = self.chan_rows(m, tokmask, off)
             if ch is not None:       # row mask x channel mask: the sum and (behind mmfm_mask_prep) the modality's count
                 K.masked_loss_chan_fwd(*self.loss_spec(mod), pred, b[f"tgt/{m}"], ch[0], ch[1], self.Tm[m], BT, n, ch[2], b["loss_sum"][j:j + 1],
@@ -1006,7 +1056,8 @@ class PlanBuilder:
             for slot, (m, mod, _) in enumerate(mods):
                 p = f"{side}_embeddings.{mod}.embedder"
                 emb = [f"{c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight"] + ([p + ".pos_embed.weight"] if self.sides[side].pos else [])
-                n.tok[side, slot] = (tl(p + ".token_embed"), tl(p + ".projection"), t(emb))
+                # (a stitched modality's read-in takes its gradient through the token_embed's input gradient: d/z is needed for it too)
+                n.tok[side, slot] = (tl(p + ".token_embed") or (m in self.st and t(self.sess_names(m, "in"))), tl(p + ".projection"), t(emb))
         bottom = {side: any(any(v) for (s, _), v in n.tok.items() if s == side) for side in ("encoder", "decoder")}
         layer = lambda side, i: t([k for k in self.e.layout.entries if k.startswith(f"{side}.{i}.")])
         enc = [layer("encoder", i) for i in range(c.n_enc)]
@@ -1035,15 +1086,17 @@ class PlanBuilder:
         norm = self.keep("decoder_norm", nd.dec_top or self.trainable(self.norm_names("decoder_norm")), self.norm_names("decoder_norm"))
         for j, (m, mod, n) in enumerate(self.mods_of["decoder"]):
             BT, (r0, r1), off = self.BTm[m], self.ydec_rows(j), self.off["decoder"][j]
+            width, n = n, self.nd[m]
             dpred = buf(f"d/pred/{m}", (BT, n))
             ch = self.chan_rows(m, tokmask, off)
+            s_out = m in self.st and self.keep(f"session_out.{mod}", self.trainable(self.sess_names(m, "out")), self.sess_names(m, "out"))
             if ch is not None:
-                if norm or self.tl(f"decoder_embeddings.{mod}.out"):
+                if norm or self.tl(f"decoder_embeddings.{mod}.out") or s_out:
                     K.masked_loss_chan_bwd(*self.loss_spec(mod), b[f"pred/{m}"], b[f"tgt/{m}"], ch[0], ch[1], self.Tm[m], BT, n, ch[2],
                                            b["gout"], b["inv_n"], dpred, plan=self.cur)
             elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
                 self.softmax_ce(self.cur, m, mod, b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), self.Tm[m], self.Tm[m], BT, n, dpred=dpred)
-            elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and self.elem_tm(m) is not None:
+            elif (norm or self.tl(f"decoder_embeddings.{mod}.out") or s_out) and self.elem_tm(m) is not None:
                 K.masked_loss_elem_bwd(*self.loss_spec(mod), b[f"pred/{m}"], b[f"tgt/{m}"], self.elem_tm(m), B, self.Tm[m], n,
                                        b["gout"], b["inv_n"], dpred, plan=self.cur)
             elif (norm or self.tl(f"decoder_embeddings.{mod}.out")) and c.loss_kind[mod] == L.LOSS_SOFTMAX_CE:
@@ -1051,6 +1104,13 @@ class PlanBuilder:
             elif norm or self.tl(f"decoder_embeddings.{mod}.out"):
                 self.loss(self.cur, mod, K.masked_loss_bwd, K.masked_loss_kind_bwd, b[f"pred/{m}"], b[f"tgt/{m}"], tokmask[:, off:],
                           Lq, self.Tm[m], BT, n, b["gout"], b["inv_n"], dpred)
+            if m in self.st:        # dpred -> df = dpred . Wout (the head's output gradient), and the read-out's own gradients
+                df = buf(f"d/sess/f/{m}", (BT, width))
+                if norm or self.tl(f"decoder_embeddings.{mod}.out"):
+                    K.session_reduce(self.sess_desc(m, "out", bias=False), dpred, df, plan=self.cur)
+                if s_out:
+                    self.sess_dw(self.cur, m, "out", dpred, b[f"sess/f/{m}"])
+                dpred, n = df, width
             self.dlin(self.cur, dpred, ydec[r0:r1], f"decoder_embeddings.{mod}.out", BT, n, H, dX=dydec[r0:r1], need_dx=norm)
         if norm:
             self.ln_b(self.cur, dydec, self.dec_last, "decoder_norm", "decnorm", None, dY, **self.destitch())
@@ -1096,6 +1156,8 @@ class PlanBuilder:
                 if self.keep(pS + ".mod_emb+pos_embed", any(nd.tok[side, slot]), emb):
                     self.stitch_b(self.cur, side, slot, dS, dextra, acc_mod=side == "encoder" and mod in shared)
         # the softsign gradient from the activation itself (bf16), or from the saved pre-activation (fp32, and every other activation)
+        s_in = {m: self.keep(f"session_in.{c.mods[m][0]}", self.trainable(self.sess_names(m, "in")), self.sess_names(m, "in")) for m in self.st}
+        du_written = set()
         for side in ("decoder", "encoder"):
             sd = self.sides[side]
             saved = self.embed_saved(sd)
@@ -1108,8 +1170,16 @@ class PlanBuilder:
                 self.dlin(self.cur, b[f"d/tok/{side}/{m}"], b[f"{side}/a/{m}"], p + ".projection", BT, H, n2, dX=dz, need_dx=nd.tok[side, slot][0],
                           act=L.ACT_SOFTSIGN_GRAD_OUT if saved == "a" else sd.emb_grad, act_scale=sd.scale,
                           gradmul_pre=b[f"{side}/{saved}/{m}"] if saved else None, live=lv)
+                # a stitched modality's read-in: du [BT, P] = sum over the sides of dz . W_token_embed (the second side adds through the
+                # residual epilogue), then its weight gradients from the padded batch and du
+                du = dict(dX=buf(f"d/sess/u/{m}", (BT, n)), **(dict(residual=b[f"d/sess/u/{m}"], ldr=n) if m in du_written else {})) if s_in.get(m) else {}
                 self.dlin(self.cur, dz, b[f"in/{m}"] if lv is None else b[self.mk(side, f"in_live/{m}")], p + ".token_embed", BT, n2, n,
-                          ldx=_align(n, 8), live=lv)
+                          ldx=_align(n, 8), live=lv, **du)
+                if du:
+                    du_written.add(m)
+        for m in self.st:
+            if s_in[m] and m in du_written:
+                self.sess_dw(self.cur, m, "in", b[f"sin/{m}"], b[f"d/sess/u/{m}"])
         self.close_segment("embed")
         if self.used_wt and refresh:            # refresh the bf16 transposes once per step, in front of everything (the optimiser rewrote the weights)
             tw = e._wt_table()

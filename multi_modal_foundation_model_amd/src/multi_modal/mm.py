@@ -28,6 +28,7 @@ from multi_modal.decoder_embeddings import DecoderLayer
 from multi_modal.encoder_embeddings import EncoderLayer
 from multi_modal.losses import SoftmaxCrossEntropy
 from multi_modal.mm_utils import create_context_mask  # noqa: F401  (re-exported like the reference)
+from multi_modal.session_layers import build_session_layers, check_sessions, read_stitch_config, session_ids
 from multi_modal_foundation_model_amd import _lib as L
 from multi_modal_foundation_model_amd import ops as K
 from multi_modal_foundation_model_amd.engine import Engine, EngineConfig
@@ -127,6 +128,8 @@ class MultiModal(nn.Module):
     input_masking = False        # the switch of mask_type: input (a class default, so that a module pickled before it existed has it too)
     neuron_padding = False       # the switch of space_attn_mask: padded channels leave the inputs and the loss (a class default, as above)
     context_mask = False         # the switch of context.forward / context.backward: windowed encoder attention (a class default, as above)
+    use_session = False          # the switch of use_session: per-session read-in / read-out layers (a class default, as above)
+    session_index = None         # eid -> session index k (use_session); saved with the module
 
     def __init__(self, encoder_embeddings: Dict[str, nn.Module], decoder_embeddings: Dict[str, nn.Module],
                  avail_mod: List, config: DictConfig, share_modality_embeddings: bool = True, **kwargs):
@@ -186,6 +189,30 @@ class MultiModal(nn.Module):
         # context_mask = ones under a TO DO).  True: a value that is not an int >= -1 raises ValueError when the engine is built
         if "context_mask" in kwargs:
             self.context_mask = bool(kwargs["context_mask"])
+        # use_session: per stitched modality (stitcher.mods) a per-session linear read-in from the session's n_k neurons to the shared
+        # width P in front of its tokenisers, and a read-out from P back to n_k behind its head (multi_modal/session_layers.py; DESIGN.md
+        # 3aa).  The layers are created last: every other parameter has the bits of the n_channel = P model without sessions
+        use, st = read_stitch_config(config)
+        sessions = kwargs.get("sessions")
+        if use and sessions is None:
+            raise ValueError("use_session: true needs sessions={eid: number of neurons}")
+        if not use and sessions is not None:
+            raise ValueError("sessions= given, but the config says use_session: false")
+        if use:
+            sessions = check_sessions(sessions)
+            unknown = [m for m in st.mods if m not in self.avail_mod]
+            if unknown:
+                raise ValueError(f"stitcher.mods names {unknown}, the model has {list(self.avail_mod)}")
+            for mod in st.mods:
+                for emb in (d[mod] for d in (self.encoder_embeddings, self.decoder_embeddings) if mod in d):
+                    if emb.n_channel != st.width or getattr(emb, "output_channel", st.width) != st.width:
+                        raise ValueError(f"modality {mod!r}: under use_session its tokenisers and its head are built with n_channel = "
+                                         f"stitcher.width = {st.width}, got {emb.n_channel}")
+            self.use_session = True
+            self.session_index = {eid: k for k, eid in enumerate(sessions)}
+            self.session_sizes = tuple(sessions.values())
+            self.stitch_mods, self.stitch_width, self.stitch_bias = tuple(st.mods), st.width, st.bias
+            self.session_in, self.session_out = build_session_layers(st.mods, self.session_sizes, st.width, st.bias)
 
     def share_modality_embeddings(self):
         for mod in self.encoder_modalities & self.decoder_modalities:
@@ -224,7 +251,9 @@ class MultiModal(nn.Module):
                                                  enc_mods=[m for m in self.avail_mod if m in self.encoder_embeddings],
                                                  dec_mods=[m for m in self.avail_mod if m in self.decoder_embeddings],
                                                  share_mod_emb=getattr(self, "_share_mod_emb", True),      # (a module pickled before the flag existed shares)
-                                                 **({"context_window": True} if self.context_mask else {}))
+                                                 **({"context_window": True} if self.context_mask else {}),
+                                                 **({"sessions": {m: self.session_sizes for m in self.stitch_mods}, "stitch_bias": self.stitch_bias}
+                                                    if self.use_session else {}))
             specs = {m: _loss_spec(self.loss_mod[m]) for m in self.avail_mod if m in self.decoder_embeddings}
             cfg.loss_kind = {m: sp[0] for m, sp in specs.items()}
             cfg.loss_param = {m: sp[1] for m, sp in specs.items()}
@@ -297,7 +326,7 @@ class MultiModal(nn.Module):
         chan = {}
         for mod, d in mod_dict.items():
             v = d.get('space_attn_mask')
-            if v is None:
+            if v is None or (self.use_session and mod in self.stitch_mods):      # (a stitched modality's mask comes from its sessions' sizes)
                 continue
             x = d['inputs']
             want = (x.shape[0], x.shape[2] if x.dim() == 3 else 1)
@@ -313,6 +342,13 @@ class MultiModal(nn.Module):
         if mods != list(self.avail_mod):
             raise Exception(f"mod_dict modalities {mods} != avail_mod {list(self.avail_mod)}")
         masks, elem = [], {}
+        # the session of every sample of a stitched modality, from the entry's eid - one string for the batch or one per sample.  An
+        # unknown eid or a batch narrower than a present session raises here, before any draw or launch
+        sess = {}
+        if self.use_session:
+            for mod in self.stitch_mods:
+                x = mod_dict[mod]['inputs']
+                sess[mod] = session_ids(mod_dict[mod].get('eid'), x.shape[0], self.session_index, self.session_sizes, x.shape[-1], mod)
         chan = self._channel_masks(mod_dict) if self.neuron_padding else {}
         if self.input_masking:
             # a softmax cross-entropy modality couples its classes: it takes a target mask only where the mask is constant over the
@@ -380,7 +416,7 @@ class MultiModal(nn.Module):
         eng = self.engine()
         out = eng.forward(B, T, [mod_dict[m]['inputs'] for m in mods], [mod_dict[m]['targets'] for m in mods], masks, ts, attn,
                           training=self.training, anchor=self._grad_anchor(), **({"elem": [elem.get(m) for m in mods]} if elem else {}),
-                          **({"chan": [chan.get(m) for m in mods]} if chan else {}))
+                          **({"chan": [chan.get(m) for m in mods]} if chan else {}), **({"sess": [sess.get(m) for m in mods]} if sess else {}))
         mod_loss, mod_n, preds, targets = {}, {}, {}, {}
         for i, mod in enumerate(dec_mods):      # the engine's outputs are the decoder's modalities, in this order
             mod_loss[mod], mod_n[mod] = out["mod_loss"][i], out["mod_n"][i]
@@ -388,6 +424,9 @@ class MultiModal(nn.Module):
             # where somebody reads them - evaluation; in training mode (the trainer's train_epoch only reads the loss) mod_preds
             # carries the engine's bf16 predictions as they are
             p_ = out["preds"][i]
+            if mod in sess:         # the engine's buffer is as wide as the largest session: the batch's own padded width goes out
+                w = mod_dict[mod]['inputs'].shape[-1]
+                p_ = p_[..., :w] if w <= p_.shape[-1] else torch.nn.functional.pad(p_, (0, w - p_.shape[-1]))     # (zeros beyond every session)
             preds[mod] = p_ if (p_.dtype == torch.float32 or self.training) else p_.float()
             targets[mod] = mod_dict[mod]['targets']
             mod_dict[mod]['gt'], mod_dict[mod]['preds'] = targets[mod], preds[mod]

@@ -71,6 +71,11 @@ def build_parser():
     ap.add_argument("--n_sessions", type=int, default=1,
                     help="K > 1: multi-session pretraining on synthetic sessions of 300..n_neurons neurons each, batch i from session "
                          "i %% K, spikes right-padded with -1 up to n_neurons (1: one session, no padding)")
+    ap.add_argument("--use_session", action="store_true",
+                    help="per-session read-in / read-out layers (sets model.use_session): every session's n_k neurons are mapped to a shared "
+                         "width in front of the spike tokenisers and back behind the head; with --n_sessions K the sizes are the loader's, "
+                         "a single session trains as {eid: n_neurons}")
+    ap.add_argument("--stitch_width", type=int, default=None, help="the shared width P of --use_session (model.stitcher.width; default n_neurons)")
     return ap
 
 
@@ -101,6 +106,11 @@ def main(argv=None):
         config["training"]["context_mask"] = True
     if args.n_sessions < 1:
         raise ValueError(f"--n_sessions must be >= 1, got {args.n_sessions}")
+    if args.stitch_width is not None and not args.use_session:
+        raise ValueError("--stitch_width belongs to --use_session")
+    if args.use_session:
+        config["model"]["use_session"] = True
+        config["model"]["stitcher"] = dict(config["model"].get("stitcher") or {}, width=args.stitch_width if args.stitch_width is not None else args.n_neurons)
     set_seed(config.seed)
 
     avail_mod = list(AVAIL_MOD)
@@ -126,14 +136,20 @@ def main(argv=None):
                                            rank=accelerator.rank, seed0=0)
         val_dataloader = SyntheticLoader(2, config.training.test_batch_size, T, n_neurons, n_behaviors, rank=accelerator.rank, seed0=10 ** 6)
 
+    # --use_session: the spike tokenisers and the head run at the shared width; the sessions are the loader's (eid session{k}, its
+    # sizes) or the one session this run trains
+    n_ap = config["model"]["stitcher"]["width"] if args.use_session else n_neurons
+    if args.use_session:
+        sizes = train_dataloader.sizes if args.n_sessions > 1 else None
+        meta_data["sessions"] = {f"session{k}": n for k, n in enumerate(sizes)} if sizes else {"synthetic": n_neurons}
     encoder_embeddings, decoder_embeddings = {}, {}
     for mod in modal_filter["input"]:
         encoder_embeddings[mod] = EncoderEmbedding(hidden_size=config.model.encoder.transformer.hidden_size,
-                                                   n_channel=n_neurons if mod == "ap" else n_behaviors, config=config.model.encoder)
+                                                   n_channel=n_ap if mod == "ap" else n_behaviors, config=config.model.encoder)
     for mod in modal_filter["output"]:
         decoder_embeddings[mod] = DecoderEmbedding(hidden_size=config.model.decoder.transformer.hidden_size,
-                                                   n_channel=n_neurons if mod == "ap" else n_behaviors,
-                                                   output_channel=n_neurons if mod == "ap" else n_behaviors, config=config.model.decoder)
+                                                   n_channel=n_ap if mod == "ap" else n_behaviors,
+                                                   output_channel=n_ap if mod == "ap" else n_behaviors, config=config.model.decoder)
 
     model = MultiModal(encoder_embeddings, decoder_embeddings, avail_mod=avail_mod, config=config.model,
                        share_modality_embeddings=True, **config.method.model_kwargs, **meta_data)
