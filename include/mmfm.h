@@ -716,6 +716,32 @@ int64_t mmfm_session_dw_workspace(int B, int P, int N_max, int S, int chunk);
 int mmfm_session_dw(const mmfm_session_desc* d, const void* a_pad, const void* q, const int32_t* runs, int chunk, float* dw, float* db,
                     int bias_from_pad, void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 
+/* ---------------------------------------------------------------------------------- span packing (sparse session all-reduce)
+ * Copies a list of spans between a flat fp32 buffer G and a packed staging buffer, so that data parallelism all-reduces the session
+ * layers a step touched in ONE collective instead of the whole session block.  MMFM_SPAN_PACK is the feature macro for the two exports
+ * (MMFM_VERSION stays, as for MMFM_NULL_BIAS: no existing struct or kernel changed).
+ *
+ * table: DEVICE int64 [>= n_spans][4], 8-byte aligned, one row {g_off, s_off, len, live} per span, in elements.  The table is data:
+ * the launch geometry depends on nothing it holds (a captured launch serves any table of the same n_spans), and rows beyond n_spans
+ * are not read.
+ *   mmfm_span_gather    stage[s_off .. s_off + len) = live ? G[g_off .. g_off + len) : 0
+ *                       A span with live == 0 is NEVER loaded from G (its bytes may be anything, NaN included): zeros are stored.
+ *   mmfm_span_scatter   G[g_off .. g_off + len) = stage[s_off .. s_off + len)   for every span, whatever `live` says
+ * A row with len <= 0 or a negative offset is skipped.  The spans must not overlap in the buffer that is written; keeping them inside
+ * both buffers is the caller's part (the table builder of ops.py checks it on the host).
+ * A span whose two addresses agree modulo 16 bytes moves in 16-byte accesses over its aligned interior and element accesses over the at
+ * most three elements of its head and of its tail; one whose addresses disagree moves element by element.  The work is cut into chunks
+ * of MMFM_SPAN_CHUNK elements and the workgroups stride over all (span, chunk) pairs in table order: one long span and many short ones
+ * both fill the device.  Exactly one lane stores each element, nothing outside the named ranges is written; no atomics, no
+ * allocation, no synchronisation (capturable).  n_spans == 0 returns 0 without a launch.
+ * Argument checks (NULL pointers, a misaligned table or buffer, n_spans outside [0, MMFM_SPAN_MAX]) return -1 before any HIP call: a
+ * machine without a GPU answers them. */
+#define MMFM_SPAN_PACK 1
+#define MMFM_SPAN_CHUNK 4096
+#define MMFM_SPAN_MAX 65536
+int mmfm_span_gather(const float* G, float* stage, const int64_t* table, int n_spans, mmfm_stream stream);
+int mmfm_span_scatter(const float* stage, float* G, const int64_t* table, int n_spans, mmfm_stream stream);
+
 /* ---------------------------------------------------------------------------------- evaluation metrics
  * utils/utils.py:107-115 (metrics_list "r2" = torcheval R2Score per series; trainer/base.py:252-262 calls it for 50
  * neurons x every trial on the host):  out[g*C + c] = 1 - sum_s (y-p)^2 / sum_s (y - mean_s y)^2 over the S elements

@@ -129,6 +129,7 @@ class SessionDesc(C.Structure):
 
 SESSION_MAX_PER_BATCH = 64       # distinct sessions in one batch (the capacity of mmfm_session_dw's chunk table)
 SESSION_RUN_HDR, SESSION_RUN_ENT = 4, 4
+SPAN_CHUNK, SPAN_MAX = 4096, 65536       # MMFM_SPAN_CHUNK, MMFM_SPAN_MAX
 
 
 class RowGemmDesc(C.Structure):
@@ -248,6 +249,9 @@ _PROTOS = {
     "mmfm_session_runs_ints": (C.c_int64, [_i, _i, _i]),
     "mmfm_session_dw_workspace": (C.c_int64, [_i, _i, _i, _i, _i]),
     "mmfm_session_dw": (C.c_int, [C.POINTER(SessionDesc), _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    # span packing for the sparse session all-reduce (MMFM_SPAN_PACK)
+    "mmfm_span_gather": (C.c_int, [_vp, _vp, _vp, _i, _vp]),
+    "mmfm_span_scatter": (C.c_int, [_vp, _vp, _vp, _i, _vp]),
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
     "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),

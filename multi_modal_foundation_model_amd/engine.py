@@ -448,6 +448,7 @@ class Engine:
         self._wt = dict(views={}, entries=[], table=None)             # bf16 transposes for the big-GEMM dX products (_w_transposed)
         self.grad_ready_hooks = []       # DDP: callables(segment_name) fired as backward completes a segment of G
         self.backward_done_hooks = []    # DDP: wait for the collectives (stream-side) before anyone reads G
+        self.forward_done_hooks = []     # DDP over per-session layers: callables() fired behind a forward that takes a gradient
         self._shared_tables: Dict[str, dict] = {}
         self._absent = frozenset()       # the parameters of the sessions without a sample in the last forward's batch (use_session)
         self._stash = None               # G's size, allocated by the first backward that accumulates (caller skipped zero_grad()), never before
@@ -1008,6 +1009,8 @@ class Engine:
                    mod_n=[count[j].clone() for j in range(len(dec))],
                    preds=[self.b[f"pred/{m}"].view(B, T[m] if seg else T, -1) for m, _, _ in dec])
         if want_grad:
+            for hook in self.forward_done_hooks:
+                hook()
             out["loss"] = _StepFn.apply(anchor, self, self._token)
         else:
             out["loss"] = self.b["loss"].clone().reshape(())
@@ -1056,7 +1059,9 @@ class Engine:
         # requires_grad is honoured twice: the plan of this freeze pattern launched only what the trainable parameters need (plan.py,
         # DESIGN.md §10), so G in the span of a frozen parameter is unspecified - and a frozen parameter never sees its slice
         for name, p in self.params.items():
-            if name in self._absent:             # a session without a sample in this batch: nothing wrote its span, .grad stays what it was
+            # a session without a sample in this batch: nothing wrote its span, .grad stays what it was.  (Under data parallelism with
+            # session_sync, EngineDDP.finish has replaced the set by the sessions absent on EVERY rank: the others' spans hold the mean)
+            if name in self._absent:
                 continue
             if not p.requires_grad:
                 p.grad = None

@@ -501,6 +501,37 @@ def grad_accumulate(g, stash, start, end, mode, plan=None):
     _emit(plan, L.lib().mmfm_grad_accumulate, (P(g), P(stash), g.numel(), int(start), int(end), int(mode)))
 
 
+def span_table(spans, g_numel, stage_numel, out=None):
+    """The host table of mmfm_span_gather / mmfm_span_scatter: int64 [len(spans)][4] rows (g_off, s_off, len, live), checked here because
+    the kernels cannot: every span inside its buffer, len >= 1, and no two spans overlapping in either buffer.  out: an int64 tensor
+    [>= len(spans)][4] to fill (a pinned one, for a non-blocking upload); its remaining rows are left as they are."""
+    rows = [(int(g), int(s), int(n), int(bool(live))) for g, s, n, live in spans]
+    if len(rows) > L.SPAN_MAX:
+        raise ValueError(f"span_table: {len(rows)} spans, at most {L.SPAN_MAX}")
+    for col, size, what in ((0, int(g_numel), "G"), (1, int(stage_numel), "the staging buffer")):
+        end = 0
+        for r in sorted(rows, key=lambda r: r[col]):
+            if r[2] < 1 or r[col] < end or r[col] + r[2] > size:
+                raise ValueError(f"span_table: span {r} overlaps its neighbour or leaves {what} of {size} elements")
+            end = r[col] + r[2]
+    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+    if out is None:
+        return t
+    out[:len(rows)].copy_(t)
+    return out
+
+
+def span_gather(G, stage, table, n_spans, plan=None):
+    """mmfm_span_gather: stage[s_off : s_off + len] = live ? G[g_off : g_off + len] : 0 for the first n_spans rows of the device table
+    (span_table); a dead span is never loaded.  n_spans = 0 launches nothing."""
+    _emit(plan, L.lib().mmfm_span_gather, (P(G), P(stage), P(table), int(n_spans)))
+
+
+def span_scatter(stage, G, table, n_spans, plan=None):
+    """mmfm_span_scatter: G[g_off : g_off + len] = stage[s_off : s_off + len] for the first n_spans rows of the device table."""
+    _emit(plan, L.lib().mmfm_span_scatter, (P(stage), P(G), P(table), int(n_spans)))
+
+
 def rng_seed(state, seed, plan=None):
     _emit(plan, L.lib().mmfm_rng_seed, (P(state), int(seed) & (2 ** 64 - 1)))
 

@@ -128,9 +128,9 @@ def main(argv=None):
     T = config.data.max_time_length
     if args.n_sessions > 1:
         train_dataloader = MultiSessionLoader(args.batches_per_epoch, config.training.train_batch_size, T, n_neurons, n_behaviors,
-                                              n_sessions=args.n_sessions, rank=accelerator.rank, seed0=0)
+                                              n_sessions=args.n_sessions, rank=accelerator.rank, seed0=0, world=accelerator.world)
         val_dataloader = MultiSessionLoader(2, config.training.test_batch_size, T, n_neurons, n_behaviors, n_sessions=args.n_sessions,
-                                            rank=accelerator.rank, seed0=10 ** 6)
+                                            rank=accelerator.rank, seed0=10 ** 6, world=accelerator.world)
     else:
         train_dataloader = SyntheticLoader(args.batches_per_epoch, config.training.train_batch_size, T, n_neurons, n_behaviors,
                                            rank=accelerator.rank, seed0=0)

@@ -69,16 +69,24 @@ def session_sizes(n_sessions, n_ap, seed=2024):
 class MultiSessionLoader(SyntheticLoader):
     """Synthetic multi-session pretraining batches as the reference loader pads them (loader/base.py:399-425): batch i belongs to
     session i % n_sessions, session k has n_k of the n_ap channels (`session_sizes`), the others are right-padded with pad_value = -1
-    and cleared in space_attn_mask; eid names the session.  The values of the real channels are synth_batch's own."""
+    and cleared in space_attn_mask; eid names the session.  The values of the real channels are synth_batch's own.
+    world > 1 (data parallelism): batch i of rank r belongs to session (i * world + r) % n_sessions, so that the ranks of one step hold
+    different sessions; world = 1 is the sequence above, whatever the rank."""
 
-    def __init__(self, n_batches, batch_size, T=100, n_ap=668, n_beh=2, n_sessions=2, rank=0, seed0=0, device=None, cache=False):
+    def __init__(self, n_batches, batch_size, T=100, n_ap=668, n_beh=2, n_sessions=2, rank=0, seed0=0, device=None, cache=False, world=1):
         super().__init__(n_batches, batch_size, T, n_ap, n_beh, rank=rank, seed0=seed0, device=device, cache=cache)
         if n_sessions < 1:
             raise ValueError(f"n_sessions must be >= 1, got {n_sessions}")
-        self.n_sessions, self.sizes = n_sessions, session_sizes(n_sessions, n_ap)
+        if world < 1 or (world > 1 and not 0 <= rank < world):
+            raise ValueError(f"world must be >= 1 and, beyond 1, rank in [0, world): got world {world}, rank {rank}")
+        self.n_sessions, self.sizes, self.world = n_sessions, session_sizes(n_sessions, n_ap), world
+
+    def session_of(self, step):
+        """The session of batch `step` of this rank."""
+        return (step * self.world + self.rank) % self.n_sessions if self.world > 1 else step % self.n_sessions
 
     def _make(self, step):
-        k = step % self.n_sessions
+        k = self.session_of(step)
         b = synth_batch(self.B, self.T, self.n_ap, self.n_beh, seed=1000 * self.rank + self.seed0 + step, eid=f"session{k}")
         b["spikes_data"][:, :, self.sizes[k]:] = -1.0
         b["space_attn_mask"][:, self.sizes[k]:] = 0
