@@ -829,6 +829,10 @@ typedef struct {
     const void* bwd_xhat; const float* bwd_rstd;
 } mmfm_rowgemm_desc;
 int mmfm_rowgemm(const mmfm_rowgemm_desc* d, mmfm_stream stream);
+/* The form a dX + norm-backward launch (ln_bwd != 0; mmfm_rowgemm, or mmfm_rowgemm_groups backward) over R rows takes at this K, as the
+ * dispatcher decides it at this moment (it reads MMFM_ROWGEMM_LNBWD_WG at every launch): 2 = the kernel of which two workgroups share a
+ * CU (K = 512 / 768 only), 1 = the one-workgroup kernels.  Both forms write bit-identical results.  A query: no launch, no error state. */
+int mmfm_rowgemm_lnbwd_form(int64_t R, int K);
 
 /* The row-owner linear over up to MMFM_ROWGEMM_MAX_GROUPS weight sets in ONE launch (the context side of cross-attention: every
  * decoder layer projects the same normalised context rows to its keys / values, and their dX products sum into one gradient).

@@ -255,6 +255,7 @@ _PROTOS = {
     "mmfm_prep_weights": (C.c_int, [_vp, _i, _i, _vp]),
     "mmfm_rowgemm": (C.c_int, [C.POINTER(RowGemmDesc), _vp]),
     "mmfm_rowgemm_groups": (C.c_int, [C.POINTER(RowGemmGroupsDesc), _vp]),
+    "mmfm_rowgemm_lnbwd_form": (C.c_int, [_i64, _i]),
     "mmfm_mlp_fwd": (C.c_int, [C.POINTER(MlpDesc), _vp]),
     "mmfm_mlp_bwd": (C.c_int, [C.POINTER(MlpDesc), _vp]),
     "mmfm_ln_linear_grad_workspace": (C.c_int64, [_i]),

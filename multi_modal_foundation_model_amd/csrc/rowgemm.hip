@@ -708,6 +708,173 @@ __global__ __launch_bounds__(NT) void rowgemm_groups_lnbwd_kernel(const mmfm_row
 }
 #pragma clang diagnostic pop
 
+// ------------------------------------------------------------------------------------------------ dX + norm backward, two workgroups per CU
+// The product and epilogue of rowgemm_lnbwd_a_kernel / rowgemm_groups_lnbwd_kernel (K = 512 / 768, one or several groups) in a form of which
+// two workgroups fit one CU: 256 registers per wave, 64 KB of LDS per workgroup.  What had to shrink, and how:
+//   operand registers   the K-deep operand rows (128 / 192 registers, or 64 + the next piece's 64 in the grouped kernel) are never held.  The
+//                       weights come as kind-2 chunks, [256 outputs][32 k]: one ring step multiplies ONE 32-deep k slice against all eight
+//                       accumulator tiles, so a step needs two operands (8 registers) and the rows stream past in 64-wide blocks (one block =
+//                       one `Lines` = 16 registers = two ring steps), one block in flight (a second one would not be waited for any later:
+//                       vector-memory operations retire in order, and the ring's wait for the chunk requested behind a block covers the
+//                       block).  Per accumulator element the MFMA sequence is k-step 0, 1, 2, ... of group 0, then group 1, ...: the order
+//                       of the kernels above, so the results are bit-identical.
+//   LDS                 no x_hat stash (64 KB per workgroup: with it not even a two-slot ring fits beside a second workgroup).  The x_hat lines
+//                       are requested BEHIND the ring loop, once for the statistics and once more (out of L2) for the output; holding them
+//                       as 64 registers of raw tiles beside the 128 accumulator registers spilled.  The round trips this exposes once per
+//                       pass are what the other workgroup covers.
+// The ring loop issues no compiler-visible vector-memory operation: the operand blocks are requested by inline asm like the ring's DMA and
+// waited for by count.  Steady state, block b (ring steps 2b, 2b+1):
+//   issue order     ... L(b) C(2b) C(2b+1) | L(b+1) C(2b+2) C(2b+3) | ...      L = 4 loads, C = 4 DMA requests per lane
+//   front of b      L(b) must have landed: the 8 younger requests may stay in flight; the block is staged, then L(b+1) is requested
+//   steps 2b, 2b+1  chunk C(s) must have landed: C(s+1) and L(b+1) may stay in flight (EXTRA = 4)
+// A pass's last block requests nothing (EXTRA = 0); the next pass's first block is requested in the epilogue, behind the second of the four
+// line-pair stores, where half the accumulators are dead: eight loads and eight stores follow it, so the same wait holds.  Anything else
+// issued in between is younger than what a wait is for and only makes it conservative.  Behind the last pass the block comes from rows
+// beyond the tensor, which the bounds check answers with zeros without touching memory.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void fetch_lines_async(Lines& L, const GBuf& b, uint32_t wrow0, uint32_t ldb, uint32_t colb, int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t off = (wrow0 + 8 * i + (lane >> 3)) * ldb + colb + 16 * (lane & 7);
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen nt" : "=v"(L.v[i]) : "v"(off), "s"(b.rs) : "memory");
+    }
+}
+// The wait for such a block is a separate statement (vm_wait_n): it pins the ORDER of request, wait and use, not the register allocation.
+// hipcc sees the load's result as ready at once, so a register copy of the block between request and wait would copy what has not landed
+// (naming the destinations as in-out operands of the wait does not compile: hipcc rejects tied 128-bit operands of this type).  There is
+// no such copy in this build: no v_mov / scratch access of the destinations on any path of either instantiation in the --save-temps
+// assembly.  Repeat that reading whenever hipcc or this kernel changes; the bit-identity test against the one-workgroup kernels
+// (tests/test_rowgemm_lnbwd_two_wg_gpu.py) fails on a block used before it landed.
+template <int NORM>
+__global__ __launch_bounds__(256, 2) void rowgemm_lnbwd2_kernel(const mmfm_rowgemm_groups_desc d, const void* wbase, const GroupOff wo) {
+    constexpr int NT = 256, NW = 4, RING_B = RINGA_SLOTS * CHUNK;
+    extern __shared__ __attribute__((aligned(16))) char smem[];       // RING_B + NW * STG_BYTES
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), m = lane & 31, h = lane >> 5;
+    const int kb = d.K >> 6, kc = 2 * kb, nblk = d.groups * kb;       // 64-wide operand blocks / 32-deep chunks per group; blocks per pass
+    const int64_t npass = (d.R + 32 * NW - 1) / (32 * NW);
+    const int my_passes = blockIdx.x < npass ? (int)((npass - 1 - blockIdx.x) / gridDim.x) + 1 : 0;
+    if (my_passes == 0) return;
+    const __amdgpu_buffer_rsrc_t rs_w = wbuf(wbase);
+    const uint32_t ldwb = (uint32_t)d.ldw * 2u;
+    int src_g = 0, src_c = 0;                           // the next chunk to request: group, k slice
+    auto src = [&](int) {
+        AChunk c;
+        c.rs = rs_w; c.off = __builtin_amdgcn_readfirstlane(pick8(wo.w, src_g) + 64u * (uint32_t)src_c); c.ldb = ldwb; c.kind = 2;
+        if (++src_c == kc) { src_c = 0; if (++src_g == d.groups) src_g = 0; }
+        return c;
+    };
+    char* stg = smem + RING_B + wave * STG_BYTES;
+    const GBuf Y = gbuf(d.y[0], d.R * d.ldy * 2), RES = gbuf(d.residual, d.R * d.ldr * 2);
+    const GBuf XH = gbuf(d.bwd_xhat, d.R * 512), RS = gbuf(d.bwd_rstd, d.R * 4);
+    const uint32_t ldxb = d.ldx * 2, ldyb = d.ldy * 2, ldrb = d.ldr * 2;
+    const int64_t xbytes = d.R * d.ldx * 2;
+    auto row_of = [&](int pi) { return (uint32_t)(((int64_t)(blockIdx.x + (int64_t)pi * gridDim.x) * NW + wave) * 32); };
+    int xs_g = 0, xs_c = 0, xs_pi = 0;                  // the next operand block to request: group, block in group, pass
+    auto xfetch = [&](Lines& L) {
+        const uint32_t row0 = xs_pi < my_passes ? row_of(xs_pi) : (uint32_t)(npass * 32 * NW);
+        fetch_lines_async(L, gbuf(pick8(d.x, xs_g), xbytes), row0, ldxb, 128u * (uint32_t)xs_c, lane);
+        if (++xs_c == kb) { xs_c = 0; if (++xs_g == d.groups) { xs_g = 0; ++xs_pi; } }
+    };
+    const ALane<NT> ring_al = alane_init<NT>(t, 0u, ldwb);
+    const AFrag fr = afrag_init(m, h);
+    RINGA_DECL(NT);
+    Lines L0;
+    xfetch(L0);
+    RINGA_START((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem, my_passes * nblk * 2, src);
+    f32x16 acc[8];
+    // one ring step: the 32-deep slice against the eight tiles, weight operands in two sets of four (tile pair x 2 k-steps), ping-pong,
+    // counted waits, one ring request behind each MFMA group (mlp_fused.hip's d(x_hat) product)
+#define L2_READS(SET, Q) do { ALDS_READ_B(wv[SET][0], slot, fr, 2 * (Q), 0); ALDS_READ_B(wv[SET][1], slot, fr, 2 * (Q), 1);          \
+                              ALDS_READ_B(wv[SET][2], slot, fr, 2 * (Q) + 1, 0); ALDS_READ_B(wv[SET][3], slot, fr, 2 * (Q) + 1, 1); } while (0)
+#define L2_MMAS(SET, Q, X0, X1) do { acc[2 * (Q)] = mfma_u4(wv[SET][0], X0, acc[2 * (Q)]); acc[2 * (Q) + 1] = mfma_u4(wv[SET][2], X0, acc[2 * (Q) + 1]); \
+                                     acc[2 * (Q)] = mfma_u4(wv[SET][1], X1, acc[2 * (Q)]); acc[2 * (Q) + 1] = mfma_u4(wv[SET][3], X1, acc[2 * (Q) + 1]); \
+                                     __builtin_amdgcn_sched_barrier(0); } while (0)
+#define L2_STEP(X0, X1, EXTRA)                                                                           \
+        {                                                                                                \
+            uint32_t slot;                                                                               \
+            RINGA_SYNC(src, slot, EXTRA);                                                                \
+            uint4 wv[2][4];                                                                              \
+            L2_READS(0, 0); L2_READS(1, 1);                                                              \
+            ALDS_WAITN(4); L2_MMAS(0, 0, X0, X1); RINGA_PIECE(0); L2_READS(0, 2);                        \
+            ALDS_WAITN(4); L2_MMAS(1, 1, X0, X1); RINGA_PIECE(1); L2_READS(1, 3);                        \
+            ALDS_WAITN(4); L2_MMAS(0, 2, X0, X1); RINGA_PIECE(2);                                        \
+            ALDS_WAITN(0); L2_MMAS(1, 3, X0, X1); RINGA_PIECE(3);                                        \
+        }
+#define L2_BLOCK(L, FETCH)                                                                               \
+        {                                                                                                \
+            vm_wait_n<8>();                                                                              \
+            stage_lines(stg, L, lane);                                                                   \
+            opnd xa[2];                              /* two operands at a time: the staged block stays until the next one */ \
+            xa[0] = unstage_opnd(stg, 0, m, h); xa[1] = unstage_opnd(stg, 1, m, h);                      \
+            if (FETCH) xfetch(L);                                                                        \
+            L2_STEP(xa[0], xa[1], (FETCH) ? 4 : 0)                                                       \
+            xa[0] = unstage_opnd(stg, 2, m, h); xa[1] = unstage_opnd(stg, 3, m, h);                      \
+            L2_STEP(xa[0], xa[1], (FETCH) ? 4 : 0)                                                       \
+        }
+    for (int pi = 0; pi < my_passes; ++pi) {
+        const uint32_t wrow0 = row_of(pi);
+#pragma unroll
+        for (int tt = 0; tt < 8; ++tt) acc[tt] = zero16();
+        for (int b = 1; b < nblk; ++b) L2_BLOCK(L0, 1)
+        L2_BLOCK(L0, 0)
+        // Epilogue.  The x_hat lines pass through two line blocks (32 registers) twice - once for the row statistics, once for the output,
+        // the second time out of L2 - and the residual-gradient lines follow through the same two: every request is issued as soon as
+        // the block it overwrites has been staged, one block ahead of its use.
+        // (its per-lane addresses are derived from a laundered lane index: held through the ring loop they cost the registers the loop lacks)
+        int le = lane;
+        asm volatile("" : "+v"(le));
+        const int me = le & 31, he = le >> 5;
+        Lines la = fetch_lines(XH, wrow0, 512u, 0u, le), lb = fetch_lines(XH, wrow0, 512u, 128u, le);
+        float rs = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+            Lines& lx = (tp & 1) ? lb : la;
+            stage_lines(stg, lx, le);
+            if (tp < 2) lx = fetch_lines(XH, wrow0, 512u, 128u * (tp + 2), le);
+            else if (tp == 2) lx = fetch_lines(XH, wrow0, 512u, 0u, le);
+            else { lx = fetch_lines(RES, wrow0, ldrb, 0u, le); rs = ld4f(RS, (wrow0 + me) * 4u); }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x16 xt = unstage_tile(stg, j, me, he);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { s1 += acc[2 * tp + j][i]; s2 = fmaf(acc[2 * tp + j][i], xt[i], s2); }
+            }
+        }
+        s1 = xhalf(s1);
+        s2 = xhalf(s2);
+        norm_bwd_stats<NORM>(s1, s2, rs);
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+            f32x16 o[2];
+            stage_lines(stg, la, le);                   // x_hat
+            if (tp + 1 < 4) la = fetch_lines(XH, wrow0, 512u, 128u * (tp + 1), le);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x16 xt = unstage_tile(stg, j, me, he);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[j][i] = rs * (acc[2 * tp + j][i] - s1 - xt[i] * s2);
+            }
+            stage_lines(stg, lb, le);                   // residual gradient
+            if (tp + 1 < 4) lb = fetch_lines(RES, wrow0, ldrb, 128u * (tp + 1), le);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {               // tile by tile, the output over the residual tile it has just read: 16 registers less
+                const f32x16 r = unstage_tile(stg, j, me, he);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[j][i] += r[i];
+                stage_tile(stg, j, me, he, o[j]);
+            }
+            flush_lines<false>(stg, Y, wrow0, ldyb, 128u * tp, le);
+            if (tp == 1) xfetch(L0);                    // the next pass's first block; behind it: eight more loads and eight line stores
+        }
+    }
+#undef L2_BLOCK
+#undef L2_STEP
+#undef L2_MMAS
+#undef L2_READS
+}
+#pragma clang diagnostic pop
+
 // ------------------------------------------------------------------------------------------------ weight preparation
 // One block per (entry, 32-row tile of W): Wp = bf16(W * gamma[k]) [N][K], WpT = its transpose [K][N] (WpP / WpTP: the same, unit-permuted),
 // bp[n] = bias[n] + sum_k W[n][k] * beta[k]  (the LayerNorm affine folded into the linear it feeds).  scalar_gain: gamma is ONE float g
@@ -771,6 +938,33 @@ int grid_for(int64_t R, int per_cu, int nw = NW) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(npass, 256 * per_cu));
 }
 
+// Which form a dX + norm-backward launch at K >= 512 takes: 2 = rowgemm_lnbwd2_kernel, two workgroups per CU; 1 = the one-workgroup kernels.
+// MMFM_ROWGEMM_LNBWD_WG = 1 or 2 forces one of them at every R.  It is a switch of its own - MMFM_ROWGEMM_WG_PER_CU keeps scaling the grids
+// of every other row-owner kernel (and of the one-workgroup kernels here), read once - and it is read at every launch, so that one process
+// can run both forms: A/B runs and the bit-identity test need one library and one process.  Default: two workgroups once there are more row
+// passes than CUs (with fewer, no CU would hold a second workgroup; B = 16, 64 and 256 measured); MMFM_ROWGEMM_RING
+// with bit 1 clear asks for the register-staged ring, which only the one-workgroup kernels have.
+int lnbwd_wg_per_cu(int64_t R) {
+    static const int ring_env = [] { const char* e = getenv("MMFM_ROWGEMM_RING"); return (e ? atoi(e) : 3) & 2; }();
+    const char* e = getenv("MMFM_ROWGEMM_LNBWD_WG");
+    const int v = e ? atoi(e) : 0;
+    if (v == 1 || v == 2) return v;
+    if (!ring_env) return 1;
+    return (R + 32 * NW - 1) / (32 * NW) > 256 ? 2 : 1;
+}
+constexpr int LDS_L2 = RINGA_SLOTS * CHUNK + NW * STG_BYTES;          // 64 KB: two workgroups per CU
+int launch_lnbwd2(const mmfm_rowgemm_groups_desc& g, int norm, const void* wbase, const GroupOff& wo, hipStream_t st, const char* who) {
+    dim3 grid(grid_for(g.R, 2)), block(NT);
+    if (norm == 2) {
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_lnbwd2_kernel<2>), LDS_L2, who)) return rc;
+        hipLaunchKernelGGL((rowgemm_lnbwd2_kernel<2>), grid, block, LDS_L2, st, g, wbase, wo);
+    } else {
+        if (int rc = mmfm_lds_opt_in(reinterpret_cast<const void*>(rowgemm_lnbwd2_kernel<1>), LDS_L2, who)) return rc;
+        hipLaunchKernelGGL((rowgemm_lnbwd2_kernel<1>), grid, block, LDS_L2, st, g, wbase, wo);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
@@ -793,7 +987,10 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
     // waves, a dedicated weight-stager wave, one 8-wave workgroup per CU, wave pairs at K >= 512 - are described in DESIGN.md sections 3b / 3e):
     //   forward-type, K = 256 : 4 waves, 2 workgroups per CU, LDS-DMA ring (LN+qkv 119 us, LN+kv 94 us, LN+q 62 us, out_proj + residual 69 us,
     //                           plain 56 us); LayerNorm + residual in one launch, and K = 512 / 768: the register-staged ring
-    //   LN-backward epilogue  : K = 256 -> wave pairs (8 waves, 101 us); K = 512 / 768 -> one wave per row tile on the LDS-DMA ring (137 / 174 us)
+    //   LN-backward epilogue  : K = 256 -> wave pairs (8 waves, 101 us); K = 512 / 768 -> beyond 256 row passes rowgemm_lnbwd2_kernel, 4 waves,
+    //                           2 workgroups per CU, operand rows streamed (114 / 146 us against 141 / 178 us of the one-workgroup kernels on the
+    //                           same box, profiles/rowgemm_lnbwd_two_wg_launches_B1024.txt; DESIGN.md section 3ac, with its rejected variants);
+    //                           up to 256 passes, MMFM_ROWGEMM_LNBWD_WG=1 or MMFM_ROWGEMM_RING bit 1 clear: one wave per row tile, one workgroup
     static const int per_cu_env = [] { const char* e = getenv("MMFM_ROWGEMM_WG_PER_CU"); return e ? atoi(e) : 0; }();
     hipStream_t st = (hipStream_t)stream;
     if (d.ln_bwd) {
@@ -803,6 +1000,12 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1, 4)), block(512);      // 4 row tiles (wave pairs) per pass
             if (sn) hipLaunchKernelGGL((rowgemm_lnbwd8_kernel<1, 2>), grid, block, 0, st, d);
             else hipLaunchKernelGGL((rowgemm_lnbwd8_kernel<1, 1>), grid, block, 0, st, d);
+        } else if (lnbwd_wg_per_cu(d.R) == 2) {                                           // the grouped descriptor's kernel with one group
+            mmfm_rowgemm_groups_desc g = {};
+            g.R = d.R; g.K = d.K; g.N = d.N; g.groups = 1;
+            g.x[0] = d.x; g.ldx = d.ldx; g.w[0] = d.w; g.ldw = d.ldw; g.y[0] = d.y; g.ldy = d.ldy;
+            g.residual = d.residual; g.ldr = d.ldr; g.ln_bwd = d.ln_bwd; g.bwd_xhat = d.bwd_xhat; g.bwd_rstd = d.bwd_rstd;
+            if (int rc = launch_lnbwd2(g, d.ln_bwd, d.w, GroupOff{}, st, "mmfm_rowgemm")) return rc;
         } else {
             dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1)), block(NT);
             static const int ring_env = [] { const char* e = getenv("MMFM_ROWGEMM_RING"); return (e ? atoi(e) : 3) & 2; }();   // bit 1 clear: register-staged ring
@@ -859,6 +1062,8 @@ extern "C" int mmfm_rowgemm(const mmfm_rowgemm_desc* dp, mmfm_stream stream) {
     return 0;
 }
 
+extern "C" int mmfm_rowgemm_lnbwd_form(int64_t R, int K) { return K == 512 || K == 768 ? lnbwd_wg_per_cu(R) : 1; }
+
 extern "C" int mmfm_rowgemm_groups(const mmfm_rowgemm_groups_desc* dp, mmfm_stream stream) {
     const mmfm_rowgemm_groups_desc d = *dp;
     MMFM_REQUIRE(d.groups >= 1 && d.groups <= GROUPS_MAX && d.R > 0, "mmfm_rowgemm_groups: groups = %d (1 .. %d), R = %lld", d.groups, GROUPS_MAX, (long long)d.R);
@@ -892,6 +1097,11 @@ extern "C" int mmfm_rowgemm_groups(const mmfm_rowgemm_groups_desc* dp, mmfm_stre
         MMFM_REQUIRE(d.N == 256 && (d.K == 256 || d.K == 512) && d.bwd_xhat && d.bwd_rstd,
                      "mmfm_rowgemm_groups: ln_bwd needs N = 256, K = 256 or 512 (got %d, %d), x_hat and rstd", d.N, d.K);
         MMFM_REQUIRE(!d.residual || (d.ldr % 8 == 0 && d.ldr >= d.N), "mmfm_rowgemm_groups: ldr %d", d.ldr);
+        if (d.K == 512 && lnbwd_wg_per_cu(d.R) == 2) {
+            if (int rc = launch_lnbwd2(d, d.ln_bwd, wbase, wo, st, "mmfm_rowgemm_groups")) return rc;
+            MMFM_LAUNCH_CHECK("mmfm_rowgemm_groups");
+            return 0;
+        }
         dim3 grid(grid_for(d.R, per_cu_env > 0 ? per_cu_env : 1)), block(NT);
         constexpr int LDS_L = RINGA_SLOTS * CHUNK + NW * STG_BYTES + NW * 4 * STG_BYTES;
 #define GLNB(KP, NORM)                                                                                                      \
