@@ -407,6 +407,36 @@ int mmfm_stitch_bwd_seg(int dtype, const void* dx, const void* dextra, const int
                         mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
                         int B, int T, int L, int off, int H, int max_F,
                         void* workspace, int64_t workspace_bytes, mmfm_stream stream);
+/* ---------------------------------------------------------------------------------- per-sample token masks
+ * MMFM_TOKEN_MASK_ROWS: x[b, l] = keep[b][l] * tok[b, l] + emb[b, l] with every sample's own keep row,
+ * keep[b][l] = (v[b][l] != 1), v = mask & attn - upstream's comparison (mm.py:145 `mask[0] == 1`) applied per sample, so at B = 1
+ * it is the keep0 of the entry points above.  What `tokens[mask == 1] = 0` would do; MultiModal.per_sample_mask.
+ *
+ * mmfm_mask_prep_rows takes the argument list of mmfm_mask_prep_seg (the uniform form passes seg_T[j] = T and one attention mask M
+ * times).  tokmask, keypad, mod_id and count are those of mmfm_mask_prep / _seg, bit for bit; keep is u8 [B][L]; keep_any u8 [L] is
+ * keep_any[l] = OR_b keep[b][l] - the mask to make live-bin records from (mmfm_live_bins): a bin is dead only where every sample
+ * masks it.  Integers only, deterministic, no allocation, hipGraph-capturable. */
+#define MMFM_TOKEN_MASK_ROWS 1
+int mmfm_mask_prep_rows(int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
+                        const int64_t* const* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad,
+                        uint8_t* keep, uint8_t* keep_any, uint8_t* mod_id, int64_t* count, mmfm_stream stream);
+/* One stitch pair for the slot of T bins at offset off with the slot's own ts [B][T] - what the uniform, _seg and _live entry points
+ * cover - under a keep mask given as base pointer and row stride: element (b, off + t) at keep[b * keep_ld + off + t].  keep_ld = 0 is
+ * the one shared row of the entry points above, and then these give the bits of mmfm_stitch_*_seg (rec == NULL) and of
+ * mmfm_stitch_*_live (rec given, off = m * T); keep_ld >= L is a per-sample mask (mmfm_mask_prep_rows: keep_ld = L).
+ * rec: NULL, or the slot's live-bin record made from keep_any (bf16 only): tok / d_tok are then over the compact rows.  Under a
+ * per-sample mask a live bin can be masked in some samples: the forward does not read that compact tok row, and the backward writes
+ * ZEROS to that compact d_tok row (the weight-gradient product over the compact rows reads it); rows of dead bins do not exist.
+ * The NULL pos_emb / d_pos contract (MMFM_EMBED_OPTS), acc_mod / acc_pos, the dropout counter (the original row b*T+t, times H, plus
+ * the column), the workspace (mmfm_stitch_bwd_seg_workspace) and the determinism are those of the entry points above.
+ * Argument errors return before any HIP call: keep_ld neither 0 nor >= L, off + T > L, rec given in fp32. */
+int mmfm_stitch_fwd_rows(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb,
+                         const int64_t* ts, const uint8_t* keep, int keep_ld, const int32_t* rec, void* x, void* emb,
+                         int B, int T, int L, int off, int H, int max_F, mmfm_stream stream);
+int mmfm_stitch_bwd_rows(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep, int keep_ld,
+                         const int32_t* rec, mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
+                         int B, int T, int L, int off, int H, int max_F,
+                         void* workspace, int64_t workspace_bytes, mmfm_stream stream);
 /* mmfm_layernorm_fwd / _bwd de-stitching over segments: with B = R / L, the output row for input row r = (b, off_j + t) is
  * B*off_j + b*seg_T[j] + t, so the final decoder_norm writes one contiguous [B*T_j][H] block per decoder modality, slot j's at row
  * B*off_j; the backward reads dy the same way.  Workspace: mmfm_layernorm_bwd_workspace(R, H). */

@@ -210,6 +210,11 @@ _PROTOS = {
     "mmfm_stitch_fwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mmfm_stitch_bwd_seg_workspace": (C.c_int64, [_i, _i, _i, _i, _i, _i, _i]),
     "mmfm_stitch_bwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    # per-sample token masks (MMFM_TOKEN_MASK_ROWS)
+    "mmfm_mask_prep_rows": (C.c_int, [_i, _i, C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "mmfm_stitch_fwd_rows": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmfm_stitch_bwd_rows": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _vp, Dropout, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mmfm_layernorm_fwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _i, C.POINTER(C.c_int32), _vp]),
     "mmfm_layernorm_bwd_seg": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, C.POINTER(C.c_int32), _vp, _i64, _vp]),
     "mmfm_masked_loss_workspace": (C.c_int64, [_i64, _i]),

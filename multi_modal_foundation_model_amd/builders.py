@@ -67,18 +67,18 @@ def _filtered(mods, modal_filter):
 
 
 def build_model(mcfg, n_ap, n_beh, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False,
-                context_mask=False, sessions=None):
+                context_mask=False, sessions=None, per_sample_mask=False):
     """train_multi_modal.py:160-189 (construction order = RNG contract).  modal_filter: dict(input=[...], output=[...]), the
     modalities the encoder / the decoder gets tokenisers for (None: both get both).  input_masking: MultiModal.input_masking.
-    neuron_padding: MultiModal.neuron_padding.  context_mask: MultiModal.context_mask.  sessions: the ordered eid -> n_k mapping of a
+    neuron_padding: MultiModal.neuron_padding.  context_mask: MultiModal.context_mask.  per_sample_mask: MultiModal.per_sample_mask.  sessions: the ordered eid -> n_k mapping of a
     `use_session: true` config (n_ap is then not read: the stitched modalities run at stitcher.width)."""
     return build_model_mods(mcfg, [("ap", n_ap), ("behavior", n_beh)], seed=seed, modal_filter=modal_filter,
                             share_modality_embeddings=share_modality_embeddings, input_masking=input_masking, neuron_padding=neuron_padding,
-                            context_mask=context_mask, sessions=sessions)
+                            context_mask=context_mask, sessions=sessions, per_sample_mask=per_sample_mask)
 
 
 def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_embeddings=True, input_masking=False, neuron_padding=False,
-                     context_mask=False, sessions=None):
+                     context_mask=False, sessions=None, per_sample_mask=False):
     """Same construction order for an arbitrary modality list [(name, channels)] (BASELINE configs[4]: 3 modalities).  Under
     `use_session: true` the stitched modalities' tokenisers and heads are built with n_channel = stitcher.width, whatever `mods` says,
     and MultiModal creates the session layers of `sessions` behind everything else."""
@@ -97,7 +97,8 @@ def build_model_mods(mcfg, mods, seed=None, modal_filter=None, share_modality_em
            for m, n in dec_mods}
     return MultiModal(enc, dec, avail_mod=[m for m, _ in mods], config=mcfg, share_modality_embeddings=share_modality_embeddings,
                       **({"input_masking": True} if input_masking else {}), **({"neuron_padding": True} if neuron_padding else {}),
-                      **({"context_mask": True} if context_mask else {}), **({"sessions": sessions} if sessions is not None else {}))
+                      **({"context_mask": True} if context_mask else {}), **({"sessions": sessions} if sessions is not None else {}),
+                      **({"per_sample_mask": per_sample_mask} if per_sample_mask is not False else {}))
 
 
 def make_optimizer(model, total_steps, lr=1e-4, wd=0.01, eps=1e-8):

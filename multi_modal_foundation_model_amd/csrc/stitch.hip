@@ -18,8 +18,12 @@ struct MaskSeg {
     int off[MAXM + 1];
 };
 
+// ROWS (mmfm_mask_prep_rows): keep0 is [B][L], every sample's own row, and keep_any[l] (zeroed by zero_rows_kernel in front of this
+// launch) is set where any sample keeps position l: every writer stores the same 1, so the outcome does not depend on their order
+template <bool ROWS>
 __global__ void mask_prep_kernel(MaskSeg src, int B, int L, int M, uint8_t* __restrict__ tokmask, uint8_t* __restrict__ keypad,
-                                 uint8_t* __restrict__ keep0, uint8_t* __restrict__ mod_id, unsigned long long* __restrict__ count) {
+                                 uint8_t* __restrict__ keep0, uint8_t* __restrict__ keep_any, uint8_t* __restrict__ mod_id,
+                                 unsigned long long* __restrict__ count) {
     unsigned long long local[MAXM];
 #pragma unroll
     for (int m = 0; m < MAXM; ++m) local[m] = 0;
@@ -42,7 +46,11 @@ __global__ void mask_prep_kernel(MaskSeg src, int B, int L, int M, uint8_t* __re
         const int64_t v = p[((size_t)b * Tn + t) * stride] & a;                     // mm.py:270
         tokmask[idx] = (uint8_t)(v != 0);
         keypad[idx] = (uint8_t)(a != 0);
-        if (b == 0) {
+        if (ROWS) {
+            keep0[idx] = (uint8_t)(v != 1);                                          // the same comparison, per sample
+            if (v != 1) keep_any[l] = 1;
+            if (b == 0) mod_id[l] = (uint8_t)m;
+        } else if (b == 0) {
             keep0[l] = (uint8_t)(v != 1);                                            // mm.py:145: argwhere(mask[0] == 1)
             mod_id[l] = (uint8_t)m;
         }
@@ -65,14 +73,22 @@ __global__ void mask_prep_kernel(MaskSeg src, int B, int L, int M, uint8_t* __re
 __global__ void zero_u64_kernel(unsigned long long* p, int n) {
     if ((int)threadIdx.x < n) p[threadIdx.x] = 0ull;
 }
+// the same for mmfm_mask_prep_rows: the counters and the L bytes of keep_any
+__global__ void zero_rows_kernel(unsigned long long* p, int n, uint8_t* __restrict__ any, int L) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0ull;
+    if (i < L) any[i] = 0;
+}
 
 // The stitch kernels work on one slot: the Tn tokens from `off` of the stitched sequence of L.  The uniform and live-row entry points
 // pass off = m * T, the segment ones (MMFM_MOD_SEGMENTS, include/mmfm.h) the slot's own offset, length and time stamps.
+// The keep mask of (b, l) is keep0[b * kld + l]: kld = 0 is the one row shared by every sample (all entry points but the _rows ones,
+// MMFM_TOKEN_MASK_ROWS), kld >= L every sample's own row.
 template <typename T>
 __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ tok, const float* __restrict__ mod_row,
                                                          const float* __restrict__ pos, const int64_t* __restrict__ ts,
                                                          const uint8_t* __restrict__ keep0, const int32_t* __restrict__ rec, T* __restrict__ x,
-                                                         T* __restrict__ emb, int B, int Tn, int L, int off, int H, int max_F) {
+                                                         T* __restrict__ emb, int B, int Tn, int L, int off, int H, int max_F, int kld) {
     const int C4 = H / 4;
     const int64_t total = (int64_t)B * Tn * C4;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -89,7 +105,7 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
         }
         const size_t o = ((size_t)b * L + l) * H + c;
         if (emb) io<T>::st4(emb + o, e);
-        if (keep0[l]) {
+        if (keep0[(size_t)b * kld + l]) {
             // rec (mmfm_stitch_fwd_live): tok holds the live rows only, (b, t) at b * T_live + rank[t]
             const int64_t tr = rec ? (int64_t)b * rec[0] + rec[4 + Tn + t] : r;
             const float4 tv = io<T>::ld4(tok + (size_t)tr * H + c);
@@ -104,7 +120,7 @@ __global__ __launch_bounds__(256) void stitch_fwd_kernel(const T* __restrict__ t
 template <typename T, bool POS>
 __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict__ dextra, const int64_t* __restrict__ ts,
                                   const uint8_t* __restrict__ keep0, const int32_t* __restrict__ rec, mmfm_dropout dropa,
-                                  T* __restrict__ d_tok, float* __restrict__ part, int B, int Tn, int L, int off, int H, int max_F, int bper) {
+                                  T* __restrict__ d_tok, float* __restrict__ part, int B, int Tn, int L, int off, int H, int max_F, int bper, int kld) {
     extern __shared__ __attribute__((aligned(16))) float tab[];
     const int CW = blockDim.x, j = threadIdx.x, col = blockIdx.x * CW + j;
     const Drop dr = drop_init(dropa);
@@ -124,9 +140,10 @@ __global__ void stitch_bwd_kernel(const T* __restrict__ dx, const T* __restrict_
                 tab[tsv * CW + j] += e;               // a thread owns its column: no race, fixed order
             }
             macc += e;
-            if (d_tok && !rec) io<T>::st(d_tok + (size_t)r * H + col, keep0[l] ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
-            else if (d_tok && keep0[l])        // live rows only, at their compact rows; the counter stays the original row's
-                io<T>::st(d_tok + ((size_t)b * rec[0] + rec[4 + Tn + t]) * H + col, dr.apply(g, (uint64_t)r * H + col));
+            const bool kp = keep0[(size_t)b * kld + l] != 0;
+            if (d_tok && !rec) io<T>::st(d_tok + (size_t)r * H + col, kp ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
+            else if (d_tok && rec[4 + Tn + t] >= 0)        // live bins only, at their compact rows; the counter stays the original row's
+                io<T>::st(d_tok + ((size_t)b * rec[0] + rec[4 + Tn + t]) * H + col, kp ? dr.apply(g, (uint64_t)r * H + col) : 0.f);
         }
     }
     float* out = part + (size_t)blockIdx.y * (max_F + 1) * H;
@@ -191,10 +208,10 @@ __global__ __launch_bounds__(256) void stitch_modsum_kernel(const uint16_t* __re
     }
 }
 
-// d_tok[b*T+t][:] = keep0[off+t] ? dropout'(dx[b][off+t][:]) : 0      (bf16, 16-B accesses; H % 8 == 0)
+// d_tok[b*T+t][:] = keep0[b*kld+off+t] ? dropout'(dx[b][off+t][:]) : 0      (bf16, 16-B accesses; H % 8 == 0)
 __global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __restrict__ dx, const uint8_t* __restrict__ keep0,
                                                           const int32_t* __restrict__ rec, mmfm_dropout dropa,
-                                                          uint16_t* __restrict__ d_tok, int B, int Tn, int L, int off, int H) {
+                                                          uint16_t* __restrict__ d_tok, int B, int Tn, int L, int off, int H, int kld) {
     const Drop dr = drop_init(dropa);
     const int C8 = H / 8;
     const int64_t total = (int64_t)B * Tn * C8;
@@ -203,10 +220,13 @@ __global__ __launch_bounds__(256) void stitch_dtok_kernel(const uint16_t* __rest
         const int c = (int)(idx % C8) * 8;
         const int b = (int)(r / Tn), l = off + (int)(r % Tn);
         uint4 o = make_uint4(0u, 0u, 0u, 0u);
-        // rec (mmfm_stitch_bwd_live): live rows only, at their compact rows; the dropout counter stays the original row's
-        if (rec && !keep0[l]) continue;
-        const int64_t orow = rec ? (int64_t)b * rec[0] + rec[4 + Tn + (int)(r % Tn)] : r;
-        if (keep0[l]) {
+        // rec (mmfm_stitch_bwd_live): live bins only, at their compact rows; the dropout counter stays the original row's.  A bin is dead
+        // where the mask the record was made from is 0: the shared row itself (kld = 0), or keep_any, the OR of the samples' rows - there
+        // a live bin can be masked in this sample, and its compact row, which the weight-gradient product reads, gets zeros
+        const int rank = rec ? rec[4 + Tn + (int)(r % Tn)] : 0;
+        if (rank < 0) continue;
+        const int64_t orow = rec ? (int64_t)b * rec[0] + rank : r;
+        if (keep0[(size_t)b * kld + l]) {
             const uint4 g = *reinterpret_cast<const uint4*>(dx + ((size_t)b * L + l) * H + c);
             if (dr.on()) {
                 const uint32_t gw[4] = {g.x, g.y, g.z, g.w};
@@ -290,10 +310,11 @@ bool oh_path(int dtype, int H) { return dtype == MMFM_BF16 && H % 8 == 0; }
 
 extern "C" int mmfm_reduce_slabs(float*, const float*, int64_t, int, int64_t, int, mmfm_stream);
 
-// Both mask-prep entry points: the slot table from the per-slot lengths and attention masks, then the counters zeroed and the kernel.
+// The mask-prep entry points: the slot table from the per-slot lengths and attention masks, then the counters zeroed and the kernel.
+// keep_any: NULL - keep0 is the shared row [L]; set (mmfm_mask_prep_rows) - keep0 is [B][L] and keep_any [L] their OR over the samples.
 static int mask_prep_impl(const char* what, int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
                           const int64_t* const* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad, uint8_t* keep0,
-                          uint8_t* mod_id, int64_t* count, mmfm_stream stream) {
+                          uint8_t* keep_any, uint8_t* mod_id, int64_t* count, mmfm_stream stream) {
     MaskSeg src;
     src.off[0] = 0;
     for (int m = 0; m < MAXM; ++m) {
@@ -308,11 +329,20 @@ static int mask_prep_impl(const char* what, int B, int M, const int32_t* seg_T, 
     const int L = src.off[M];
     MMFM_REQUIRE(L <= 65535, "%s: sequence too long", what);
     hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)B * L;
+    const dim3 grid((int)std::min<int64_t>(256, (n + 255) / 256));
+    if (keep_any) {
+        hipLaunchKernelGGL(zero_rows_kernel, dim3(cdiv(std::max(L, M), 256)), dim3(256), 0, st, (unsigned long long*)count, M, keep_any, L);
+        MMFM_LAUNCH_CHECK(what);
+        hipLaunchKernelGGL(mask_prep_kernel<true>, grid, dim3(256), 0, st, src, B, L, M, tokmask, keypad, keep0, keep_any, mod_id,
+                           (unsigned long long*)count);
+        MMFM_LAUNCH_CHECK(what);
+        return 0;
+    }
     hipLaunchKernelGGL(zero_u64_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)count, M);
     MMFM_LAUNCH_CHECK(what);
-    const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(mask_prep_kernel, dim3((int)std::min<int64_t>(256, (n + 255) / 256)), dim3(256), 0, st, src, B, L, M, tokmask, keypad,
-                       keep0, mod_id, (unsigned long long*)count);
+    hipLaunchKernelGGL(mask_prep_kernel<false>, grid, dim3(256), 0, st, src, B, L, M, tokmask, keypad, keep0, (uint8_t*)nullptr, mod_id,
+                       (unsigned long long*)count);
     MMFM_LAUNCH_CHECK(what);
     return 0;
 }
@@ -325,7 +355,7 @@ extern "C" int mmfm_mask_prep(int B, int T, int M, const int64_t* const* mask_sr
     int32_t seg_T[MAXM];
     const int64_t* attns[MAXM];
     for (int m = 0; m < MAXM; ++m) { seg_T[m] = T; attns[m] = attn; }       // slot j at j * T, one attention mask for all
-    return mask_prep_impl("mmfm_mask_prep", B, M, seg_T, mask_src, mask_stride, attns, channels, tokmask, keypad, keep0, mod_id, count, stream);
+    return mask_prep_impl("mmfm_mask_prep", B, M, seg_T, mask_src, mask_stride, attns, channels, tokmask, keypad, keep0, nullptr, mod_id, count, stream);
 }
 
 extern "C" int mmfm_mask_prep_seg(int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
@@ -334,7 +364,17 @@ extern "C" int mmfm_mask_prep_seg(int B, int M, const int32_t* seg_T, const int6
     static_assert(MAXM == MMFM_MAX_SEGMENTS, "mmfm_mask_prep and the segment table hold the same number of slots");
     MMFM_REQUIRE(B > 0 && M > 0 && M <= MAXM, "mmfm_mask_prep_seg: bad shape B=%d M=%d (M <= %d)", B, M, MAXM);
     MMFM_REQUIRE(seg_T && mask_src && mask_stride && attn && channels && tokmask && keypad && keep0 && mod_id && count, "mmfm_mask_prep_seg: null pointer");
-    return mask_prep_impl("mmfm_mask_prep_seg", B, M, seg_T, mask_src, mask_stride, attn, channels, tokmask, keypad, keep0, mod_id, count, stream);
+    return mask_prep_impl("mmfm_mask_prep_seg", B, M, seg_T, mask_src, mask_stride, attn, channels, tokmask, keypad, keep0, nullptr, mod_id, count, stream);
+}
+
+extern "C" int mmfm_mask_prep_rows(int B, int M, const int32_t* seg_T, const int64_t* const* mask_src, const int64_t* mask_stride,
+                                   const int64_t* const* attn, const int64_t* channels, uint8_t* tokmask, uint8_t* keypad, uint8_t* keep,
+                                   uint8_t* keep_any, uint8_t* mod_id, int64_t* count, mmfm_stream stream) {
+    MMFM_REQUIRE(B > 0 && M > 0 && M <= MAXM, "mmfm_mask_prep_rows: bad shape B=%d M=%d (M <= %d)", B, M, MAXM);
+    MMFM_REQUIRE(seg_T && mask_src && mask_stride && attn && channels && tokmask && keypad && keep && keep_any && mod_id && count,
+                 "mmfm_mask_prep_rows: null pointer");
+    return mask_prep_impl("mmfm_mask_prep_rows", B, M, seg_T, mask_src, mask_stride, attn, channels, tokmask, keypad, keep, keep_any, mod_id, count,
+                          stream);
 }
 
 extern "C" int mmfm_collate_csr(int B, int max_T, int max_N, float pad_value, const uint8_t* data, const int32_t* indices,
@@ -351,19 +391,20 @@ extern "C" int mmfm_collate_csr(int B, int max_T, int max_N, float pad_value, co
 }
 
 // The three stitch forwards.  what: the entry point's name, for its messages; off: the slot's first token (int64: m * T of the uniform
-// forms is checked here before it is narrowed); rec: the live-bin record of mmfm_stitch_fwd_live, else NULL.
+// forms is checked here before it is narrowed); rec: the live-bin record of mmfm_stitch_fwd_live, else NULL; keep_ld: 0, or the row
+// stride of a per-sample keep mask (mmfm_stitch_fwd_rows).
 static int stitch_fwd_impl(const char* what, int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
-                           const uint8_t* keep0, const int32_t* rec, void* x, void* emb, int B, int T, int L, int64_t off, int H, int max_F,
-                           mmfm_stream stream) {
+                           const uint8_t* keep0, int keep_ld, const int32_t* rec, void* x, void* emb, int B, int T, int L, int64_t off, int H,
+                           int max_F, mmfm_stream stream) {
     MMFM_REQUIRE(tok && mod_emb_row && (ts || !pos_emb) && keep0 && x, "%s: null pointer", what);       // pos_emb NULL: no position table
     MMFM_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && off >= 0 && off + T <= L && max_F > 0, "%s: bad shape", what);
     const int64_t n = (int64_t)B * T * (H / 4);
     dim3 grid((int)std::min<int64_t>(4096, (n + 255) / 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMFM_F32)
-        hipLaunchKernelGGL(stitch_fwd_kernel<float>, grid, block, 0, st, (const float*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (float*)x, (float*)emb, B, T, L, (int)off, H, max_F);
+        hipLaunchKernelGGL(stitch_fwd_kernel<float>, grid, block, 0, st, (const float*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (float*)x, (float*)emb, B, T, L, (int)off, H, max_F, keep_ld);
     else if (dtype == MMFM_BF16)
-        hipLaunchKernelGGL(stitch_fwd_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (uint16_t*)x, (uint16_t*)emb, B, T, L, (int)off, H, max_F);
+        hipLaunchKernelGGL(stitch_fwd_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)tok, mod_emb_row, pos_emb, ts, keep0, rec, (uint16_t*)x, (uint16_t*)emb, B, T, L, (int)off, H, max_F, keep_ld);
     else
         return mmfm_set_error(-1, "%s: bad dtype %d", what, dtype);
     MMFM_LAUNCH_CHECK(what);
@@ -371,17 +412,31 @@ static int stitch_fwd_impl(const char* what, int dtype, const void* tok, const f
 }
 extern "C" int mmfm_stitch_fwd(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
                                const uint8_t* keep0, void* x, void* emb, int B, int T, int L, int m, int H, int max_F, mmfm_stream stream) {
-    return stitch_fwd_impl("mmfm_stitch_fwd", dtype, tok, mod_emb_row, pos_emb, ts, keep0, nullptr, x, emb, B, T, L, (int64_t)m * T, H, max_F, stream);
+    return stitch_fwd_impl("mmfm_stitch_fwd", dtype, tok, mod_emb_row, pos_emb, ts, keep0, 0, nullptr, x, emb, B, T, L, (int64_t)m * T, H, max_F, stream);
 }
 extern "C" int mmfm_stitch_fwd_live(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
                                     const uint8_t* keep0, const int32_t* rec, void* x, void* emb, int B, int T, int L, int m, int H, int max_F,
                                     mmfm_stream stream) {
     MMFM_REQUIRE(rec, "mmfm_stitch_fwd_live: null live-bin record");
-    return stitch_fwd_impl("mmfm_stitch_fwd_live", dtype, tok, mod_emb_row, pos_emb, ts, keep0, rec, x, emb, B, T, L, (int64_t)m * T, H, max_F, stream);
+    return stitch_fwd_impl("mmfm_stitch_fwd_live", dtype, tok, mod_emb_row, pos_emb, ts, keep0, 0, rec, x, emb, B, T, L, (int64_t)m * T, H, max_F, stream);
 }
 extern "C" int mmfm_stitch_fwd_seg(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
                                    const uint8_t* keep0, void* x, void* emb, int B, int T, int L, int off, int H, int max_F, mmfm_stream stream) {
-    return stitch_fwd_impl("mmfm_stitch_fwd_seg", dtype, tok, mod_emb_row, pos_emb, ts, keep0, nullptr, x, emb, B, T, L, off, H, max_F, stream);
+    return stitch_fwd_impl("mmfm_stitch_fwd_seg", dtype, tok, mod_emb_row, pos_emb, ts, keep0, 0, nullptr, x, emb, B, T, L, off, H, max_F, stream);
+}
+// The _rows pair (MMFM_TOKEN_MASK_ROWS): its own argument checks, then the same launches as every other entry point.
+static int stitch_rows_args(const char* what, int dtype, const void* keep, int keep_ld, const int32_t* rec, int T, int L, int off) {
+    MMFM_REQUIRE(keep, "%s: null pointer", what);
+    MMFM_REQUIRE(keep_ld == 0 || keep_ld >= L, "%s: keep_ld = %d is neither 0 (one shared row) nor >= L = %d", what, keep_ld, L);
+    MMFM_REQUIRE(T > 0 && off >= 0 && (int64_t)off + T <= L, "%s: the slot [%d, %d + %d) leaves the sequence of %d", what, off, off, T, L);
+    MMFM_REQUIRE(!rec || dtype == MMFM_BF16, "%s: a live-bin record needs bf16", what);
+    return 0;
+}
+extern "C" int mmfm_stitch_fwd_rows(int dtype, const void* tok, const float* mod_emb_row, const float* pos_emb, const int64_t* ts,
+                                    const uint8_t* keep, int keep_ld, const int32_t* rec, void* x, void* emb, int B, int T, int L, int off, int H,
+                                    int max_F, mmfm_stream stream) {
+    if (int rc = stitch_rows_args("mmfm_stitch_fwd_rows", dtype, keep, keep_ld, rec, T, L, off)) return rc;
+    return stitch_fwd_impl("mmfm_stitch_fwd_rows", dtype, tok, mod_emb_row, pos_emb, ts, keep, keep_ld, rec, x, emb, B, T, L, off, H, max_F, stream);
 }
 
 extern "C" int64_t mmfm_stitch_bwd_workspace(int dtype, int B, int T, int L, int H, int max_F) {
@@ -401,7 +456,7 @@ extern "C" int64_t mmfm_stitch_bwd_seg_workspace(int dtype, int B, int T, int L,
 }
 
 // The three stitch backwards: what, off and rec as in stitch_fwd_impl.  Every check comes before the first launch.
-static int stitch_bwd_impl(const char* what, int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
+static int stitch_bwd_impl(const char* what, int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, int keep_ld,
                            const int32_t* rec, mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B,
                            int T, int L, int64_t off64, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
     MMFM_REQUIRE(dx && (ts || !d_pos) && keep0 && d_mod_row, "%s: null pointer", what);                        // d_pos NULL: no position table
@@ -419,7 +474,7 @@ static int stitch_bwd_impl(const char* what, int dtype, const void* dx, const vo
         if (d_tok) {
             const int64_t n = (int64_t)B * T * (H / 8);
             hipLaunchKernelGGL(stitch_dtok_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, st, (const uint16_t*)dx, keep0,
-                               rec, drop, (uint16_t*)d_tok, B, T, L, off, H);
+                               rec, drop, (uint16_t*)d_tok, B, T, L, off, H, keep_ld);
         }
         if (!d_pos) {
             // the column sum: as many slabs of H floats as samples, at most 256, and no more than the workspace bound of the one-hot
@@ -461,7 +516,7 @@ static int stitch_bwd_impl(const char* what, int dtype, const void* dx, const vo
     dim3 grid(H / cw, nch), block(cw);
     const int F = d_pos ? max_F : 0;                  // no position table: no LDS table, a chunk's partial is one row of H floats
     const size_t lds = (size_t)F * cw * sizeof(float);
-#define STITCH_BWD(TT, POS) hipLaunchKernelGGL((stitch_bwd_kernel<TT, POS>), grid, block, lds, st, (const TT*)dx, (const TT*)dextra, ts, keep0, rec, drop, (TT*)d_tok, (float*)workspace, B, T, L, off, H, F, bper)
+#define STITCH_BWD(TT, POS) hipLaunchKernelGGL((stitch_bwd_kernel<TT, POS>), grid, block, lds, st, (const TT*)dx, (const TT*)dextra, ts, keep0, rec, drop, (TT*)d_tok, (float*)workspace, B, T, L, off, H, F, bper, keep_ld)
     if (dtype == MMFM_F32) { if (d_pos) STITCH_BWD(float, true); else STITCH_BWD(float, false); }
     else { if (d_pos) STITCH_BWD(uint16_t, true); else STITCH_BWD(uint16_t, false); }
 #undef STITCH_BWD
@@ -475,20 +530,27 @@ static int stitch_bwd_impl(const char* what, int dtype, const void* dx, const vo
 extern "C" int mmfm_stitch_bwd(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0,
                                mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
                                int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
-    return stitch_bwd_impl("mmfm_stitch_bwd", dtype, dx, dextra, ts, keep0, nullptr, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
+    return stitch_bwd_impl("mmfm_stitch_bwd", dtype, dx, dextra, ts, keep0, 0, nullptr, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
                            (int64_t)m * T, H, max_F, workspace, workspace_bytes, stream);
 }
 extern "C" int mmfm_stitch_bwd_live(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, const int32_t* rec,
                                     mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T,
                                     int L, int m, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
     MMFM_REQUIRE(rec, "mmfm_stitch_bwd_live: null live-bin record");
-    return stitch_bwd_impl("mmfm_stitch_bwd_live", dtype, dx, dextra, ts, keep0, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
+    return stitch_bwd_impl("mmfm_stitch_bwd_live", dtype, dx, dextra, ts, keep0, 0, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
                            (int64_t)m * T, H, max_F, workspace, workspace_bytes, stream);
 }
 extern "C" int mmfm_stitch_bwd_seg(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep0, mmfm_dropout drop,
                                    void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos, int B, int T, int L, int off, int H,
                                    int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
-    return stitch_bwd_impl("mmfm_stitch_bwd_seg", dtype, dx, dextra, ts, keep0, nullptr, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
+    return stitch_bwd_impl("mmfm_stitch_bwd_seg", dtype, dx, dextra, ts, keep0, 0, nullptr, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
+                           off, H, max_F, workspace, workspace_bytes, stream);
+}
+extern "C" int mmfm_stitch_bwd_rows(int dtype, const void* dx, const void* dextra, const int64_t* ts, const uint8_t* keep, int keep_ld,
+                                    const int32_t* rec, mmfm_dropout drop, void* d_tok, float* d_mod_row, float* d_pos, int acc_mod, int acc_pos,
+                                    int B, int T, int L, int off, int H, int max_F, void* workspace, int64_t workspace_bytes, mmfm_stream stream) {
+    if (int rc = stitch_rows_args("mmfm_stitch_bwd_rows", dtype, keep, keep_ld, rec, T, L, off)) return rc;
+    return stitch_bwd_impl("mmfm_stitch_bwd_rows", dtype, dx, dextra, ts, keep, keep_ld, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, L,
                            off, H, max_F, workspace, workspace_bytes, stream);
 }
 

@@ -61,6 +61,9 @@ CONTEXT = ("context",)
 # at).  stitch_bias: the session layers have biases.  Constructor keywords and attributes like the groups above, no dataclass fields;
 # None - the default - is today's model
 SESSION = ("sessions", "stitch_bias")
+# Per-sample token masking (MultiModal.per_sample_mask): every sample's tokens are zeroed where its OWN mask is 1, not where
+# sample 0's is.  A constructor keyword and attribute like the groups above, no dataclass field.  False - the default - is today's model
+TOKEN_MASK = ("per_sample_mask",)
 Sides = namedtuple("Sides", "encoder decoder")
 
 
@@ -115,12 +118,16 @@ class EngineConfig:
     context: InitVar[Optional[Tuple[int, int]]] = None
     sessions: InitVar[Optional[Dict[str, Tuple[int, ...]]]] = None
     stitch_bias: InitVar[bool] = True
+    per_sample_mask: InitVar[bool] = False
     # `hidden` has no per-side form (decoder_proj_context is H -> H and cross-attention reads the encoder's rows), nor has
     # `n_modality` (a shared mod_emb is one tensor, mm.py:84-87, and the row is the modality's index in `mods` on either side).  Read a
     # side's values through `side()`
 
     def __post_init__(self, embed_act="softsign", embed_pos=True, embed_bias=True, enc_mods=None, dec_mods=None, share_mod_emb=True,
-                      loss_weight=None, context=None, sessions=None, stitch_bias=True):
+                      loss_weight=None, context=None, sessions=None, stitch_bias=True, per_sample_mask=False):
+        if not isinstance(per_sample_mask, bool):
+            raise ValueError(f"EngineConfig.per_sample_mask = {per_sample_mask!r}: True or False")
+        self.per_sample_mask = per_sample_mask
         if sessions is not None:
             names = [m for m, _ in self.mods]
             sessions = {m: tuple(int(n) for n in sizes) for m, sizes in sessions.items()}
@@ -158,7 +165,7 @@ class EngineConfig:
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA + CONTEXT + SESSION)
+        return all(getattr(self, k) == getattr(other, k) for k in tuple(f.name for f in fields(self)) + PER_SIDE_EMBED + MODAL + LOSS_EXTRA + CONTEXT + SESSION + TOKEN_MASK)
 
     __hash__ = None
 
@@ -201,7 +208,8 @@ class EngineConfig:
 
     @staticmethod
     def from_model_config(mc, mods, per_side: bool = False, embedder_opts: bool = False, enc_mods=None, dec_mods=None,
-                          share_mod_emb: bool = True, context_window: bool = False, sessions=None, stitch_bias: bool = True) -> "EngineConfig":
+                          share_mod_emb: bool = True, context_window: bool = False, sessions=None, stitch_bias: bool = True,
+                          per_sample_mask: bool = False) -> "EngineConfig":
         """per_side = True (what MultiModal passes): every PER_SIDE quantity is read from its own section.  per_side = False, the
         two-argument call from before the sections were independent, keeps its contract for callers that rely on it: transformer
         sections that differ in n_heads, inter_size or dropout raise ValueError, in use_scalenorm or act NotImplementedError, as they
@@ -211,7 +219,8 @@ class EngineConfig:
         contract it had: any act but softsign, pos: false and bias: false raise NotImplementedError.
         enc_mods / dec_mods / share_mod_emb: the config's fields of those names (modal_filter, share_modality_embeddings).
         context_window = True (what MultiModal passes under its context_mask switch): context.forward / context.backward are read into
-        `context` - a value that is not an int >= -1 raises ValueError here.  Without it the two keys are not looked at, as upstream."""
+        `context` - a value that is not an int >= -1 raises ValueError here.  Without it the two keys are not looked at, as upstream.
+        per_sample_mask = True (what MultiModal passes under its switch of that name): the field of that name."""
         context = None
         if context_window:
             ctx = mc["context"]
@@ -259,7 +268,7 @@ class EngineConfig:
                             enc_attn_bias=bool(et["attention_bias"]), enc_mlp_bias=bool(et["mlp_bias"]),
                             dec_attn_bias=bool(dtf["attention_bias"]), dec_mlp_bias=bool(dtf["mlp_bias"]),
                             enc_mods=enc_mods, dec_mods=dec_mods, share_mod_emb=share_mod_emb, context=context,
-                            sessions=sessions, stitch_bias=stitch_bias)
+                            sessions=sessions, stitch_bias=stitch_bias, per_sample_mask=per_sample_mask)
 
 
 # a block's linear: name, the norm that feeds it (None: plain), weight [N, K], has a bias, the adjacent nn.Linear's a fused projection aliases
@@ -742,9 +751,13 @@ class Engine:
     def plan_key(self, B, T, training, grad=True, pattern=None, elem=None):
         """The key of a step plan in `plans`.  Without a context window (EngineConfig.context None) the keys are what they always were:
         (B, T, training, grad), with the freeze pattern behind it where there is one, and the six-entry form (..., pattern, elem) for an
-        element-masked plan.  Under a window the key is always the six-entry form with ("window", lo, hi) behind it."""
+        element-masked plan.  Under a window the key is always the six-entry form with ("window", lo, hi) behind it; under per-sample
+        token masks (EngineConfig.per_sample_mask) the marker ("rows",) stands behind the six-entry form, or behind the window's entry."""
+        rows = (("rows",),) if getattr(self.cfg, "per_sample_mask", False) else ()       # (a config from before the switch has none)
         if self.cfg.context is not None:
-            return (B, T, bool(training), bool(grad), pattern, elem, ("window",) + K.context_window(*self.cfg.context))
+            return (B, T, bool(training), bool(grad), pattern, elem, ("window",) + K.context_window(*self.cfg.context)) + rows
+        if rows:
+            return (B, T, bool(training), bool(grad), pattern, elem) + rows
         if elem is not None:
             return (B, T, bool(training), bool(grad), pattern, elem)
         return (B, T, bool(training), bool(grad)) + (() if pattern is None else (pattern,))

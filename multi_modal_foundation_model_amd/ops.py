@@ -319,6 +319,33 @@ def stitch_bwd_seg(dx, dextra, ts, keep0, drop, d_tok, d_mod_row, d_pos, acc_mod
                 off, H, max_F, ws)
 
 
+# ---- per-sample token masks (MMFM_TOKEN_MASK_ROWS): every sample's own keep row, keep [B][L], and keep_any [L], their OR
+def mask_prep_rows(B, Ts, masks, strides, attns, channels, tokmask, keypad, keep, keep_any, mod_id, count, plan=None):
+    """mask_prep_seg's arguments (the uniform form passes T and the one attention mask once per slot); keep u8 [B][L], keep_any u8 [L]."""
+    M = len(masks)
+    if not (len(Ts) == len(attns) == len(strides) == len(channels) == M):
+        raise ValueError("mask_prep_rows: one length, mask, stride, attention mask and channel count per slot")
+    seg = _seg_T(Ts)
+    src = (C.c_void_p * M)(*[m.data_ptr() for m in masks])
+    at = (C.c_void_p * M)(*[a.data_ptr() for a in attns])
+    st = (C.c_int64 * M)(*strides)
+    ch = (C.c_int64 * M)(*channels)
+    _emit(plan, L.lib().mmfm_mask_prep_rows, (B, M, seg, src, st, at, ch, P(tokmask), P(keypad), P(keep), P(keep_any), P(mod_id), P(count)),
+          keep=(seg, src, st, at, ch))
+
+
+def stitch_fwd_rows(tok, mod_row, pos, ts, keep, keep_ld, rec, x, emb, B, T, Lseq, off, H, max_F, plan=None):
+    """The slot of T bins at `off` under keep[b * keep_ld + off + t] (keep_ld 0: one shared row); rec: the slot's live-bin record or None."""
+    _emit(plan, L.lib().mmfm_stitch_fwd_rows, (dt(tok), P(tok), P(mod_row), P(pos), P(ts), P(keep), int(keep_ld), P(rec), P(x), P(emb), B, T, Lseq,
+                                               off, H, max_F))
+
+
+def stitch_bwd_rows(dx, dextra, ts, keep, keep_ld, rec, drop, d_tok, d_mod_row, d_pos, acc_mod, acc_pos, B, T, Lseq, off, H, max_F, ws, plan=None):
+    _emit(plan, L.lib().mmfm_stitch_bwd_rows, (dt(dx), P(dx), P(dextra), P(ts), P(keep), int(keep_ld), P(rec),
+                                               drop if drop is not None else L.NO_DROP, P(d_tok), P(d_mod_row), P(d_pos), int(acc_mod),
+                                               int(acc_pos), B, T, Lseq, off, H, max_F, P(ws), ws.numel() * ws.element_size()))
+
+
 def layernorm_fwd_seg(x, gamma, beta, y, mean, rstd, R, H, Ts, eps=1e-5, plan=None):
     seg = _seg_T(Ts)
     _emit(plan, L.lib().mmfm_layernorm_fwd_seg, (dt(x), P(x), P(gamma), P(beta), P(y), P(mean), P(rstd), R, H, eps, len(Ts), seg), keep=(seg,))

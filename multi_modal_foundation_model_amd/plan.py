@@ -170,6 +170,10 @@ class PlanBuilder:
         # the mask products (tokmask / keypad / keep0 / mod_id / count) come from the side's own modalities' masks: one buffer set while
         # the two sides have the same modalities, else the decoder's own under "dec/"
         self.split_masks = [m for m, _, _ in self.mods_of["encoder"]] != [m for m, _, _ in self.mods_of["decoder"]]
+        # EngineConfig.per_sample_mask: per side, keep [B, Lq] - every sample's own row - and keep_any [Lq], their OR, stand
+        # where keep0 [Lq] stands; the mask launch is mmfm_mask_prep_rows, the stitch launches the _rows pair, and the live-bin records
+        # come from keep_any.  False: no buffer, launch or argument of the plan differs from what it always was
+        self.per_sample = bool(getattr(c, "per_sample_mask", False))
         self.staged = sorted({m for side in self.mods_of.values() for m, _, _ in side})      # modalities some side uses
         self.sides = {side: Side(c.side(side), training) for side in ("encoder", "decoder")}
         # stitched modalities (EngineConfig.sessions): st[m] = the neuron counts of m's sessions.  Such a modality's inputs,
@@ -324,7 +328,11 @@ class PlanBuilder:
         buf("loss_sum", (Mmax,), f32)
         for pre in ("", "dec/") if self.split_masks else ("",):
             buf(pre + "tokmask", (B, Lq), u8); buf(pre + "keypad", (B, Lq), u8)
-            buf(pre + "keep0", (Lq,), u8); buf(pre + "mod_id", (Lq,), u8); buf(pre + "count", (Mmax,), i64)
+            if self.per_sample:
+                buf(pre + "keep", (B, Lq), u8); buf(pre + "keep_any", (Lq,), u8)
+            else:
+                buf(pre + "keep0", (Lq,), u8)
+            buf(pre + "mod_id", (Lq,), u8); buf(pre + "count", (Mmax,), i64)
         max_slab = 1
         for m, n in zip(self.staged, chans):
             # the same arguments the launches below pass (the token embedding reads its input rows padded to 16 B: ldn selects the
@@ -585,15 +593,22 @@ class PlanBuilder:
 
     def stitch_mode(self, side, slot):
         """The stitch entry points of slot `slot` of `side` - segment, live-row or uniform - as the suffix of their names, and the
-        operands the three differ in: the slot's own stamps and offset, or the shared stamps and the slot index (and the live-bin record)."""
-        if self.seg:
-            return "_seg", dict(ts=self.b[f"ts/{self.mods_of[side][slot][0]}"], off=self.off[side][slot])
+        operands the three differ in: the slot's own stamps and offset, or the shared stamps and the slot index (and the live-bin record).
+        Under per-sample masks the one _rows pair serves all three: the slot's stamps and offset, the side's keep [B, Lq] with its row
+        stride, and the live-bin record or None."""
         lv = self.lv.get((side, slot))
-        return ("", dict(ts=self.b["ts"], m=slot)) if lv is None else ("_live", dict(ts=self.b["ts"], m=slot, rec=lv._keep))
+        if self.per_sample:
+            ts = self.b[f"ts/{self.mods_of[side][slot][0]}"] if self.seg else self.b["ts"]
+            return "_rows", dict(ts=ts, off=self.off[side][slot], keep=self.b[self.mk(side, "keep")], keep_ld=self.Lq,
+                                 rec=None if lv is None else lv._keep)
+        keep0 = self.b[self.mk(side, "keep0")]
+        if self.seg:
+            return "_seg", dict(ts=self.b[f"ts/{self.mods_of[side][slot][0]}"], off=self.off[side][slot], keep0=keep0)
+        return ("", dict(ts=self.b["ts"], m=slot, keep0=keep0)) if lv is None else ("_live", dict(ts=self.b["ts"], m=slot, rec=lv._keep, keep0=keep0))
 
     def stitch_f(self, plan, side, slot, tok, mod_row, pos, x, emb):
         sfx, kw = self.stitch_mode(side, slot)
-        getattr(K, "stitch_fwd" + sfx)(tok=tok, mod_row=mod_row, pos=pos, keep0=self.b[self.mk(side, "keep0")], x=x, emb=emb, B=self.B,
+        getattr(K, "stitch_fwd" + sfx)(tok=tok, mod_row=mod_row, pos=pos, x=x, emb=emb, B=self.B,
                                        T=self.Tm[self.mods_of[side][slot][0]], Lseq=self.Lq, H=self.H, max_F=self.sides[side].max_F,
                                        plan=plan, **kw)
 
@@ -603,7 +618,7 @@ class PlanBuilder:
         m, mod, _ = self.mods_of[side][slot]
         pS = f"{side}_embeddings.{mod}.embedder"
         sfx, kw = self.stitch_mode(side, slot)
-        getattr(K, "stitch_bwd" + sfx)(dx=dS, dextra=dextra, keep0=self.b[self.mk(side, "keep0")], drop=e._drop(f"{side}/embdrop/{m}", sd.dpe),
+        getattr(K, "stitch_bwd" + sfx)(dx=dS, dextra=dextra, drop=e._drop(f"{side}/embdrop/{m}", sd.dpe),
                                        d_tok=self.buf(f"d/tok/{side}/{m}", (self.BTm[m], self.H)),
                                        d_mod_row=e.Gv(f"{self.c.mod_emb_owner(side, mod)}_embeddings.{mod}.embedder.mod_emb.weight")[m],
                                        d_pos=e.Gv(pS + ".pos_embed.weight") if sd.pos else None, acc_mod=acc_mod, acc_pos=False, B=self.B,
@@ -768,6 +783,13 @@ class PlanBuilder:
         mk = self.mk
         for side in ("encoder", "decoder") if self.split_masks else ("encoder",):       # mm.py:147-149 / 169-171: each side's own masks
             mods = self.mods_of[side]
+            if self.per_sample:
+                outs = [b[mk(side, k)] for k in ("tokmask", "keypad", "keep", "keep_any", "mod_id", "count")]
+                K.mask_prep_rows(B, [self.Tm[m] for m, _, _ in mods], [b[f"mask/{m}"] for m, _, _ in mods], [1] * len(mods),
+                                 [b[f"attn/{m}"] if self.seg else b["attn"] for m, _, _ in mods], [n for _, _, n in mods], *outs, plan=fwd)
+                if self.live:       # a bin is dead only where every sample masks it
+                    K.live_bins(b[mk(side, "keep_any")], T, M, buf(mk(side, "live"), (M, L.live_rec_ints(T)), torch.int32), plan=fwd)
+                continue
             outs = [b[mk(side, k)] for k in ("tokmask", "keypad", "keep0", "mod_id", "count")]
             if self.seg:
                 K.mask_prep_seg(B, [self.Tm[m] for m, _, _ in mods], [b[f"mask/{m}"] for m, _, _ in mods], [1] * len(mods),

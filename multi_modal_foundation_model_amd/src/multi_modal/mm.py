@@ -128,6 +128,7 @@ class MultiModal(nn.Module):
     input_masking = False        # the switch of mask_type: input (a class default, so that a module pickled before it existed has it too)
     neuron_padding = False       # the switch of space_attn_mask: padded channels leave the inputs and the loss (a class default, as above)
     context_mask = False         # the switch of context.forward / context.backward: windowed encoder attention (a class default, as above)
+    per_sample_mask = False      # the switch of per-sample token masking: each sample's own masked tokens are zeroed (a class default, as above)
     use_session = False          # the switch of use_session: per-session read-in / read-out layers (a class default, as above)
     session_index = None         # eid -> session index k (use_session); saved with the module
 
@@ -189,6 +190,13 @@ class MultiModal(nn.Module):
         # context_mask = ones under a TO DO).  True: a value that is not an int >= -1 raises ValueError when the engine is built
         if "context_mask" in kwargs:
             self.context_mask = bool(kwargs["context_mask"])
+        # per-sample token masking: the tokens of sample b are zeroed where sample b's own mask is 1 - `tokens[mask == 1] = 0`, what the
+        # loss's per-sample mask evidently expects - on both sides.  False: the rows of argwhere(mask[0] == 1) are zeroed in every sample,
+        # as upstream (mm.py:147-149, 169-171).  At B = 1 the two are one model
+        if "per_sample_mask" in kwargs:
+            if not isinstance(kwargs["per_sample_mask"], bool):
+                raise ValueError(f"per_sample_mask must be True or False, got {kwargs['per_sample_mask']!r}")
+            self.per_sample_mask = kwargs["per_sample_mask"]
         # use_session: per stitched modality (stitcher.mods) a per-session linear read-in from the session's n_k neurons to the shared
         # width P in front of its tokenisers, and a read-out from P back to n_k behind its head (multi_modal/session_layers.py; DESIGN.md
         # 3aa).  The layers are created last: every other parameter has the bits of the n_channel = P model without sessions
@@ -223,7 +231,7 @@ class MultiModal(nn.Module):
         # fast path (every forward): the cached engine is still valid if a few sentinel parameters are still
         # views of its flat buffer on the same device (.to()/load_state_dict(assign=True) replace them all)
         eng = self._engine
-        if eng is not None and eng.cfg.context != self._context():
+        if eng is not None and (eng.cfg.context != self._context() or eng.cfg.per_sample_mask != bool(self.per_sample_mask)):
             eng = self._engine = None                   # the switch moved after the engine was built: another config, another engine
         if eng is not None and eng.dtype == self.compute_dtype and self._sentinels and \
                 all(eng.owns_one(p) for p in self._sentinels):
@@ -252,6 +260,7 @@ class MultiModal(nn.Module):
                                                  dec_mods=[m for m in self.avail_mod if m in self.decoder_embeddings],
                                                  share_mod_emb=getattr(self, "_share_mod_emb", True),      # (a module pickled before the flag existed shares)
                                                  **({"context_window": True} if self.context_mask else {}),
+                                                 **({"per_sample_mask": True} if self.per_sample_mask else {}),
                                                  **({"sessions": {m: self.session_sizes for m in self.stitch_mods}, "stitch_bias": self.stitch_bias}
                                                     if self.use_session else {}))
             specs = {m: _loss_spec(self.loss_mod[m]) for m in self.avail_mod if m in self.decoder_embeddings}

@@ -68,6 +68,9 @@ def build_parser():
     ap.add_argument("--context_mask", action="store_true",
                     help="honour context.forward / context.backward of the model config: the encoder's self-attention and the "
                          "cross-attention see a key only inside that window over the time stamps (sets training.context_mask)")
+    ap.add_argument("--per_sample_mask", action="store_true",
+                    help="zero each sample's tokens where its own mask is 1 instead of where the first sample's is, on both sides (sets "
+                         "training.per_sample_mask)")
     ap.add_argument("--n_sessions", type=int, default=1,
                     help="K > 1: multi-session pretraining on synthetic sessions of 300..n_neurons neurons each, batch i from session "
                          "i %% K, spikes right-padded with -1 up to n_neurons (1: one session, no padding)")
@@ -104,6 +107,8 @@ def main(argv=None):
         config["training"]["neuron_padding"] = True
     if args.context_mask:
         config["training"]["context_mask"] = True
+    if args.per_sample_mask:
+        config["training"]["per_sample_mask"] = True
     if args.n_sessions < 1:
         raise ValueError(f"--n_sessions must be >= 1, got {args.n_sessions}")
     if args.stitch_width is not None and not args.use_session:

@@ -143,6 +143,14 @@ class MultiModalTrainer():
             inner = getattr(self.model, "module", self.model)
             inner.context_mask = True
             inner._context()
+        # training.per_sample_mask (no key of the reference's YAML either: absent = false): zero each sample's tokens where its OWN mask
+        # is 1, not where sample 0's is (MultiModal.per_sample_mask)
+        per_sample_mask = self.config.training.get("per_sample_mask", False) if hasattr(self.config.training, "get") else False
+        if not isinstance(per_sample_mask, bool):
+            raise ValueError(f"training.per_sample_mask must be true or false, got {per_sample_mask!r}")
+        self.per_sample_mask = per_sample_mask
+        if per_sample_mask:
+            getattr(self.model, "module", self.model).per_sample_mask = True
         self.mixed_training = kwargs.get("mixed_training", False)
         if self.mixed_training:
             self.training_schemes = list(OBJECTIVES)
